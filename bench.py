@@ -3,6 +3,8 @@
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 the driver launches
 one rank per GPU with torch.distributed.run.  Rank 0 prints ONE JSON line.
+The headline is W untimed steps followed by exactly K timed steps in one region; `ms_per_step` = that region / K.
+`--dump-outputs DIR` writes what the last timed step computed on rank 0, as float32 .npy files (see dump_outputs()).
 `--gpus N` means N: under a launcher it must equal WORLD_SIZE (anything else exits 2, no line); run plainly
 (`python bench.py --gpus 4`, no WORLD_SIZE) the script starts its own N ranks as a child process - before it has
 touched the GPU itself - and leaves with the child's exit code; under RCCL it refuses more ranks than the node has GPUs
@@ -105,10 +107,11 @@ def traffic_fields(stamp, note, algorithmic):
     if t < 0.95 * algorithmic:
         return {"traffic": None, "traffic_raw": raw, "traffic_withheld": t,
                 "traffic_source": note + "; corrected traffic below 0.95 x algorithmic bytes: withheld"}
+    # traffic = FETCH_SIZE x 2 + WRITE_SIZE (MI355X_MICROARCH.md, HBM: FETCH_SIZE tallies 64 B per 128-B request);
+    # traffic_raw = FETCH_SIZE + WRITE_SIZE as counted
     return {"traffic": t, "traffic_raw": raw, "traffic_over_algorithmic": round(t / algorithmic, 3),
             "traffic_read_x2": stamp.get("read_bytes_x2"), "traffic_write": stamp.get("write_bytes"),
-            "traffic_source": note + ": FETCH_SIZE x 2 + WRITE_SIZE (MI355X_MICROARCH.md, HBM: FETCH_SIZE tallies 64 B per "
-                                     "128-B request); traffic_raw = FETCH_SIZE + WRITE_SIZE as counted"}
+            "traffic_source": note}
 
 
 def valu_fields(stamp, note, kernel_ms, samples_per_recurrence, role):
@@ -130,10 +133,9 @@ def valu_fields(stamp, note, kernel_ms, samples_per_recurrence, role):
          "wave_insts_per_s": round(rate * 1e9, 1), "peak_wave_insts_per_s": round(peak_mix * 1e9, 1),
          "cycles_per_inst_assumed": mix, "clock_ghz_assumed": CLOCK_GHZ,
          "frac": round(rate / peak_mix, 5),
+         # peak = 1024 SIMDs x 2.4 GHz / cycles_per_inst_assumed: what a SIMD retires of this kernel's instruction mix (see
+         # MIX_CYCLES above); the full rate of 2 cycles applies only to add/sub/logic/right-shift/mov
          "peak_full_rate_wave_insts_per_s": peak_full * 1e9, "frac_of_full_rate": round(rate / peak_full, 5),
-         "peak_note": "peak = 1024 SIMDs x 2.4 GHz / %.2f cycles: what a SIMD retires of this kernel's instruction mix (multiplies, "
-                      "64-bit multiply-adds, VOP3, DPP, SDWA, conversions: 4 cycles each on gfx950; only add/sub/logic/right-shift/mov "
-                      "go at the full rate of 2) - profiles/r03_microbench_valu_rate.txt" % mix,
          "source": note + " (SQ_INSTS_VALU, SQ_WAVES); duration from this run"}
     if "SQ_ACTIVE_INST_VALU" in stamp and stamp.get("GRBM_GUI_ACTIVE"):
         # clock-independent: quad-cycles in which a SIMD issued VALU work / SIMD-cycles of the profiled launch
@@ -146,13 +148,12 @@ def valu_fields(stamp, note, kernel_ms, samples_per_recurrence, role):
             v["clock_ghz_measured"] = round(clk, 3)
             v["frac_at_measured_clock"] = round(rate / (SIMDS * clk / mix), 5)
     if waves <= SIMDS:
-        # fewer waves than SIMDs: each wave is alone on its SIMD and is offered an issue slot every ~4 cycles
+        # fewer waves than SIMDs: each wave is alone on its SIMD and is offered an issue slot every ~4 cycles, so the launch can
+        # use at most lone_wave_peak_frac of the chip's VALU peak; lone_wave_issue_frac is the share of THOSE slots it fills
         lone_peak = occupied * CLOCK_GHZ / LONE_WAVE_CYCLES_PER_INST
         v["occupied_simds"] = int(occupied)
         v["lone_wave_issue_frac"] = round(rate / lone_peak, 4)
-        v["lone_wave_note"] = ("%d waves on %d SIMDs: a wave alone on its SIMD issues at most one instruction per ~%.0f cycles, so "
-                               "this launch can use at most %.3f of the chip's VALU peak; lone_wave_issue_frac is the share of "
-                               "THOSE slots it fills" % (waves, SIMDS, LONE_WAVE_CYCLES_PER_INST, lone_peak / peak_mix))
+        v["lone_wave_peak_frac"] = round(lone_peak / peak_mix, 3)
     return v
 
 
@@ -263,6 +264,28 @@ def measure(engine, torch, dist, pcm, param, steps, warmup, world, event_every=1
         enc.close()
         dec.close()
     return res
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, img, out):
+    """What the caller of the timed step receives from its last step, as float32 (exact for uint8 and int16):
+    encoded_images.npy [streams, image_size] (the .aad images) and decoded_pcm.npy [streams, samples, channels].
+    When the two exceed DUMP_LIMIT_BYTES, both hold the same fixed, seeded sample of streams (sorted), and
+    stream_index.npy (float64) lists which."""
+    import numpy as np
+    streams = img.shape[0]
+    row_bytes = 4 * (img[0].size + out[0].size)
+    rows = np.arange(streams)
+    if streams * row_bytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)  # room for the index and the three .npy headers
+        rows = np.sort(np.random.default_rng(0).choice(streams, keep, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "encoded_images.npy"), img[rows].astype(np.float32))
+    np.save(os.path.join(directory, "decoded_pcm.npy"), out[rows].astype(np.float32))
+    if len(rows) < streams:
+        np.save(os.path.join(directory, "stream_index.npy"), rows.astype(np.float64))
 
 
 # ---- golden checks against the hashes the compiled reference produced (tests/golden/manifest.json) ----
@@ -502,25 +525,10 @@ def end_to_end(engine, torch, pcm_np, param, reps=20):
                 note="PCIe-inclusive: never the headline `value` (inputs are resident in HBM there)")
 
 
-def config_counters(stamp_key, streams, samples, algorithmic, enc_ms, dec_ms, spb):
-    """Counter evidence of a `configs[]` row from the committed rocprofv3 passes (tools/collect_config_profiles.sh): per kernel the
-    HBM traffic (FETCH_SIZE x 2 + WRITE_SIZE), its ratio to the algorithmic bytes, the VMEM instruction counts and the
-    wave-instructions per sample.  Same stamp rule as the headline: withheld when the kernel sources have changed since."""
-    out = {}
-    for role, kms, per_rec in (("encode", enc_ms, samples), ("decode", dec_ms, min(spb, samples))):
-        st, note = pmc_stamp(stamp_key, role, streams, samples) if stamp_key else (None, "no PMC passes for this row")
-        row = dict({"kernel": (st or {}).get("kernel")}, **traffic_fields(st, note, algorithmic))
-        if st and st.get("SQ_WAVES"):
-            v = valu_fields(st, note, kms, per_rec, role)
-            row["valu"] = {k: v.get(k) for k in ("insts_per_sample", "insts_per_wave", "waves", "frac", "frac_of_full_rate", "lone_wave_issue_frac") if k in v}
-            row["vmem_rd_insts"], row["vmem_wr_insts"] = st.get("SQ_INSTS_VMEM_RD"), st.get("SQ_INSTS_VMEM_WR")
-        out[role] = row
-    return out
-
-
-def config_entry(engine, torch, dist, name, streams, samples, ch, bits, trials, steps, golden, stamp_key=None):
-    """One of the other BASELINE shapes: kernel time (HIP events), Msamples/s, HBM-roof fraction, the counter traffic of the
-    committed PMC passes and the bit-exact flag against the compiled reference's hashes for the same corpus."""
+def config_entry(engine, torch, dist, name, streams, samples, ch, bits, trials, steps, golden):
+    """One of the other BASELINE shapes: kernel time (HIP events), Msamples/s, HBM-roof fraction and the bit-exact flag against
+    the compiled reference's hashes for the same corpus.  Their counter passes stay in the committed stamp file
+    (tools/collect_config_profiles.sh, tools/config_pmc_summary.py): quoted here they made the line too long to read back."""
     from aad_amd.capi import make_parameter
     from aad_amd.synth import synth_pcm
     pcm_np = synth_pcm(streams, samples, ch, seed=1234)
@@ -541,7 +549,6 @@ def config_entry(engine, torch, dist, name, streams, samples, ch, bits, trials, 
                 bytes_per_sample=round(bps, 4), algorithmic_bytes_per_launch=int(round(n * bps)),
                 encode_frac=round(n * bps / (m["enc_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
                 decode_frac=round(n * bps / (m["dec_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
-                counters=config_counters(stamp_key, streams, samples, int(round(n * bps)), m["enc_ms"], m["dec_ms"], hd.num_samples_per_block),
                 bit_exact_vs_reference_golden=flag)
 
 
@@ -664,11 +671,13 @@ def main():
     ap.add_argument("--in-flight", type=int, default=2, choices=(1, 2),
                     help="steps in flight: 2 (default) = two encode + decode pipelines on four streams, stepped in turn; 1 = one pipeline (rounds 2-3)")
     ap.add_argument("--event-every", type=int, default=8, help="bracket the kernels with HIP events on every n-th timed step")
-    ap.add_argument("--repeats", type=int, default=9, help="time the K-step region at least this many times; the line reports the median region")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0, help="...and until this much timed work has accumulated (at most 101 regions)")
     ap.add_argument("--no-config5", action="store_true",
                     help="N = 1: skip the batched-file leg under a one-rank RCCL group (BASELINE config 5's code path with the collectives forced)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the encoded images and decoded PCM of the last timed step (rank 0) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     plan = resolve_world(args.gpus, os.environ)
     if plan[0] == "error":
@@ -730,12 +739,14 @@ def main():
     torch.cuda.synchronize()
     # everything timed below is launched on the engine's stream, and the HIP events are recorded on it
     torch.cuda.set_stream(engine.stream)
+    # the headline: --warmup untimed steps, then ONE region of exactly --steps timed steps
     m = measure(engine, torch, dist, pcm, param, args.steps, args.warmup, world, args.event_every, keep=(rank == 0),
-                decode_engine=decode_engine, repeats=args.repeats, min_timed_s=args.min_timed_ms * 1e-3, max_repeats=max(args.repeats, 101),
-                more_pipelines=more)
+                decode_engine=decode_engine, more_pipelines=more)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["img"], m["out"])
     hd = m["header"]
     n_step = args.streams * samples * ch  # channel-samples per direction per rank
-    value = 2.0 * n_step * world * args.steps / m["wall_s"] / 1e6  # the MEDIAN K-step region
+    value = 2.0 * n_step * world * args.steps / m["wall_s"] / 1e6
     bps = algorithmic_bytes_per_sample(ch, hd.block_size, hd.num_samples_per_block)
     enc_gbs = n_step * bps / (m["enc_ms"] * 1e-3) / 1e9
     dec_gbs = n_step * bps / (m["dec_ms"] * 1e-3) / 1e9
@@ -752,12 +763,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(m["wall_s"] / args.steps * 1e3, 5),
-        "value_min": round(2.0 * n_step * world * args.steps / m["wall_max_s"] / 1e6, 3),
-        "value_max": round(2.0 * n_step * world * args.steps / m["wall_min_s"] / 1e6, 3),
-        "timed_regions": {"count": m["regions"], "steps_each": args.steps, "timed_s": round(m["timed_s"], 6),
-                          "rule": "the K-step region (barrier + synchronize on both sides) is timed at least %d times and until "
-                                  "%.0f ms of timed work; value / ms_per_step are the MEDIAN region, value_min / value_max the "
-                                  "slowest / fastest" % (args.repeats, args.min_timed_ms)},
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -864,12 +869,12 @@ def main():
 
     def configs_leg():
         cfgs = [
-            ("cfg2(ii) 1000 stereo 4-bit streams x 16 blocks", 1000, 992 * 16, 2, 4, 0, 5, "corpus", "cfg2ii"),
+            ("cfg2(ii) 1000 stereo 4-bit streams x 16 blocks", 1000, 992 * 16, 2, 4, 0, 5, "corpus"),
             ("cfg2(iii) 1 stereo 4-bit stream x 1000 blocks (serial worst case: 2 encode recurrences)", 1, 992 * 1000, 2, 4, 0, 2, "corpus"),
             ("cfg2(iii) with trials 2", 1, 992 * 1000, 2, 4, 2, 1, "corpus"),
-            ("cfg4 10000 x 8-channel 3-bit one-block segments", 10000, 292, 8, 3, 0, 10, "eight", "cfg4_3bit"),
-            ("cfg4 10000 x 8-channel 2-bit one-block segments", 10000, 444, 8, 2, 0, 10, "eight", "cfg4_2bit"),
-            ("cfg5 per-GPU shard: 1250 stereo 4-bit files x 10 blocks", 1250, 9920, 2, 4, 0, 5, "corpus", "cfg5_shard"),
+            ("cfg4 10000 x 8-channel 3-bit one-block segments", 10000, 292, 8, 3, 0, 10, "eight"),
+            ("cfg4 10000 x 8-channel 2-bit one-block segments", 10000, 444, 8, 2, 0, 10, "eight"),
+            ("cfg5 per-GPU shard: 1250 stereo 4-bit files x 10 blocks", 1250, 9920, 2, 4, 0, 5, "corpus"),
         ]
         rows = []
         for c in cfgs:
@@ -899,11 +904,10 @@ def main():
             "decode_frac": round(nb * bps / (ms["dec_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
             "algorithmic_bytes_per_launch": int(round(nb * bps)),
         }
-        for role, kms, per_rec in (("encode", ms["enc_ms"], samples), ("decode", ms["dec_ms"], hd.num_samples_per_block)):
-            st, note = pmc_stamp("saturated", role, big_streams, samples)
-            sat[role] = dict({"kernel": (st or {}).get("kernel"), "kernel_ms": round(kms, 5)},
-                                           **traffic_fields(st, note, int(round(nb * bps))),
-                                           **{"valu": valu_fields(st, note, kms, per_rec, role)})
+        for role, kms in (("encode", ms["enc_ms"]), ("decode", ms["dec_ms"])):
+            # the counter passes of this batch stay in the committed stamp file, as for `configs`
+            st, _ = pmc_stamp("saturated", role, big_streams, samples)
+            sat[role] = {"kernel": (st or {}).get("kernel"), "kernel_ms": round(kms, 5)}
 
         if extras:
             # the other fast-path geometries on chip-filling batches of one-block streams (524 288 recurrences each),

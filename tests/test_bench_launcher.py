@@ -33,3 +33,26 @@ def test_mismatch_exits_2_without_a_line():
     env = dict(os.environ, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"], env=env, capture_output=True, text=True, timeout=120)
     assert p.returncode == 2 and p.stdout == "" and "WORLD_SIZE=4" in p.stderr
+
+
+def test_dump_outputs_float32_and_a_fixed_sample_when_too_large(tmp_path, monkeypatch):
+    import numpy as np
+    rng = np.random.default_rng(5)
+    img = rng.integers(0, 256, (40, 70), dtype=np.uint8)
+    out = rng.integers(-32768, 32768, (40, 30, 2), dtype=np.int16)
+    bench.dump_outputs(str(tmp_path / "all"), img, out)
+    a, b = np.load(tmp_path / "all" / "encoded_images.npy"), np.load(tmp_path / "all" / "decoded_pcm.npy")
+    assert a.dtype == np.float32 and b.dtype == np.float32
+    assert np.array_equal(a, img) and np.array_equal(b, out)
+    assert not (tmp_path / "all" / "stream_index.npy").exists()
+    # over the limit: the same seeded rows in both arrays, every run, and the whole dump within the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 10 * (4 * (70 + 60) + 8))
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), img, out)
+    rows = np.load(tmp_path / "s1" / "stream_index.npy")
+    assert rows.dtype == np.float64 and len(rows) == 10 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "stream_index.npy"))
+    r = rows.astype(int)
+    assert np.array_equal(np.load(tmp_path / "s1" / "encoded_images.npy"), img[r])
+    assert np.array_equal(np.load(tmp_path / "s1" / "decoded_pcm.npy"), out[r])
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= bench.DUMP_LIMIT_BYTES
