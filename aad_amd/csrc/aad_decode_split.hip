@@ -12,7 +12,6 @@
 #include <cstring>
 
 #include "aad_decode_split.hip.h"
-#include "aad_decode_split_launch.h"
 #include "aad_launch.h"
 
 namespace aad {
@@ -28,29 +27,19 @@ static void launch_bits(const SplitDecodeArgs &sa, dim3 grid, dim3 block, hipStr
     AAD_LAUNCH((decode_split_kernel<BITS, 2, false, LDSRES>), grid, block, 0, stream, sa);
 }
 
-bool decode_split_fits_lds(const DecodeArgs &args)
+void launch_decode_split(const DecodeArgs &args, const DecodeLaunch &p, int32_t *residual, hipStream_t stream)
 {
-  const uint32_t coded = args.samples_per_block > 4 ? args.samples_per_block - 4 : 0;
-  return coded <= kLdsResidualMax && args.total_blocks * args.channels <= 4096; /* one workgroup per CU */
-}
-
-bool launch_decode_split(const DecodeArgs &args, int32_t *residual, uint32_t residual_stride, hipStream_t stream)
-{
-  if (args.channels < 1 || args.channels > 2) return false;
   SplitDecodeArgs sa;
   sa.d = args;
   sa.residual = residual;
-  sa.residual_stride = residual_stride;
+  sa.residual_stride = p.residual_stride;
   sa.reserved = 0;
-  const uint64_t recurrences = args.total_blocks * args.channels;
-  const dim3 grid((unsigned)((recurrences + 15) / 16)), block(1024); /* 16 recurrences per workgroup */
-  const bool lds = residual == nullptr;
-  if (lds && !decode_split_fits_lds(args)) return false;
+  const dim3 grid(p.grid), block(p.workgroup);
+  const bool lds = p.kernel == DecodeKernel::SplitLds;
   switch (args.bits) {
-    case 4: lds ? launch_bits<4, true>(sa, grid, block, stream) : launch_bits<4, false>(sa, grid, block, stream); return true;
-    case 3: lds ? launch_bits<3, true>(sa, grid, block, stream) : launch_bits<3, false>(sa, grid, block, stream); return true;
-    case 2: lds ? launch_bits<2, true>(sa, grid, block, stream) : launch_bits<2, false>(sa, grid, block, stream); return true;
-    default: return false;
+    case 4: lds ? launch_bits<4, true>(sa, grid, block, stream) : launch_bits<4, false>(sa, grid, block, stream); break;
+    case 3: lds ? launch_bits<3, true>(sa, grid, block, stream) : launch_bits<3, false>(sa, grid, block, stream); break;
+    default: lds ? launch_bits<2, true>(sa, grid, block, stream) : launch_bits<2, false>(sa, grid, block, stream); break;
   }
 }
 

@@ -421,13 +421,6 @@ __device__ __forceinline__ void predict_for_quad(const SplitDecodeArgs &a, uint6
  * residuals cross over through LDS when a block's worth fits (LDSRES) and through the scratch
  * buffer in device memory otherwise.
  */
-/* LDS-resident residuals: rows of kLdsResidualRow dwords, enough for blocks of up to
- * kLdsResidualMax coded samples per channel (every 4-bit geometry up to max_block_size 1024 and
- * most others); the row length is 20 mod 32 dwords so that the sixteen rows a wave reads at the
- * same sample offset spread over the banks.  132 KB of the CU's 160 KB: one workgroup per CU,
- * which is what this path is for (the host uses it up to one workgroup per CU). */
-constexpr uint32_t kLdsResidualMax = 2048;
-constexpr uint32_t kLdsResidualRow = kLdsResidualMax + kChunk + 4;
 
 template <int BITS, int CHF, bool MS, bool LDSRES>
 __global__ void __launch_bounds__(1024) decode_split_kernel(SplitDecodeArgs a)

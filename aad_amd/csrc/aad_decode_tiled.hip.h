@@ -42,7 +42,7 @@ template <int BITS, int CHF>
 struct DecodeTile {
   static_assert((BITS == 4 || BITS == 3 || BITS == 2) && (CHF == 1 || CHF == 2), "mono / stereo");
   static constexpr bool k3 = BITS == 3;                        /* 3-bit codes: see "3-bit rows" below */
-  static constexpr int kWaves = 4;                             /* waves per workgroup */
+  static constexpr int kWaves = kTiledWaves;                   /* waves per workgroup */
   static constexpr int kRows = 64 / CHF;                       /* rows (blocks) per wave */
   static constexpr int kG = CHF == 1 ? 64 : 128;               /* granule bytes, both directions */
   static constexpr int kGLog2 = CHF == 1 ? 6 : 7;

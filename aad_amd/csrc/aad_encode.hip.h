@@ -767,23 +767,6 @@ struct ByteRing {
   }
 };
 
-/* which dense encoders stage their codes, where the staging area starts in their LDS block, and its size */
-template <int BITS, int CHF, bool QUAD>
-constexpr bool kStagedCodes = !QUAD && (CHF == 1 || (CHF == 2 && BITS != 4));
-constexpr int kLdsCodeStageOff = (kLdsBytesQuadEnc + 15) & ~15;
-template <int BITS, int CHF, bool QUAD>
-constexpr int kLdsBytesEncoder = kStagedCodes<BITS, CHF, QUAD> ? kLdsCodeStageOff + 4 * 8 * 64 * (BITS == 2 ? 4 : 8) : kLdsBytesQuadEnc;
-/* the instantiations that move their output through ByteRing: dense, mono / stereo, 4- and 2-bit codes (pieces of whole dwords) */
-template <int BITS, int CHF, bool QUAD>
-constexpr bool kRingable = !QUAD && (CHF == 1 || CHF == 2);
-/* The rows' byte rings live in DYNAMIC LDS, one wave's worth per wave of the workgroup (the launch asks for blockDim.x / 64 of
- * them): a static area for four waves cost the one-wave workgroups of 16 385 .. 65 536-lane batches a resident wave per CU
- * (72 864 B mono / 54 432 B stereo 4-bit per workgroup instead of 45 216 / 40 608). */
-template <int CHF>
-constexpr int kLdsRingBytesPerWave = (64 / (CHF ? CHF : 1)) * 144;
-template <int BITS, int CHF, bool QUAD, bool RING>
-constexpr int kLdsBytesEncoderStatic = RING ? kLdsCodeStageOff : kLdsBytesEncoder<BITS, CHF, QUAD>;
-
 /* the lane's bytes of a chunk in memory order (mono: its 8 / 4 code bytes; stereo: its half of the pair's interleaved bytes,
  * as store_chunk_codes / CodeStage::put build them): 4-bit -> d0, d1; 2-bit -> d0 */
 template <int BITS, int CHF>

@@ -20,9 +20,7 @@
 
 #include "../../include/aad_hip.h"
 #include "aad_compare.hip.h"
-#include "aad_decode_split_launch.h"
-#include "aad_launch.h"
-#include "aad_decode_tiled_launch.h"
+#include "aad_launch.h" /* and aad_launch_policy.h */
 #include "aad_decode.hip.h"
 #include "aad_encode.hip.h"
 #include "aad_format.h"
@@ -92,8 +90,8 @@ struct AADHipContext {
   /* AADHip_ContextSetOption; the defaults come from the environment ONCE, at creation */
   aad::LaunchSignal signal_next; /* AADHip_ContextSignalNextRun: the events the next plan run records around its work (one-shot) */
   bool signal_refused;           /* ROC_SYSTEM_SCOPE_SIGNAL=0 at creation: an event on a dispatch packet is never seen by another queue */
-  int32_t lane_mapping; /* enum AADHipLaneMapping */
-  int32_t trial_lanes;  /* enum AADHipTrialLanes */
+  aad::Device device_info; /* filled once at creation: the launch policy's residency terms */
+  aad::Knobs knobs;        /* lane mapping, trial lanes (enum AADHipLaneMapping / AADHipTrialLanes) and the measurement aids */
   int32_t compare_sequential; /* AAD_HIP_OPTION_COMPARE_ORDER: the -c sums always in the reference's order */
   int64_t tile_bytes;      /* 0 = the built-in tile budget of the host-memory path, else that many bytes */
   void *d_state;           /* predictor states of a group of streams between its tiles (host-memory encode) */
@@ -201,329 +199,78 @@ bool upload(AADHipContext *ctx, T **dst, const T *src, size_t count)
          hip_ok(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
 }
 
-
-/* Lanes are scarce in every BASELINE config: while the batch has fewer
- * waves than the chip has SIMDs (256 CUs x 4) each wave gets a workgroup of its own so the
- * dispatcher spreads them over as many SIMDs as possible; big batches use 256-thread
- * workgroups so four waves share one LDS copy of the tables. */
-unsigned pick_workgroup(uint64_t threads) { return threads <= 64ull * 1024ull ? 64u : 256u; }
-
-/* Lane mapping by batch size.  "quad" (four lanes per recurrence, fewer instructions on the
- * recurrence's critical path) while the batch cannot fill the chip anyway, "dense" (one lane per
- * recurrence, fewest total instructions) beyond; the decoder has the split quad kernel below the
- * fused one.  The crossovers were measured per (bits, channels) geometry on one-block streams
- * (tools/mapping_crossover.py, profiles/r02_mapping_crossover.jsonl): they sit where the quad
- * mappings start to put a second wave on a SIMD (4 x 16384 lanes = one wave on each of the 1024
- * SIMDs) and depend on the geometry only for the split decoder, whose 3-bit stereo unpacking is the
- * most expensive strand-1 work.  A context option (AADHip_ContextSetOption, default from
- * AAD_HIP_MAPPING at context creation) forces one mapping; the parity tests run all of them. */
-struct MappingLimits {
-  uint32_t encode_quad;  /* recurrences up to which encode uses the quad mapping */
-  uint32_t decode_split; /* ... decode uses the split quad decoder */
-  uint32_t decode_fused; /* ... the fused quad decoder; dense beyond */
-};
-
-MappingLimits mapping_limits(uint32_t bits, uint32_t channels)
+/* ---- dispatch: from a plan (aad_launch_policy.h) to a template instantiation ---------------------------------------------- */
+/* encode_streams_kernel by channels and M/S; RING: the dense encoders whose output goes through the rows' byte rings
+ * (aad_encode.hip.h ByteRing), mono / stereo only */
+template <int BITS, bool QUAD, bool TRIALS, bool DUAL, bool RING = false>
+void launch_encode_mapped(const aad::EncodeArgs &a, const aad::EncodeLaunch &p, hipStream_t stream)
 {
-  /* tools/mapping_crossover.py, profiles/r02_mapping_crossover.jsonl.  Since the dense decoder's sample
-   * went from 32.5 to 24 instructions it is as fast as the fused quad decoder at every batch size
-   * (59-60 us on one-block stereo 4-bit streams, 250 to 48 000 recurrences; fused 61-67 us up to 16 384):
-   * "auto" no longer picks the fused kernel (its range is empty), the option still forces it. */
-  /* Round 4 (tools/size_sweep.py --mapping quad | dense, profiles/r04_decode_split_crossover.txt): the split decoder runs
-   * 1024-thread workgroups of 16 recurrences, ONE to a CU (84-94 VGPRs x 16 waves), i.e. rounds of 4096 recurrences: its time is
-   * about 0.025 + 0.015 ms x rounds on stereo 4-bit.  Up to two rounds (8192 recurrences) it beats the dense kernel in every
-   * geometry (mono 4-bit 0.090 vs 0.116 ms at 8192), from the third round on (9000) it loses in every
-   * geometry (0.120 vs 0.116) and its residual scratch (recurrences x block x 4 bytes, ~100 MB at 12 288 mono rows) pushes the
-   * NEXT launch's input out of the caches: a mono 4-bit encode behind it took 0.15-0.20 ms instead of 0.127.  Round 2's
-   * per-geometry limits (12 288; 9 216 / 8 192 for 4- / 3-bit stereo) predate the dense decoder's round-3 speed-ups. */
-  MappingLimits m = {16384u, 8192u, 0u};
-  m.decode_fused = m.decode_split;
-  return m;
-}
-
-bool pick_quad(const AADHipContext *ctx, uint64_t recurrences, uint32_t channels, uint32_t bits)
-{
-  if (channels > 2) return false;
-  if (ctx->lane_mapping == AAD_HIP_LANE_MAPPING_DENSE || ctx->lane_mapping == AAD_HIP_LANE_MAPPING_DENSE_TILED) return false;
-  if (ctx->lane_mapping == AAD_HIP_LANE_MAPPING_QUAD || ctx->lane_mapping == AAD_HIP_LANE_MAPPING_QUAD_FUSED) return true;
-  return recurrences <= mapping_limits(bits, channels).encode_quad;
-}
-
-/* lds_pad: dynamic LDS the kernel never touches - it only lowers the number of workgroups a CU holds (see dense_encode_lds_pad) */
-/* the dense encoders whose output goes through the rows' byte rings (aad_encode.hip.h ByteRing): mono / stereo */
-template <int BITS, bool TRIALS>
-bool launch_encode_ring(const aad::EncodeArgs &a, dim3 grid, dim3 block, hipStream_t stream, unsigned lds_pad)
-{
+  const dim3 grid(p.grid), block(p.workgroup);
   if (a.channels == 1)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 1, false, false, TRIALS, false, true>), grid, block, lds_pad, stream, a);
+    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 1, false, QUAD, TRIALS, DUAL, RING>), grid, block, p.lds, stream, a);
   else if (a.channels == 2 && a.mid_side)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, true, false, TRIALS, false, true>), grid, block, lds_pad, stream, a);
+    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, true, QUAD, TRIALS, DUAL, RING>), grid, block, p.lds, stream, a);
   else if (a.channels == 2)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, false, false, TRIALS, false, true>), grid, block, lds_pad, stream, a);
-  else
-    return false;
-  return true;
+    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, false, QUAD, TRIALS, DUAL, RING>), grid, block, p.lds, stream, a);
+  else if constexpr (!QUAD && !RING)
+    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 0, false, false, TRIALS, false>), grid, block, p.lds, stream, a);
 }
-
-/* Which dense encoders append to the byte ring.  Policy (same-box A/B on the saturated batches, profiles/r03_encoder_byte_ring.txt):
- * every mono encoder and the stereo 4-bit one - their writes fall from 1.3-2.1x to 1.00-1.06x of the code bytes and the kernels
- * get 3-8 % faster; stereo 3- and 2-bit - no: they are VALU-saturated (95 % active), wrote only 1.18x in total before, and the
- * ring's extra ~1 VALU instruction per sample costs them 3-7 % of their time.  AAD_HIP_ENCODE_RING (read at every launch: the
- * tests flip it) = 0: never (A/B measurements), = 2: every geometry that can.
- * Round 4: only in four-wave workgroups.  Batches of 16 385 .. 65 536 lanes run one-wave workgroups (a wave per SIMD, as many
- * CUs as possible); there the ring is 1-4 % SLOWER than the plain stores (same-box A/B, profiles/r04_encoder_ring_midsize.txt:
- * mono 40 000 streams 0.1835 vs 0.1811 ms, stereo 4-bit 28 000 streams 0.1044 vs 0.1003 ms) - a launch that leaves SIMDs idle
- * gains nothing from fewer write sectors and pays the ring's instructions on its critical path. */
-bool encode_ring_wanted(uint32_t bits, uint32_t channels, unsigned workgroup)
-{
-  const char *e = getenv("AAD_HIP_ENCODE_RING");
-  if (e != nullptr && e[0] == '0') return false;
-  if (e != nullptr && e[0] == '2') return true;
-  return workgroup == 256u && (channels == 1 || bits == 4);
-}
-
-/* One-wave workgroups (pick_workgroup: up to 65 536 lanes) only while ALL of them can be resident at once: a dense mono encoder
- * holds 45-52 KB of LDS per workgroup (wide table + code staging or ring rows), so a CU takes three of them and its fourth SIMD
- * stays empty - from 49 153 lanes (769 waves) on the launch ran in two rounds (mono 4-bit, 64 000 one-block streams: 0.35-0.41 ms
- * against 0.19 ms for 48 000, profiles/r04_encoder_ring_midsize.txt).  Four-wave workgroups share one table: two per CU. */
-unsigned dense_encode_workgroup(uint64_t lanes, unsigned lds_one_wave)
-{
-  const unsigned wg = pick_workgroup(lanes);
-  if (wg != 64u) return wg;
-  const uint64_t waves = (lanes + 63u) / 64u;
-  const uint64_t resident = 256ull * ((160u << 10) / ((lds_one_wave + 1023u) & ~1023u)); /* CUs x workgroups whose LDS fits */
-  return waves > resident ? 256u : 64u;
-}
-
-template <int BITS, bool QUAD, bool TRIALS, bool DUAL>
-void launch_encode_mapped(const aad::EncodeArgs &a, dim3 grid, dim3 block, hipStream_t stream, unsigned lds_pad = 0)
-{
-  if (a.channels == 1)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 1, false, QUAD, TRIALS, DUAL>), grid, block, lds_pad, stream, a);
-  else if (a.channels == 2 && a.mid_side)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, true, QUAD, TRIALS, DUAL>), grid, block, lds_pad, stream, a);
-  else if (a.channels == 2)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, false, QUAD, TRIALS, DUAL>), grid, block, lds_pad, stream, a);
-  else if constexpr (!QUAD)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 0, false, false, TRIALS, false>), grid, block, lds_pad, stream, a);
-}
-
-/* Occupancy cap of the dense 4-bit encoders on chip-filling batches: unused dynamic LDS up to 80 KB per workgroup, so that a
- * CU holds two workgroups = two waves per SIMD instead of three or four.  These kernels are bound by VALU issue (85 % VALU-
- * active with two waves as with four), but every resident lane keeps one 128-byte line of PCM and one sector of codes alive
- * in the L2 between its visits: 8192 lines per CU at four waves per SIMD - 8 MiB per XCD against 4 MiB of L2 - and a line
- * was fetched 2.2 (mono) / 1.27 (stereo) times; with two waves per SIMD 1.57 / 1.01 times, at the same kernel time
- * (profiles/r03_encoder_occupancy_cap.txt).  The 3- and 2-bit encoders are VALU-saturated (96-103 % active) and lose 4-6 % of
- * their time under the same cap for a similar cut in traffic: they keep their occupancy.  AAD_HIP_ENCODE_LDS_PAD (bytes, read
- * once) overrides the policy for experiments. */
-unsigned dense_encode_lds_pad(uint32_t bits, uint64_t lanes, unsigned static_lds)
-{
-  static const int forced = [] {
-    const char *e = getenv("AAD_HIP_ENCODE_LDS_PAD");
-    return e ? atoi(e) : -1;
-  }();
-  if (forced >= 0) return (unsigned)forced;
-  constexpr unsigned kTarget = 80u << 10; /* two workgroups per CU (160 KB of LDS) */
-  if (bits != 4 || lanes < 65536 || static_lds >= kTarget) return 0;
-  return kTarget - static_lds;
-}
-
-/* On the quad mapping the trial search's probe strand gets lanes of its own ("dual"): one pass of
- * latency less per block with a predecessor, nothing lost otherwise (tools/trial_probe.py).
- * AAD_HIP_OPTION_TRIAL_LANES = single keeps both strands on the same lanes (the parity tests run both). */
-/* Round 4: ... up to kDualMaxRecurrences.  The dual layout spends eight lanes per recurrence; from ~640 waves on (5120 recurrences)
- * its launch slows down faster than the work grows and the one-after-the-other layout - flat up to 16 384 recurrences - overtakes it
- * in every geometry (stereo 4-bit, t = 2: dual 0.146 / 0.161 / 0.231 ms at 4096 / 5120 / 6144 recurrences, single 0.188-0.190;
- * profiles/r04_trial_search_size_sweep.txt). */
-constexpr uint64_t kDualMaxRecurrences = 5120;
-bool pick_dual(const AADHipContext *ctx, const aad::EncodeArgs &a, bool quad)
-{
-  if (!quad || a.trials == 0) return false;
-  if (a.trial_scratch == nullptr) return false; /* run_encode could not provide the slots */
-  if ((uint64_t)a.num_streams * a.channels > kDualMaxRecurrences) return false;
-  return ctx->trial_lanes != AAD_HIP_TRIAL_LANES_SINGLE;
-}
-
-/* the dual trial search keeps up to two alternative encodes of a block (and what measuring lanes write)
- * beside the image: three slots of one block per stream */
-constexpr uint64_t kMaxTrialScratchBytes = 1ull << 30;
-uint32_t trial_slot_bytes(const aad::EncodeArgs &a) { return (a.block_size + 16u + 63u) & ~63u; }
 
 template <int BITS>
-void launch_encode(const AADHipContext *ctx, const aad::EncodeArgs &a)
+void launch_encode(const aad::EncodeArgs &a, const aad::EncodeLaunch &p, hipStream_t stream)
 {
-  const hipStream_t stream = ctx->stream;
-  const uint64_t lanes = (uint64_t)a.num_streams * a.channels;
-  const bool quad = pick_quad(ctx, lanes, a.channels, BITS);
-  const bool dual = pick_dual(ctx, a, quad);
-  const uint64_t threads = quad ? lanes * (dual ? 8 : 4) : lanes;
-  /* dual: eight lanes per recurrence put a wave on twice as many CUs as the trial-free launch; two waves
-   * per workgroup (two SIMDs of one CU) keep a small batch on half the chip, so that a decode launched
-   * beside it finds free CUs (bench.py's pipelined step with trials 2: 158 -> see DESIGN.md) */
-  /* (round 4: two-wave workgroups only while there is at most one of them per CU - 256 workgroups, 4096 recurrences.  Beyond that a
-   * CU receives a second workgroup whose two waves land on the SIMDs the first one's already use, the other two SIMDs stay empty
-   * and the launch takes 1.6x as long: stereo 4-bit, t = 2, 6000 recurrences 0.229 ms against 0.143 at 4096;
-   * profiles/r04_trial_search_size_sweep.txt.  One-wave workgroups spread over the SIMDs.) */
-  unsigned wg = dual && threads <= 32ull * 1024ull ? 128u : pick_workgroup(threads);
-  if (!quad) /* the dense encoders, with and without the trial search: one-wave workgroups only while their LDS lets all of them be resident */
-    wg = dense_encode_workgroup(lanes, a.channels == 1 ? (unsigned)aad::kLdsBytesEncoder<BITS, 1, false>
-                                       : (a.channels == 2 ? (unsigned)aad::kLdsBytesEncoder<BITS, 2, false> : (unsigned)aad::kLdsBytesEncoder<BITS, 0, false>));
-  const dim3 grid((unsigned)((threads + wg - 1) / wg)), block(wg);
-  if (a.trials) {
-    if (dual) launch_encode_mapped<BITS, true, true, true>(a, grid, block, stream);
-    else if (quad) launch_encode_mapped<BITS, true, true, false>(a, grid, block, stream);
-    else launch_encode_mapped<BITS, false, true, false>(a, grid, block, stream);
+  if (p.trials) {
+    if (p.kernel == aad::EncodeKernel::QuadDual) launch_encode_mapped<BITS, true, true, true>(a, p, stream);
+    else if (p.kernel == aad::EncodeKernel::Quad) launch_encode_mapped<BITS, true, true, false>(a, p, stream);
+    else launch_encode_mapped<BITS, false, true, false>(a, p, stream);
+  } else if (p.kernel == aad::EncodeKernel::Quad) {
+    launch_encode_mapped<BITS, true, false, false>(a, p, stream);
+  } else if (p.kernel == aad::EncodeKernel::DenseRing) {
+    launch_encode_mapped<BITS, false, false, false, true>(a, p, stream);
   } else {
-    if (quad) launch_encode_mapped<BITS, true, false, false>(a, grid, block, stream);
-    else {
-      const bool ring = a.ring_ok && a.channels <= 2 && encode_ring_wanted(BITS, a.channels, wg);
-      /* the rows' byte rings: dynamic LDS, one wave's worth per wave of the workgroup */
-      const unsigned ring_lds = ring ? (wg / 64u) * (unsigned)(a.channels == 1 ? aad::kLdsRingBytesPerWave<1> : aad::kLdsRingBytesPerWave<2>) : 0u;
-      const unsigned static_lds = ring ? (unsigned)aad::kLdsCodeStageOff + ring_lds
-                                  : (a.channels == 1 ? (unsigned)aad::kLdsBytesEncoder<BITS, 1, false>
-                                                     : (a.channels == 2 ? (unsigned)aad::kLdsBytesEncoder<BITS, 2, false> : (unsigned)aad::kLdsBytesEncoder<BITS, 0, false>));
-      const unsigned pad = wg == 256u ? dense_encode_lds_pad(BITS, lanes, static_lds) : 0u;
-      if (!(ring && launch_encode_ring<BITS, false>(a, grid, block, stream, ring_lds + pad)))
-        launch_encode_mapped<BITS, false, false, false>(a, grid, block, stream, pad);
-    }
+    launch_encode_mapped<BITS, false, false, false>(a, p, stream);
   }
 }
 
-/* Occupancy cap of the per-lane dense decoders on chip-filling batches (what is left to them since the sector-tiled kernel:
- * 3-bit streams, layouts whose PCM is not 16-byte aligned, more than two channels): unused dynamic LDS up to 80 KB per
- * workgroup = two workgroups per CU = two waves per SIMD.  These kernels wait for memory (56-59 % VALU-active on mono 3-bit
- * streams), and what they wait for is lines that were evicted between two visits of the same lane: with fewer lanes resident
- * the L2 keeps more of them.  Mono 3-bit, 524 288 blocks: 2.00 -> 1.72 ms (688 -> 801 Gsamples/s), stereo 3-bit 0.762 -> 0.733 ms;
- * one wave per SIMD is slower again (1.75 / 0.86 ms); profiles/r03_decoder_occupancy_cap.txt.  AAD_HIP_DECODE_LDS_PAD (bytes, read once) overrides the policy. */
-unsigned dense_decode_lds_pad(uint64_t lanes, uint32_t channels, uint32_t bits)
-{
-  static const int forced = [] {
-    const char *e = getenv("AAD_HIP_DECODE_LDS_PAD");
-    return e ? atoi(e) : -1;
-  }();
-  if (forced >= 0) return (unsigned)forced;
-  constexpr unsigned kTarget = 80u << 10;
-  /* same-box A/B of every geometry on this kernel: mono 4- / 3- / 2-bit +0 / +16 / +7 %, stereo 3- / 2-bit +4 / +2 %, stereo
-   * 4-bit (streamed stores) -4 %: that one keeps its occupancy, and so do the any-channel launches (no change) */
-  const bool gains = channels == 1 || (channels == 2 && bits != 4);
-  return gains && lanes >= 65536 ? kTarget - (unsigned)aad::kLdsBytesDenseDec : 0u;
-}
-
-/* The dense stereo decoder's streamed (non-temporal) PCM stores: AAD_HIP_DECODE_NT_MIN (lanes, read once) is the batch size
- * from which they are taken where the layout allows (DecodeArgs::stream_stores); measurement aid, never changes a byte. */
-uint64_t decode_nt_min_lanes()
-{
-  static const uint64_t v = [] {
-    const char *e = getenv("AAD_HIP_DECODE_NT_MIN");
-    return e ? (uint64_t)atoll(e) : 0ull;
-  }();
-  return v;
-}
-
+/* decode_blocks_kernel by channels and M/S; the dense stereo 4- / 2-bit kernels in their streamed-store form when the plan says so */
 template <int BITS, bool QUAD>
-void launch_decode_mapped(const aad::DecodeArgs &args, dim3 grid, dim3 block, hipStream_t stream)
+void launch_decode_mapped(const aad::DecodeArgs &a, const aad::DecodeLaunch &p, hipStream_t stream)
 {
-  aad::DecodeArgs a = args;
-  if (a.total_blocks * a.channels < decode_nt_min_lanes()) a.stream_stores = 0;
-  const unsigned lds_pad = !QUAD && block.x == 256u ? dense_decode_lds_pad(a.total_blocks * a.channels, a.channels, a.bits) : 0u;
+  const dim3 grid(p.grid), block(p.workgroup);
   if (a.channels == 1)
-    AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 1, false, QUAD>), grid, block, lds_pad, stream, a);
+    AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 1, false, QUAD>), grid, block, p.lds, stream, a);
   else if (a.channels == 2 && a.mid_side) {
     if constexpr (!QUAD && BITS != 3) {
-      if (a.stream_stores) {
-        AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 2, true, false, true>), grid, block, lds_pad, stream, a);
+      if (p.stream_stores) {
+        AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 2, true, false, true>), grid, block, p.lds, stream, a);
         return;
       }
     }
-    AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 2, true, QUAD>), grid, block, lds_pad, stream, a);
+    AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 2, true, QUAD>), grid, block, p.lds, stream, a);
   } else if (a.channels == 2) {
     if constexpr (!QUAD && BITS != 3) {
-      if (a.stream_stores) {
-        AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 2, false, false, true>), grid, block, lds_pad, stream, a);
+      if (p.stream_stores) {
+        AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 2, false, false, true>), grid, block, p.lds, stream, a);
         return;
       }
     }
-    AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 2, false, QUAD>), grid, block, lds_pad, stream, a);
+    AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 2, false, QUAD>), grid, block, p.lds, stream, a);
   }
   else if constexpr (!QUAD)
-    AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 0, false, false>), grid, block, lds_pad, stream, a);
-}
-
-/* Quad decode runs its two strands on different lanes (aad_decode_split.hip.h) unless
- * AAD_HIP_MAPPING=quad-fused asks for the one-lane-does-both kernel or the residual scratch would be
- * unreasonably large. */
-constexpr uint64_t kMaxResidualBytes = 1ull << 30;
-
-/* Decode mapping by batch size: see mapping_limits.  The context option forces one. */
-enum class DecodeMapping { Dense, QuadFused, QuadSplit };
-/* Dense batches at and beyond this many recurrences take the sector-tiled kernel where it applies (aad_decode_tiled.hip.h).
- * Measured against the per-lane kernel (with its own occupancy cap) on one-block streams, same box, tools/saturated_probe.py
- * (profiles/r03_tiled_decode_crossover.txt): mono 4-bit wins from 65 536 blocks on (one wave per SIMD: 0.156 vs 0.198 ms;
- * 0.43 vs 0.48 ms at 196 608; 1.10 vs 1.29 ms at 524 288), stereo 4-bit from ~393 216 recurrences (0.42 vs 0.45 ms; equal at
- * 262 144, the per-lane kernel ahead below); mono 2-bit like mono 4-bit (2.15 vs 2.52 ms at 524 288 blocks); mono 3-bit (where
- * the batch's layout admits it: aad_decode_tiled.hip.h "3-bit rows") 1.41-1.43 vs 1.70 ms at 524 288 blocks.  On STEREO 2-bit
- * streams the tiled kernel moves 1.02x the algorithmic bytes instead of 1.35x but takes 3-7 % longer (1.04-1.08 vs 1.01-1.02 ms),
- * on stereo 3-bit streams both take 0.73 ms: "auto" keeps the per-lane kernel there, AAD_HIP_LANE_MAPPING_DENSE_TILED selects the
- * tiled one at any size. */
-uint64_t tiled_decode_min(uint32_t bits, uint32_t channels)
-{
-  /* round 4 (tools/size_sweep.py --mapping dense | dense-tiled): at exactly 65 536 mono lanes the per-lane kernel still runs one
-   * wave per SIMD in one-wave workgroups and is 7 % ahead (0.154 vs 0.165 ms); from the next lane on it needs a second wave per
-   * SIMD and the tiled kernel is level (80 000) to 18 % ahead (524 288) */
-  if (channels == 1) return 65537u;
-  return bits == 4 ? 393216u : ~0ull;
-}
-
-DecodeMapping pick_decode_mapping(const AADHipContext *ctx, uint64_t recurrences, uint32_t channels, uint32_t bits)
-{
-  if (channels > 2) return DecodeMapping::Dense;
-  switch (ctx->lane_mapping) {
-    case AAD_HIP_LANE_MAPPING_DENSE:
-    case AAD_HIP_LANE_MAPPING_DENSE_TILED: return DecodeMapping::Dense;
-    case AAD_HIP_LANE_MAPPING_QUAD_FUSED: return DecodeMapping::QuadFused;
-    case AAD_HIP_LANE_MAPPING_QUAD: return DecodeMapping::QuadSplit;
-    default: break;
-  }
-  const MappingLimits m = mapping_limits(bits, channels);
-  if (recurrences <= m.decode_split) return DecodeMapping::QuadSplit;
-  if (recurrences <= m.decode_fused) return DecodeMapping::QuadFused;
-  return DecodeMapping::Dense;
-}
-
-bool want_split_decode(const AADHipContext *ctx, const aad::DecodeArgs &a, uint64_t *bytes, uint32_t *stride)
-{
-  const uint64_t recurrences = a.total_blocks * a.channels;
-  if (pick_decode_mapping(ctx, recurrences, a.channels, a.bits) != DecodeMapping::QuadSplit) return false;
-  /* 64-bit: samples_per_block comes straight from a file header and may be anything */
-  const uint64_t coded = a.samples_per_block > 4 ? (uint64_t)a.samples_per_block - 4 : 0;
-  const uint64_t row = (coded + 15u) / 16u * 16u + 16u;
-  if (row > kMaxResidualBytes / sizeof(int32_t)) return false;
-  *stride = (uint32_t)row;
-  *bytes = recurrences * row * sizeof(int32_t);
-  return *bytes <= kMaxResidualBytes; /* else the fused quad kernel */
+    AAD_LAUNCH((aad::decode_blocks_kernel<BITS, 0, false, false>), grid, block, p.lds, stream, a);
 }
 
 template <int BITS>
-void launch_decode(const AADHipContext *ctx, const aad::DecodeArgs &a, int32_t *residual, uint32_t residual_stride)
+void launch_decode(const aad::DecodeArgs &a, const aad::DecodeLaunch &p, int32_t *residual, hipStream_t stream)
 {
-  const hipStream_t stream = ctx->stream;
-  if (residual != nullptr && aad::launch_decode_split(a, residual, residual_stride, stream)) return;
-  const uint64_t lanes = a.total_blocks * a.channels;
-  /* a split decode that could not have its scratch buffer: the fused kernel when the quad mapping is
-   * forced, the dense one otherwise */
-  const DecodeMapping pick = pick_decode_mapping(ctx, lanes, a.channels, BITS);
-  /* dense: the sector-tiled kernel for chip-filling batches (or when the option asks for it), where it applies */
-  if (pick == DecodeMapping::Dense && ctx->lane_mapping != AAD_HIP_LANE_MAPPING_DENSE &&
-      (ctx->lane_mapping == AAD_HIP_LANE_MAPPING_DENSE_TILED || lanes >= tiled_decode_min(BITS, a.channels)) && aad::launch_decode_tiled(a, stream))
-    return;
-  const bool quad = pick == DecodeMapping::QuadFused || (pick == DecodeMapping::QuadSplit && ctx->lane_mapping == AAD_HIP_LANE_MAPPING_QUAD);
-  const uint64_t threads = quad ? lanes * 4 : lanes;
-  const unsigned wg = pick_workgroup(threads);
-  const dim3 grid((unsigned)((threads + wg - 1) / wg)), block(wg);
-  if (quad) launch_decode_mapped<BITS, true>(a, grid, block, stream);
-  else launch_decode_mapped<BITS, false>(a, grid, block, stream);
+  switch (p.kernel) {
+    case aad::DecodeKernel::SplitLds:
+    case aad::DecodeKernel::SplitScratch: aad::launch_decode_split(a, p, residual, stream); break;
+    case aad::DecodeKernel::Tiled: aad::launch_decode_tiled(a, p, stream); break;
+    case aad::DecodeKernel::QuadFused: launch_decode_mapped<BITS, true>(a, p, stream); break;
+    case aad::DecodeKernel::Dense: launch_decode_mapped<BITS, false>(a, p, stream); break;
+  }
 }
-
 } /* namespace */
 
 /* ---- plan construction without any device work ------------------------------------------------
@@ -666,37 +413,40 @@ AADApiResult finish_signal(AADHipContext *ctx, const aad::LaunchSignal &signal, 
   return rc;
 }
 
+/* grow-only device scratch of a context (dual trial search, split decoder); the old buffer may still be in use by queued work */
+template <typename T>
+bool scratch_reserve(AADHipContext *ctx, T **buf, uint64_t *capacity, uint64_t bytes, const char *what)
+{
+  if (*capacity >= bytes) return true;
+  if (*buf) {
+    if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) return false;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *capacity = 0;
+  }
+  if (!hip_ok(ctx, hipMalloc((void **)buf, bytes), what)) return false;
+  *capacity = bytes;
+  return true;
+}
+
 AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args)
 {
   if (args.num_streams == 0) return AAD_APIRESULT_OK;
+  if (args.bits < 2 || args.bits > 4) return AAD_APIRESULT_INVALID_FORMAT;
   aad::EncodeArgs a = args;
-  a.trial_scratch = nullptr;
-  a.trial_slot_bytes = 0;
   if ((reinterpret_cast<uintptr_t>(a.data) & 63u) != 0) a.ring_ok = 0;
-  if (a.trials != 0 && a.channels <= 2 && ctx->trial_lanes != AAD_HIP_TRIAL_LANES_SINGLE &&
-      (uint64_t)a.num_streams * a.channels <= kDualMaxRecurrences &&
-      pick_quad(ctx, (uint64_t)a.num_streams * a.channels, a.channels, a.bits)) {
-    const uint64_t want = (uint64_t)a.num_streams * 3u * trial_slot_bytes(a);
-    if (want <= kMaxTrialScratchBytes) { /* else: the search and the encode one after the other on the same lanes */
-      if (ctx->trial_capacity < want) {
-        if (ctx->d_trial) {
-          if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) return AAD_APIRESULT_NG;
-          (void)hipFree(ctx->d_trial);
-          ctx->d_trial = nullptr;
-          ctx->trial_capacity = 0;
-        }
-        if (!hip_ok(ctx, hipMalloc((void **)&ctx->d_trial, want), "hipMalloc trial scratch")) return AAD_APIRESULT_NG;
-        ctx->trial_capacity = want;
-      }
-      a.trial_scratch = ctx->d_trial;
-      a.trial_slot_bytes = trial_slot_bytes(a);
-    }
+  const aad::EncodeLaunch p =
+      aad::plan_encode(ctx->device_info, ctx->knobs, aad::EncodeBatch{a.bits, a.channels, a.num_streams, a.trials, a.block_size, a.ring_ok != 0});
+  a.trial_scratch = nullptr;
+  a.trial_slot_bytes = p.trial_slot_bytes;
+  if (p.trial_scratch_bytes != 0) {
+    if (!scratch_reserve(ctx, &ctx->d_trial, &ctx->trial_capacity, p.trial_scratch_bytes, "hipMalloc trial scratch")) return AAD_APIRESULT_NG;
+    a.trial_scratch = ctx->d_trial;
   }
   switch (a.bits) {
-    case 4: launch_encode<4>(ctx, a); break;
-    case 3: launch_encode<3>(ctx, a); break;
-    case 2: launch_encode<2>(ctx, a); break;
-    default: return AAD_APIRESULT_INVALID_FORMAT;
+    case 4: launch_encode<4>(a, p, ctx->stream); break;
+    case 3: launch_encode<3>(a, p, ctx->stream); break;
+    default: launch_encode<2>(a, p, ctx->stream); break;
   }
   return hip_ok(ctx, hipGetLastError(), "encode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
 }
@@ -704,33 +454,20 @@ AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args)
 AADApiResult run_decode(AADHipContext *ctx, const aad::DecodeArgs &a)
 {
   if (a.total_blocks == 0) return AAD_APIRESULT_OK;
-  uint64_t residual_bytes = 0;
-  uint32_t residual_stride = 0;
+  if (a.bits < 2 || a.bits > 4) return AAD_APIRESULT_INVALID_FORMAT;
+  const aad::DecodeLaunch p = aad::plan_decode(
+      ctx->device_info, ctx->knobs,
+      aad::DecodeBatch{a.total_blocks, a.num_streams, a.channels, a.bits, a.samples_per_block, a.block_size, a.code_phase_uniform,
+                       a.pcm_aligned16 != 0, (reinterpret_cast<uintptr_t>(a.pcm) & 15u) == 0, a.stream_stores != 0});
   int32_t *residual = nullptr;
-  const bool split = want_split_decode(ctx, a, &residual_bytes, &residual_stride);
-  const bool split_in_lds = split && aad::decode_split_fits_lds(a);
-  if (split && !split_in_lds) {
-    if (ctx->residual_capacity < residual_bytes) { /* first such decode of this size on the context */
-      if (ctx->d_residual) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->d_residual);
-        ctx->d_residual = nullptr;
-        ctx->residual_capacity = 0;
-      }
-      if (!hip_ok(ctx, hipMalloc((void **)&ctx->d_residual, residual_bytes), "hipMalloc residual scratch")) return AAD_APIRESULT_NG;
-      ctx->residual_capacity = residual_bytes;
-    }
+  if (p.residual_bytes != 0) {
+    if (!scratch_reserve(ctx, &ctx->d_residual, &ctx->residual_capacity, p.residual_bytes, "hipMalloc residual scratch")) return AAD_APIRESULT_NG;
     residual = ctx->d_residual;
   }
-  if (split_in_lds) {
-    if (!aad::launch_decode_split(a, nullptr, 0, ctx->stream)) return AAD_APIRESULT_INVALID_FORMAT;
-    return hip_ok(ctx, hipGetLastError(), "decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
-  }
   switch (a.bits) {
-    case 4: launch_decode<4>(ctx, a, residual, residual_stride); break;
-    case 3: launch_decode<3>(ctx, a, residual, residual_stride); break;
-    case 2: launch_decode<2>(ctx, a, residual, residual_stride); break;
-    default: return AAD_APIRESULT_INVALID_FORMAT;
+    case 4: launch_decode<4>(a, p, residual, ctx->stream); break;
+    case 3: launch_decode<3>(a, p, residual, ctx->stream); break;
+    default: launch_decode<2>(a, p, residual, ctx->stream); break;
   }
   return hip_ok(ctx, hipGetLastError(), "decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
 }
@@ -803,10 +540,13 @@ AADApiResult AADHip_ContextCreate(int32_t device_index, void *hip_stream, struct
    * use), never on a launch path */
   AADHipInternal_ContextOptionsFromEnvironment(ctx);
   DeviceGuard guard(ctx);
-  if (!guard.ok) {
+  int cus = 0, lds_per_cu = 0;
+  if (!guard.ok || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_index) != hipSuccess ||
+      hipDeviceGetAttribute(&lds_per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device_index) != hipSuccess) {
     delete ctx;
     return AAD_APIRESULT_NG;
   }
+  ctx->device_info = aad::Device{(uint32_t)cus, (uint32_t)lds_per_cu};
   if (hip_stream == nullptr) {
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
       delete ctx;
@@ -868,8 +608,15 @@ void AADHipInternal_ContextOptionsFromEnvironment(struct AADHipContext *ctx)
   static const char *const kMappings[] = {"auto", "dense", "quad", "quad-fused", "dense-tiled"};
   static const char *const kTrialLanes[] = {"dual", "single"};
   ctx->signal_refused = AADHip_SignalNextRunSupported() == 0;
-  ctx->lane_mapping = option_from_env("AAD_HIP_MAPPING", kMappings, 5);
-  ctx->trial_lanes = option_from_env("AAD_HIP_TRIAL_LANES", kTrialLanes, 2);
+  ctx->knobs.lane_mapping = option_from_env("AAD_HIP_MAPPING", kMappings, 5);
+  ctx->knobs.trial_lanes = option_from_env("AAD_HIP_TRIAL_LANES", kTrialLanes, 2);
+  /* measurement aids */
+  const char *ring = getenv("AAD_HIP_ENCODE_RING"), *enc_pad = getenv("AAD_HIP_ENCODE_LDS_PAD");
+  const char *dec_pad = getenv("AAD_HIP_DECODE_LDS_PAD"), *nt_min = getenv("AAD_HIP_DECODE_NT_MIN");
+  ctx->knobs.encode_ring = ring != nullptr && ring[0] == '0' ? 0 : (ring != nullptr && ring[0] == '2' ? 2 : 1);
+  ctx->knobs.encode_lds_pad = enc_pad ? atoi(enc_pad) : -1;
+  ctx->knobs.decode_lds_pad = dec_pad ? atoi(dec_pad) : -1;
+  ctx->knobs.decode_nt_min = nt_min ? (uint64_t)atoll(nt_min) : 0ull;
   static const char *const kCompareOrders[] = {"auto", "sequential"};
   ctx->compare_sequential = option_from_env("AAD_HIP_COMPARE_ORDER", kCompareOrders, 2);
   const char *threads = getenv("AAD_HIP_STAGING_THREADS");
@@ -913,11 +660,11 @@ AADApiResult AADHip_ContextSetOption(struct AADHipContext *ctx, int32_t option, 
   switch (option) {
     case AAD_HIP_OPTION_LANE_MAPPING:
       if (value < AAD_HIP_LANE_MAPPING_AUTO || value > AAD_HIP_LANE_MAPPING_DENSE_TILED) return AAD_APIRESULT_INVALID_ARGUMENT;
-      ctx->lane_mapping = value;
+      ctx->knobs.lane_mapping = value;
       return AAD_APIRESULT_OK;
     case AAD_HIP_OPTION_TRIAL_LANES:
       if (value != AAD_HIP_TRIAL_LANES_DUAL && value != AAD_HIP_TRIAL_LANES_SINGLE) return AAD_APIRESULT_INVALID_ARGUMENT;
-      ctx->trial_lanes = value;
+      ctx->knobs.trial_lanes = value;
       return AAD_APIRESULT_OK;
     case AAD_HIP_OPTION_COMPARE_ORDER:
       if (value != 0 && value != 1) return AAD_APIRESULT_INVALID_ARGUMENT;

@@ -14,11 +14,20 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include "aad_launch_policy.h"
+
 namespace aad {
 struct LaunchSignal {
   hipEvent_t start, stop; /* either may be null */
 };
 extern thread_local LaunchSignal tl_launch_signal; /* defined in aad_hip_engine.hip; both null when no run asked for events */
+
+/* The decoders with translation units of their own, launched as planned (aad_launch_policy.h).  aad_decode_split.hip is compiled
+ * with its own instruction-scheduling strategy (see the Makefile); the residual rows of DecodeKernel::SplitScratch go through
+ * `residual` (p.residual_bytes of device memory).  aad_decode_tiled.hip: DecodeKernel::Tiled. */
+struct DecodeArgs;
+void launch_decode_split(const DecodeArgs &args, const DecodeLaunch &p, int32_t *residual, hipStream_t stream);
+void launch_decode_tiled(const DecodeArgs &args, const DecodeLaunch &p, hipStream_t stream);
 }
 
 #define AAD_LAUNCH(kernel, grid, block, lds, stream, ...)                                                           \

@@ -610,7 +610,7 @@ def test_extreme_block_sizes(engine, mapping):
                                              (4096, 2, 1), (8192, 2, 1), (8193, 4, 1), (12289, 4, 1), (16384, 3, 1), (17000, 3, 1)])
 def test_decode_mapping_ranges_auto(engine, streams, bits, ch):
     """The host's own choice of mapping on both sides of every threshold of its per-geometry table
-    (mapping option "auto"; aad_hip_engine.hip mapping_limits: encode quad up to 16384 recurrences,
+    (mapping option "auto"; aad_launch_policy.h plan_encode / plan_decode: encode quad up to 16384 recurrences,
     decode split up to 8192 recurrences - 4096 of them with the residual rows in LDS -, dense beyond): split
     decoder with the residuals in LDS / in a device scratch buffer, dense kernel -
     one-block streams, sampled against the oracle, and the whole batch through the round trip

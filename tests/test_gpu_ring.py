@@ -18,10 +18,13 @@ from aad_amd.synth import synth_pcm
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def engine():
+@pytest.fixture
+def engine(monkeypatch):
+    """AAD_HIP_ENCODE_RING=2: every geometry that can (the host's policy leaves stereo 2-bit on its per-lane stores); a context reads
+    it when it is created"""
     import torch  # noqa: F401
     from aad_amd.engine import Engine
+    monkeypatch.setenv("AAD_HIP_ENCODE_RING", "2")
     e = Engine(0)
     yield e
     e.close()
@@ -30,9 +33,8 @@ def engine():
 @pytest.mark.parametrize("bits", [4, 3, 2])
 @pytest.mark.parametrize("channels", [1, 2])
 @pytest.mark.parametrize("uniform", [True, False])
-def test_ring_encoder_matches_oracle(engine, bits, channels, uniform, monkeypatch):
+def test_ring_encoder_matches_oracle(engine, bits, channels, uniform):
     import torch
-    monkeypatch.setenv("AAD_HIP_ENCODE_RING", "2")  # every geometry that can (the host's policy leaves stereo 2-bit on its per-lane stores)
     rng = np.random.default_rng(8800 + 10 * bits + channels + (100 if uniform else 0) + 1000 * int(os.environ.get("AAD_TEST_SEED_OFFSET", "0")))
     engine.set_mapping("dense")
     try:
@@ -89,11 +91,10 @@ def test_ring_encoder_matches_oracle(engine, bits, channels, uniform, monkeypatc
 
 
 @pytest.mark.parametrize("bits,channels", [(4, 2), (4, 1), (3, 2), (3, 1), (2, 2), (2, 1)])
-def test_ring_encoder_chip_filling_batch(engine, bits, channels, monkeypatch):
+def test_ring_encoder_chip_filling_batch(engine, bits, channels):
     """a batch big enough for "auto" to take the dense encoders (workgroups of four waves: four waves of rows share the ring
     area), two blocks per stream - against the oracle on a sample of streams, and every repetition of the tile against the first"""
     import torch
-    monkeypatch.setenv("AAD_HIP_ENCODE_RING", "2")
     spb = {4: 1984, 3: 2632, 2: 3960}[bits] // channels
     streams = 70000 // channels
     param = make_parameter(channels, bits, 1024, 48000, False, 0)

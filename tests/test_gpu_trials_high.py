@@ -88,8 +88,8 @@ def test_batches_with_high_counts_and_tiles(engine, trials, trial_lanes):
     (33000, 2, 3, 1, False),  # 66 000 lanes: beyond one wave per SIMD
 ])
 def test_trial_search_launch_ranges(engine, streams, ch, bits, trials, ms):
-    """Both sides of every launch-geometry switch of the trial search (aad_hip_engine.hip: pick_dual / kDualMaxRecurrences, the dual
-    kernel's workgroup size, mapping_limits.encode_quad, dense_encode_workgroup) under the default options: device-resident
+    """Both sides of every launch-geometry switch of the trial search (aad_launch_policy.h plan_encode: kDualMaxRecurrences, the dual
+    kernel's workgroup size, encode_quad, dense_encode_workgroup) under the default options: device-resident
     one-block batches, sampled streams against the oracle, and every copy of a base stream identical."""
     import torch
     engine.set_mapping("auto", trial_lanes="dual")
