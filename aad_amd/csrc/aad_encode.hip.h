@@ -123,7 +123,7 @@ __device__ __forceinline__ void encode_chunk16(S &L, const int32_t *x, const cha
     const uint32_t mag = min((uint32_t)__builtin_fmaf(__builtin_fabsf(f), __uint_as_float(e.z), __uint_as_float(e.y)), Pack<BITS>::kMagMax);
     const int32_t delta = *reinterpret_cast<const int16_t *>(lds + kLdsDeltaScaledOff + (mag << 1)); /* kIdxScale * delta */
     __builtin_amdgcn_sched_barrier(0);
-    /* B: (step * (2 mag + 1)) >> (BITS - 1) as ONE high multiply on the 24-bit multiplier, as in the quad body */
+    /* B: (step * (2 mag + 1)) >> (BITS - 1) as ONE high multiply on the 24-bit multiplier */
     const uint32_t m21s = (mag << (25 - BITS)) | (1u << (24 - BITS));
     uint32_t code = 0;
     if (EMIT) { /* pinned HERE, several instructions in front of its reader: no s_nop behind the pin */
@@ -244,14 +244,19 @@ __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C,
     idxj = min(max(idxj + index_delta_arith_scaled<BITS>(mag), kIdxScale * kIdxMin), kIdxScale * kIdxMax);
     e = *reinterpret_cast<const u32x3 *>(lds + kLdsWideOff + wide4_addr(idxj, copy));
     __builtin_amdgcn_sched_barrier(0);
-    /* B: q = (step * (2 mag + 1)) >> (BITS-1) as ONE high multiply on the 24-bit multiplier
-     * (v_mul_hi_u32_u24 issues like an add, the 32-bit v_mul_hi_u32 costs a lone wave ~1.5 cycles more):
-     * (step << 9) * ((2 mag + 1) << (24 - BITS)) = step * (2 mag + 1) * 2^(33 - BITS), upper 32 bits of
-     * the 48-bit product.  step < 2^15 and 2 mag + 1 < 2^BITS, so both factors fit 24 bits. */
-    const uint32_t m21s = (mag << (25 - BITS)) | (1u << (24 - BITS));
-    const int32_t q = (int32_t)(uint32_t)(((uint64_t)(step9_j & 0xFFFFFFu) * (uint64_t)(m21s & 0xFFFFFFu)) >> 32); /* v_mul_hi_u32_u24 */
-    const int32_t qd = (q ^ m) - m;
-    const int32_t y = clip16(qd + p);
+    /* B: dequantise, sign and reconstruct in ONE v_mad_i64_i32, whose upper dword is qd + p:
+     *   (step << 9) * g + {lo: m, hi: p},   g = ((mag ^ m) << (25 - BITS)) | 2^(24 - BITS) = +-(2 mag + 1) << (24 - BITS)
+     * (step << 9) * ((2 mag + 1) << (24 - BITS)) = X = step * (2 mag + 1) * 2^(33 - BITS), whose upper dword is
+     * q = (step * (2 mag + 1)) >> (BITS - 1) and whose lower dword is a multiple of 2^(33 - BITS) below 2^32.
+     * A negative difference multiplies by -(2 mag + 1) << (24 - BITS) instead and adds 2^32 - 1 to the lower
+     * dword, which rounds -X up to -q exactly (step << 9 < 2^24 < 2^(33 - BITS)).  p rides in the addend's
+     * upper dword, so the sum comes out reconstructed; qd itself (the LMS, the RMSE) is one subtract.
+     * tests/encoder_body_equiv.c proves it for every step, magnitude, sign and bit width. */
+    const uint32_t g = ((mag ^ (uint32_t)m) << (25 - BITS)) | (1u << (24 - BITS));
+    const uint64_t mp = (uint64_t)(uint32_t)m | ((uint64_t)(uint32_t)p << 32);
+    const int32_t yq = (int32_t)((uint64_t)((int64_t)(int32_t)step9_j * (int64_t)(int32_t)g + (int64_t)mp) >> 32); /* v_mad_i64_i32 */
+    const int32_t qd = yq - p;
+    const int32_t y = clip16(yq);
     lms_and_shift<kEncTM ? kShiftBankMask : kShiftBitSelect>(L, qd, y);
     /* prediction of the next sample, with the two instructions that pack this sample's code
      * placed in the wait states its DPP adds need (see decode_chunk16_quad) */
