@@ -46,6 +46,10 @@ class AADHipStreamDesc(C.Structure):  # include/aad_hip.h
                 ("data_size", C.c_uint64), ("num_samples", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class AADHipSegmentation(C.Structure):  # include/aad_hip.h
+    _fields_ = [("segment_blocks", C.c_uint32), ("warmup_blocks", C.c_uint32)]
+
+
 class AADHipLaneState(C.Structure):  # include/aad_hip.h
     _fields_ = [("weight", C.c_int32 * 4), ("history", C.c_int32 * 4),
                 ("stepsize_index", C.c_int32), ("quantize_error", C.c_int32)]
@@ -76,7 +80,7 @@ HIP_SYMBOLS = [
     "AADHip_EncodePlanDestroy", "AADHip_EncodePlanRun", "AADHip_DecodePlanCreate", "AADHip_DecodePlanDestroy",
     "AADHip_DecodePlanRun", "AADHip_EncodeBatch", "AADHip_DecodeBatch",
     "AADHip_ReconstructPlanCreate", "AADHip_ReconstructPlanDestroy", "AADHip_ReconstructPlanRun",
-    "AADHip_ReconstructBatch",
+    "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -144,6 +148,9 @@ def _declare_hip(lib):
     lib.AADHip_CalculateEncodedSize.restype = C.c_uint64
     lib.AADHip_EncodePlanCreate.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, C.POINTER(vp)]
     lib.AADHip_EncodePlanCreate.restype = C.c_int
+    lib.AADHip_SegmentedEncodePlanCreate.argtypes = [vp, C.POINTER(AADEncodeParameter), C.POINTER(AADHipSegmentation), C.c_uint32, vp,
+                                                     C.POINTER(vp)]
+    lib.AADHip_SegmentedEncodePlanCreate.restype = C.c_int
     lib.AADHip_EncodePlanDestroy.argtypes = [vp]
     lib.AADHip_EncodePlanDestroy.restype = None
     lib.AADHip_EncodePlanRun.argtypes = [vp, vp, vp, vp]

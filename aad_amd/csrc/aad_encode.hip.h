@@ -8,6 +8,7 @@
 #define AAD_ENCODE_HIP_H
 
 #include "aad_device.hip.h"
+#include "aad_segments.h"
 
 namespace aad {
 
@@ -311,7 +312,10 @@ __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C,
 /* ================================================================================ encode == */
 
 struct EncodeArgs {
-  const StreamDesc *streams;
+  union {
+    const StreamDesc *streams;
+    const ChainDesc *chains; /* SEG: the chain table (aad_segments.h), num_streams = chains; the layout of the arguments stays put */
+  };
   const int16_t *pcm;
   uint8_t *data;
   const LaneStateRecord *state; /* carried state read at the start; may be null (fresh encoders) */
@@ -1630,13 +1634,29 @@ __device__ __forceinline__ void encode_block_dual(Lane &F, int32_t &last_qd, con
 /*
  * Stream-parallel encode (reference src/aad_encoder.c:814-891 with EncodeBlock :565-727 and the
  * optional trial search :470-562 inlined).  lane = (stream, channel).
+ *
+ * SEG (segmented plans, AADHip_SegmentedEncodePlanCreate): lane = (chain, channel), a chain being a fresh encoder over one
+ * segment of a stream with its warm-up in front (aad_segments.h).  The chain's frames are its whole input - frame 0 is its first
+ * warm-up frame, so the trial search has no look-back block at the chain's first block, as a fresh encoder over that slice has
+ * not - and its blocks land at 31 + (first_block + i) * block_size in the stream's image.  Warm-up blocks run the block procedure
+ * of an encode - search, the header's rounding of the weights, the recurrence - and store nothing: the recurrence runs as a
+ * measuring pass, which on a whole block (coded samples a whole number of pack units, aad_format.c) walks exactly the samples
+ * the encode pass walks.  Neighbouring segments of a stream share 64-byte sectors and run at the same time on different CUs,
+ * so no store of a chain may touch a byte outside its kept blocks (and the file header, chain 0 only).  That holds because
+ * every store of the block procedure lies inside its block: the dense stereo 4-bit burst stores and their defer3 carry (the
+ * last three bytes of a group wait for the next group of the SAME block, or for the block's end), the tail units, and the quad
+ * `writer` lane's and staged stores all address [block start, block start + bytes of the block).  Warm-up blocks are not
+ * "parked" in the first kept block's slot: that block may be the stream's short last one, and a whole warm-up block written
+ * there would run past the image.  The byte ring is never used (it stores whole sectors of an image written from its start:
+ * segmented plans set ring_ok = 0); the dual trial search has three scratch slots per chain; no state is read or written.
  */
-template <int BITS, int CHF, bool MS, bool QUAD, bool TRIALS, bool DUAL = false, bool RING = false>
+template <int BITS, int CHF, bool MS, bool QUAD, bool TRIALS, bool DUAL = false, bool RING = false, bool SEG = false>
 __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgs a)
 {
   static_assert(!QUAD || CHF != 0, "the quad mapping exists for the mono / stereo fast paths");
   static_assert(!DUAL || (QUAD && TRIALS), "the dual mapping is the trial search on the quad mapping");
   static_assert(!RING || kRingable<BITS, CHF, QUAD>, "the byte ring: dense mono / stereo encoders");
+  static_assert(!(SEG && RING), "segmented plans never take the byte ring");
   __shared__ __attribute__((aligned(16))) char lds[kLdsBytesEncoderStatic<BITS, CHF, QUAD, RING>]; /* dense and quad encoders share the wide table; dense: + code staging */
   extern __shared__ __attribute__((aligned(16))) char ring_lds[]; /* RING: the rows' byte rings, kLdsRingBytesPerWave per wave (then the occupancy pad, unused) */
   AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
@@ -1657,7 +1677,25 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgs a)
   const bool writer = tap == 0 && role == 0;         /* quad: all four lanes hold the codes, one stores them */
   if (lane >= (uint64_t)a.num_streams * ch) return; /* whole quads / stereo pairs / role groups leave together */
   const uint32_t s = (uint32_t)(lane / ch), c = (uint32_t)(lane % ch);
-  const StreamDesc sd = a.uni.enabled ? uniform_stream(a.uni, s) : a.streams[s];
+  StreamDesc sd;
+  uint64_t block0 = 0;      /* SEG: the chain's first block in its stream */
+  uint64_t warm_end = 0;    /* SEG: frames of warm-up at the chain's head */
+  bool head = true;         /* the file header is written here */
+  uint32_t head_samples = 0; /* SEG: the stream's num_samples */
+  if constexpr (SEG) {
+    const ChainDesc cd = a.chains[s];
+    sd.pcm_offset = cd.pcm_offset;
+    sd.data_offset = cd.data_offset;
+    sd.data_size = 0;
+    sd.num_samples = cd.num_frames;
+    sd.reserved = 0;
+    block0 = cd.first_block;
+    warm_end = (uint64_t)cd.warmup_blocks * a.samples_per_block;
+    head = cd.writes_header != 0;
+    head_samples = cd.header_samples;
+  } else {
+    sd = a.uni.enabled ? uniform_stream(a.uni, s) : a.streams[s];
+  }
   const SampleSource<MS> src = {a.pcm + sd.pcm_offset, ch, c, sd.num_samples};
   uint8_t *out = a.data + sd.data_offset;
   const uint32_t total = sd.num_samples, spb = a.samples_per_block;
@@ -1667,7 +1705,7 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgs a)
   using S = std::conditional_t<QUAD, QuadLane, Lane>;
   Lane F = {0, 0, 0, 0, 0, 0, 0, 0, kIdxBias};
   int32_t last_qd = 0;
-  if (a.state) {
+  if (!SEG && a.state) {
     const LaneStateRecord r = a.state[lane];
     F = {r.weight[0], r.weight[1], r.weight[2], r.weight[3],
          r.history[0], r.history[1], r.history[2], r.history[3],
@@ -1692,8 +1730,8 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgs a)
     ring.advance(kFileHeaderBytes);
     ring.carry_from_ring();
   }
-  if (!RING && c == 0 && writer) { /* file header - reference src/aad_encoder.c:190-214 */
-    const uint32_t encoded = total - a.lead_frames;
+  if (!RING && c == 0 && writer && head) { /* file header - reference src/aad_encoder.c:190-214 */
+    const uint32_t encoded = SEG ? head_samples : total - a.lead_frames; /* SEG: the stream's count, not the chain's */
     /* 31 bytes as seven dwords and three bytes; the sample count is big-endian in bytes 14..17 */
     const uint32_t *t = reinterpret_cast<const uint32_t *>(a.header_template);
 #pragma unroll
@@ -1707,11 +1745,26 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgs a)
     out[30] = (uint8_t)(t[7] >> 16);
   }
 
-  uint64_t block_off = kFileHeaderBytes;
+  uint64_t block_off = kFileHeaderBytes + block0 * a.block_size;
   for (uint64_t first = a.lead_frames; first < total; first += spb, block_off += a.block_size) {
     const uint32_t n = total - first < spb ? (uint32_t)(total - first) : spb;
     S L;
     AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
+    if constexpr (SEG) {
+      if (first < warm_end) { /* warm-up block (always a whole one): the encode's state, nothing stored */
+        if constexpr (TRIALS) { /* the dual mapping's roles both run it: the same state on every lane of the chain */
+          if constexpr (QUAD) L = to_quad(F, tap); else L = F;
+          search_best_lane<BITS, CHF, MS, QUAD>(L, src, first, n, spb, a.trials, ch, c, tap, lds);
+          if constexpr (QUAD) F = from_quad<kEncTM>(L); else F = L;
+        }
+        seed_history(F, src, first, n);
+        (void)write_block_header(F, nullptr, false); /* the header's rounding of the weights, no store */
+        if constexpr (QUAD) L = to_quad(F, tap); else L = F;
+        (void)run_block<BITS, CHF, MS, QUAD, kPassRmse>(L, src, first, n, ch, c, false, nullptr, lds, last_qd);
+        if constexpr (QUAD) F = from_quad<kEncTM>(L); else F = L;
+        continue;
+      }
+    }
     if constexpr (DUAL) { /* search and encode side by side, see encode_block_dual */
       encode_block_dual<BITS, CHF, MS>(F, last_qd, src, first, n, spb, a.trials, c, tap, role, out + block_off,
                                        a.trial_scratch + (uint64_t)s * 3u * a.trial_slot_bytes, a.trial_slot_bytes, lds);
@@ -1752,7 +1805,7 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgs a)
   }
   if constexpr (RING) ring.finish(); /* the stream's last, incomplete sector */
 
-  if (a.state_out && writer) {
+  if (!SEG && a.state_out && writer) {
     LaneStateRecord r;
     r.weight[0] = F.w0; r.weight[1] = F.w1; r.weight[2] = F.w2; r.weight[3] = F.w3;
     r.history[0] = F.h0; r.history[1] = F.h1; r.history[2] = F.h2; r.history[3] = F.h3;

@@ -104,6 +104,8 @@ struct AADHipEncodePlan {
   AADHipContext *ctx;
   aad::EncodeArgs args;
   aad::StreamDesc *d_streams;
+  aad::ChainDesc *d_chains; /* segmented plans: the chain table (args.chains), d_streams stays null */
+  bool segmented;
 };
 
 struct AADHipDecodePlan {
@@ -201,34 +203,34 @@ bool upload(AADHipContext *ctx, T **dst, const T *src, size_t count)
 
 /* ---- dispatch: from a plan (aad_launch_policy.h) to a template instantiation ---------------------------------------------- */
 /* encode_streams_kernel by channels and M/S; RING: the dense encoders whose output goes through the rows' byte rings
- * (aad_encode.hip.h ByteRing), mono / stereo only */
-template <int BITS, bool QUAD, bool TRIALS, bool DUAL, bool RING = false>
+ * (aad_encode.hip.h ByteRing), mono / stereo only; SEG: the chains of a segmented plan */
+template <int BITS, bool QUAD, bool TRIALS, bool DUAL, bool RING = false, bool SEG = false>
 void launch_encode_mapped(const aad::EncodeArgs &a, const aad::EncodeLaunch &p, hipStream_t stream)
 {
   const dim3 grid(p.grid), block(p.workgroup);
   if (a.channels == 1)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 1, false, QUAD, TRIALS, DUAL, RING>), grid, block, p.lds, stream, a);
+    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 1, false, QUAD, TRIALS, DUAL, RING, SEG>), grid, block, p.lds, stream, a);
   else if (a.channels == 2 && a.mid_side)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, true, QUAD, TRIALS, DUAL, RING>), grid, block, p.lds, stream, a);
+    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, true, QUAD, TRIALS, DUAL, RING, SEG>), grid, block, p.lds, stream, a);
   else if (a.channels == 2)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, false, QUAD, TRIALS, DUAL, RING>), grid, block, p.lds, stream, a);
+    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, false, QUAD, TRIALS, DUAL, RING, SEG>), grid, block, p.lds, stream, a);
   else if constexpr (!QUAD && !RING)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 0, false, false, TRIALS, false>), grid, block, p.lds, stream, a);
+    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 0, false, false, TRIALS, false, false, SEG>), grid, block, p.lds, stream, a);
 }
 
-template <int BITS>
+template <int BITS, bool SEG>
 void launch_encode(const aad::EncodeArgs &a, const aad::EncodeLaunch &p, hipStream_t stream)
 {
   if (p.trials) {
-    if (p.kernel == aad::EncodeKernel::QuadDual) launch_encode_mapped<BITS, true, true, true>(a, p, stream);
-    else if (p.kernel == aad::EncodeKernel::Quad) launch_encode_mapped<BITS, true, true, false>(a, p, stream);
-    else launch_encode_mapped<BITS, false, true, false>(a, p, stream);
+    if (p.kernel == aad::EncodeKernel::QuadDual) launch_encode_mapped<BITS, true, true, true, false, SEG>(a, p, stream);
+    else if (p.kernel == aad::EncodeKernel::Quad) launch_encode_mapped<BITS, true, true, false, false, SEG>(a, p, stream);
+    else launch_encode_mapped<BITS, false, true, false, false, SEG>(a, p, stream);
   } else if (p.kernel == aad::EncodeKernel::Quad) {
-    launch_encode_mapped<BITS, true, false, false>(a, p, stream);
+    launch_encode_mapped<BITS, true, false, false, false, SEG>(a, p, stream);
   } else if (p.kernel == aad::EncodeKernel::DenseRing) {
-    launch_encode_mapped<BITS, false, false, false, true>(a, p, stream);
+    if constexpr (!SEG) launch_encode_mapped<BITS, false, false, false, true>(a, p, stream); /* SEG: ring_ok = 0, never planned */
   } else {
-    launch_encode_mapped<BITS, false, false, false>(a, p, stream);
+    launch_encode_mapped<BITS, false, false, false, false, SEG>(a, p, stream);
   }
 }
 
@@ -429,7 +431,8 @@ bool scratch_reserve(AADHipContext *ctx, T **buf, uint64_t *capacity, uint64_t b
   return true;
 }
 
-AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args)
+/* segmented: args.chains holds a chain table and num_streams counts chains (AADHip_SegmentedEncodePlanCreate) */
+AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args, bool segmented = false)
 {
   if (args.num_streams == 0) return AAD_APIRESULT_OK;
   if (args.bits < 2 || args.bits > 4) return AAD_APIRESULT_INVALID_FORMAT;
@@ -443,10 +446,18 @@ AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args)
     if (!scratch_reserve(ctx, &ctx->d_trial, &ctx->trial_capacity, p.trial_scratch_bytes, "hipMalloc trial scratch")) return AAD_APIRESULT_NG;
     a.trial_scratch = ctx->d_trial;
   }
-  switch (a.bits) {
-    case 4: launch_encode<4>(a, p, ctx->stream); break;
-    case 3: launch_encode<3>(a, p, ctx->stream); break;
-    default: launch_encode<2>(a, p, ctx->stream); break;
+  if (segmented) {
+    switch (a.bits) {
+      case 4: launch_encode<4, true>(a, p, ctx->stream); break;
+      case 3: launch_encode<3, true>(a, p, ctx->stream); break;
+      default: launch_encode<2, true>(a, p, ctx->stream); break;
+    }
+  } else {
+    switch (a.bits) {
+      case 4: launch_encode<4, false>(a, p, ctx->stream); break;
+      case 3: launch_encode<3, false>(a, p, ctx->stream); break;
+      default: launch_encode<2, false>(a, p, ctx->stream); break;
+    }
   }
   return hip_ok(ctx, hipGetLastError(), "encode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
 }
@@ -708,6 +719,8 @@ AADApiResult AADHip_EncodePlanCreate(struct AADHipContext *ctx, const struct AAD
   if (p == nullptr) return AAD_APIRESULT_NG;
   p->ctx = ctx;
   p->d_streams = nullptr;
+  p->d_chains = nullptr;
+  p->segmented = false;
   DeviceGuard guard(ctx);
   if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams)) {
     if (p->d_streams) (void)hipFree(p->d_streams);
@@ -727,8 +740,47 @@ void AADHip_EncodePlanDestroy(struct AADHipEncodePlan *plan)
   if (guard.ok) {
     (void)hipStreamSynchronize(plan->ctx->stream);
     (void)hipFree(plan->d_streams);
+    (void)hipFree(plan->d_chains);
   }
   delete plan;
+}
+
+AADApiResult AADHip_SegmentedEncodePlanCreate(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                              const struct AADHipSegmentation *segmentation, uint32_t num_streams,
+                                              const struct AADHipStreamDesc *streams, struct AADHipEncodePlan **plan)
+{
+  if (ctx == nullptr || parameter == nullptr || segmentation == nullptr || plan == nullptr || (num_streams != 0 && streams == nullptr))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *plan = nullptr;
+  if (segmentation->segment_blocks == 0) return AAD_APIRESULT_INVALID_ARGUMENT;
+  aad::EncodeArgs args;
+  const AADApiResult rc = encode_plan_init(parameter, num_streams, streams, &args);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  std::vector<aad::ChainDesc> chains;
+  if (!aad::build_segment_chains(streams, num_streams, args.channels, args.samples_per_block, args.block_size,
+                                 segmentation->segment_blocks, segmentation->warmup_blocks, &chains)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "segmented encode plan: more than %u chains", (unsigned)UINT32_MAX);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  AADHipEncodePlan *p = new (std::nothrow) AADHipEncodePlan();
+  if (p == nullptr) return AAD_APIRESULT_NG;
+  p->ctx = ctx;
+  p->d_streams = nullptr;
+  p->d_chains = nullptr;
+  p->segmented = true;
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &p->d_chains, chains.data(), chains.size())) {
+    if (p->d_chains) (void)hipFree(p->d_chains);
+    delete p;
+    return AAD_APIRESULT_NG;
+  }
+  p->args = args;
+  p->args.chains = p->d_chains;
+  p->args.num_streams = (uint32_t)chains.size();
+  p->args.ring_ok = 0; /* the byte ring writes an image from its start (aad_encode.hip.h, SEG) */
+  p->args.uni.enabled = 0;
+  *plan = p;
+  return AAD_APIRESULT_OK;
 }
 
 AADApiResult AADHip_EncodePlanRun(struct AADHipEncodePlan *plan, const int16_t *device_pcm, uint8_t *device_data,
@@ -739,6 +791,7 @@ AADApiResult AADHip_EncodePlanRun(struct AADHipEncodePlan *plan, const int16_t *
   const aad::LaunchSignal signal = take_signal(ctx);
   DeviceGuard guard(ctx);
   if (!guard.ok) return AAD_APIRESULT_NG;
+  if (plan->segmented && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
   if (plan->args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
   aad::EncodeArgs a = plan->args;
   a.pcm = device_pcm;
@@ -746,7 +799,7 @@ AADApiResult AADHip_EncodePlanRun(struct AADHipEncodePlan *plan, const int16_t *
   a.state = reinterpret_cast<const aad::LaneStateRecord *>(device_state);
   a.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
   aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
-  return finish_signal(ctx, signal, run_encode(ctx, a));
+  return finish_signal(ctx, signal, run_encode(ctx, a, plan->segmented));
 }
 
 /* ------------------------------------------------------------------------------- decode -- */

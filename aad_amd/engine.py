@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import (AADApiResult, AADHeaderInfo, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
+from .capi import (AADApiResult, AADHeaderInfo, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
                    OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
                    STREAM_DESC_DTYPE, TRIAL_LANES, load_library, make_parameter)
 
@@ -115,12 +115,23 @@ class Engine:
         return int(self.lib.AADHip_CalculateEncodedSize(C.byref(param), num_samples))
 
     # ---- plans ---------------------------------------------------------------------------
-    def encode_plan(self, param, descs):
+    def encode_plan(self, param, descs, segment_blocks=None, warmup_blocks=0):
+        """segment_blocks: None for the reference encoder's bytes, else a segmented plan
+        (AADHip_SegmentedEncodePlanCreate): chains of segment_blocks kept blocks, each after warmup_blocks
+        discarded ones - a valid stream, not the reference encoder's bytes (include/aad_hip.h)."""
         descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
         plan = C.c_void_p()
-        _check("AADHip_EncodePlanCreate",
-               self.lib.AADHip_EncodePlanCreate(self._ctx, C.byref(param), len(descs), descs.ctypes.data, C.byref(plan)))
-        return EncodePlan(self, plan, param, descs)
+        if segment_blocks is None:
+            _check("AADHip_EncodePlanCreate",
+                   self.lib.AADHip_EncodePlanCreate(self._ctx, C.byref(param), len(descs), descs.ctypes.data, C.byref(plan)))
+        else:
+            seg = AADHipSegmentation(int(segment_blocks), int(warmup_blocks))
+            _check("AADHip_SegmentedEncodePlanCreate",
+                   self.lib.AADHip_SegmentedEncodePlanCreate(self._ctx, C.byref(param), C.byref(seg), len(descs),
+                                                             descs.ctypes.data, C.byref(plan)))
+        p = EncodePlan(self, plan, param, descs)
+        p.segmented = segment_blocks is not None
+        return p
 
     def decode_plan(self, header, descs, has_file_header=True):
         descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
@@ -131,7 +142,7 @@ class Engine:
         return DecodePlan(self, plan, header, descs)
 
     # ---- uniform batches (every stream the same length) -----------------------------------
-    def uniform_encode_plan(self, param, num_streams, num_samples):
+    def uniform_encode_plan(self, param, num_streams, num_samples, segment_blocks=None, warmup_blocks=0):
         """Stream table for a [streams, samples, channels] int16 tensor and a [streams, stride]
         uint8 output; stride = encoded size rounded up to 64 bytes (images on 64-byte boundaries let the
         dense stereo encoder store whole granules - aad_encode.hip.h run_block)."""
@@ -145,7 +156,7 @@ class Engine:
         d["data_offset"] = i * np.uint64(stride)
         d["data_size"] = stride
         d["num_samples"] = num_samples
-        plan = self.encode_plan(param, d)
+        plan = self.encode_plan(param, d, segment_blocks, warmup_blocks)
         plan.image_size, plan.stride = size, stride
         return plan
 
@@ -158,13 +169,16 @@ class Engine:
         d["num_samples"] = header.num_samples
         return self.decode_plan(header, d, True)
 
-    def encode_uniform(self, pcm, param, state=None):
+    def encode_uniform(self, pcm, param, state=None, segment_blocks=None, warmup_blocks=0):
         """pcm: int16 cuda tensor [streams, samples, channels] -> uint8 tensor [streams, stride]
-        (each row starts with a complete .aad image of plan.image_size bytes)."""
+        (each row starts with a complete .aad image of plan.image_size bytes).  segment_blocks / warmup_blocks:
+        a segmented encode (see encode_plan), which takes no state."""
         torch = self.torch
+        if state is not None and segment_blocks is not None:
+            raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
         streams, samples, ch = pcm.shape
         assert ch == param.num_channels and pcm.dtype == torch.int16 and pcm.is_contiguous()
-        plan = self.uniform_encode_plan(param, streams, samples)
+        plan = self.uniform_encode_plan(param, streams, samples, segment_blocks, warmup_blocks)
         out = torch.zeros((streams, plan.stride), dtype=torch.uint8, device=pcm.device)
         plan.run(pcm, out, state)
         return out, plan.image_size
@@ -268,11 +282,14 @@ class EncodePlan:
     def __init__(self, engine, handle, param, descs):
         self.engine, self.handle, self.param, self.descs = engine, handle, param, descs
         self.image_size = self.stride = None
+        self.segmented = False
 
     def run(self, pcm, data, state=None, ordered=True):
         """pcm: int16 cuda tensor, data: uint8 cuda tensor, state: int32 cuda tensor [lanes, 10] or None.
         ordered=False: launch on the engine's stream without ordering it against torch's current stream
         (the caller orders the streams itself, with events - see bench.py's pipelined step)."""
+        if state is not None and self.segmented:
+            raise ValueError("a segmented encode plan takes no state")
         sp = state.data_ptr() if state is not None else None
         cur = self.engine._enter() if ordered else None
         _check("AADHip_EncodePlanRun",

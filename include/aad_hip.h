@@ -146,6 +146,39 @@ AADApiResult AADHip_EncodePlanRun(
     struct AADHipEncodePlan *plan, const int16_t *device_pcm, uint8_t *device_data,
     struct AADHipLaneState *device_state);
 
+/* ---- segmented encode: long streams as parallel block chains -------------------------------- */
+
+/* An encode plan is one serial chain of blocks per stream and channel: the weights and the step index carry from each block to
+ * the next (src/aad_encoder.c:853-886), so a run takes as long as the longest stream's block count, however many streams share
+ * it.  Every block header carries the decoder's whole state (src/aad_decoder.c:362-379) and decoding never looks across a block
+ * boundary, so a segmented plan cuts each stream into segments encoded by independent chains side by side.
+ *
+ * Definition.  A stream of N frames has B = ceil(N / spb) blocks (spb: samples per block of the parameter's geometry).  With
+ * L = segment_blocks and W = warmup_blocks, segment s keeps blocks [s L, min((s + 1) L, B)); with w = min(W, s L) its bytes are
+ * those of a fresh reference encoder (AADEncoder_Create, AADEncoder_SetEncodeParameter with the same parameter and trial
+ * count, AADEncoder_EncodeWhole) over frames [(s L - w) spb, min((s + 1) L spb, N)), without its file header and without its
+ * first w blocks (the warm-up).  The image is the stream's 31-byte file header with the whole stream's N, then the segments'
+ * bytes in order: AADHip_CalculateEncodedSize bytes, as for any plan.  The bytes depend on the PCM, the parameter, L and W only.
+ *
+ * The image is a valid format-v4 stream that any decoder (the reference's included) decodes to what the chains reconstructed.
+ * It is NOT the reference encoder's bytes unless L >= B (or W >= (segments - 1) L): each chain starts from a fresh state, and the
+ * warm-up does not converge onto the serial encode's.  The quality cost, the RMSE of the decoded image against the serial
+ * encode's, depends on the signal, L and W; tools/segment_quality.py measures it ("Segmented encode").
+ *
+ * AADHip_SegmentedEncodePlanCreate validates `parameter` and `streams` exactly like AADHip_EncodePlanCreate (same errors) and
+ * returns an ordinary plan: AADHip_EncodePlanRun, AADHip_EncodePlanDestroy and AADHip_ContextSignalNextRun work on it.
+ * AAD_APIRESULT_INVALID_ARGUMENT: a null `segmentation`, segment_blocks == 0, more than UINT32_MAX segments in the batch, and
+ * from AADHip_EncodePlanRun a non-null device_state (a segmented plan always starts from fresh encoders and leaves no state). */
+struct AADHipSegmentation {
+  uint32_t segment_blocks; /* L >= 1: blocks kept per chain */
+  uint32_t warmup_blocks;  /* W: blocks encoded before a segment and discarded (clamped at the stream's start) */
+};
+AADApiResult AADHip_SegmentedEncodePlanCreate(
+    struct AADHipContext *context, const struct AADEncodeParameter *parameter,
+    const struct AADHipSegmentation *segmentation,
+    uint32_t num_streams, const struct AADHipStreamDesc *streams,
+    struct AADHipEncodePlan **plan);
+
 /* ---- decode ------------------------------------------------------------------------------ */
 
 /* `format` supplies channels / bits / block geometry / channel process method for the whole
