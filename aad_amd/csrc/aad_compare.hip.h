@@ -11,13 +11,17 @@
  * (that the second operand is y and not y << 16 is how the reference is written; a drop-in
  * prints what it prints).  fp64 division on gfx950 is IEEE-exact, so every e is bit-identical to
  * the host's; only the ORDER of the fp64 sums differs (fixed tree here, channel-major walk there).
- * Both sums are sums of N non-negative terms, so any two orders agree to 2 N 2^-53 relative; the
+ * Both sums are sums of N non-negative terms, so any two orders agree to about 2 N 2^-53 relative; the
  * printed line (%f: six decimals) is therefore THE SAME unless a rounding boundary (k + 0.5) 1e-6
- * lies inside that interval around the value.  compare_finish_kernel checks exactly that, and
- * when it does - or when the context asks for it - one lane walks the stream in the reference's
- * order (channel by channel, sample by sample, separately rounded multiply and add: no FMA
- * contraction), which gives the reference's doubles bit for bit (tests/test_gpu_reconstruct.py
- * runs every case that way too and compares with ==).
+ * lies inside that interval around the value.  compare_finish_kernel checks exactly that
+ * (aad_compare_round.h, proven on the CPU by tests/test_compare_round.py), and when it does - or
+ * when the context asks for it - one lane walks the stream in the reference's order (channel by
+ * channel, sample by sample, separately rounded multiply and add: no FMA contraction), which gives
+ * the reference's doubles bit for bit (tests/test_gpu_reconstruct.py compares with ==: every case
+ * forced into that order, and the streams of tests/golden/stats_ties.json, which lie on a
+ * boundary, in the default order).  With
+ * the residual output that walk reads the residual the segments kernel wrote over `decoded`: the
+ * reconstruction and the 32-bit gap both follow from it and the original exactly.
  *
  * HBM-bound by construction: 4 B read (+2 B written for the residual) per value, nothing else.
  */
@@ -28,6 +32,7 @@
 #include <stdint.h>
 
 #include "aad_decode.hip.h" /* StreamDesc, find_stream */
+#include "aad_compare_round.h"
 
 namespace aad {
 
@@ -127,15 +132,24 @@ __global__ __launch_bounds__(kCompareThreads) void compare_segments_kernel(Compa
  * pragma is what keeps e * e and the addition from becoming one fused multiply-add (one rounding instead of two: the
  * last bit of the sum differed from the host's). */
 __device__ __attribute__((noinline)) void sums_in_reference_order(const int16_t *x, const int16_t *y, uint32_t num_samples,
-                                                                  uint32_t channels, double *sum_sq, double *sum_abs)
+                                                                  uint32_t channels, uint32_t residual, double *sum_sq,
+                                                                  double *sum_abs)
 {
 #pragma clang fp contract(off)
   double ssq = 0.0, sab = 0.0;
   for (uint32_t c = 0; c < channels; c++) {
     for (uint32_t i = 0; i < num_samples; i++) {
       const size_t at = (size_t)i * channels + c;
-      const int32_t xv = x[at], yv = y[at];
-      const int32_t gap = (int32_t)(((uint32_t)xv << 16) - ((uint32_t)yv << 16));
+      const int32_t xv = x[at];
+      int32_t yv, gap;
+      if (residual) { /* y holds r = (x - y) mod 2^16, the top half of the gap: both come back exactly */
+        const int32_t rv = y[at];
+        yv = (int16_t)(xv - rv);
+        gap = (int32_t)((uint32_t)rv << 16);
+      } else {
+        yv = y[at];
+        gap = (int32_t)(((uint32_t)xv << 16) - ((uint32_t)yv << 16));
+      }
       const double p1 = __ddiv_rn((double)gap, 2147483647.0), p2 = __ddiv_rn((double)yv, 2147483647.0);
       const double e = p1 - p2;
       const double sq = e * e; /* pow(e, 2) == e * e, rounded once */
@@ -171,19 +185,14 @@ __global__ __launch_bounds__(64) void compare_finish_kernel(CompareArgs a)
     r.rms_error = __dsqrt_rn(__ddiv_rn(sq, n)); /* correctly rounded forms: the host's sqrt and division are */
     r.mean_abs_error = __ddiv_rn(ab, n);
     r.max_abs_error = mx; /* a maximum does not depend on the order */
-    /* Could the reference's summation order print another sixth decimal?  |tree sum - sequential sum| <= 2 N u |sum|
-     * (u = 2^-53, non-negative terms); the square root halves a relative error, the division and the root add an ulp
-     * each - rel covers both with room to spare. */
-    const double rel = 2.5 * n * 1.1102230246251565e-16 + 1e-15;
-    auto crosses = [](double v, double rel_err) { /* a %f rounding boundary inside v (1 +- rel_err)? */
-      const double lo = v * (1.0 - rel_err) * 1e6, hi = v * (1.0 + rel_err) * 1e6;
-      return floor(lo + 0.5 - 1e-9) != floor(hi + 0.5 + 1e-9); /* the 1e-9: the products above are rounded themselves */
-    };
-    const bool tie = crosses(r.rms_error, rel) || crosses(r.mean_abs_error, rel);
-    if ((tie || a.sequential) && !a.write_residual) { /* (with the residual written over `decoded` the terms are gone) */
+    /* Could the reference's summation order print another sixth decimal?  (aad_compare_round.h: the bound and the test) */
+    const double rel = compare_reorder_bound(n);
+    const bool tie = compare_crosses_boundary(r.rms_error, rel) || compare_crosses_boundary(r.mean_abs_error, rel);
+    if (tie || a.sequential) { /* a residual written over `decoded` still holds every term: see sums_in_reference_order */
       const StreamDesc sd = a.streams[s];
       double ssq = 0.0, sab = 0.0;
-      sums_in_reference_order(a.original + sd.pcm_offset, a.decoded + sd.pcm_offset, sd.num_samples, a.channels, &ssq, &sab);
+      sums_in_reference_order(a.original + sd.pcm_offset, a.decoded + sd.pcm_offset, sd.num_samples, a.channels,
+                              a.write_residual, &ssq, &sab);
       r.rms_error = __dsqrt_rn(__ddiv_rn(ssq, n));
       r.mean_abs_error = __ddiv_rn(sab, n);
     }

@@ -246,7 +246,8 @@ AADApiResult AADHip_ReconstructPlanCreate(
     struct AADHipReconstructPlan **plan);
 void AADHip_ReconstructPlanDestroy(struct AADHipReconstructPlan *plan);
 
-/* device_stats: NULL, or num_streams records.  Fresh encoders (as the CLI creates per file). */
+/* device_stats: NULL, or num_streams records, the same doubles whichever output_kind (AAD_HIP_OPTION_COMPARE_ORDER holds for
+ * both).  Fresh encoders (as the CLI creates per file). */
 AADApiResult AADHip_ReconstructPlanRun(
     struct AADHipReconstructPlan *plan, const int16_t *device_pcm, uint8_t *device_data,
     int16_t *device_out, int32_t output_kind, struct AADHipErrorStats *device_stats);

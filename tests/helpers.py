@@ -88,3 +88,71 @@ def wav_bytes_depth(pcm, rate, depth, salt=0):
     head = b"RIFF" + struct.pack("<I", 36 + len(payload)) + b"WAVE" + b"fmt " + struct.pack(
         "<IHHIIHH", 16, 1, ch, rate, rate * bps * ch, bps * ch, depth) + b"data" + struct.pack("<I", len(payload))
     return head + payload
+
+
+def stats_tie_cases():
+    """tests/golden/stats_ties.json: streams whose `aad -c` RMSE or MSD lies on a rounding boundary of the printed six
+    decimals (tie) or just outside the device's window (control); make_stats_ties_golden.py"""
+    import json
+    with open(os.path.join(GOLDEN, "stats_ties.json")) as f:
+        return json.load(f)["cases"]
+
+
+def stats_tie_input(case):
+    """the int16 [frames, channels] input of a stats_ties.json case"""
+    from aad_amd.synth import synth_pcm
+    return synth_pcm(1, case["frames"], case["channels"], seed=case["seed"], kind=case["kind"])[0]
+
+
+def build_compare_round_driver(directory):
+    """tests/compare_round_driver.cpp built with g++ against aad_amd/csrc/aad_compare_round.h -> path of the executable"""
+    import subprocess
+    exe = os.path.join(str(directory), "compare_round_driver")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
+                    "-I", os.path.join(ROOT, "aad_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "compare_round_driver.cpp")], check=True)
+    return exe
+
+
+def compare_round(driver, rows):
+    """[(n, v)] -> [(compare_reorder_bound(n), compare_crosses_boundary(v, that bound))] through the driver"""
+    import subprocess
+    text = "".join("%d %s\n" % (n, float(v).hex()) for n, v in rows)
+    out = subprocess.run([driver], input=text, check=True, capture_output=True, text=True).stdout.split()
+    assert len(out) == 2 * len(rows)
+    return [(float.fromhex(out[2 * i]), out[2 * i + 1] == "1") for i in range(len(rows))]
+
+
+def reorder_bound(n):
+    """delta(n), exact (fractions.Fraction): how far, relative, the RMSE or MSD of n values summed in any order lies from the
+    reference's - and from the exact value.  Derived in tests/test_compare_round.py's docstring."""
+    from fractions import Fraction
+    u = Fraction(1, 2 ** 53)
+    g = n * u / (1 - n * u)
+    a = (1 + g) / (1 - g)
+    d = (1 + u) / (1 - u)
+    return max(a * d, (1 + a * d) / 2 * d) - 1
+
+
+def exact_sum(values):
+    """the exact sum (fractions.Fraction) of a float64 array: every double is an integer times a power of two; integers with the
+    same exponent are summed in int64 halves that cannot overflow"""
+    from fractions import Fraction
+    v = np.asarray(values, dtype=np.float64).ravel()
+    mant, expo = np.frexp(v)
+    m = (mant * 2.0 ** 53).astype(np.int64)  # exact: |mant| < 1, 53 bits
+    total = Fraction(0)
+    for x in np.unique(expo):
+        sel = m[expo == x]
+        s = (int(np.sum(sel >> 26)) << 26) + int(np.sum(sel & ((1 << 26) - 1)))
+        total += Fraction(s) * Fraction(2) ** (int(x) - 53)
+    return total
+
+
+def exact_squares(e):
+    """e * e exactly, as three float64 arrays whose sum it is (Veltkamp's split: 26-bit halves, every product exact)"""
+    e = np.asarray(e, dtype=np.float64)
+    t = e * 134217729.0
+    hi = t - (t - e)
+    lo = e - hi
+    return hi * hi, 2.0 * hi * lo, lo * lo

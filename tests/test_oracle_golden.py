@@ -9,7 +9,8 @@ import pytest
 
 import oracle_binding as ob
 from aad_amd.synth import synth_pcm
-from helpers import GOLDEN, cli_mode_input, read_wav16, sha256, wav16_bytes
+from helpers import (GOLDEN, build_compare_round_driver, cli_mode_input, compare_round, read_wav16, sha256, stats_tie_cases,
+                     stats_tie_input, wav16_bytes)
 
 FIX = os.path.join(GOLDEN, "ref_fixtures")
 MANIFEST = json.load(open(os.path.join(GOLDEN, "manifest.json")))
@@ -185,3 +186,46 @@ def test_oracle_on_reference_roundtrip_suite():
         assert suite_rmse(pcm, dec) < c["rms_epsilon"], c
         if file_bytes is not None:
             assert len(image) < file_bytes // 2, c
+
+
+def _tie_stats(case):
+    return tuple(float.fromhex(h) for h in case["stats_hex"])
+
+
+def test_stats_tie_fixtures_are_what_they_claim(tmp_path):
+    """tests/golden/stats_ties.json (make_stats_ties_golden.py): the oracle recomputes every case to the stored doubles and the
+    stored `aad -c` line, and the device's tie rule (aad_compare_round.h, through tests/compare_round_driver.cpp) calls every tie
+    case a tie and every control not one - so the GPU tests over these cases really take both sides of compare_finish_kernel's
+    branch.  Mono and stereo, RMSE and MSD ties, streams of up to 2M values."""
+    cases = stats_tie_cases()
+    ties = [c for c in cases if c["tie"]]
+    assert sum(c["statistic"] == "rmse" for c in ties) >= 4 and sum(c["statistic"] == "msd" for c in ties) >= 4
+    assert 2 <= len(cases) - len(ties) and {c["channels"] for c in ties} == {1, 2}
+    rows = []
+    for c in cases:
+        pcm = stats_tie_input(c)
+        assert pcm.size <= 2_000_000
+        rec, _ = ob.decode(ob.encode(pcm, c["bits"], c["block_size"], 48000, c["ms"], c["trials"]))
+        st = ob.error_stats(pcm, rec)
+        assert st == _tie_stats(c), c
+        assert ob.stats_line(st) == c["stats_line"], c
+        rows += [(pcm.size, st[0]), (pcm.size, st[1])]
+    answers = compare_round(build_compare_round_driver(tmp_path), rows)
+    for i, c in enumerate(cases):
+        (_, rmse_crosses), (_, msd_crosses) = answers[2 * i], answers[2 * i + 1]
+        if c["tie"]:
+            assert (rmse_crosses if c["statistic"] == "rmse" else msd_crosses), c
+        else:
+            assert not rmse_crosses and not msd_crosses, c
+
+
+@pytest.mark.ref
+def test_stats_tie_fixtures_against_reference_cli(tmp_path):
+    """the compiled reference CLI prints the stored line for every case's WAV"""
+    import subprocess
+    for c in stats_tie_cases():
+        wav = tmp_path / "in.wav"
+        wav.write_bytes(wav16_bytes(stats_tie_input(c), 48000))
+        opts = ["-b", str(c["bits"]), "-s", str(c["block_size"]), "-t", str(c["trials"])] + (["-m"] if c["ms"] else [])
+        out = subprocess.run([ob.REF_CLI, "-c"] + opts + [str(wav)], check=True, capture_output=True, text=True).stdout
+        assert out == c["stats_line"], c
