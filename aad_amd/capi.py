@@ -80,7 +80,8 @@ HIP_SYMBOLS = [
     "AADHip_EncodePlanDestroy", "AADHip_EncodePlanRun", "AADHip_DecodePlanCreate", "AADHip_DecodePlanDestroy",
     "AADHip_DecodePlanRun", "AADHip_EncodeBatch", "AADHip_DecodeBatch",
     "AADHip_ReconstructPlanCreate", "AADHip_ReconstructPlanDestroy", "AADHip_ReconstructPlanRun",
-    "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate",
+    "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate", "AADHip_SegmentedEncodeBatch",
+    "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -173,6 +174,15 @@ def _declare_hip(lib):
     lib.AADHip_ReconstructPlanRun.restype = C.c_int
     lib.AADHip_ReconstructBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, C.c_int32, vp, vp]
     lib.AADHip_ReconstructBatch.restype = C.c_int
+    lib.AADHip_SegmentedEncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.POINTER(AADHipSegmentation), C.c_uint32, vp, vp,
+                                                vp, vp, vp]
+    lib.AADHip_SegmentedEncodeBatch.restype = C.c_int
+    lib.AADHip_SegmentedReconstructPlanCreate.argtypes = [vp, C.POINTER(AADEncodeParameter), C.POINTER(AADHipSegmentation), C.c_uint32,
+                                                          vp, C.POINTER(vp)]
+    lib.AADHip_SegmentedReconstructPlanCreate.restype = C.c_int
+    lib.AADHip_SegmentedReconstructBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.POINTER(AADHipSegmentation), C.c_uint32, vp,
+                                                     vp, C.c_int32, vp, vp]
+    lib.AADHip_SegmentedReconstructBatch.restype = C.c_int
     lib.AADWav_ParseHeader.argtypes = [vp, C.c_uint64, C.POINTER(AADWavInfo)]
     lib.AADWav_ParseHeader.restype = C.c_int
     lib.AADWav_WriteHeader.argtypes = [vp, C.c_uint32, C.c_uint16, C.c_uint32, C.c_uint32]

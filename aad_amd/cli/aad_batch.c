@@ -18,7 +18,10 @@
  *
  * Batch additions: -o/--output-dir DIR; -l/--list FILE (one input path per line, added to the
  * positional ones); -D/--devices 0,1,... (default: $AAD_HIP_DEVICE or 0; a device may be named
- * more than once to run several contexts on it).
+ * more than once to run several contexts on it); -S/--segment-blocks L[,W] (-e / -r / -g / -c: a
+ * segmented encode, include/aad_hip.h - each file is cut into chains of L kept blocks after W
+ * warm-up blocks, W = 0 by default, encoded side by side; a file of at most L blocks is one chain
+ * and keeps the reference's bytes, a longer one gets a valid image that is not the reference's).
  *
  * Partitioning: inputs are sorted by size and dealt longest-first onto the
  * least-loaded device, O(n log n); sizes come from stat(), nothing is read for it.  Each device
@@ -40,8 +43,8 @@
  * the statistics of all its files in one run) and stage it through the same pinned blocks in chunks.
  *
  * Output names are OUTDIR/<stem><ext>; two inputs with the same stem would overwrite each other,
- * so that is refused up front.  Every output is byte-identical to what the reference CLI writes
- * for the same input.  Host C only; all codec work happens in libaad_hip.so.
+ * so that is refused up front.  Without -S every output is byte-identical to what the reference
+ * CLI writes for the same input.  Host C only; all codec work happens in libaad_hip.so.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <errno.h>
@@ -87,6 +90,8 @@ struct Options {
   uint64_t wave_bytes;
   const char *outdir;
   struct AADEncodeParameter param;
+  int segmented;                  /* -S given */
+  struct AADHipSegmentation seg;
 };
 
 /* a wave: files [first, last) of a slot's list */
@@ -444,8 +449,15 @@ static int run_group(struct Slot *s, struct AADHipContext *ctx, struct File **g,
         if (out[k] == NULL) goto done;
       }
     }
-    if (mode == 'e')
+    if (mode == 'e' && opt->segmented)
+      r = AADHip_SegmentedEncodeBatch(ctx, &param, &opt->seg, (uint32_t)n, (const int16_t *const *)in, frames, (uint8_t *const *)out,
+                                      sizes, got);
+    else if (mode == 'e')
       r = AADHip_EncodeBatch(ctx, &param, (uint32_t)n, (const int16_t *const *)in, frames, (uint8_t *const *)out, sizes, got, NULL);
+    else if (opt->segmented)
+      r = AADHip_SegmentedReconstructBatch(ctx, &param, &opt->seg, (uint32_t)n, (const int16_t *const *)in, frames,
+                                           mode == 'g' ? AAD_HIP_RECONSTRUCT_RESIDUAL : AAD_HIP_RECONSTRUCT_DECODED,
+                                           mode == 'c' ? NULL : (int16_t *const *)out, mode == 'c' ? stats : NULL);
     else
       r = AADHip_ReconstructBatch(ctx, &param, (uint32_t)n, (const int16_t *const *)in, frames,
                                   mode == 'g' ? AAD_HIP_RECONSTRUCT_RESIDUAL : AAD_HIP_RECONSTRUCT_DECODED,
@@ -553,8 +565,8 @@ static void *writer_main(void *arg)
 
 static void print_usage_lines(FILE *to)
 {
-  fprintf(to, "usage: aad_batch -e|-r|-g [-b bits] [-s max_block_size] [-t trials] [-m] [-D dev,dev,...] -o OUTDIR [-l LIST] in.wav...\n"
-              "       aad_batch -c       [-b bits] [-s max_block_size] [-t trials] [-m] [-D dev,dev,...] [-l LIST] in.wav...\n"
+  fprintf(to, "usage: aad_batch -e|-r|-g [-b bits] [-s max_block_size] [-t trials] [-m] [-S L[,W]] [-D dev,dev,...] -o OUTDIR [-l LIST] in.wav...\n"
+              "       aad_batch -c       [-b bits] [-s max_block_size] [-t trials] [-m] [-S L[,W]] [-D dev,dev,...] [-l LIST] in.wav...\n"
               "       aad_batch -d [-D dev,dev,...] -o OUTDIR [-l LIST] in.aad...\n"
               "       aad_batch -i [-l LIST] in.aad...\n"
               "       aad_batch -h | -v\n");
@@ -587,6 +599,8 @@ static int print_help(void)
     {'o', "output-dir", 1, "Directory the outputs go to, as <input stem>.aad / .wav (every mode but -c and -i)"},
     {'l', "list", 1, "File with one input path per line, in addition to the paths on the command line"},
     {'D', "devices", 1, "Comma-separated device indices; a device may be named more than once (default: AAD_HIP_DEVICE or 0)"},
+    {'S', "segment-blocks", 1, "L[,W]: encode each file as chains of L blocks after W warm-up blocks (default W: 0), side by side; "
+                               "files longer than L blocks are then not the reference's bytes (-e, -r, -g, -c)"},
   };
   size_t k;
   print_usage_lines(stdout);
@@ -654,6 +668,33 @@ static int is_opt(const char *arg, const char *shortname, const char *longname)
   return strcmp(arg, shortname) == 0 || strcmp(arg, longname) == 0;
 }
 
+/* a decimal uint32 at *p, advancing *p past it; 0 when there is none or it does not fit */
+static int parse_u32(const char **p, uint32_t *v)
+{
+  char *end;
+  unsigned long long x;
+  if (**p < '0' || **p > '9') return 0;
+  errno = 0;
+  x = strtoull(*p, &end, 10);
+  if (errno != 0 || x > 0xFFFFFFFFull) return 0;
+  *v = (uint32_t)x;
+  *p = end;
+  return 1;
+}
+
+/* -S L[,W]: L >= 1, W >= 0, nothing behind them */
+static int parse_segmentation(const char *arg, struct AADHipSegmentation *seg)
+{
+  const char *p = arg;
+  seg->warmup_blocks = 0;
+  if (!parse_u32(&p, &seg->segment_blocks) || seg->segment_blocks == 0) return 0;
+  if (*p == ',') {
+    p++;
+    if (!parse_u32(&p, &seg->warmup_blocks)) return 0;
+  }
+  return *p == 0;
+}
+
 static int by_size_desc(const void *a, const void *b)
 {
   const struct File *x = *(const struct File *const *)a, *y = *(const struct File *const *)b;
@@ -687,7 +728,7 @@ int main(int argc, char **argv)
   struct Slot slots[MAX_DEVICES];
   uint64_t load[MAX_DEVICES];
   int devices[MAX_DEVICES], ndev = 0, counts[MAX_DEVICES];
-  const char *list = NULL, *devarg = getenv("AAD_HIP_DEVICE");
+  const char *list = NULL, *devarg = getenv("AAD_HIP_DEVICE"), *segarg = NULL;
   char **paths = NULL, *listbuf = NULL;
   struct File *files = NULL, **order = NULL;
   int i, k, npaths = 0, cap, rc = 1, started = 0;
@@ -731,10 +772,15 @@ int main(int argc, char **argv)
     else if (has_value && is_opt(a, "-o", "--output-dir")) opt.outdir = argv[++i];
     else if (has_value && is_opt(a, "-l", "--list")) list = argv[++i];
     else if (has_value && is_opt(a, "-D", "--devices")) devarg = argv[++i];
+    else if (has_value && is_opt(a, "-S", "--segment-blocks")) segarg = argv[++i];
     else if (a[0] == '-' && a[1] != 0) goto bad_usage;
     else paths[npaths++] = argv[i];
   }
   if (opt.mode == 0 || (opt.mode != 'c' && opt.mode != 'i' && opt.outdir == NULL)) goto bad_usage;
+  if (segarg != NULL) { /* a segmented encode: the modes that encode */
+    if (opt.mode == 'd' || opt.mode == 'i' || !parse_segmentation(segarg, &opt.seg)) goto bad_usage;
+    opt.segmented = 1;
+  }
 
   if (list != NULL) { /* one path per line; LF, CRLF or bare CR endings */
     struct File lf;

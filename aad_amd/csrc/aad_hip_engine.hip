@@ -1358,6 +1358,200 @@ AADApiResult encode_host(AADHipContext *ctx, const struct AADEncodeParameter *pa
   return rc;
 }
 
+/* grow-only device block of a context (the device-resident waves of the segmented encode and of the reconstruction modes) */
+bool device_block_reserve(AADHipContext *ctx, void **block, size_t *capacity, size_t bytes, const char *what)
+{
+  if (*capacity >= bytes) return true;
+  if (*block) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(*block);
+  }
+  *block = nullptr;
+  *capacity = 0;
+  const size_t want = bytes + bytes / 8 + 4096; /* some slack, so that a slightly larger next wave does not reallocate */
+  if (hipMalloc(block, want) == hipSuccess) {
+    *capacity = want;
+    return true;
+  }
+  (void)hipGetLastError();
+  *block = nullptr;
+  if (!hip_ok(ctx, hipMalloc(block, bytes), what)) {
+    *block = nullptr;
+    return false;
+  }
+  *capacity = bytes;
+  return true;
+}
+
+/* bytes of the pinned chunks that stage a device-resident wave */
+uint64_t staging_chunk(const AADHipContext *ctx) { return ctx->tile_bytes > 0 ? (uint64_t)ctx->tile_bytes : kChunkBudget; }
+
+/* device bytes a wave may take: what is free now plus what this context's own grow-only blocks already hold, less a quarter for
+ * everybody else; a forced tile size forces small waves too (64 tiles' worth), so that the tests walk every path */
+bool wave_budget(AADHipContext *ctx, uint64_t *budget)
+{
+  if (ctx->tile_bytes > 0) {
+    *budget = (uint64_t)ctx->tile_bytes * 64u;
+    return true;
+  }
+  DeviceGuard guard(ctx);
+  size_t free_bytes = 0, total_bytes = 0;
+  if (!guard.ok || !hip_ok(ctx, hipMemGetInfo(&free_bytes, &total_bytes), "hipMemGetInfo")) return false;
+  const uint64_t own = ctx->rc_in_capacity + ctx->rc_out_capacity + ctx->scratch_capacity;
+  *budget = ((uint64_t)free_bytes + own) / 4 * 3;
+  return true;
+}
+
+/*
+ * Segmented encode of host streams (AADHip_SegmentedEncodeBatch).  The serial path's tiles are block ranges of every stream of a
+ * group with the predictor state carried between them; a segmented encode has no state to carry, and what it needs is all its
+ * chains in ONE launch - a launch costs a chain's (L + W) blocks however few chains it holds.  So the COMPUTE is whole, as in
+ * the reconstruction modes: a wave of consecutive chains (aad_segments.h build_segment_waves) is resident on the device - its chain
+ * table and every chain's frames, warm-up included, then its output - and one kernel encodes all of it; only the STAGING is cut,
+ * the input going up and the output coming down through the context's two pinned blocks in chunks, chunk k + 1 being filled /
+ * chunk k - 1 being scattered while chunk k is on the bus.  A batch beyond three quarters of the device's free memory runs as
+ * several waves.  No chain brings a look-back block: the trial search of a chain's first block has none, whatever precedes it in
+ * the stream.  Each stream's file header, with the whole stream's count, is written by its first chain on the device.
+ * fill(i, offset, size, dst): bytes [offset, offset + size) of stream i's interleaved int16 PCM; drain as in encode_host.
+ */
+template <class Fill, class Drain>
+AADApiResult encode_host_segmented(AADHipContext *ctx, const struct AADEncodeParameter *parameter, const struct AADHipSegmentation *seg,
+                                   uint32_t num_streams, const uint32_t *num_samples, const uint64_t *data_capacity,
+                                   uint64_t *output_size, Fill fill, Drain drain)
+{
+  AADHeaderInfo h;
+  if (AADFormat_ParameterToHeader(parameter, 1, AAD_HIP_MAX_NUM_CHANNELS, &h) != AAD_APIRESULT_OK ||
+      !AADFormat_HeaderFieldsValid(&h, AAD_HIP_MAX_NUM_CHANNELS))
+    return AAD_APIRESULT_INVALID_FORMAT;
+  const uint32_t ch = h.num_channels, spb = h.num_samples_per_block;
+  std::vector<uint64_t> sizes(num_streams);
+  for (uint32_t i = 0; i < num_streams; i++) {
+    if (num_samples[i] == 0) return AAD_APIRESULT_INVALID_FORMAT; /* src/aad_encoder.c:157-159 */
+    h.num_samples = num_samples[i];
+    sizes[i] = AADFormat_EncodedSize(&h);
+    if (data_capacity[i] < sizes[i]) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
+  }
+  aad::EncodeArgs base;
+  AADApiResult rc = encode_plan_init(parameter, 0, nullptr, &base);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  base.ring_ok = 0; /* as the segmented plans: chains as streams, no byte ring */
+  base.uni.enabled = 0;
+  uint64_t budget;
+  if (!wave_budget(ctx, &budget)) return AAD_APIRESULT_NG;
+  std::vector<aad::SegmentWave> waves;
+  if (!aad::build_segment_waves(num_samples, sizes.data(), num_streams, ch, spb, h.block_size, seg->segment_blocks,
+                                seg->warmup_blocks, budget, &waves)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "segmented encode: more than %u chains", (unsigned)UINT32_MAX);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !ensure_events(ctx)) return AAD_APIRESULT_NG;
+  const size_t chunk = (size_t)round_up(staging_chunk(ctx) < 4096 ? 4096 : staging_chunk(ctx), 64);
+  std::vector<uint64_t> row, spot; /* per chain of a wave: where its PCM starts in the input block, its bytes in the output block */
+  for (size_t wi = 0; wi < waves.size() && rc == AAD_APIRESULT_OK; wi++) {
+    const aad::SegmentWave &t = waves[wi];
+    const uint32_t n = (uint32_t)t.chains.size();
+    /* input block: chain table | pcm ; output block: lead-in | the chains' bytes */
+    const uint64_t table_bytes = round_up(sizeof(aad::ChainDesc) * (uint64_t)n, 64), in_bytes = table_bytes + t.pcm_elems * sizeof(int16_t);
+    row.resize((size_t)n + 1);
+    spot.resize((size_t)n + 1);
+    for (uint32_t k = 0; k < n; k++) {
+      row[k] = table_bytes + t.chains[k].pcm_offset * sizeof(int16_t);
+      spot[k] = t.where[k].out_offset;
+    }
+    row[n] = in_bytes;
+    spot[n] = t.out_bytes;
+    auto span = [&](const std::vector<uint64_t> &at, uint64_t lo, uint64_t hi, uint32_t *a, uint32_t *b) { /* chains meeting [lo, hi) */
+      *a = (uint32_t)(std::upper_bound(at.begin(), at.end(), lo) - at.begin());
+      *a = *a ? *a - 1 : 0;
+      *b = (uint32_t)(std::lower_bound(at.begin(), at.end(), hi) - at.begin());
+      if (*b > n) *b = n;
+    };
+    rc = AAD_APIRESULT_NG;
+    do {
+      if (!device_block_reserve(ctx, &ctx->d_rc_in, &ctx->rc_in_capacity, in_bytes + 64, "hipMalloc segmented encode input") ||
+          !device_block_reserve(ctx, &ctx->d_rc_out, &ctx->rc_out_capacity, t.out_bytes + 64, "hipMalloc segmented encode output"))
+        break;
+      const size_t stage = in_bytes < chunk ? (size_t)in_bytes + 64 : chunk;
+      if (!staging_reserve(ctx, ctx->in[0], stage) || (in_bytes > chunk && !staging_reserve(ctx, ctx->in[1], stage))) break;
+      uint8_t *d_in = static_cast<uint8_t *>(ctx->d_rc_in), *d_out = static_cast<uint8_t *>(ctx->d_rc_out);
+
+      /* ---- up: bytes [lo, hi) of the input block; chunk k is filled while chunk k - 1 is on the bus ---- */
+      bool ok = true;
+      uint32_t k = 0;
+      for (uint64_t lo = 0; lo < in_bytes && ok; lo += chunk, k++) {
+        const uint64_t hi = lo + chunk < in_bytes ? lo + chunk : in_bytes;
+        if (k >= 2) ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[k & 1]), "hipEventSynchronize"); /* the block's last copy has left it */
+        if (!ok) break;
+        uint8_t *host = static_cast<uint8_t *>(ctx->in[k & 1].host);
+        const uint64_t table_end = sizeof(aad::ChainDesc) * (uint64_t)n;
+        if (lo < table_end)
+          memcpy(host, reinterpret_cast<const uint8_t *>(t.chains.data()) + lo, (size_t)((hi < table_end ? hi : table_end) - lo));
+        uint32_t a, b;
+        span(row, lo, hi, &a, &b);
+        staged_span(ctx, a, b, row, [&](uint32_t x, uint32_t y) {
+          for (uint32_t c = x; c < y; c++) {
+            const uint64_t r0 = row[c], r1 = r0 + (uint64_t)t.chains[c].num_frames * ch * sizeof(int16_t);
+            const uint64_t c0 = r0 > lo ? r0 : lo, c1 = r1 < hi ? r1 : hi;
+            if (c1 > c0)
+              fill(t.where[c].stream, (uint64_t)t.where[c].frame0 * ch * sizeof(int16_t) + (c0 - r0), c1 - c0, host + (c0 - lo));
+          }
+        });
+        ok = hip_ok(ctx, hipMemcpyAsync(d_in + lo, host, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream), "H2D block") &&
+             hip_ok(ctx, hipEventRecord(ctx->chunk_done[k & 1], ctx->stream), "hipEventRecord");
+      }
+      if (!ok) break;
+
+      /* ---- compute: one launch over every chain of the wave ---- */
+      aad::EncodeArgs args = base;
+      args.chains = reinterpret_cast<const aad::ChainDesc *>(d_in);
+      args.num_streams = n;
+      args.pcm = reinterpret_cast<const int16_t *>(d_in + table_bytes);
+      args.data = d_out;
+      if (run_encode(ctx, args, true) != AAD_APIRESULT_OK) break;
+
+      /* ---- down: bytes [out_begin, out_bytes) of the output block; chunk k - 1 is scattered while chunk k is on the bus ---- */
+      const uint64_t down_lo = t.out_begin, down_hi = t.out_bytes;
+      const size_t dstage = down_hi - down_lo < chunk ? (size_t)(down_hi - down_lo) + 64 : chunk;
+      if (!staging_reserve(ctx, ctx->out[0], dstage) || (down_hi - down_lo > chunk && !staging_reserve(ctx, ctx->out[1], dstage))) break;
+      auto scatter = [&](uint32_t kk, uint64_t lo, uint64_t hi) { /* host block kk & 1 holds bytes [lo, hi) of the output block */
+        const uint8_t *host = static_cast<const uint8_t *>(ctx->out[kk & 1].host);
+        uint32_t a, b;
+        span(spot, lo, hi, &a, &b);
+        staged_span(ctx, a, b, spot, [&](uint32_t x, uint32_t y) {
+          for (uint32_t c = x; c < y; c++) {
+            const aad::WaveChain &w = t.where[c];
+            const uint64_t c0 = w.out_offset > lo ? w.out_offset : lo, e = w.out_offset + w.image_bytes, c1 = e < hi ? e : hi;
+            if (c1 > c0) drain(w.stream, w.image_offset + (c0 - w.out_offset), host + (c0 - lo), c1 - c0);
+          }
+        });
+      };
+      uint64_t prev_lo = 0, prev_hi = 0;
+      bool have_prev = false;
+      k = 0;
+      for (uint64_t lo = down_lo; lo < down_hi && ok; lo += chunk, k++) {
+        const uint64_t hi = lo + chunk < down_hi ? lo + chunk : down_hi;
+        ok = hip_ok(ctx, hipMemcpyAsync(ctx->out[k & 1].host, d_out + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream), "D2H block") &&
+             hip_ok(ctx, hipEventRecord(ctx->chunk_done[k & 1], ctx->stream), "hipEventRecord");
+        if (ok && have_prev) { /* the other block: its copy was queued one round ago */
+          ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[(k - 1) & 1]), "hipEventSynchronize");
+          if (ok) scatter(k - 1, prev_lo, prev_hi);
+        }
+        prev_lo = lo, prev_hi = hi, have_prev = true;
+      }
+      if (ok && have_prev) {
+        ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[(k - 1) & 1]), "hipEventSynchronize");
+        if (ok) scatter(k - 1, prev_lo, prev_hi);
+      }
+      if (!ok) break;
+      rc = AAD_APIRESULT_OK;
+    } while (0);
+  }
+  if (rc != AAD_APIRESULT_OK) (void)hipStreamSynchronize(ctx->stream); /* nothing of this call stays in flight */
+  if (rc == AAD_APIRESULT_OK && output_size) memcpy(output_size, sizes.data(), sizeof(uint64_t) * num_streams);
+  return rc;
+}
+
 /*
  * Decode num_streams host images of one format.  fill(i, offset, size, dst) writes bytes
  * [offset, offset + size) of stream i's image, drain(i, frame0, src, frames) receives that range
@@ -1544,6 +1738,24 @@ AADApiResult AADHip_EncodeBatch(struct AADHipContext *ctx, const struct AADEncod
                      [&](uint32_t i, uint64_t offset, const uint8_t *src, uint64_t size) { memcpy(data[i] + offset, src, size); });
 }
 
+AADApiResult AADHip_SegmentedEncodeBatch(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                         const struct AADHipSegmentation *segmentation, uint32_t num_streams,
+                                         const int16_t *const *pcm, const uint32_t *num_samples, uint8_t *const *data,
+                                         const uint64_t *data_capacity, uint64_t *output_size)
+{
+  if (ctx == nullptr || parameter == nullptr || segmentation == nullptr || segmentation->segment_blocks == 0 ||
+      (num_streams != 0 && (pcm == nullptr || num_samples == nullptr || data == nullptr || data_capacity == nullptr)))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  if (num_streams == 0) return AAD_APIRESULT_OK;
+  for (uint32_t i = 0; i < num_streams; i++)
+    if (pcm[i] == nullptr || data[i] == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return encode_host_segmented(ctx, parameter, segmentation, num_streams, num_samples, data_capacity, output_size,
+                               [&](uint32_t i, uint64_t offset, uint64_t size, uint8_t *dst) {
+                                 memcpy(dst, reinterpret_cast<const uint8_t *>(pcm[i]) + offset, (size_t)size);
+                               },
+                               [&](uint32_t i, uint64_t offset, const uint8_t *src, uint64_t size) { memcpy(data[i] + offset, src, size); });
+}
+
 /* AADEncoder_EncodeWhole's data path (src/aad_encoder.c:814-891): planar int32 rows in, one image
  * out.  The planar -> interleaved int16 conversion writes straight into the pinned block; samples
  * must already be in int16 range, which the reference only asserts (src/aad_encoder.c:612) -
@@ -1630,18 +1842,18 @@ AADApiResult AADHip_DecodeBatch(struct AADHipContext *ctx, uint32_t num_streams,
 
 /* ------------------------------------------------------------------- reconstruction modes -- */
 
-AADApiResult AADHip_ReconstructPlanCreate(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
-                                          uint32_t num_streams, const struct AADHipStreamDesc *streams,
-                                          struct AADHipReconstructPlan **plan)
+/* segmentation: null for the reference encoder's images, else those of a segmented encode plan */
+static AADApiResult reconstruct_plan_create(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                            const struct AADHipSegmentation *segmentation, uint32_t num_streams,
+                                            const struct AADHipStreamDesc *streams, struct AADHipReconstructPlan **plan)
 {
-  if (ctx == nullptr || parameter == nullptr || plan == nullptr || (num_streams != 0 && streams == nullptr))
-    return AAD_APIRESULT_INVALID_ARGUMENT;
   *plan = nullptr;
   AADHipReconstructPlan *p = new (std::nothrow) AADHipReconstructPlan();
   if (p == nullptr) return AAD_APIRESULT_NG;
   memset(static_cast<void *>(p), 0, sizeof(*p));
   p->ctx = ctx;
-  AADApiResult rc = AADHip_EncodePlanCreate(ctx, parameter, num_streams, streams, &p->encode);
+  AADApiResult rc = segmentation ? AADHip_SegmentedEncodePlanCreate(ctx, parameter, segmentation, num_streams, streams, &p->encode)
+                                 : AADHip_EncodePlanCreate(ctx, parameter, num_streams, streams, &p->encode);
   if (rc == AAD_APIRESULT_OK) {
     /* the decoder sees exactly the images the encoder writes */
     AADHeaderInfo h;
@@ -1675,6 +1887,26 @@ AADApiResult AADHip_ReconstructPlanCreate(struct AADHipContext *ctx, const struc
   }
   *plan = p;
   return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_ReconstructPlanCreate(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                          uint32_t num_streams, const struct AADHipStreamDesc *streams,
+                                          struct AADHipReconstructPlan **plan)
+{
+  if (ctx == nullptr || parameter == nullptr || plan == nullptr || (num_streams != 0 && streams == nullptr))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  return reconstruct_plan_create(ctx, parameter, nullptr, num_streams, streams, plan);
+}
+
+AADApiResult AADHip_SegmentedReconstructPlanCreate(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                                   const struct AADHipSegmentation *segmentation, uint32_t num_streams,
+                                                   const struct AADHipStreamDesc *streams, struct AADHipReconstructPlan **plan)
+{
+  if (ctx == nullptr || parameter == nullptr || segmentation == nullptr || plan == nullptr || (num_streams != 0 && streams == nullptr))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *plan = nullptr;
+  if (segmentation->segment_blocks == 0) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return reconstruct_plan_create(ctx, parameter, segmentation, num_streams, streams, plan);
 }
 
 void AADHip_ReconstructPlanDestroy(struct AADHipReconstructPlan *plan)
@@ -1754,33 +1986,10 @@ uint64_t reconstruct_footprint(uint64_t samples, uint32_t ch, uint64_t image)
   return 2 * round_up(samples * ch, 8) * sizeof(int16_t) + round_up(image, 16) + sizeof(AADHipErrorStats);
 }
 
-bool device_block_reserve(AADHipContext *ctx, void **block, size_t *capacity, size_t bytes, const char *what)
-{
-  if (*capacity >= bytes) return true;
-  if (*block) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(*block);
-  }
-  *block = nullptr;
-  *capacity = 0;
-  const size_t want = bytes + bytes / 8 + 4096; /* some slack, so that a slightly larger next wave does not reallocate */
-  if (hipMalloc(block, want) == hipSuccess) {
-    *capacity = want;
-    return true;
-  }
-  (void)hipGetLastError();
-  *block = nullptr;
-  if (!hip_ok(ctx, hipMalloc(block, bytes), what)) {
-    *block = nullptr;
-    return false;
-  }
-  *capacity = bytes;
-  return true;
-}
 
 /* one wave: streams [first, first + count) of the batch, device-resident compute, chunked staging */
-AADApiResult reconstruct_wave(AADHipContext *ctx, const struct AADEncodeParameter *parameter, uint32_t count,
-                              const int16_t *const *pcm, const uint32_t *num_samples, int32_t output_kind,
+AADApiResult reconstruct_wave(AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                              const struct AADHipSegmentation *segmentation, uint32_t count, const int16_t *const *pcm, const uint32_t *num_samples, int32_t output_kind,
                               int16_t *const *out_pcm, struct AADHipErrorStats *stats, uint64_t chunk_bytes)
 {
   const uint32_t ch = parameter->num_channels;
@@ -1800,7 +2009,7 @@ AADApiResult reconstruct_wave(AADHipContext *ctx, const struct AADEncodeParamete
   }
   byte_prefix[count] = pcm_elems * sizeof(int16_t);
   AADHipReconstructPlan *plan = nullptr;
-  AADApiResult rc = AADHip_ReconstructPlanCreate(ctx, parameter, count, table.data(), &plan);
+  AADApiResult rc = reconstruct_plan_create(ctx, parameter, segmentation, count, table.data(), &plan);
   if (rc != AAD_APIRESULT_OK) return rc;
   DeviceGuard guard(ctx);
   /* device: [pcm in] ; [pcm out | statistics] ; [images].  The statistics sit behind the output PCM so that one flat range
@@ -1906,14 +2115,11 @@ AADApiResult reconstruct_wave(AADHipContext *ctx, const struct AADEncodeParamete
   return rc;
 }
 
-} /* namespace */
-
-AADApiResult AADHip_ReconstructBatch(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
-                                     uint32_t num_streams, const int16_t *const *pcm, const uint32_t *num_samples,
-                                     int32_t output_kind, int16_t *const *out_pcm, struct AADHipErrorStats *stats)
+/* AADHip_ReconstructBatch and its segmented form (segmentation non-null, segment_blocks checked) */
+AADApiResult reconstruct_batch(AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                               const struct AADHipSegmentation *segmentation, uint32_t num_streams, const int16_t *const *pcm,
+                               const uint32_t *num_samples, int32_t output_kind, int16_t *const *out_pcm, struct AADHipErrorStats *stats)
 {
-  if (ctx == nullptr || parameter == nullptr || (num_streams != 0 && (pcm == nullptr || num_samples == nullptr)))
-    return AAD_APIRESULT_INVALID_ARGUMENT;
   if (num_streams == 0) return AAD_APIRESULT_OK;
   const uint32_t ch = parameter->num_channels;
   std::vector<uint64_t> footprint(num_streams);
@@ -1923,28 +2129,52 @@ AADApiResult AADHip_ReconstructBatch(struct AADHipContext *ctx, const struct AAD
     if (size == 0) return AAD_APIRESULT_INVALID_FORMAT;
     footprint[i] = reconstruct_footprint(num_samples[i], ch, size);
   }
-  const uint64_t chunk = ctx->tile_bytes > 0 ? (uint64_t)ctx->tile_bytes : kChunkBudget;
-  uint64_t budget;
-  if (ctx->tile_bytes > 0) {
-    budget = (uint64_t)ctx->tile_bytes * 64u; /* a forced tile size: small waves too (tests) */
-  } else {
-    DeviceGuard guard(ctx);
-    size_t free_bytes = 0, total_bytes = 0;
-    if (!guard.ok || !hip_ok(ctx, hipMemGetInfo(&free_bytes, &total_bytes), "hipMemGetInfo")) return AAD_APIRESULT_NG;
-    /* what is free now plus what this context's own grow-only blocks already hold, less a quarter for everybody else */
-    const uint64_t own = ctx->rc_in_capacity + ctx->rc_out_capacity + ctx->scratch_capacity;
-    budget = ((uint64_t)free_bytes + own) / 4 * 3;
+  if (segmentation != nullptr) { /* the plans of the waves count chains per wave; the batch's count is refused up front */
+    AADHeaderInfo h; /* valid: CalculateEncodedSize took it */
+    (void)AADFormat_ParameterToHeader(parameter, 1, AAD_HIP_MAX_NUM_CHANNELS, &h);
+    uint64_t chains = 0;
+    for (uint32_t i = 0; i < num_streams; i++)
+      chains += (aad::stream_blocks(num_samples[i], h.num_samples_per_block) + segmentation->segment_blocks - 1) / segmentation->segment_blocks;
+    if (chains > UINT32_MAX) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "segmented reconstruction: more than %u chains", (unsigned)UINT32_MAX);
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
   }
+  const uint64_t chunk = staging_chunk(ctx);
+  uint64_t budget;
+  if (!wave_budget(ctx, &budget)) return AAD_APIRESULT_NG;
   AADApiResult rc = AAD_APIRESULT_OK;
   for (uint32_t first = 0; first < num_streams && rc == AAD_APIRESULT_OK;) {
     uint32_t n = 0;
     uint64_t sum = 0;
     while (first + n < num_streams && (n == 0 || sum + footprint[first + n] <= budget)) sum += footprint[first + n++]; /* a stream alone is always tried */
-    rc = reconstruct_wave(ctx, parameter, n, pcm + first, num_samples + first, output_kind, out_pcm ? out_pcm + first : nullptr,
+    rc = reconstruct_wave(ctx, parameter, segmentation, n, pcm + first, num_samples + first, output_kind, out_pcm ? out_pcm + first : nullptr,
                           stats ? stats + first : nullptr, chunk);
     first += n;
   }
   return rc;
+}
+
+} /* namespace */
+
+AADApiResult AADHip_ReconstructBatch(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                     uint32_t num_streams, const int16_t *const *pcm, const uint32_t *num_samples,
+                                     int32_t output_kind, int16_t *const *out_pcm, struct AADHipErrorStats *stats)
+{
+  if (ctx == nullptr || parameter == nullptr || (num_streams != 0 && (pcm == nullptr || num_samples == nullptr)))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  return reconstruct_batch(ctx, parameter, nullptr, num_streams, pcm, num_samples, output_kind, out_pcm, stats);
+}
+
+AADApiResult AADHip_SegmentedReconstructBatch(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                              const struct AADHipSegmentation *segmentation, uint32_t num_streams,
+                                              const int16_t *const *pcm, const uint32_t *num_samples, int32_t output_kind,
+                                              int16_t *const *out_pcm, struct AADHipErrorStats *stats)
+{
+  if (ctx == nullptr || parameter == nullptr || segmentation == nullptr || segmentation->segment_blocks == 0 ||
+      (num_streams != 0 && (pcm == nullptr || num_samples == nullptr)))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  return reconstruct_batch(ctx, parameter, segmentation, num_streams, pcm, num_samples, output_kind, out_pcm, stats);
 }
 
 #if AAD_PHASE_TIMING

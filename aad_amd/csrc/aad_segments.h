@@ -75,6 +75,97 @@ inline bool build_segment_chains(const AADHipStreamDesc *streams, uint32_t num_s
   return true;
 }
 
+/* ---- waves of the host-memory path (AADHip_SegmentedEncodeBatch) ----------------------------------------------------------------
+ *
+ * A wave is a run of consecutive chains of the batch's chain table that is resident on the device at once and encoded by ONE launch,
+ * so that all its chains run side by side: each chain's frames, warm-up included, in the wave's PCM block, and the bytes it keeps in
+ * the wave's output block, one chain after the other.  The budget is the device memory a wave may take; only the staging between
+ * the caller's buffers and those blocks is cut into chunks.  Chains carry no state, so a wave may end between any two chains; a
+ * chain whose input and output alone exceed the budget is a wave of its own.
+ *
+ * Addressing.  The kernel stores a chain's kept block i at data_offset + 31 + (first_block + w + i) block_size and the file header
+ * at data_offset (writes_header only), w being its warm-up.  A wave's table sets first_block = 0 and points data_offset at a VIRTUAL
+ * image start `lead` = 31 + w block_size bytes in front of the chain's kept bytes (0 for the header chain, which keeps block 0).
+ * Those lead bytes overlap the previous chain's bytes or the block's lead-in and are never written: warm-up blocks store nothing.
+ * The lead-in (out_begin) is as large as it must be for every data_offset to be a plain, non-negative offset. */
+struct WaveChain {
+  uint32_t stream;       /* the chain's stream in the batch */
+  uint32_t frame0;       /* first frame of the stream that the chain encodes (its first warm-up frame, if any) */
+  uint64_t image_offset; /* first byte of the stream's image that the chain writes: 0 (file header), or 31 + kept block * block_size */
+  uint64_t image_bytes;  /* bytes it writes there: up to its last kept block's end, the stream's short last block included */
+  uint64_t out_offset;   /* where those bytes lie in the wave's output block */
+};
+
+struct SegmentWave {
+  std::vector<ChainDesc> chains; /* the launch's chain table: pcm_offset into the wave's PCM block, data_offset into its output block */
+  std::vector<WaveChain> where;  /* per chain: its stream, its frames, the bytes it delivers */
+  uint64_t pcm_elems = 0;        /* int16 in the PCM block (every chain's frames start on 16 bytes) */
+  uint64_t out_begin = 0;        /* the output block's lead-in: its kept bytes are [out_begin, out_bytes) */
+  uint64_t out_bytes = 0;
+};
+
+inline uint64_t round_up16(uint64_t v) { return (v + 15) / 16 * 16; }
+
+/* The waves of a batch of host streams: num_samples[i] frames, an image of image_size[i] bytes (AADFormat_EncodedSize).  budget:
+ * bytes of PCM in + bytes out per wave.  False (and `out` untouched) as build_segment_chains. */
+inline bool build_segment_waves(const uint32_t *num_samples, const uint64_t *image_size, uint32_t num_streams, uint32_t channels,
+                                uint32_t spb, uint32_t block_size, uint32_t segment_blocks, uint32_t warmup_blocks, uint64_t budget,
+                                std::vector<SegmentWave> *out)
+{
+  std::vector<AADHipStreamDesc> streams(num_streams);
+  for (uint32_t i = 0; i < num_streams; i++) streams[i] = AADHipStreamDesc{0, 0, 0, num_samples[i], 0};
+  std::vector<ChainDesc> all;
+  if (!build_segment_chains(streams.data(), num_streams, channels, spb, block_size, segment_blocks, warmup_blocks, &all)) return false;
+  std::vector<SegmentWave> waves;
+  SegmentWave t;
+  uint64_t cost = 0, pos = 0; /* pos: the chains' bytes so far, from the lead-in's end */
+  auto close = [&]() {
+    if (t.chains.empty()) return;
+    uint64_t lead_in = 0;
+    for (size_t k = 0; k < t.chains.size(); k++) {
+      const uint64_t lead = t.chains[k].data_offset; /* still the chain's lead, at this point */
+      if (lead > t.where[k].out_offset && lead - t.where[k].out_offset > lead_in) lead_in = lead - t.where[k].out_offset;
+    }
+    t.out_begin = round_up16(lead_in);
+    for (size_t k = 0; k < t.chains.size(); k++) {
+      t.where[k].out_offset += t.out_begin;
+      t.chains[k].data_offset = t.where[k].out_offset - t.chains[k].data_offset;
+    }
+    t.out_bytes = t.out_begin + pos;
+    waves.push_back(std::move(t));
+    t = SegmentWave();
+    cost = pos = 0;
+  };
+  /* The table's own records say where a stream starts (its one writes_header chain, the first of its chains) and ends (the next
+   * stream's start, or the table's end): nothing here depends on how build_segment_chains counts a stream's segments. */
+  uint32_t stream = 0;
+  for (size_t c = 0; c < all.size(); c++) {
+    const ChainDesc &d = all[c];
+    if (d.writes_header && c != 0) stream++;
+    if (stream >= num_streams) return false; /* a table that does not match the batch: refused, never misread */
+    const bool last = c + 1 == all.size() || all[c + 1].writes_header;
+    const uint64_t kept = d.first_block + d.warmup_blocks;
+    const uint64_t begin = d.writes_header ? 0 : AAD_HEADER_SIZE + kept * block_size;
+    const uint64_t end = last ? image_size[stream] : AAD_HEADER_SIZE + (kept + segment_blocks) * block_size;
+    const uint64_t elems = ((uint64_t)d.num_frames * channels + 7) / 8 * 8, bytes = end - begin;
+    const uint64_t chain_cost = elems * sizeof(int16_t) + round_up16(bytes);
+    if (!t.chains.empty() && cost + chain_cost > budget) close();
+    ChainDesc e = d;
+    e.pcm_offset = t.pcm_elems;
+    e.data_offset = d.writes_header ? 0 : AAD_HEADER_SIZE + (uint64_t)d.warmup_blocks * block_size; /* the lead, made an offset by close() */
+    e.first_block = 0;
+    t.chains.push_back(e);
+    t.where.push_back(WaveChain{stream, (uint32_t)(d.pcm_offset / channels), begin, bytes, pos});
+    t.pcm_elems += elems;
+    pos += round_up16(bytes);
+    cost += chain_cost;
+  }
+  if (num_streams != 0 && stream + 1 != num_streams) return false;
+  close();
+  out->swap(waves);
+  return true;
+}
+
 } /* namespace aad */
 
 #endif /* AAD_SEGMENTS_H */

@@ -194,10 +194,11 @@ class Engine:
         return pcm, header
 
     # ---- reconstruction modes (the reference CLI's -r / -g / -c, src/main.c:275-503) ----------
-    def reconstruct_uniform(self, pcm, param, residual=False, want_stats=True):
+    def reconstruct_uniform(self, pcm, param, residual=False, want_stats=True, segment_blocks=None, warmup_blocks=0):
         """pcm: int16 cuda tensor [streams, samples, channels] -> (out int16 tensor of the same
         shape, stats float64 tensor [streams, 3] = RMSE, MSD, MaxAE or None).  Encode, decode and
-        the comparison run back to back on the device; the images stay in a scratch tensor."""
+        the comparison run back to back on the device; the images stay in a scratch tensor.
+        segment_blocks / warmup_blocks: over the images of a segmented encode (see encode_plan)."""
         torch = self.torch
         streams, samples, ch = pcm.shape
         assert ch == param.num_channels and pcm.dtype == torch.int16 and pcm.is_contiguous()
@@ -212,8 +213,14 @@ class Engine:
         d["data_size"] = stride
         d["num_samples"] = samples
         plan = C.c_void_p()
-        _check("AADHip_ReconstructPlanCreate",
-               self.lib.AADHip_ReconstructPlanCreate(self._ctx, C.byref(param), streams, d.ctypes.data, C.byref(plan)))
+        if segment_blocks is None:
+            _check("AADHip_ReconstructPlanCreate",
+                   self.lib.AADHip_ReconstructPlanCreate(self._ctx, C.byref(param), streams, d.ctypes.data, C.byref(plan)))
+        else:
+            seg = AADHipSegmentation(int(segment_blocks), int(warmup_blocks))
+            _check("AADHip_SegmentedReconstructPlanCreate",
+                   self.lib.AADHip_SegmentedReconstructPlanCreate(self._ctx, C.byref(param), C.byref(seg), streams, d.ctypes.data,
+                                                                  C.byref(plan)))
         try:
             images = torch.empty((streams, stride), dtype=torch.uint8, device=pcm.device)
             out = torch.empty_like(pcm)
@@ -228,9 +235,10 @@ class Engine:
             self.lib.AADHip_ReconstructPlanDestroy(plan)  # synchronises the stream first
         return out, stats
 
-    def reconstruct_host(self, pcm_list, param, residual=False, want_pcm=True, want_stats=True):
+    def reconstruct_host(self, pcm_list, param, residual=False, want_pcm=True, want_stats=True, segment_blocks=None, warmup_blocks=0):
         """pcm_list: int16 arrays [samples, channels] -> (list of int16 arrays or None,
-        ERROR_STATS_DTYPE array [streams] or None) through AADHip_ReconstructBatch."""
+        ERROR_STATS_DTYPE array [streams] or None) through AADHip_ReconstructBatch, or with segment_blocks
+        AADHip_SegmentedReconstructBatch (the images of a segmented encode, see encode_plan)."""
         n = len(pcm_list)
         pcm_list = [np.ascontiguousarray(p, dtype=np.int16) for p in pcm_list]
         nsamp = np.array([p.shape[0] for p in pcm_list], dtype=np.uint32)
@@ -238,16 +246,25 @@ class Engine:
         stats = np.zeros(n, dtype=ERROR_STATS_DTYPE) if want_stats else None
         pp = (C.c_void_p * n)(*[p.ctypes.data for p in pcm_list])
         op = (C.c_void_p * n)(*[o.ctypes.data for o in outs]) if want_pcm else None
-        _check("AADHip_ReconstructBatch",
-               self.lib.AADHip_ReconstructBatch(self._ctx, C.byref(param), n, pp, nsamp.ctypes.data,
-                                                RECONSTRUCT_RESIDUAL if residual else RECONSTRUCT_DECODED, op,
-                                                stats.ctypes.data if want_stats else None))
+        kind = RECONSTRUCT_RESIDUAL if residual else RECONSTRUCT_DECODED
+        sp = stats.ctypes.data if want_stats else None
+        if segment_blocks is None:
+            _check("AADHip_ReconstructBatch",
+                   self.lib.AADHip_ReconstructBatch(self._ctx, C.byref(param), n, pp, nsamp.ctypes.data, kind, op, sp))
+        else:
+            seg = AADHipSegmentation(int(segment_blocks), int(warmup_blocks))
+            _check("AADHip_SegmentedReconstructBatch",
+                   self.lib.AADHip_SegmentedReconstructBatch(self._ctx, C.byref(param), C.byref(seg), n, pp, nsamp.ctypes.data,
+                                                             kind, op, sp))
         return outs, stats
 
     # ---- host-memory batches ----------------------------------------------------------------
-    def encode_host(self, pcm_list, param, state=None):
+    def encode_host(self, pcm_list, param, state=None, segment_blocks=None, warmup_blocks=0):
         """pcm_list: list of int16 arrays [samples, channels] -> list of bytes.  state: optional
-        LANE_STATE_DTYPE array [streams * channels], updated in place."""
+        LANE_STATE_DTYPE array [streams * channels], updated in place.  segment_blocks / warmup_blocks:
+        a segmented encode (AADHip_SegmentedEncodeBatch, see encode_plan), which takes no state."""
+        if state is not None and segment_blocks is not None:
+            raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
         n = len(pcm_list)
         pcm_list = [np.ascontiguousarray(p, dtype=np.int16) for p in pcm_list]
         nsamp = np.array([p.shape[0] for p in pcm_list], dtype=np.uint32)
@@ -256,10 +273,16 @@ class Engine:
         sizes = np.zeros(n, dtype=np.uint64)
         pp = (C.c_void_p * n)(*[p.ctypes.data for p in pcm_list])
         op = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        sp = state.ctypes.data if state is not None else None
-        _check("AADHip_EncodeBatch",
-               self.lib.AADHip_EncodeBatch(self._ctx, C.byref(param), n, pp, nsamp.ctypes.data, op,
-                                           caps.ctypes.data, sizes.ctypes.data, sp))
+        if segment_blocks is None:
+            sp = state.ctypes.data if state is not None else None
+            _check("AADHip_EncodeBatch",
+                   self.lib.AADHip_EncodeBatch(self._ctx, C.byref(param), n, pp, nsamp.ctypes.data, op,
+                                               caps.ctypes.data, sizes.ctypes.data, sp))
+        else:
+            seg = AADHipSegmentation(int(segment_blocks), int(warmup_blocks))
+            _check("AADHip_SegmentedEncodeBatch",
+                   self.lib.AADHip_SegmentedEncodeBatch(self._ctx, C.byref(param), C.byref(seg), n, pp, nsamp.ctypes.data, op,
+                                                        caps.ctypes.data, sizes.ctypes.data))
         return [o[: int(s)].tobytes() for o, s in zip(outs, sizes)]
 
     def decode_host(self, images):

@@ -206,6 +206,20 @@ AADApiResult AADHip_EncodeBatch(
     uint8_t *const *data, const uint64_t *data_capacity, uint64_t *output_size,
     struct AADHipLaneState *state);
 
+/* AADHip_EncodeBatch for a segmented encode: for the same PCM, parameter and segmentation, exactly the bytes of
+ * AADHip_SegmentedEncodePlanCreate + AADHip_EncodePlanRun on device-resident copies (see above the struct AADHipSegmentation).
+ * No state argument: a segmented encode starts from fresh encoders.  As in AADHip_ReconstructBatch, the compute runs over a WAVE
+ * resident on the device: every chain of it, each with its warm-up frames, in one launch.  The PCM goes up and the images come
+ * down through the context's pinned blocks in chunks.  A batch beyond three quarters of the device's free memory runs as several
+ * waves of consecutive chains.  Results do not depend on any of it.
+ * Errors are those of AADHip_EncodeBatch, plus AAD_APIRESULT_INVALID_ARGUMENT for a null `segmentation`, segment_blocks == 0 and
+ * more than UINT32_MAX chains in the batch. */
+AADApiResult AADHip_SegmentedEncodeBatch(
+    struct AADHipContext *context, const struct AADEncodeParameter *parameter,
+    const struct AADHipSegmentation *segmentation,
+    uint32_t num_streams, const int16_t *const *pcm, const uint32_t *num_samples,
+    uint8_t *const *data, const uint64_t *data_capacity, uint64_t *output_size);
+
 /* data[i]/data_size[i]: .aad images (all of one format); pcm[i] must hold
  * pcm_capacity_frames[i] >= header.num_samples frames.  decoded_frames[i] (may be NULL) receives
  * the frames written: header.num_samples, or fewer when the image ends early - the reference's
@@ -260,6 +274,22 @@ AADApiResult AADHip_ReconstructPlanRun(
  * quarters of the device's free memory is run as several waves of consecutive streams.  Results do not depend on any of it. */
 AADApiResult AADHip_ReconstructBatch(
     struct AADHipContext *context, const struct AADEncodeParameter *parameter,
+    uint32_t num_streams, const int16_t *const *pcm, const uint32_t *num_samples,
+    int32_t output_kind, int16_t *const *out_pcm, struct AADHipErrorStats *stats);
+
+/* The reconstruction modes over the images of a segmented encode (AADHip_SegmentedEncodePlanCreate): the images are the segmented
+ * ones, the statistics keep their meaning - the decoded segmented image against the original, with the same tie rule and
+ * AAD_HIP_OPTION_COMPARE_ORDER.  The plan is an ordinary one: AADHip_ReconstructPlanRun and AADHip_ReconstructPlanDestroy work on
+ * it.  The batch form takes the waves and chunked staging of AADHip_ReconstructBatch.  Errors are those of the unsegmented forms,
+ * plus AAD_APIRESULT_INVALID_ARGUMENT for a null `segmentation`, segment_blocks == 0 and more than UINT32_MAX chains. */
+AADApiResult AADHip_SegmentedReconstructPlanCreate(
+    struct AADHipContext *context, const struct AADEncodeParameter *parameter,
+    const struct AADHipSegmentation *segmentation,
+    uint32_t num_streams, const struct AADHipStreamDesc *streams,
+    struct AADHipReconstructPlan **plan);
+AADApiResult AADHip_SegmentedReconstructBatch(
+    struct AADHipContext *context, const struct AADEncodeParameter *parameter,
+    const struct AADHipSegmentation *segmentation,
     uint32_t num_streams, const int16_t *const *pcm, const uint32_t *num_samples,
     int32_t output_kind, int16_t *const *out_pcm, struct AADHipErrorStats *stats);
 
