@@ -58,6 +58,8 @@ class AADHipLaneState(C.Structure):  # include/aad_hip.h
 STREAM_DESC_DTYPE = np.dtype([("pcm_offset", "<u8"), ("data_offset", "<u8"), ("data_size", "<u8"),
                               ("num_samples", "<u4"), ("reserved", "<u4")])
 ERROR_STATS_DTYPE = np.dtype([("rms_error", "<f8"), ("mean_abs_error", "<f8"), ("max_abs_error", "<f8")])  # AADHipErrorStats
+WINDOW_DTYPE = np.dtype([("stream", "<i8"), ("first_frame", "<i8")])  # struct AADHipWindow: an int64 pair, a torch int64 [N, 2] row
+SAMPLE_INT16, SAMPLE_FLOAT32 = 0, 1  # enum AADHipSampleType
 RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL = 0, 1  # enum AADHipReconstructOutput
 OPTION_LANE_MAPPING, OPTION_TRIAL_LANES, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_COMPARE_ORDER = 0, 1, 2, 3, 4  # enum AADHipOption
 LANE_MAPPINGS = {"auto": 0, "dense": 1, "quad": 2, "quad-fused": 3, "dense-tiled": 4}  # enum AADHipLaneMapping
@@ -82,6 +84,7 @@ HIP_SYMBOLS = [
     "AADHip_ReconstructPlanCreate", "AADHip_ReconstructPlanDestroy", "AADHip_ReconstructPlanRun",
     "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate", "AADHip_SegmentedEncodeBatch",
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
+    "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -162,6 +165,12 @@ def _declare_hip(lib):
     lib.AADHip_DecodePlanDestroy.restype = None
     lib.AADHip_DecodePlanRun.argtypes = [vp, vp, vp]
     lib.AADHip_DecodePlanRun.restype = C.c_int
+    lib.AADHip_WindowDecodePlanCreate.argtypes = [vp, C.POINTER(AADHeaderInfo), C.c_int32, C.c_uint32, vp, C.POINTER(vp)]
+    lib.AADHip_WindowDecodePlanCreate.restype = C.c_int
+    lib.AADHip_WindowDecodePlanDestroy.argtypes = [vp]
+    lib.AADHip_WindowDecodePlanDestroy.restype = None
+    lib.AADHip_WindowDecodePlanRun.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp]
+    lib.AADHip_WindowDecodePlanRun.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

@@ -1,0 +1,258 @@
+/*
+ * aad_decode_window.hip.h - window decode (AADHip_WindowDecodePlanRun): sample-accurate crops of many streams, straight into
+ * planar [windows, channels, frames] rows of int16 or float32.
+ *
+ * Every block header carries the decoder's whole state (reference src/aad_decoder.c:364-380), so the frames of a crop come from the
+ * blocks that cover it alone.  One lane per (window, block-in-window, channel): a window of T frames touches at most
+ * K = ceil((T - 1) / spb) + 1 blocks (aad_launch_policy.h window_blocks_spanned), lane k of a window decodes block
+ * first_frame / spb + k of its stream and the lanes past the window's own last block idle.  A lane decodes its block from the
+ * header on - the samples in front of the crop carry the state - with the per-lane dense decoder's pieces (aad_decode.hip.h: header
+ * parse, code fetch one chunk ahead, decode_chunk16, byte-load tail, M/S finish through pair_swap), stops after the last sample the
+ * window needs, and stores only the samples inside the window: whole 16-sample chunks as 16-byte vectors at the row's own
+ * (2- or 4-byte) alignment, the head and tail of a row sample by sample.  Frames the stream does not produce (past num_samples,
+ * past the bytes that are there, a stream index out of range) are written as zeros by the lane whose block holds them.
+ *
+ * Reads: the 18-byte channel headers only when that many bytes are present, chunk loads only while they lie inside the stream's
+ * bytes, the tail byte by byte against the same bound - exactly decode_blocks_kernel's `avail` rule, so no byte outside
+ * [data_offset, data_offset + data_size) is read and a truncated image decodes as under AADHip_DecodePlanRun.
+ */
+#ifndef AAD_DECODE_WINDOW_HIP_H
+#define AAD_DECODE_WINDOW_HIP_H
+
+#include "aad_decode.hip.h"
+
+namespace aad {
+
+struct WindowArgs {
+  const StreamDesc *streams;
+  const uint8_t *data;
+  const uint64_t *windows; /* [num_windows][2]: stream, first_frame (struct AADHipWindow) */
+  void *out;               /* [num_windows][channels][frames] int16 or float32 */
+  uint64_t lanes;          /* num_windows * blocks_per_window * channels */
+  uint32_t blocks_per_window;
+  uint32_t frames;
+  uint32_t num_streams;
+  uint32_t channels;
+  uint32_t block_size;
+  uint32_t samples_per_block;
+  uint32_t header_bytes; /* 31 (file image) or 0 (bare block) */
+  uint32_t mid_side;
+  uint32_t bits;
+  uint32_t reserved;
+};
+
+typedef float f32x4_u4 __attribute__((ext_vector_type(4), aligned(4))); /* a 16-byte store at 4-byte alignment */
+
+/* one row segment of a lane: output element t = base + i for sample i of the block, kept where lo <= t < hi */
+template <bool F32>
+struct WindowRow {
+  using T = std::conditional_t<F32, float, int16_t>;
+  T *row;
+  int64_t base, lo, hi;
+  __device__ __forceinline__ static T convert(int32_t y)
+  {
+    if constexpr (F32) return (float)y * (1.0f / 32768.0f); /* exact: an int16 times a power of two */
+    else return (T)y;
+  }
+  __device__ __forceinline__ void one(uint32_t i, int32_t y) const
+  {
+    const int64_t t = base + (int64_t)i;
+    if (t >= lo && t < hi) row[t] = convert(y);
+  }
+  /* samples i0 .. i0 + 15 */
+  __device__ __forceinline__ void chunk(uint32_t i0, const int32_t *y) const
+  {
+    const int64_t t0 = base + (int64_t)i0;
+    if (t0 + kChunk <= lo || t0 >= hi) return;
+    if (t0 >= lo && t0 + kChunk <= hi) {
+      T *p = row + t0;
+      if constexpr (F32) {
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+          *reinterpret_cast<f32x4_u4 *>(p + 4 * q) = f32x4_u4{convert(y[4 * q]), convert(y[4 * q + 1]), convert(y[4 * q + 2]), convert(y[4 * q + 3])};
+      } else {
+        const ChunkPcm o = pack_chunk_pcm<1, false>(y, 0);
+        store_u32x4<false>(p, o.v[0]);
+        store_u32x4<false>(p + 8, o.v[1]);
+      }
+      return;
+    }
+#pragma unroll
+    for (int j = 0; j < kChunk; j++) one(i0 + (uint32_t)j, y[j]);
+  }
+  /* zeros over [from, hi) */
+  __device__ __forceinline__ void zeros(int64_t from) const
+  {
+    for (int64_t t = from > lo ? from : lo; t < hi; t++) row[t] = (T)0;
+  }
+};
+
+/* CHF: 1 / 2 = the mono / stereo fast paths (wide chunk loads), 0 = any channel count (byte loads) */
+template <int BITS, int CHF, bool MS, bool F32>
+__device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane)
+{
+  const uint32_t ch = CHF ? CHF : a.channels;
+  const uint64_t per_window = (uint64_t)a.blocks_per_window * ch;
+  const uint64_t w = lane / per_window;
+  const uint32_t r = (uint32_t)(lane - w * per_window);
+  const uint32_t k = r / ch, c = r - k * ch;
+  const uint64_t stream = a.windows[2 * w], first_frame = a.windows[2 * w + 1];
+  const uint64_t spb = a.samples_per_block, frames = a.frames;
+  const uint64_t phase = first_frame % spb;
+  const uint64_t kspb = (uint64_t)k * spb;
+  if (kspb >= frames + phase) return; /* past the window's last block: lanes of one (window, block) leave together */
+
+  WindowRow<F32> out;
+  out.row = reinterpret_cast<typename WindowRow<F32>::T *>(a.out) + (w * ch + c) * frames;
+  out.base = (int64_t)kspb - (int64_t)phase;
+  out.lo = out.base > 0 ? out.base : 0;
+  out.hi = out.base + (int64_t)spb < (int64_t)frames ? out.base + (int64_t)spb : (int64_t)frames;
+
+  /* samples of this block the window needs, as far as the stream has them (n = 0: none) */
+  uint32_t n = 0, avail = 0;
+  const uint8_t *src = a.data;
+  if (stream < a.num_streams) {
+    const StreamDesc sd = a.streams[stream];
+    if (first_frame < sd.num_samples) {
+      const uint64_t b = first_frame / spb + k;
+      const uint64_t first = b * spb;
+      if (first < sd.num_samples) {
+        const uint64_t left = sd.num_samples - first, need = (uint64_t)(out.hi - out.base);
+        n = (uint32_t)(left < need ? left : need);
+      }
+      /* bytes of this stream still present from the start of this block */
+      const uint64_t block_off = a.header_bytes + b * a.block_size;
+      const uint64_t avail64 = sd.data_size > block_off ? sd.data_size - block_off : 0;
+      avail = avail64 > 0x7FFFFFFFu ? 0x7FFFFFFFu : (uint32_t)avail64;
+      src = a.data + sd.data_offset + block_off;
+      if (avail < (uint32_t)kBlockHeaderBytesPerCh * ch) n = 0; /* DecodeBlock: INSUFFICIENT_DATA */
+    }
+  }
+
+  Lane L = {0, 0, 0, 0, 0, 0, 0, 0, kIdxBias};
+  if (n) { /* block header - reference src/aad_decoder.c:364-380 */
+    const uint8_t *hp = src + c * kBlockHeaderBytesPerCh;
+    const uint32_t v = load_be16(hp);
+    L.idxb = min((int32_t)(v >> 4), (int32_t)kHeaderIdxMax) + kIdxBias;
+    const uint32_t shift = v & 0xFu;
+    L.w0 = (int32_t)((uint32_t)(int32_t)(int16_t)load_be16(hp + 2) << shift);
+    L.h0 = (int16_t)load_be16(hp + 4);
+    L.w1 = (int32_t)((uint32_t)(int32_t)(int16_t)load_be16(hp + 6) << shift);
+    L.h1 = (int16_t)load_be16(hp + 8);
+    L.w2 = (int32_t)((uint32_t)(int32_t)(int16_t)load_be16(hp + 10) << shift);
+    L.h2 = (int16_t)load_be16(hp + 12);
+    L.w3 = (int32_t)((uint32_t)(int32_t)(int16_t)load_be16(hp + 14) << shift);
+    L.h3 = (int16_t)load_be16(hp + 16);
+  }
+
+  /* inverse mid/side: the partner channel is the neighbouring lane, of the same window and block, with the same trip counts */
+  auto finish = [&](int32_t y) -> int32_t {
+    if (MS) {
+      const int32_t other = (int32_t)pair_swap<false>((uint32_t)y, c);
+      return c == 0 ? clip16(y + other) : clip16(other - y);
+    }
+    return y;
+  };
+
+  constexpr int US = Pack<BITS>::kUnitSamples, UB = Pack<BITS>::kUnitBytes;
+  const uint32_t coded = n > (uint32_t)kTaps ? n - kTaps : 0;
+  uint32_t done = 0;
+
+  /* the first four samples are stored verbatim in the header - reference :386-391 */
+  {
+    const int32_t y0 = finish(L.h3), y1 = finish(L.h2), y2 = finish(L.h1), y3 = finish(L.h0);
+    if (n > 0) out.one(0, y0);
+    if (n > 1) out.one(1, y1);
+    if (n > 2) out.one(2, y2);
+    if (n > 3) out.one(3, y3);
+  }
+
+  if constexpr (CHF != 0) {
+    /* full 16-sample chunks whose wide load stays inside the stream's bytes, fetched one chunk ahead */
+    using CC = ChunkCodes<BITS, (CHF ? CHF : 1)>;
+    constexpr uint32_t kStride = Pack<BITS>::kChunkBytes * (CHF ? CHF : 1);
+    const uint32_t body = (uint32_t)kBlockHeaderBytesPerCh * ch;
+    uint32_t full = coded / kChunk;
+    if (avail < body + CC::kLoadBytes) {
+      full = 0;
+    } else {
+      const uint32_t fit = (avail - body - CC::kLoadBytes) / kStride + 1;
+      full = full < fit ? full : fit;
+    }
+    const uint8_t *cp = src + body;
+    CC next;
+    next.r[0] = next.r[1] = next.r[2] = next.r[3] = 0;
+    if (full) next.load(cp);
+    next.touch();
+    for (uint32_t q = 0; q < full; q++) {
+      uint32_t wd[2] = {0, 0};
+      next.unpack(c, wd);
+      if (q + 1 < full) cp += kStride; /* unconditional prefetch: the last iteration re-reads its own chunk */
+      next.load(cp);
+      int32_t y[kChunk];
+      decode_chunk16<BITS>(L, wd, lds, y, finish);
+      next.touch();
+      out.chunk((uint32_t)kTaps + q * kChunk, y);
+    }
+    done = full * kChunk;
+  } else {
+    /* any channel count: the units of a channel are UB * channels bytes apart (byte loads) */
+    using CA = ChunkCodesAny<BITS>;
+    const uint32_t body = (uint32_t)kBlockHeaderBytesPerCh * ch;
+    const uint32_t unit_stride = UB * ch, row = CA::kUnits * unit_stride;
+    uint32_t full = coded / kChunk;
+    const uint32_t fit = avail > body ? (avail - body) / row : 0u;
+    full = full < fit ? full : fit;
+    const uint8_t *cp = src + body + c * UB;
+    CA next;
+    for (auto &v : next.b) v = 0;
+    if (full) next.load(cp, unit_stride);
+    next.touch();
+    for (uint32_t q = 0; q < full; q++) {
+      uint32_t wd[2] = {0, 0};
+      next.unpack(wd);
+      if (q + 1 < full) cp += row;
+      next.load(cp, unit_stride);
+      int32_t y[kChunk];
+      decode_chunk16<BITS>(L, wd, lds, y, finish);
+      next.touch();
+      out.chunk((uint32_t)kTaps + q * kChunk, y);
+    }
+    done = full * kChunk;
+  }
+
+  /* remaining units: byte loads, bytes past the stream read as zero */
+  {
+    const uint32_t unit_stride = UB * ch;
+    const uint32_t base = (uint32_t)kBlockHeaderBytesPerCh * ch + c * UB;
+    for (uint32_t i = done; i < coded; i += US) {
+      const uint32_t o = base + (i / US) * unit_stride;
+      uint32_t acc = 0;
+#pragma unroll
+      for (int q = 0; q < UB; q++) acc = (acc << 8) | (o + q < avail ? (uint32_t)src[o + q] : 0u);
+      acc <<= 32 - 8 * UB; /* codes to the top of the word */
+#pragma unroll
+      for (int q = 0; q < US; q++) {
+        const int32_t y = finish(decode_step<BITS>(L, acc >> (32 - BITS), lds));
+        acc <<= BITS;
+        if (i + q < coded) out.one((uint32_t)kTaps + i + q, y);
+      }
+    }
+  }
+  out.zeros(out.base + (int64_t)n);
+}
+
+template <int BITS, int CHF, bool MS, bool F32>
+__global__ void __launch_bounds__(256) decode_window_kernel(WindowArgs a)
+{
+  __shared__ __attribute__((aligned(16))) char lds[kLdsBytesDenseDec];
+  stage_tables<BITS, false>(lds);
+  stage_dense_decode_tables<BITS>(lds);
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x; /* a multiple of 64: the lanes of a channel pair stay neighbours */
+  for (uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; lane < a.lanes; lane += stride)
+    window_lane<BITS, CHF, MS, F32>(a, lds, lane);
+}
+
+} /* namespace aad */
+
+#endif /* AAD_DECODE_WINDOW_HIP_H */

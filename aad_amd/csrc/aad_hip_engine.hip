@@ -2,7 +2,8 @@
  * aad_hip_engine.hip - host side of the batched C-ABI declared in include/aad_hip.h:
  * contexts, plans (uploaded stream tables), kernel launches and the host-memory convenience
  * calls.  Device code lives in aad_encode.hip.h / aad_decode.hip.h (shared parts: aad_device.hip.h)
- * and, for the split decoder, in its own unit aad_decode_split.hip.  gfx950 only; no CPU code path -
+ * and, for the split, sector-tiled and window decoders, in units of their own (aad_decode_split.hip,
+ * aad_decode_tiled.hip, aad_decode_window.hip).  gfx950 only; no CPU code path -
  * every entry point that needs the GPU fails with AAD_APIRESULT_NG when HIP does.
  */
 #include <hip/hip_runtime.h>
@@ -22,6 +23,7 @@
 #include "aad_compare.hip.h"
 #include "aad_launch.h" /* and aad_launch_policy.h */
 #include "aad_decode.hip.h"
+#include "aad_decode_window.hip.h"
 #include "aad_encode.hip.h"
 #include "aad_format.h"
 #include "aad_hip_internal.h"
@@ -113,6 +115,12 @@ struct AADHipDecodePlan {
   aad::DecodeArgs args;
   aad::StreamDesc *d_streams;
   uint64_t *d_prefix;
+};
+
+struct AADHipWindowDecodePlan {
+  AADHipContext *ctx;
+  aad::DecodeArgs args; /* format and table (decode_plan_init); the windows come with each run */
+  aad::StreamDesc *d_streams;
 };
 
 struct AADHipReconstructPlan {
@@ -862,6 +870,91 @@ AADApiResult AADHip_DecodePlanRun(struct AADHipDecodePlan *plan, const uint8_t *
   if ((reinterpret_cast<uintptr_t>(device_pcm) & 63u) != 0) a.stream_stores = 0;
   aad::tl_launch_signal = signal;
   return finish_signal(ctx, signal, run_decode(ctx, a));
+}
+
+/* ------------------------------------------------------------------------- window decode -- */
+
+static_assert(sizeof(AADHipWindow) == 2 * sizeof(uint64_t), "window table layout");
+
+AADApiResult AADHip_WindowDecodePlanCreate(struct AADHipContext *ctx, const struct AADHeaderInfo *format, int32_t has_file_header,
+                                           uint32_t num_streams, const struct AADHipStreamDesc *streams,
+                                           struct AADHipWindowDecodePlan **plan)
+{
+  if (ctx == nullptr || format == nullptr || plan == nullptr || (num_streams != 0 && streams == nullptr))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *plan = nullptr;
+  std::vector<uint64_t> prefix((size_t)num_streams + 1);
+  aad::DecodeArgs args;
+  const AADApiResult rc = decode_plan_init(format, has_file_header, num_streams, streams, prefix.data(), &args);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  AADHipWindowDecodePlan *p = new (std::nothrow) AADHipWindowDecodePlan();
+  if (p == nullptr) return AAD_APIRESULT_NG;
+  p->ctx = ctx;
+  p->d_streams = nullptr;
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams)) {
+    if (p->d_streams) (void)hipFree(p->d_streams);
+    delete p;
+    return AAD_APIRESULT_NG;
+  }
+  p->args = args;
+  p->args.streams = p->d_streams;
+  *plan = p;
+  return AAD_APIRESULT_OK;
+}
+
+void AADHip_WindowDecodePlanDestroy(struct AADHipWindowDecodePlan *plan)
+{
+  if (plan == nullptr) return;
+  DeviceGuard guard(plan->ctx);
+  if (guard.ok) {
+    (void)hipStreamSynchronize(plan->ctx->stream);
+    (void)hipFree(plan->d_streams);
+  }
+  delete plan;
+}
+
+AADApiResult AADHip_WindowDecodePlanRun(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
+                                        const struct AADHipWindow *device_windows, uint32_t frames_per_window, int32_t sample_type,
+                                        void *device_out)
+{
+  if (plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = plan->ctx;
+  const aad::LaunchSignal signal = take_signal(ctx);
+  if (frames_per_window == 0 || (sample_type != AAD_HIP_SAMPLE_INT16 && sample_type != AAD_HIP_SAMPLE_FLOAT32) ||
+      (num_windows != 0 && (device_data == nullptr || device_windows == nullptr || device_out == nullptr)))
+    return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  const aad::DecodeArgs &d = plan->args;
+  const aad::WindowLaunch p =
+      aad::plan_window_decode(ctx->device_info, ctx->knobs, aad::WindowBatch{num_windows, frames_per_window, d.channels, d.bits, d.samples_per_block});
+  if (!p.ok) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "window decode: %llu windows x %u channels x %u frames overflow 64 bits",
+             (unsigned long long)num_windows, d.channels, frames_per_window);
+    return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+  if (num_windows == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
+  if (d.bits < 2 || d.bits > 4) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_FORMAT);
+  aad::WindowArgs a;
+  memset(&a, 0, sizeof(a));
+  a.streams = d.streams;
+  a.data = device_data;
+  a.windows = reinterpret_cast<const uint64_t *>(device_windows);
+  a.out = device_out;
+  a.lanes = p.lanes;
+  a.blocks_per_window = p.blocks_per_window;
+  a.frames = frames_per_window;
+  a.num_streams = d.num_streams;
+  a.channels = d.channels;
+  a.block_size = d.block_size;
+  a.samples_per_block = d.samples_per_block;
+  a.header_bytes = d.header_bytes;
+  a.mid_side = d.mid_side;
+  a.bits = d.bits;
+  aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
+  aad::launch_decode_window(a, p, sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+  return finish_signal(ctx, signal, hip_ok(ctx, hipGetLastError(), "window decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG);
 }
 
 } /* extern "C" */

@@ -28,6 +28,9 @@ extern thread_local LaunchSignal tl_launch_signal; /* defined in aad_hip_engine.
 struct DecodeArgs;
 void launch_decode_split(const DecodeArgs &args, const DecodeLaunch &p, int32_t *residual, hipStream_t stream);
 void launch_decode_tiled(const DecodeArgs &args, const DecodeLaunch &p, hipStream_t stream);
+/* aad_decode_window.hip: the window decoder (AADHip_WindowDecodePlanRun), int16 or float32 rows */
+struct WindowArgs;
+void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
 }
 
 #define AAD_LAUNCH(kernel, grid, block, lds, stream, ...)                                                           \

@@ -304,6 +304,49 @@ inline DecodeLaunch plan_decode(const Device &d, const Knobs &k, const DecodeBat
   return p;
 }
 
+/* ---- window decode (AADHip_WindowDecodePlanRun): one lane per (window, block-in-window, channel) ---------------------------- */
+struct WindowBatch {
+  uint64_t windows;
+  uint32_t frames, channels, bits, samples_per_block;
+};
+struct WindowLaunch {
+  bool ok;                    /* false: N * C * T elements (or their bytes as float32) or the lane count overflow 64 bits */
+  uint32_t blocks_per_window; /* K: the most blocks a window of `frames` frames can touch */
+  uint32_t workgroup, grid, lds;
+  uint64_t lanes;    /* windows * K * channels; the kernel walks them grid-stride when the grid is capped */
+  uint64_t elements; /* windows * channels * frames */
+};
+
+/* blocks touched by frames [first, first + frames) when `first` sits `phase` frames into its block (frames >= 1) */
+inline uint64_t window_blocks_at(uint64_t phase, uint64_t frames, uint64_t spb) { return (phase + frames - 1) / spb + 1; }
+/* ... at the worst phase (spb - 1): ceil((frames - 1) / spb) + 1 */
+inline uint64_t window_blocks_spanned(uint64_t frames, uint64_t spb) { return frames == 0 ? 0 : (frames - 1 + spb - 1) / spb + 1; }
+
+/* 2^20 workgroups (2^28 threads at 256) and beyond that the kernel's grid-stride loop: a dispatch's grid is a 32-bit work-item count */
+constexpr uint64_t kWindowMaxGrid = 1ull << 20;
+
+/* The window kernel is the per-lane dense decoder with predicated stores: the dense decoder's workgroup rule (one-wave workgroups
+ * while the batch has at most one wave per SIMD) and its occupancy cap (dense_decode_lds_pad) */
+inline WindowLaunch plan_window_decode(const Device &d, const Knobs &k, const WindowBatch &b)
+{
+  WindowLaunch p = {};
+  if (b.frames == 0 || b.samples_per_block == 0 || b.channels == 0) return p;
+  const uint64_t kb = window_blocks_spanned(b.frames, b.samples_per_block);
+  uint64_t per_window = 0, elements = 0, bytes = 0;
+  if (__builtin_mul_overflow(kb, (uint64_t)b.channels, &per_window) || __builtin_mul_overflow(b.windows, per_window, &p.lanes)) return p;
+  if (__builtin_mul_overflow(b.windows, (uint64_t)b.channels * b.frames, &elements) || __builtin_mul_overflow(elements, (uint64_t)4, &bytes))
+    return p;
+  p.ok = true;
+  p.blocks_per_window = (uint32_t)kb;
+  p.elements = elements;
+  if (p.lanes == 0) return p;
+  p.workgroup = pick_workgroup(d, p.lanes);
+  const uint64_t groups = (p.lanes + p.workgroup - 1) / p.workgroup;
+  p.grid = (uint32_t)(groups < kWindowMaxGrid ? groups : kWindowMaxGrid);
+  if (p.workgroup == 256u) p.lds = dense_decode_lds_pad(d, k, p.lanes, b.channels, b.bits);
+  return p;
+}
+
 } /* namespace aad */
 
 #endif /* AAD_LAUNCH_POLICY_H */

@@ -10,7 +10,7 @@ import numpy as np
 
 from .capi import (AADApiResult, AADHeaderInfo, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
                    OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
-                   STREAM_DESC_DTYPE, TRIAL_LANES, load_library, make_parameter)
+                   SAMPLE_FLOAT32, SAMPLE_INT16, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, load_library, make_parameter)
 
 
 def _check(where, rc):
@@ -141,6 +141,16 @@ class Engine:
                                                 descs.ctypes.data, C.byref(plan)))
         return DecodePlan(self, plan, header, descs)
 
+    def window_decode_plan(self, header, descs, has_file_header=True):
+        """A stream table for window decodes (AADHip_WindowDecodePlanCreate; pcm_offset is ignored): WindowDecodePlan.run
+        decodes crops [first_frame, first_frame + frames) of any streams of it into planar [N, C, T] rows."""
+        descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
+        plan = C.c_void_p()
+        _check("AADHip_WindowDecodePlanCreate",
+               self.lib.AADHip_WindowDecodePlanCreate(self._ctx, C.byref(header), 1 if has_file_header else 0, len(descs),
+                                                      descs.ctypes.data, C.byref(plan)))
+        return WindowDecodePlan(self, plan, header, descs)
+
     # ---- uniform batches (every stream the same length) -----------------------------------
     def uniform_encode_plan(self, param, num_streams, num_samples, segment_blocks=None, warmup_blocks=0):
         """Stream table for a [streams, samples, channels] int16 tensor and a [streams, stride]
@@ -192,6 +202,25 @@ class Engine:
         pcm = torch.zeros((data.shape[0], header.num_samples, header.num_channels), dtype=torch.int16, device=data.device)
         plan.run(data, pcm)
         return pcm, header
+
+    def uniform_window_decode_plan(self, header, num_streams, stride, image_size):
+        d = np.zeros(num_streams, dtype=STREAM_DESC_DTYPE)
+        d["data_offset"] = np.arange(num_streams, dtype=np.uint64) * np.uint64(stride)
+        d["data_size"] = image_size
+        d["num_samples"] = header.num_samples
+        return self.window_decode_plan(header, d, True)
+
+    def decode_windows(self, data, image_size, windows, frames, dtype=None):
+        """data: uint8 cuda tensor [streams, stride] of same-format images (encode_uniform's output); windows: int64 cuda tensor
+        [N, 2] of (stream, first_frame) -> [N, channels, frames] tensor of `dtype` (torch.float32 = sample / 32768, or torch.int16).
+        The header is read once, from the first image; the windows are never read on the host."""
+        head = bytes(data[0, :31].cpu().numpy())
+        header = parse_header(head)
+        plan = self.uniform_window_decode_plan(header, data.shape[0], data.shape[1], image_size)
+        try:
+            return plan.run(data, windows, frames, dtype)
+        finally:
+            plan.close()  # synchronises the context's stream first
 
     # ---- reconstruction modes (the reference CLI's -r / -g / -c, src/main.c:275-503) ----------
     def reconstruct_uniform(self, pcm, param, residual=False, want_stats=True, segment_blocks=None, warmup_blocks=0):
@@ -355,6 +384,47 @@ class DecodePlan:
             pass
 
 
+class WindowDecodePlan:
+    def __init__(self, engine, handle, header, descs):
+        self.engine, self.handle, self.header, self.descs = engine, handle, header, descs
+
+    def run(self, data, windows, frames, dtype=None, out=None, ordered=True):
+        """data: uint8 cuda tensor of the images; windows: int64 cuda tensor [N, 2] of (stream, first_frame) ->
+        `out` ([N, channels, frames] of dtype torch.float32 - sample / 32768 - or torch.int16; allocated when None).
+        Asynchronous on the engine's stream, ordered against torch's current one; the windows stay on the device."""
+        torch = self.engine.torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.int16):
+            raise ValueError("window decode writes torch.float32 or torch.int16, not %s" % dtype)
+        if windows.dtype != torch.int64 or windows.dim() != 2 or windows.shape[1] != 2 or not windows.is_cuda:
+            raise ValueError("windows: an int64 cuda tensor [N, 2] of (stream, first_frame)")
+        windows = windows.contiguous()
+        n, ch, frames = int(windows.shape[0]), int(self.header.num_channels), int(frames)
+        if out is None:
+            out = torch.empty((n, ch, frames), dtype=dtype, device=windows.device)
+        elif out.dtype != dtype or tuple(out.shape) != (n, ch, frames) or not out.is_contiguous():
+            raise ValueError("out: a contiguous %s tensor [%d, %d, %d]" % (dtype, n, ch, frames))
+        kind = SAMPLE_FLOAT32 if dtype == torch.float32 else SAMPLE_INT16
+        cur = self.engine._enter() if ordered else None
+        _check("AADHip_WindowDecodePlanRun",
+               self.engine.lib.AADHip_WindowDecodePlanRun(self.handle, data.data_ptr(), n, windows.data_ptr(), frames, kind,
+                                                          out.data_ptr()))
+        if ordered:
+            self.engine._exit(cur)
+        return out
+
+    def close(self):
+        if self.handle:
+            self.engine.lib.AADHip_WindowDecodePlanDestroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HipEvent:
     """A hipEvent_t of our own (timing disabled): what AADHip_ContextSignalNextRun takes and hipStreamWaitEvent waits for.
     torch.cuda.Event cannot wrap a foreign handle and creates its own lazily, hence the few runtime calls made directly."""
@@ -487,4 +557,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "DecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE"]
+__all__ = ["Engine", "EncodePlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE"]

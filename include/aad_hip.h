@@ -70,8 +70,8 @@ const char *AADHip_ContextLastError(const struct AADHipContext *context);
 
 /* Cross-stream ordering and kernel timing without packets of their own.  `hip_start_event` / `hip_stop_event` (hipEvent_t the
  * caller owns; either may be NULL, both NULL withdraws) are recorded when the work of the NEXT AADHip_EncodePlanRun /
- * AADHip_DecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot: the run takes them.  An
- * encode or decode plan run is one kernel, and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
+ * AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
+ * the run takes them.  An encode, decode or window decode plan run is one kernel, and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
  * stop events) instead of on barrier packets around it: a hipEventRecord behind every launch of a back-to-back sequence costs
  * the queue 2.9 us per launch on MI355X, the attached event nothing (profiles/r03_microbench_event_gap.txt), and
  * hipEventElapsedTime between the two is the kernel's own duration.  Another stream waits for the stop event with
@@ -194,6 +194,46 @@ void AADHip_DecodePlanDestroy(struct AADHipDecodePlan *plan);
 
 AADApiResult AADHip_DecodePlanRun(
     struct AADHipDecodePlan *plan, const uint8_t *device_data, int16_t *device_pcm);
+
+/* ---- window decode: sample-accurate crops into planar int16 / float32 rows ------------------ */
+
+/* Every block header carries the decoder's whole state (src/aad_decoder.c:362-379), so any stretch of a stream decodes from the
+ * blocks that cover it alone.  A window decode plan holds a stream table; each run takes a table of windows FROM DEVICE MEMORY
+ * (the host never reads it: windows drawn on the device, e.g. by torch.randint, need no synchronisation) and writes every window
+ * as planar rows.
+ *
+ * Definition.  Let D_s be what AADHip_DecodePlanRun writes for stream s of the same format, has_file_header and table into a
+ * zero-filled buffer of num_samples frames.  Then for window w = {stream, first_frame}, channel c < C and t < T:
+ *   out[(w * C + c) * T + t] = D_s[first_frame + t][c]   converted to the sample type,
+ * 0 where first_frame + t >= num_samples, and the whole window is 0 where stream >= num_streams.  Huge or "negative" (wrapped
+ * int64) values are not an error: they give zeros and read nothing.  As under AADHip_DecodePlanRun no byte outside
+ * [data_offset, data_offset + data_size) of a stream is read, and a truncated image decodes the same.
+ *
+ * AADHip_WindowDecodePlanCreate validates `format`, the flag and the table exactly as AADHip_DecodePlanCreate does (same errors);
+ * pcm_offset is ignored.  One plan serves any number of windows and any window length.
+ * AADHip_WindowDecodePlanRun: one kernel (AADHip_ContextSignalNextRun's events ride on it), asynchronous on the context's stream.
+ * device_windows: num_windows records, 8-byte aligned (a contiguous torch int64 tensor [N, 2] on the device IS the table);
+ * device_out: N * C * T samples.  num_windows == 0 is OK and launches nothing.  AAD_APIRESULT_INVALID_ARGUMENT for
+ * frames_per_window == 0, an unknown sample_type, a null pointer while num_windows > 0, and N * C * T elements (or their float32
+ * bytes) or the kernel's lane count N * (ceil((T - 1) / spb) + 1) * C overflowing 64 bits. */
+struct AADHipWindow {
+  uint64_t stream;      /* index into the plan's stream table */
+  uint64_t first_frame; /* first frame of the window */
+};
+enum AADHipSampleType {
+  AAD_HIP_SAMPLE_INT16 = 0,  /* the decoded sample */
+  AAD_HIP_SAMPLE_FLOAT32 = 1 /* the decoded sample / 32768.0f (exact) */
+};
+struct AADHipWindowDecodePlan;
+AADApiResult AADHip_WindowDecodePlanCreate(
+    struct AADHipContext *context, const struct AADHeaderInfo *format, int32_t has_file_header,
+    uint32_t num_streams, const struct AADHipStreamDesc *streams,
+    struct AADHipWindowDecodePlan **plan);
+void AADHip_WindowDecodePlanDestroy(struct AADHipWindowDecodePlan *plan);
+AADApiResult AADHip_WindowDecodePlanRun(
+    struct AADHipWindowDecodePlan *plan, const uint8_t *device_data,
+    uint64_t num_windows, const struct AADHipWindow *device_windows,
+    uint32_t frames_per_window, int32_t sample_type, void *device_out);
 
 /* ---- host-memory convenience (stage -> run -> copy back, synchronous) ---------------------- */
 

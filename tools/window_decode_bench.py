@@ -1,0 +1,234 @@
+"""Window decode against today's composite (profiles/r05_window_decode.txt).
+
+Corpus: --streams stereo 4-bit streams of --seconds s at 48 kHz resident on the device as .aad images, synthesised from a seed
+(aad_amd/synth.py) and encoded on the device with a segmented plan (the images' bytes do not matter to a decode, only their layout).
+Windows: N random (stream, first_frame) pairs drawn on the device, T frames each; one table per N, the same for every row.
+
+Rows (kernel times from the events of AADHip_ContextSignalNextRun, median of --reps; call times wall clock with a device synchronise):
+  (a) the existing decoder over the same covering blocks as a bare-block plan (AADHip_DecodePlanRun, has_file_header = 0, one table
+      entry per block), int16 interleaved: the "auto" policy's choice and "dense" - kernel only, the plan made beforehand;
+  (b) today's composite per call: covering-block table on the host from the windows (.cpu()), plan create + upload, bare-block decode,
+      torch gather + transpose to [N, C, T], .float() / 32768;
+  (c) the window run (AADHip_WindowDecodePlanRun), int16 and float32: kernel and call.
+Bit-exact: (a) auto == (a) dense; every crop of (b) and (c) == the crop gathered from (a) dense, float32 == int16 / 32768 bitwise;
+and a few windows against the oracle's decode of the whole stream (tests/oracle_binding.py, when present).
+
+Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25]"""
+import argparse
+import concurrent.futures as cf
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+HBM = 8.0e12
+
+
+def build_corpus(engine, torch, streams, samples, chunk=25, seed=11):
+    from aad_amd.capi import make_parameter
+    from aad_amd.synth import synth_pcm
+    param = make_parameter(2, 4, 1024)
+    size = engine.encoded_size(param, samples)
+    stride = (size + 63) // 64 * 64
+    corpus = torch.zeros((streams, stride), dtype=torch.uint8, device="cuda")
+    starts = list(range(0, streams, chunk))
+    gen = lambda s0: synth_pcm(min(chunk, streams - s0), samples, 2, seed=seed, first_stream=s0)
+    with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+        for s0, pcm in zip(starts, pool.map(gen, starts)):
+            img, got = engine.encode_uniform(torch.from_numpy(pcm).cuda(), param, segment_blocks=16, warmup_blocks=1)
+            assert got == size
+            corpus[s0:s0 + img.shape[0], :] = img[:, :stride]
+            del img
+    torch.cuda.synchronize()
+    return corpus, size, stride
+
+
+def covering_blocks(win, frames, spb, bs, size, samples, stride):
+    """host table of the blocks that cover each window (one bare-block stream each) and where each window's crop starts in
+    the decoded frames"""
+    s, f = win[:, 0].astype(np.uint64), win[:, 1].astype(np.uint64)
+    b0, b1 = f // spb, (f + frames - 1) // spb
+    count = (b1 - b0 + 1).astype(np.int64)
+    total = int(count.sum())
+    first = np.concatenate([[0], np.cumsum(count)[:-1]])
+    w_of = np.repeat(np.arange(len(win)), count)
+    blk = b0[w_of] + (np.arange(total) - first[w_of]).astype(np.uint64)
+    from aad_amd.capi import STREAM_DESC_DTYPE
+    t = np.zeros(total, dtype=STREAM_DESC_DTYPE)
+    t["data_offset"] = s[w_of] * np.uint64(stride) + np.uint64(31) + blk * np.uint64(bs)
+    t["data_size"] = np.minimum(np.uint64(bs), np.uint64(size - 31) - blk * np.uint64(bs))
+    t["num_samples"] = np.minimum(np.uint64(spb), np.uint64(samples) - blk * np.uint64(spb))
+    t["pcm_offset"] = np.arange(total, dtype=np.uint64) * np.uint64(spb * 2)
+    crop0 = first.astype(np.int64) * spb + (f % np.uint64(spb)).astype(np.int64)  # frame of each crop in the decoded blocks
+    return t, crop0
+
+
+def kernel_ms(engine, HipEvent, fn, reps):
+    out = []
+    for _ in range(reps):
+        start, stop = HipEvent(timing=True), HipEvent(timing=True)
+        engine.signal_next(stop, start=start)
+        fn()
+        stop.synchronize()
+        out.append(start.elapsed_ms(stop))
+        start.close()
+        stop.close()
+    return float(np.median(out))
+
+
+def call_ms(torch, fn, reps):
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(out))
+
+
+def gather(torch, pcm_blocks, crop0, frames):
+    """decoded interleaved frames [frames_total, 2] -> [N, 2, T] int16"""
+    idx = torch.as_tensor(crop0, device="cuda")[:, None] + torch.arange(frames, device="cuda")[None, :]
+    return pcm_blocks.view(-1, 2)[idx].transpose(1, 2).contiguous()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=1000)
+    ap.add_argument("--seconds", type=float, default=60.0)
+    ap.add_argument("--windows", type=int, nargs="+", default=[4096, 64])
+    ap.add_argument("--frames", type=int, default=48000)
+    ap.add_argument("--reps", type=int, default=25)
+    ap.add_argument("--seed", type=int, default=11)
+    ap.add_argument("--out", default=None, help="also write the report here")
+    args = ap.parse_args()
+
+    import torch
+    from aad_amd.engine import Engine, HipEvent, parse_header
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    engine = Engine(0)
+    samples = int(round(args.seconds * 48000))
+    t0 = time.perf_counter()
+    corpus, size, stride = build_corpus(engine, torch, args.streams, samples, seed=args.seed)
+    hd = parse_header(bytes(corpus[0, :31].cpu().numpy()))
+    spb, bs = hd.num_samples_per_block, hd.block_size
+    say("window decode: %d stereo 4-bit streams x %d frames on the device (%.2f GB of images, built in %.1f s); T = %d frames; "
+        "spb %d, block %d bytes; median of %d; device %s" % (args.streams, samples, args.streams * stride / 1e9,
+                                                             time.perf_counter() - t0, args.frames, spb, bs, args.reps,
+                                                             torch.cuda.get_device_name(0)))
+    wplan = engine.uniform_window_decode_plan(hd, args.streams, stride, size)
+    frames = args.frames
+    results = []
+    for n in args.windows:
+        g = torch.Generator(device="cuda")
+        g.manual_seed(args.seed + n)
+        d_win = torch.stack([torch.randint(0, args.streams, (n,), device="cuda", generator=g),
+                             torch.randint(0, samples - frames + 1, (n,), device="cuda", generator=g)], dim=1)
+        win = d_win.cpu().numpy()
+        table, crop0 = covering_blocks(win, frames, spb, bs, size, samples, stride)
+        nblk = len(table)
+        out_bytes16, out_bytes32 = n * 2 * frames * 2, n * 2 * frames * 4
+        row = {"windows": n, "frames": frames, "covering_blocks": nblk}
+        say("")
+        say("N = %d windows x T = %d: %d covering blocks (%.2f per window), output %.1f MB int16 / %.1f MB float32"
+            % (n, frames, nblk, nblk / n, out_bytes16 / 1e6, out_bytes32 / 1e6))
+
+        # (a) the existing decoder over the covering blocks, plan made beforehand
+        pcm_a = {m: torch.zeros(nblk * spb * 2, dtype=torch.int16, device="cuda") for m in ("auto", "dense")}
+        dplan = engine.decode_plan(hd, table, False)
+        t_a = {}
+        for m in ("auto", "dense"):
+            engine.set_mapping(m)
+            t_a[m] = kernel_ms(engine, HipEvent, lambda: dplan.run(corpus, pcm_a[m]), args.reps)
+        engine.set_mapping("auto")
+        torch.cuda.synchronize()
+        exact_a = bool(torch.equal(pcm_a["auto"], pcm_a["dense"]))
+        ref16 = gather(torch, pcm_a["dense"], crop0, frames)
+        dplan.close()
+        del pcm_a
+        torch.cuda.synchronize()
+
+        # (b) today's composite per call
+        def composite():
+            w = d_win.cpu().numpy()
+            t, c0 = covering_blocks(w, frames, spb, bs, size, samples, stride)
+            p = engine.decode_plan(hd, t, False)
+            pcm = torch.zeros(len(t) * spb * 2, dtype=torch.int16, device="cuda")
+            p.run(corpus, pcm)
+            res = gather(torch, pcm, c0, frames).float() / 32768
+            p.close()
+            return res
+        t_b = call_ms(torch, composite, args.reps)
+        out_b = composite()
+        torch.cuda.synchronize()
+        exact_b = bool(torch.equal(out_b.view(torch.int32), (ref16.float() / 32768).view(torch.int32)))
+        del out_b
+
+        # (c) the window run
+        out16 = torch.empty((n, 2, frames), dtype=torch.int16, device="cuda")
+        out32 = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        k16 = kernel_ms(engine, HipEvent, lambda: wplan.run(corpus, d_win, frames, torch.int16, out=out16), args.reps)
+        k32 = kernel_ms(engine, HipEvent, lambda: wplan.run(corpus, d_win, frames, torch.float32, out=out32), args.reps)
+        c16 = call_ms(torch, lambda: wplan.run(corpus, d_win, frames, torch.int16, out=out16), args.reps)
+        c32 = call_ms(torch, lambda: wplan.run(corpus, d_win, frames, torch.float32, out=out32), args.reps)
+        torch.cuda.synchronize()
+        exact_c16 = bool(torch.equal(out16, ref16))
+        exact_c32 = bool(torch.equal(out32.view(torch.int32), (ref16.float() / 32768).view(torch.int32)))
+
+        # a few windows against the oracle's decode of the whole stream
+        oracle = None
+        try:
+            import oracle_binding as ob
+            oracle = True
+            for w in range(min(3, n)):
+                s, f = int(win[w, 0]), int(win[w, 1])
+                whole = ob.decode(bytes(corpus[s, :size].cpu().numpy()))[0]
+                oracle = oracle and np.array_equal(out16[w].cpu().numpy(), whole[f:f + frames].T)
+        except (ImportError, OSError):
+            pass
+
+        def gbs(nbytes, ms):
+            return nbytes / (ms * 1e-3) / 1e9
+
+        say("  (a) bare-block decode, auto   kernel %8.4f ms   int16 interleaved   %7.1f GB/s out (%.3f of 8 TB/s)"
+            % (t_a["auto"], gbs(nblk * spb * 4, t_a["auto"]), gbs(nblk * spb * 4, t_a["auto"]) * 1e9 / HBM))
+        say("  (a) bare-block decode, dense  kernel %8.4f ms   int16 interleaved   %7.1f GB/s out (%.3f of 8 TB/s)   bit-exact vs auto: %s"
+            % (t_a["dense"], gbs(nblk * spb * 4, t_a["dense"]), gbs(nblk * spb * 4, t_a["dense"]) * 1e9 / HBM, exact_a))
+        say("  (b) composite per call        call   %8.4f ms   float32 planar      %7.1f GB/s out                    bit-exact: %s"
+            % (t_b, gbs(out_bytes32, t_b), exact_b))
+        say("  (c) window run, int16         kernel %8.4f ms   call %8.4f ms   %7.1f GB/s out (%.3f of 8 TB/s)   bit-exact: %s"
+            % (k16, c16, gbs(out_bytes16, k16), gbs(out_bytes16, k16) * 1e9 / HBM, exact_c16))
+        say("  (c) window run, float32       kernel %8.4f ms   call %8.4f ms   %7.1f GB/s out (%.3f of 8 TB/s)   bit-exact: %s"
+            % (k32, c32, gbs(out_bytes32, k32), gbs(out_bytes32, k32) * 1e9 / HBM, exact_c32))
+        say("  targets: (c) float32 kernel / (a) dense kernel = %.3f (<= 1.25: %s); (c) float32 call / (b) call = %.3f (< 1: %s)"
+            "; oracle spot check: %s" % (k32 / t_a["dense"], k32 / t_a["dense"] <= 1.25, c32 / t_b, c32 < t_b, oracle))
+        row.update(a_auto_ms=t_a["auto"], a_dense_ms=t_a["dense"], b_call_ms=t_b, c_int16_kernel_ms=k16, c_int16_call_ms=c16,
+                   c_float32_kernel_ms=k32, c_float32_call_ms=c32,
+                   bit_exact=dict(a=exact_a, b=exact_b, c_int16=exact_c16, c_float32=exact_c32, oracle=oracle))
+        results.append(row)
+        del out16, out32, ref16
+        torch.cuda.synchronize()
+    say("")
+    say("json " + json.dumps(results))
+    wplan.close()
+    engine.close()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
