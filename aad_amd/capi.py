@@ -50,6 +50,10 @@ class AADHipSegmentation(C.Structure):  # include/aad_hip.h
     _fields_ = [("segment_blocks", C.c_uint32), ("warmup_blocks", C.c_uint32)]
 
 
+class AADHipPlanarLayout(C.Structure):  # include/aad_hip.h
+    _fields_ = [("sample_type", C.c_int32), ("reserved", C.c_uint32), ("channel_stride", C.c_uint64)]
+
+
 class AADHipLaneState(C.Structure):  # include/aad_hip.h
     _fields_ = [("weight", C.c_int32 * 4), ("history", C.c_int32 * 4),
                 ("stepsize_index", C.c_int32), ("quantize_error", C.c_int32)]
@@ -85,6 +89,7 @@ HIP_SYMBOLS = [
     "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate", "AADHip_SegmentedEncodeBatch",
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
+    "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -155,6 +160,11 @@ def _declare_hip(lib):
     lib.AADHip_SegmentedEncodePlanCreate.argtypes = [vp, C.POINTER(AADEncodeParameter), C.POINTER(AADHipSegmentation), C.c_uint32, vp,
                                                      C.POINTER(vp)]
     lib.AADHip_SegmentedEncodePlanCreate.restype = C.c_int
+    lib.AADHip_PlanarEncodePlanCreate.argtypes = [vp, C.POINTER(AADEncodeParameter), C.POINTER(AADHipPlanarLayout),
+                                                  C.POINTER(AADHipSegmentation), C.c_uint32, vp, C.POINTER(vp)]
+    lib.AADHip_PlanarEncodePlanCreate.restype = C.c_int
+    lib.AADHip_PlanarEncodePlanRun.argtypes = [vp, vp, vp, vp]
+    lib.AADHip_PlanarEncodePlanRun.restype = C.c_int
     lib.AADHip_EncodePlanDestroy.argtypes = [vp]
     lib.AADHip_EncodePlanDestroy.restype = None
     lib.AADHip_EncodePlanRun.argtypes = [vp, vp, vp, vp]

@@ -8,6 +8,7 @@
 #define AAD_ENCODE_HIP_H
 
 #include "aad_device.hip.h"
+#include "aad_pcm_convert.h"
 #include "aad_segments.h"
 
 namespace aad {
@@ -340,20 +341,61 @@ struct EncodeArgs {
   alignas(4) uint8_t header_template[32]; /* 31-byte file header with num_samples = 0 */
 };
 
+/* Input layouts of encode_streams_kernel (its IN): channel-interleaved int16 frames (AADHip_EncodePlanRun), or one row per
+ * channel of int16 or float32 samples (AADHip_PlanarEncodePlanRun) - row c of a stream at pcm_offset + c * channel_stride.
+ * Every read of PCM goes through the layout's cursor (PcmCursor) and its chunk loads (ChunkSamples / PlanarChunk, the quad
+ * encoder's Raw / PlanarRaw); the chunk bodies downstream see the same packed words either way.  A float32 sample becomes the
+ * int16 the encoder sees (pcm_from_f32, aad_pcm_convert.h) as its chunk is unpacked, off the recurrence. */
+enum PcmLayout { kInInterleaved = 0, kInPlanarI16 = 1, kInPlanarF32 = 2 };
+template <int IN> using PcmElem = std::conditional_t<IN == kInPlanarF32, float, int16_t>;
+
+/* the planar kernels' arguments (the interleaved ones keep EncodeArgs as it is) */
+struct PlanarEncodeArgs : EncodeArgs {
+  uint64_t channel_stride; /* elements from one channel's row of a stream to the next */
+};
+template <int IN> using EncodeArgsFor = std::conditional_t<IN == kInInterleaved, EncodeArgs, PlanarEncodeArgs>;
+
+/* planar input at a frame: channel 0's row there, and the distance to the next row */
+template <typename T>
+struct PlanarRows {
+  const T *p;
+  uint64_t stride; /* elements */
+  __device__ __forceinline__ PlanarRows operator+(uint64_t frames) const { return {p + frames, stride}; }
+  __device__ __forceinline__ PlanarRows &operator+=(uint64_t frames)
+  {
+    p += frames;
+    return *this;
+  }
+  __device__ __forceinline__ const T *row(uint32_t c) const { return p + (uint64_t)c * stride; }
+};
+/* interleaved: a plain pointer, advanced by frames * channels */
+template <int IN> using PcmCursor = std::conditional_t<IN == kInInterleaved, const int16_t *, PlanarRows<PcmElem<IN>>>;
+
+__device__ __forceinline__ int32_t pcm_value(int16_t v) { return v; }
+__device__ __forceinline__ int32_t pcm_value(float v) { return pcm_from_f32(v); }
+
 /* sample i of channel c of a stream, after the optional L/R -> M/S transform
  * (reference src/aad_encoder.c:413-428; the clip there can never trigger for int16 input) */
-template <bool MS>
+template <bool MS, int IN = kInInterleaved>
 struct SampleSource {
-  const int16_t *x;
+  PcmCursor<IN> x;
   uint32_t ch, c;
   uint32_t total; /* frames in the stream */
   __device__ __forceinline__ int32_t at(uint64_t i) const
   {
-    if (MS) {
-      const int32_t l = x[i * 2], r = x[i * 2 + 1];
-      return c == 0 ? (l + r) >> 1 : (l - r) >> 1;
+    if constexpr (IN != kInInterleaved) {
+      if (MS) {
+        const int32_t l = pcm_value(x.p[i]), r = pcm_value(x.row(1)[i]);
+        return c == 0 ? (l + r) >> 1 : (l - r) >> 1;
+      }
+      return pcm_value(x.row(c)[i]);
+    } else {
+      if (MS) {
+        const int32_t l = x[i * 2], r = x[i * 2 + 1];
+        return c == 0 ? (l + r) >> 1 : (l - r) >> 1;
+      }
+      return x[i * ch + c];
     }
-    return x[i * ch + c];
   }
 };
 
@@ -408,6 +450,92 @@ struct ChunkSamples {
     return (int32_t)d[j];
   }
 };
+
+/* ChunkSamples for planar input (same interface, same values out of pair() / get()).  A lane loads its own row's 16 samples -
+ * 32 bytes of int16 or 64 of float32 - and, for M/S, both rows of its pair (the transform needs L and R).  The words stay as
+ * loaded until the chunk body takes them apart (pair / get: the float32 conversion happens there, a chunk after the loads were
+ * issued, so nothing waits on memory for it). */
+template <int CHF, bool MS, typename T>
+struct PlanarChunk {
+  static constexpr int kRows = CHF == 2 && MS ? 2 : 1;
+  static constexpr int kRowWords = 16 * (int)sizeof(T) / 4;
+  uint32_t d[kRows * kRowWords];
+  __device__ __forceinline__ void load(const PlanarRows<T> &x, uint32_t, uint32_t c)
+  {
+#pragma unroll
+    for (int r = 0; r < kRows; r++) {
+      const T *row = x.row(kRows == 2 ? (uint32_t)r : c);
+#pragma unroll
+      for (int k = 0; k < kRowWords / 4; k++) {
+        const u32x4 a = reinterpret_cast<const U32x4 *>(row + (16 / (int)sizeof(T)) * k)->v;
+        d[r * kRowWords + 4 * k] = a.x; d[r * kRowWords + 4 * k + 1] = a.y; d[r * kRowWords + 4 * k + 2] = a.z; d[r * kRowWords + 4 * k + 3] = a.w;
+      }
+    }
+  }
+  __device__ __forceinline__ void touch()
+  {
+#pragma unroll
+    for (int v = 0; v < kRows * kRowWords / 8; v++)
+      asm volatile("" : "+v"(d[8 * v]), "+v"(d[8 * v + 1]), "+v"(d[8 * v + 2]), "+v"(d[8 * v + 3]), "+v"(d[8 * v + 4]), "+v"(d[8 * v + 5]),
+                        "+v"(d[8 * v + 6]), "+v"(d[8 * v + 7]) :: "memory");
+  }
+  /* sample j of loaded row r */
+  __device__ __forceinline__ int32_t sample(int r, int j) const
+  {
+    if constexpr (sizeof(T) == 4) return pcm_from_f32(__uint_as_float(d[r * kRowWords + j]));
+    else return __builtin_amdgcn_sbfe((int32_t)d[r * kRowWords + (j >> 1)], (j & 1) * 16, 16);
+  }
+  /* samples 2k and 2k+1 of the lane's channel, low half first (no M/S) */
+  __device__ __forceinline__ uint32_t pair(int k, uint32_t) const
+  {
+    if constexpr (sizeof(T) == 4) return ((uint32_t)sample(0, 2 * k) & 0xFFFFu) | ((uint32_t)sample(0, 2 * k + 1) << 16);
+    else return d[k];
+  }
+  __device__ __forceinline__ int32_t get(int j, uint32_t c) const
+  {
+    if (kRows == 2) {
+      const int32_t l = sample(0, j), r = sample(1, j);
+      return c == 0 ? (l + r) >> 1 : (l - r) >> 1;
+    }
+    return sample(0, j);
+  }
+};
+
+/* the quad encoder's chunk as loaded (run_block's Raw) for planar input without M/S: the lane's own row, 16 samples.  The body
+ * reads them as kPairs words (pack); int16 rows are those words already. */
+template <typename T>
+struct PlanarRaw {
+  static constexpr int kWords = 16 * (int)sizeof(T) / 4;
+  static constexpr int kParts = kWords / 4; /* 16-byte loads */
+  uint32_t d[kWords];
+  __device__ __forceinline__ void load_part(const T *x, int k)
+  {
+    const u32x4 a = reinterpret_cast<const U32x4 *>(x + (16 / (int)sizeof(T)) * k)->v;
+    d[4 * k] = a.x; d[4 * k + 1] = a.y; d[4 * k + 2] = a.z; d[4 * k + 3] = a.w;
+  }
+  __device__ __forceinline__ void load(const T *x)
+  {
+#pragma unroll
+    for (int k = 0; k < kParts; k++) load_part(x, k);
+  }
+  __device__ __forceinline__ int32_t sample(int j) const
+  {
+    if constexpr (sizeof(T) == 4) return pcm_from_f32(__uint_as_float(d[j]));
+    else return __builtin_amdgcn_sbfe((int32_t)d[j >> 1], (j & 1) * 16, 16);
+  }
+  __device__ __forceinline__ void pack(uint32_t *w) const
+  {
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = sizeof(T) == 4 ? ((uint32_t)sample(2 * k) & 0xFFFFu) | ((uint32_t)sample(2 * k + 1) << 16) : d[k];
+  }
+};
+
+/* where the quad encoder's lane reads its chunks: interleaved - the frame (the channel-1 lane one int16 further on, see run_block);
+ * planar - its channel's row */
+template <int CHF>
+__device__ __forceinline__ const int16_t *lane_row(const int16_t *x, uint32_t c) { return x + (CHF == 2 ? c : 0); }
+template <int CHF, typename T>
+__device__ __forceinline__ const T *lane_row(const PlanarRows<T> &x, uint32_t c) { return x.row(c); }
 
 template <typename Src>
 __device__ __forceinline__ void seed_history(Lane &L, const Src &src, uint64_t first, uint32_t n)
@@ -835,8 +963,8 @@ constexpr bool kBurstStores = EMIT && CHF == 2 && BITS == 4;
  * the last whole unit) or like a measurement (at the last real sample) - the sum covers real samples
  * either way. */
 /* RING: the encode pass appends its bytes to the row's ByteRing (`ring`) instead of storing them under `body` */
-template <int BITS, int CHF, bool MS, bool QUAD, int PASS, bool RING = false, typename S>
-__device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, uint64_t first, uint32_t n, uint32_t ch,
+template <int BITS, int CHF, bool MS, bool QUAD, int PASS, bool RING = false, typename S, int IN = kInInterleaved>
+__device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &src, uint64_t first, uint32_t n, uint32_t ch,
                                              uint32_t c, bool writer, uint8_t *body, const char *lds, int32_t &last_qd,
                                              bool defer3 = false, uint32_t deferred = 0, bool pad = true,
                                              ByteRing<(CHF ? CHF : 1)> *ring = nullptr)
@@ -862,9 +990,11 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
     at[2] = (uint8_t)(three >> 16);
   };
   {
-    using CS = ChunkSamples<CHF, MS>;
+    using CS = std::conditional_t<IN == kInInterleaved, ChunkSamples<CHF, MS>, PlanarChunk<CHF, MS, PcmElem<IN>>>;
     const uint32_t full = coded / kChunk;
-    const int16_t *xp = src.x + (first + kTaps) * ch;
+    /* the cursor moves by frames * ch int16 (interleaved) or by frames elements (planar rows): (IN == kInInterleaved ? ch : 1u)
+     * below, written out at every use - a variable of its own changed the interleaved kernels' schedules */
+    auto xp = src.x + (first + kTaps) * (IN == kInInterleaved ? ch : 1u);
     constexpr uint32_t kOutStride = Pack<BITS>::kChunkBytes;
     CS next;
     for (auto &v : next.d) v = 0;
@@ -882,8 +1012,9 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
        * Stereo: the channel-1 lane loads from one int16 further on, so that its sample is the low
        * half of every dword as well; the last full chunk of a stream that ends on a chunk boundary
        * is left to the tail loop - its channel-1 load would read two bytes past the stream. */
-      constexpr int FMT = CHF == 1 ? kPairs : kFrames;
-      constexpr int kParts = CHF == 1 ? 2 : 4; /* 16-byte loads per chunk */
+      /* planar: the lane's own row, read as pairs whatever the channel count (PlanarRaw) */
+      constexpr int FMT = IN != kInInterleaved || CHF == 1 ? kPairs : kFrames;
+      constexpr int kParts = IN != kInInterleaved ? PlanarRaw<PcmElem<IN>>::kParts : (CHF == 1 ? 2 : 4); /* 16-byte loads per chunk */
       struct Raw { /* one chunk as loaded: 32 (mono) / 64 (stereo) bytes */
         uint32_t d[CHF == 1 ? 8 : 16];
         __device__ __forceinline__ void load_part(const int16_t *x, int k) /* k compile-time after unrolling */
@@ -897,20 +1028,22 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
           for (int k = 0; k < kParts; k++) load_part(x, k);
         }
       };
+      using RawT = std::conditional_t<IN == kInInterleaved, Raw, PlanarRaw<PcmElem<IN>>>;
       uint32_t chunks = full;
-      if (CHF == 2 && chunks && chunks * kChunk == coded && first + n >= (uint64_t)src.total) chunks--;
-      const int16_t *rp = xp + (CHF == 2 ? c : 0);
-      Raw b0, b1, b2;
+      if (IN == kInInterleaved && CHF == 2 && chunks && chunks * kChunk == coded && first + n >= (uint64_t)src.total) chunks--;
+      auto rp = lane_row<CHF>(xp, c);
+      RawT b0, b1, b2;
       for (auto &v : b0.d) v = 0;
       for (auto &v : b1.d) v = 0;
       for (auto &v : b2.d) v = 0;
       EncodeCarry C;
       if (chunks) {
         b0.load(rp);
-        if (chunks > 1) rp += (uint64_t)kChunk * ch;
+        if (chunks > 1) rp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
         b1.load(rp);
-        if (chunks > 2) rp += (uint64_t)kChunk * ch; /* rp: where chunk min(2, chunks - 1) starts - what the first chunk prefetches */
-        encode_prime_quad<BITS>(L, C, (int32_t)(int16_t)b0.d[0], lds); /* both formats: sample 0 is the low half of dword 0 */
+        if (chunks > 2) rp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u); /* rp: where chunk min(2, chunks - 1) starts - what the first chunk prefetches */
+        if constexpr (IN == kInInterleaved) encode_prime_quad<BITS>(L, C, (int32_t)(int16_t)b0.d[0], lds); /* both formats: sample 0 is the low half of dword 0 */
+        else encode_prime_quad<BITS>(L, C, b0.sample(0), lds);
       }
       /* The chunk-level work rides in the first DPP gap of the samples (see encode_chunk16_quad): the
        * loads of chunk k+2 in samples 0-3, then - stereo 4-bit, the BASELINE shape - the store of chunk
@@ -924,12 +1057,12 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
       /* A = channel 0's word, B = channel 1's: lane c holds (keep, recv) = c ? (B.., A..) : (A.., B..), so the
        * byte selectors of store_chunk_codes get their source halves swapped on the channel-1 lane */
       const uint32_t sel_x = c ? (0x02060307u ^ 0x04040404u) : 0x02060307u, sel_y = c ? (0x00040105u ^ 0x04040404u) : 0x00040105u;
-      auto one = [&](uint32_t k, const Raw &cur, const Raw &ahead, Raw &incoming) {
+      auto one = [&](uint32_t k, const RawT &cur, const RawT &ahead, RawT &incoming) {
         uint32_t w[2] = {0, 0};
         const bool pending = kStaged && k != 0;
         if constexpr (!kStaged) { /* (the other shapes ran 1-3 % slower with their loads in the gaps: measured, same box) */
           incoming.load(rp); /* prefetch chunk k+2 (clamped to the last full one) */
-          if (k + 3 < chunks) rp += (uint64_t)kChunk * ch;
+          if (k + 3 < chunks) rp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
         }
         auto fill = [&](auto jc) {
           constexpr int j = decltype(jc)::value;
@@ -950,11 +1083,17 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
             }
             if constexpr (j == 10) sp += pending ? kOutStride * 2 : 0u;
             if constexpr (j == 12) {
-              if (k + 3 < chunks) rp += (uint64_t)kChunk * ch; /* for the next chunk's prefetch */
+              if (k + 3 < chunks) rp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u); /* for the next chunk's prefetch */
             }
           }
         };
-        encode_chunk16_quad<BITS, PASS, FMT>(L, C, reinterpret_cast<const int32_t *>(cur.d), (int32_t)ahead.d[0], lds, w, last_qd, sq, fill);
+        if constexpr (IN == kInInterleaved) {
+          encode_chunk16_quad<BITS, PASS, FMT>(L, C, reinterpret_cast<const int32_t *>(cur.d), (int32_t)ahead.d[0], lds, w, last_qd, sq, fill);
+        } else {
+          uint32_t xw[8];
+          cur.pack(xw);
+          encode_chunk16_quad<BITS, PASS, FMT>(L, C, reinterpret_cast<const int32_t *>(xw), ahead.sample(0), lds, w, last_qd, sq, fill);
+        }
         if constexpr (kStaged) {
           wp0 = w[0];
           wp1 = w[1];
@@ -988,7 +1127,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
       EncodeCarry C;
       if (full) {
         extract(x);
-        if (full > 1) xp += (uint64_t)kChunk * ch;
+        if (full > 1) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
         next.load(xp, ch, c);
         next.touch();
         extract(xn);
@@ -998,7 +1137,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
        * chunk k+2 are extracted straight into the buffer chunk k has just freed - rotating the
        * buffers with moves cost 30 instructions per chunk */
       auto one = [&](uint32_t k, int32_t(&cur)[kN], const int32_t(&ahead)[kN]) {
-        if (k + 2 < full) xp += (uint64_t)kChunk * ch; /* prefetch chunk k+2 (clamped to the last full one) */
+        if (k + 2 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u); /* prefetch chunk k+2 (clamped to the last full one) */
         next.load(xp, ch, c);
         uint32_t w[2] = {0, 0};
         encode_chunk16_quad<BITS, PASS, kWide>(L, C, cur, ahead[0], lds, w, last_qd, sq);
@@ -1020,7 +1159,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
         int32_t x[kN];
 #pragma unroll
         for (int j = 0; j < kN; j++) x[j] = PK ? (int32_t)next.pair(j, pair_sel) : next.get(j, c);
-        if (k + 1 < full) xp += (uint64_t)kChunk * ch;
+        if (k + 1 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
         next.load(xp, ch, c);
         uint32_t w[2] = {0, 0};
         encode_chunk16<BITS, EMIT, PK>(L, x, lds, w, last_qd, sq);
@@ -1050,7 +1189,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
         int32_t x[kN];
 #pragma unroll
         for (int j = 0; j < kN; j++) x[j] = PK ? (int32_t)next.pair(j, pair_sel) : next.get(j, c);
-        if (k + 1 < full) xp += (uint64_t)kChunk * ch; /* unconditional prefetch, see below */
+        if (k + 1 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u); /* unconditional prefetch, see below */
         next.load(xp, ch, c);
         uint32_t w[2] = {0, 0};
         encode_chunk16<BITS, EMIT, PK>(L, x, lds, w, last_qd, sq);
@@ -1099,7 +1238,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
       CodeStage<BITS, kStage ? CHF : 1> stage;
       if constexpr (kStage) stage.init(const_cast<char *>(lds) + kLdsCodeStageOff);
       uint32_t k0 = 0;
-      if constexpr (CHF == 1) {
+      if constexpr (CHF == 1 && IN == kInInterleaved) {
         /* mono: the samples of TWO chunks (64 bytes) with one group of loads, a pair ahead - a lane that reads
          * 32 bytes per chunk visits every 64-byte sector of its stream three times, a chunk's worth of time apart
          * (the saturated mono encoder fetched 2.2x its PCM), in pairs twice.  The 64-byte window starts at the
@@ -1187,7 +1326,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
             int32_t x[kN];
 #pragma unroll
             for (int j = 0; j < kN; j++) x[j] = PK ? (int32_t)next.pair(j, pair_sel) : next.get(j, c);
-            if (k0 + h + 1 < full) xp += (uint64_t)kChunk * ch;
+            if (k0 + h + 1 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
             next.load(xp, ch, c);
             w2[h][0] = w2[h][1] = 0;
             encode_chunk16<BITS, EMIT, PK>(L, x, lds, w2[h], last_qd, sq);
@@ -1209,7 +1348,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
             int32_t x[kN];
 #pragma unroll
             for (int j = 0; j < kN; j++) x[j] = PK ? (int32_t)next.pair(j, pair_sel) : next.get(j, c);
-            if (k0 + h + 1 < full) xp += (uint64_t)kChunk * ch;
+            if (k0 + h + 1 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
             next.load(xp, ch, c);
             uint32_t w[2] = {0, 0};
             encode_chunk16<BITS, EMIT, PK>(L, x, lds, w, last_qd, sq);
@@ -1226,7 +1365,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
 #pragma unroll
         for (int j = 0; j < kN; j++) x[j] = PK ? (int32_t)next.pair(j, pair_sel) : next.get(j, c);
         /* unconditional prefetch (the last iteration re-reads its own chunk), see the decoder */
-        if (k + 1 < full) xp += (uint64_t)kChunk * ch;
+        if (k + 1 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
         next.load(xp, ch, c);
         uint32_t w[2] = {0, 0};
         encode_chunk16<BITS, EMIT, PK>(L, x, lds, w, last_qd, sq);
@@ -1391,8 +1530,8 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS> &src, 
 
 /* RMSE of the dequantised differences over one block while the lane adapts - reference
  * src/aad_encoder.c:431-467 (divisor = the block length, sum over the coded samples only) */
-template <int BITS, int CHF, bool MS, bool QUAD, typename S>
-__device__ __forceinline__ double rmse_pass(S &L, const SampleSource<MS> &src, uint64_t first, uint32_t n, uint32_t ch,
+template <int BITS, int CHF, bool MS, bool QUAD, typename S, int IN>
+__device__ __forceinline__ double rmse_pass(S &L, const SampleSource<MS, IN> &src, uint64_t first, uint32_t n, uint32_t ch,
                                             uint32_t c, uint32_t tap, const char *lds)
 {
   if (n < (uint32_t)kTaps) return 0.0;
@@ -1403,8 +1542,8 @@ __device__ __forceinline__ double rmse_pass(S &L, const SampleSource<MS> &src, u
 }
 
 /* trial search - reference src/aad_encoder.c:470-562 (per channel; channels are independent) */
-template <int BITS, int CHF, bool MS, bool QUAD, typename S>
-__device__ __forceinline__ void search_best_lane(S &L, const SampleSource<MS> &src, uint64_t first, uint32_t n, uint32_t spb,
+template <int BITS, int CHF, bool MS, bool QUAD, typename S, int IN>
+__device__ __forceinline__ void search_best_lane(S &L, const SampleSource<MS, IN> &src, uint64_t first, uint32_t n, uint32_t spb,
                                                  uint32_t trials, uint32_t ch, uint32_t c, uint32_t tap, const char *lds)
 {
   const bool have_prev = first >= spb;
@@ -1470,8 +1609,8 @@ __device__ __forceinline__ double role_swap_f64(double v)
   return __longlong_as_double((long long)r);
 }
 
-template <int BITS, int CHF, bool MS>
-__device__ __forceinline__ void encode_block_dual(Lane &F, int32_t &last_qd, const SampleSource<MS> &src, uint64_t first, uint32_t n,
+template <int BITS, int CHF, bool MS, int IN>
+__device__ __forceinline__ void encode_block_dual(Lane &F, int32_t &last_qd, const SampleSource<MS, IN> &src, uint64_t first, uint32_t n,
                                                   uint32_t spb, uint32_t trials, uint32_t c, uint32_t tap, uint32_t role,
                                                   uint8_t *img, uint8_t *slots, uint32_t slot_bytes, const char *lds)
 {
@@ -1649,9 +1788,12 @@ __device__ __forceinline__ void encode_block_dual(Lane &F, int32_t &last_qd, con
  * "parked" in the first kept block's slot: that block may be the stream's short last one, and a whole warm-up block written
  * there would run past the image.  The byte ring is never used (it stores whole sectors of an image written from its start:
  * segmented plans set ring_ok = 0); the dual trial search has three scratch slots per chain; no state is read or written.
+ *
+ * IN (PcmLayout): interleaved int16 frames, or planar int16 / float32 rows (AADHip_PlanarEncodePlanRun; arguments
+ * PlanarEncodeArgs, instantiated in aad_encode_planar.hip).  Only the reads of PCM differ; see "Input layouts" above.
  */
-template <int BITS, int CHF, bool MS, bool QUAD, bool TRIALS, bool DUAL = false, bool RING = false, bool SEG = false>
-__global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgs a)
+template <int BITS, int CHF, bool MS, bool QUAD, bool TRIALS, bool DUAL = false, bool RING = false, bool SEG = false, int IN = kInInterleaved>
+__global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgsFor<IN> a)
 {
   static_assert(!QUAD || CHF != 0, "the quad mapping exists for the mono / stereo fast paths");
   static_assert(!DUAL || (QUAD && TRIALS), "the dual mapping is the trial search on the quad mapping");
@@ -1696,7 +1838,12 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgs a)
   } else {
     sd = a.uni.enabled ? uniform_stream(a.uni, s) : a.streams[s];
   }
-  const SampleSource<MS> src = {a.pcm + sd.pcm_offset, ch, c, sd.num_samples};
+  /* where the stream's samples start: pcm_offset counts elements of the layout's type (planar: channel 0's row).  Built in
+   * place - through a helper function the interleaved kernels came out scheduled differently. */
+  PcmCursor<IN> x0;
+  if constexpr (IN == kInInterleaved) x0 = a.pcm + sd.pcm_offset;
+  else x0 = {reinterpret_cast<const PcmElem<IN> *>(a.pcm) + sd.pcm_offset, a.channel_stride};
+  const SampleSource<MS, IN> src = {x0, ch, c, sd.num_samples};
   uint8_t *out = a.data + sd.data_offset;
   const uint32_t total = sd.num_samples, spb = a.samples_per_block;
 

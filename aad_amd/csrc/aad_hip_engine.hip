@@ -2,8 +2,8 @@
  * aad_hip_engine.hip - host side of the batched C-ABI declared in include/aad_hip.h:
  * contexts, plans (uploaded stream tables), kernel launches and the host-memory convenience
  * calls.  Device code lives in aad_encode.hip.h / aad_decode.hip.h (shared parts: aad_device.hip.h)
- * and, for the split, sector-tiled and window decoders, in units of their own (aad_decode_split.hip,
- * aad_decode_tiled.hip, aad_decode_window.hip).  gfx950 only; no CPU code path -
+ * and, for the split, sector-tiled and window decoders and the planar-input encoders, in units of their own
+ * (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_planar.hip).  gfx950 only; no CPU code path -
  * every entry point that needs the GPU fails with AAD_APIRESULT_NG when HIP does.
  */
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "aad_decode.hip.h"
 #include "aad_decode_window.hip.h"
 #include "aad_encode.hip.h"
+#include "aad_encode_launch.hip.h"
 #include "aad_format.h"
 #include "aad_hip_internal.h"
 
@@ -108,6 +109,9 @@ struct AADHipEncodePlan {
   aad::StreamDesc *d_streams;
   aad::ChainDesc *d_chains; /* segmented plans: the chain table (args.chains), d_streams stays null */
   bool segmented;
+  bool planar;             /* AADHip_PlanarEncodePlanCreate: runs through AADHip_PlanarEncodePlanRun only */
+  int32_t sample_type;     /* planar: enum AADHipSampleType */
+  uint64_t channel_stride; /* planar: elements from one channel's row to the next */
 };
 
 struct AADHipDecodePlan {
@@ -210,37 +214,7 @@ bool upload(AADHipContext *ctx, T **dst, const T *src, size_t count)
 }
 
 /* ---- dispatch: from a plan (aad_launch_policy.h) to a template instantiation ---------------------------------------------- */
-/* encode_streams_kernel by channels and M/S; RING: the dense encoders whose output goes through the rows' byte rings
- * (aad_encode.hip.h ByteRing), mono / stereo only; SEG: the chains of a segmented plan */
-template <int BITS, bool QUAD, bool TRIALS, bool DUAL, bool RING = false, bool SEG = false>
-void launch_encode_mapped(const aad::EncodeArgs &a, const aad::EncodeLaunch &p, hipStream_t stream)
-{
-  const dim3 grid(p.grid), block(p.workgroup);
-  if (a.channels == 1)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 1, false, QUAD, TRIALS, DUAL, RING, SEG>), grid, block, p.lds, stream, a);
-  else if (a.channels == 2 && a.mid_side)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, true, QUAD, TRIALS, DUAL, RING, SEG>), grid, block, p.lds, stream, a);
-  else if (a.channels == 2)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 2, false, QUAD, TRIALS, DUAL, RING, SEG>), grid, block, p.lds, stream, a);
-  else if constexpr (!QUAD && !RING)
-    AAD_LAUNCH((aad::encode_streams_kernel<BITS, 0, false, false, TRIALS, false, false, SEG>), grid, block, p.lds, stream, a);
-}
-
-template <int BITS, bool SEG>
-void launch_encode(const aad::EncodeArgs &a, const aad::EncodeLaunch &p, hipStream_t stream)
-{
-  if (p.trials) {
-    if (p.kernel == aad::EncodeKernel::QuadDual) launch_encode_mapped<BITS, true, true, true, false, SEG>(a, p, stream);
-    else if (p.kernel == aad::EncodeKernel::Quad) launch_encode_mapped<BITS, true, true, false, false, SEG>(a, p, stream);
-    else launch_encode_mapped<BITS, false, true, false, false, SEG>(a, p, stream);
-  } else if (p.kernel == aad::EncodeKernel::Quad) {
-    launch_encode_mapped<BITS, true, false, false, false, SEG>(a, p, stream);
-  } else if (p.kernel == aad::EncodeKernel::DenseRing) {
-    if constexpr (!SEG) launch_encode_mapped<BITS, false, false, false, true>(a, p, stream); /* SEG: ring_ok = 0, never planned */
-  } else {
-    launch_encode_mapped<BITS, false, false, false, false, SEG>(a, p, stream);
-  }
-}
+/* the encoders: aad_encode_launch.hip.h */
 
 /* decode_blocks_kernel by channels and M/S; the dense stereo 4- / 2-bit kernels in their streamed-store form when the plan says so */
 template <int BITS, bool QUAD>
@@ -439,8 +413,10 @@ bool scratch_reserve(AADHipContext *ctx, T **buf, uint64_t *capacity, uint64_t b
   return true;
 }
 
-/* segmented: args.chains holds a chain table and num_streams counts chains (AADHip_SegmentedEncodePlanCreate) */
-AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args, bool segmented = false)
+/* segmented: args.chains holds a chain table and num_streams counts chains (AADHip_SegmentedEncodePlanCreate); planar: the input is
+ * rows of that sample type (enum AADHipSampleType, AADHip_PlanarEncodePlanCreate), -1 the interleaved int16 frames */
+AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args, bool segmented = false, int32_t planar = -1,
+                        uint64_t channel_stride = 0)
 {
   if (args.num_streams == 0) return AAD_APIRESULT_OK;
   if (args.bits < 2 || args.bits > 4) return AAD_APIRESULT_INVALID_FORMAT;
@@ -454,17 +430,21 @@ AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args, bool se
     if (!scratch_reserve(ctx, &ctx->d_trial, &ctx->trial_capacity, p.trial_scratch_bytes, "hipMalloc trial scratch")) return AAD_APIRESULT_NG;
     a.trial_scratch = ctx->d_trial;
   }
-  if (segmented) {
+  if (planar == AAD_HIP_SAMPLE_FLOAT32) {
+    aad::launch_encode_planar_f32(a, channel_stride, p, segmented, ctx->stream);
+  } else if (planar == AAD_HIP_SAMPLE_INT16 && a.channels != 1) { /* mono int16 rows ARE interleaved frames: the kernels below */
+    aad::launch_encode_planar_i16(a, channel_stride, p, segmented, ctx->stream);
+  } else if (segmented) {
     switch (a.bits) {
-      case 4: launch_encode<4, true>(a, p, ctx->stream); break;
-      case 3: launch_encode<3, true>(a, p, ctx->stream); break;
-      default: launch_encode<2, true>(a, p, ctx->stream); break;
+      case 4: aad::launch_encode<4, true>(a, p, ctx->stream); break;
+      case 3: aad::launch_encode<3, true>(a, p, ctx->stream); break;
+      default: aad::launch_encode<2, true>(a, p, ctx->stream); break;
     }
   } else {
     switch (a.bits) {
-      case 4: launch_encode<4, false>(a, p, ctx->stream); break;
-      case 3: launch_encode<3, false>(a, p, ctx->stream); break;
-      default: launch_encode<2, false>(a, p, ctx->stream); break;
+      case 4: aad::launch_encode<4, false>(a, p, ctx->stream); break;
+      case 3: aad::launch_encode<3, false>(a, p, ctx->stream); break;
+      default: aad::launch_encode<2, false>(a, p, ctx->stream); break;
     }
   }
   return hip_ok(ctx, hipGetLastError(), "encode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
@@ -729,6 +709,8 @@ AADApiResult AADHip_EncodePlanCreate(struct AADHipContext *ctx, const struct AAD
   p->d_streams = nullptr;
   p->d_chains = nullptr;
   p->segmented = false;
+  p->planar = false;
+  p->sample_type = 0;
   DeviceGuard guard(ctx);
   if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams)) {
     if (p->d_streams) (void)hipFree(p->d_streams);
@@ -776,6 +758,8 @@ AADApiResult AADHip_SegmentedEncodePlanCreate(struct AADHipContext *ctx, const s
   p->d_streams = nullptr;
   p->d_chains = nullptr;
   p->segmented = true;
+  p->planar = false;
+  p->sample_type = 0;
   DeviceGuard guard(ctx);
   if (!guard.ok || !upload(ctx, &p->d_chains, chains.data(), chains.size())) {
     if (p->d_chains) (void)hipFree(p->d_chains);
@@ -800,6 +784,7 @@ AADApiResult AADHip_EncodePlanRun(struct AADHipEncodePlan *plan, const int16_t *
   DeviceGuard guard(ctx);
   if (!guard.ok) return AAD_APIRESULT_NG;
   if (plan->segmented && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  if (plan->planar) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* rows, not frames: AADHip_PlanarEncodePlanRun */
   if (plan->args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
   aad::EncodeArgs a = plan->args;
   a.pcm = device_pcm;
@@ -808,6 +793,96 @@ AADApiResult AADHip_EncodePlanRun(struct AADHipEncodePlan *plan, const int16_t *
   a.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
   aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
   return finish_signal(ctx, signal, run_encode(ctx, a, plan->segmented));
+}
+
+/* ------------------------------------------------------------------------ planar encode -- */
+
+AADApiResult AADHip_PlanarEncodePlanCreate(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                           const struct AADHipPlanarLayout *layout, const struct AADHipSegmentation *segmentation,
+                                           uint32_t num_streams, const struct AADHipStreamDesc *streams, struct AADHipEncodePlan **plan)
+{
+  if (ctx == nullptr || parameter == nullptr || layout == nullptr || plan == nullptr || (num_streams != 0 && streams == nullptr))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *plan = nullptr;
+  if ((layout->sample_type != AAD_HIP_SAMPLE_INT16 && layout->sample_type != AAD_HIP_SAMPLE_FLOAT32) || layout->reserved != 0)
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  if (segmentation != nullptr && segmentation->segment_blocks == 0) return AAD_APIRESULT_INVALID_ARGUMENT;
+  aad::EncodeArgs args;
+  const AADApiResult rc = encode_plan_init(parameter, num_streams, streams, &args);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  /* every row of every stream lies inside [0, 2^64) elements and bytes: the last element a stream reads is
+   * pcm_offset + (C - 1) channel_stride + num_samples - 1 */
+  const uint64_t elem = layout->sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4u : 2u;
+  for (uint32_t i = 0; i < num_streams; i++) {
+    if (args.channels > 1 && layout->channel_stride < streams[i].num_samples) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "planar encode plan: channel_stride %llu < num_samples %u of stream %u",
+               (unsigned long long)layout->channel_stride, streams[i].num_samples, i);
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    uint64_t span = 0, end = 0, bytes = 0;
+    if (__builtin_mul_overflow((uint64_t)(args.channels - 1), layout->channel_stride, &span) ||
+        __builtin_add_overflow(span, (uint64_t)streams[i].num_samples, &span) ||
+        __builtin_add_overflow(streams[i].pcm_offset, span, &end) || __builtin_mul_overflow(end, elem, &bytes)) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "planar encode plan: the rows of stream %u overflow 64-bit offsets", i);
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+  }
+  std::vector<aad::ChainDesc> chains;
+  if (segmentation != nullptr &&
+      !aad::build_segment_chains(streams, num_streams, args.channels, args.samples_per_block, args.block_size,
+                                 segmentation->segment_blocks, segmentation->warmup_blocks, &chains, true)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "planar encode plan: more than %u chains", (unsigned)UINT32_MAX);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  AADHipEncodePlan *p = new (std::nothrow) AADHipEncodePlan();
+  if (p == nullptr) return AAD_APIRESULT_NG;
+  p->ctx = ctx;
+  p->d_streams = nullptr;
+  p->d_chains = nullptr;
+  p->segmented = segmentation != nullptr;
+  p->planar = true;
+  p->sample_type = layout->sample_type;
+  DeviceGuard guard(ctx);
+  const bool ok = guard.ok && (p->segmented ? upload(ctx, &p->d_chains, chains.data(), chains.size())
+                                            : upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams));
+  if (!ok) {
+    if (p->d_streams) (void)hipFree(p->d_streams);
+    if (p->d_chains) (void)hipFree(p->d_chains);
+    delete p;
+    return AAD_APIRESULT_NG;
+  }
+  p->args = args;
+  p->channel_stride = layout->channel_stride;
+  if (p->segmented) { /* as AADHip_SegmentedEncodePlanCreate */
+    p->args.chains = p->d_chains;
+    p->args.num_streams = (uint32_t)chains.size();
+    p->args.ring_ok = 0;
+    p->args.uni.enabled = 0;
+  } else {
+    p->args.streams = p->d_streams;
+  }
+  *plan = p;
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_PlanarEncodePlanRun(struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data,
+                                        struct AADHipLaneState *device_state)
+{
+  if (plan == nullptr || device_samples == nullptr || device_data == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = plan->ctx;
+  const aad::LaunchSignal signal = take_signal(ctx);
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (!plan->planar) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* frames, not rows: AADHip_EncodePlanRun */
+  if (plan->segmented && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  if (plan->args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
+  aad::EncodeArgs a = plan->args;
+  a.pcm = static_cast<const int16_t *>(device_samples); /* the kernels read it as the plan's sample type */
+  a.data = device_data;
+  a.state = reinterpret_cast<const aad::LaneStateRecord *>(device_state);
+  a.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
+  aad::tl_launch_signal = signal;
+  return finish_signal(ctx, signal, run_encode(ctx, a, plan->segmented, plan->sample_type, plan->channel_stride));
 }
 
 /* ------------------------------------------------------------------------------- decode -- */

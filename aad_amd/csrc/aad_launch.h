@@ -31,6 +31,11 @@ void launch_decode_tiled(const DecodeArgs &args, const DecodeLaunch &p, hipStrea
 /* aad_decode_window.hip: the window decoder (AADHip_WindowDecodePlanRun), int16 or float32 rows */
 struct WindowArgs;
 void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
+/* aad_encode_planar.hip (compiled once per sample type): the planar-input encoders (AADHip_PlanarEncodePlanRun); segmented: args.chains
+ * holds a chain table, as for the interleaved kernels */
+struct EncodeArgs;
+void launch_encode_planar_i16(const EncodeArgs &args, uint64_t channel_stride, const EncodeLaunch &p, bool segmented, hipStream_t stream);
+void launch_encode_planar_f32(const EncodeArgs &args, uint64_t channel_stride, const EncodeLaunch &p, bool segmented, hipStream_t stream);
 }
 
 #define AAD_LAUNCH(kernel, grid, block, lds, stream, ...)                                                           \

@@ -18,7 +18,8 @@ namespace aad {
 
 /* one chain of a segmented encode: one segment of one stream, all of its channels */
 struct ChainDesc {
-  uint64_t pcm_offset;     /* index of the int16 that starts the chain's first encoded frame (a warm-up frame, if any) */
+  uint64_t pcm_offset;     /* index of the int16 that starts the chain's first encoded frame (a warm-up frame, if any); planar input:
+                            * of the element that starts channel 0's row there */
   uint64_t data_offset;    /* byte offset of the STREAM's image */
   uint64_t first_block;    /* index in the stream of the chain's first encoded block (the first warm-up block, if any) */
   uint32_t num_frames;     /* frames the chain encodes, warm-up included */
@@ -43,9 +44,12 @@ inline uint64_t segment_chain_count(const AADHipStreamDesc *streams, uint32_t nu
 
 /* The chain table of a batch, stream by stream and segment by segment.  False (and `out` untouched) when a geometry term is zero
  * or the batch has more than UINT32_MAX chains (the kernel indexes chains with 32 bits).  block_size only bounds the table: a
- * chain's blocks lie at 31 + block * block_size in its stream's image, which the 64-bit offsets hold for any stream. */
+ * chain's blocks lie at 31 + block * block_size in its stream's image, which the 64-bit offsets hold for any stream.
+ * planar: the streams' PCM is one row per channel (AADHip_PlanarEncodePlanCreate) - a chain starts first_frame elements into
+ * channel 0's row, not first_frame frames of interleaved samples into the stream. */
 inline bool build_segment_chains(const AADHipStreamDesc *streams, uint32_t num_streams, uint32_t channels, uint32_t spb,
-                                 uint32_t block_size, uint32_t segment_blocks, uint32_t warmup_blocks, std::vector<ChainDesc> *out)
+                                 uint32_t block_size, uint32_t segment_blocks, uint32_t warmup_blocks, std::vector<ChainDesc> *out,
+                                 bool planar = false)
 {
   if (channels == 0 || spb == 0 || block_size == 0 || segment_blocks == 0) return false;
   const uint64_t count = segment_chain_count(streams, num_streams, spb, segment_blocks);
@@ -61,7 +65,7 @@ inline bool build_segment_chains(const AADHipStreamDesc *streams, uint32_t num_s
       const uint64_t kept = s * L, w = warmup_blocks < kept ? warmup_blocks : kept;
       const uint64_t first_frame = (kept - w) * spb, end_frame = (s + 1) * L * spb < n ? (s + 1) * L * spb : n;
       ChainDesc c;
-      c.pcm_offset = sd.pcm_offset + first_frame * channels;
+      c.pcm_offset = sd.pcm_offset + first_frame * (planar ? 1u : channels);
       c.data_offset = sd.data_offset;
       c.first_block = kept - w;
       c.num_frames = (uint32_t)(end_frame - first_frame);

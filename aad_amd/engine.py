@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import (AADApiResult, AADHeaderInfo, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
+from .capi import (AADApiResult, AADHeaderInfo, AADHipPlanarLayout, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
                    OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
                    SAMPLE_FLOAT32, SAMPLE_INT16, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, load_library, make_parameter)
 
@@ -133,6 +133,25 @@ class Engine:
         p.segmented = segment_blocks is not None
         return p
 
+    def planar_encode_plan(self, param, descs, channel_stride, dtype, segment_blocks=None, warmup_blocks=0):
+        """A plan over planar input (AADHip_PlanarEncodePlanCreate): stream i's channel c is the row of num_samples elements at
+        pcm_offset + c * channel_stride of a torch.int16 or torch.float32 buffer (float32: sample * 32768, rounded to even and
+        clamped, NaN as 0).  The bytes are encode_plan's on the interleaved int16 of those samples; segment_blocks /
+        warmup_blocks as there.  PlanarEncodePlan.run encodes."""
+        torch = self.torch
+        if dtype not in (torch.int16, torch.float32):
+            raise ValueError("planar encode reads torch.int16 or torch.float32 rows, not %s" % dtype)
+        descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
+        layout = AADHipPlanarLayout(SAMPLE_FLOAT32 if dtype == torch.float32 else SAMPLE_INT16, 0, int(channel_stride))
+        seg = AADHipSegmentation(int(segment_blocks), int(warmup_blocks)) if segment_blocks is not None else None
+        plan = C.c_void_p()
+        _check("AADHip_PlanarEncodePlanCreate",
+               self.lib.AADHip_PlanarEncodePlanCreate(self._ctx, C.byref(param), C.byref(layout), C.byref(seg) if seg is not None else None,
+                                                      len(descs), descs.ctypes.data, C.byref(plan)))
+        p = PlanarEncodePlan(self, plan, param, descs, dtype)
+        p.segmented = segment_blocks is not None
+        return p
+
     def decode_plan(self, header, descs, has_file_header=True):
         descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
         plan = C.c_void_p()
@@ -192,6 +211,42 @@ class Engine:
         out = torch.zeros((streams, plan.stride), dtype=torch.uint8, device=pcm.device)
         plan.run(pcm, out, state)
         return out, plan.image_size
+
+    def encode_planar(self, x, param, num_samples=None, state=None, segment_blocks=None, warmup_blocks=0):
+        """x: int16 or float32 cuda tensor [N, C, T] - a view is fine as long as x.stride(-1) == 1 - -> (uint8 tensor [N, stride],
+        image_sizes): row i starts with the .aad image of x[i, :, :num_samples[i]] (num_samples: per-row lengths <= T, default T),
+        image_sizes[i] bytes long; rows lie on 64-byte boundaries as in encode_uniform.  float32 samples are read as
+        sample * 32768 (rounded to even, clamped, NaN as 0); the rows are encoded where they are, with no copy or conversion pass."""
+        torch = self.torch
+        if state is not None and segment_blocks is not None:
+            raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
+        if x.dim() != 3 or not x.is_cuda or x.dtype not in (torch.int16, torch.float32):
+            raise ValueError("encode_planar takes an int16 or float32 cuda tensor [N, C, T]")
+        n, ch, t = (int(v) for v in x.shape)
+        if ch != param.num_channels:
+            raise ValueError("x has %d channels, the parameter %d" % (ch, param.num_channels))
+        if x.stride(-1) != 1:
+            raise ValueError("encode_planar needs x.stride(-1) == 1 (each channel's samples contiguous); got strides %s - pass "
+                             "x.contiguous() if a copy is intended" % (tuple(x.stride()),))
+        lengths = np.full(n, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
+        if len(lengths) != n or (n and (lengths.min() < 1 or lengths.max() > t)):
+            raise ValueError("num_samples: %d lengths in [1, %d]" % (n, t))
+        sizes = np.array([self.encoded_size(param, int(v)) for v in lengths], dtype=np.uint64)
+        if n and sizes.min() == 0:
+            raise ApiError("AADHip_CalculateEncodedSize", AADApiResult.INVALID_FORMAT)
+        stride = _round_up(int(sizes.max()), 64) if n else 64
+        d = np.zeros(n, dtype=STREAM_DESC_DTYPE)
+        d["pcm_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(x.stride(0))
+        d["data_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(stride)
+        d["data_size"] = stride
+        d["num_samples"] = lengths
+        out = torch.zeros((n, stride), dtype=torch.uint8, device=x.device)
+        plan = self.planar_encode_plan(param, d, x.stride(1), x.dtype, segment_blocks, warmup_blocks)
+        try:
+            plan.run(x, out, state)
+        finally:
+            plan.close()  # synchronises the context's stream first
+        return out, [int(v) for v in sizes]
 
     def decode_uniform(self, data, image_size):
         """data: uint8 cuda tensor [streams, stride] of same-format images -> int16 [streams, samples, channels]"""
@@ -359,6 +414,26 @@ class EncodePlan:
             self.close()
         except Exception:
             pass
+
+
+class PlanarEncodePlan(EncodePlan):
+    def __init__(self, engine, handle, param, descs, dtype):
+        super().__init__(engine, handle, param, descs)
+        self.dtype = dtype
+
+    def run(self, x, data, state=None, ordered=True):
+        """x: cuda tensor of the plan's dtype whose data_ptr() the table's pcm_offsets count from (elements), data: uint8 cuda
+        tensor, state: int32 cuda tensor [lanes, 10] or None; ordered as EncodePlan.run"""
+        if x.dtype != self.dtype or not x.is_cuda:
+            raise ValueError("this plan reads %s cuda rows, not %s" % (self.dtype, x.dtype))
+        if state is not None and self.segmented:
+            raise ValueError("a segmented encode plan takes no state")
+        sp = state.data_ptr() if state is not None else None
+        cur = self.engine._enter() if ordered else None
+        _check("AADHip_PlanarEncodePlanRun",
+               self.engine.lib.AADHip_PlanarEncodePlanRun(self.handle, x.data_ptr(), data.data_ptr(), sp))
+        if ordered:
+            self.engine._exit(cur)
 
 
 class DecodePlan:
@@ -557,4 +632,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE"]

@@ -17,7 +17,8 @@
  * AADEncoder_ / AADDecoder_ symbols are implemented on top of these with a batch of one.
  *
  * Device data layout
- *   PCM   : int16, channel-interleaved frames, one contiguous run per stream.
+ *   PCM   : int16, channel-interleaved frames, one contiguous run per stream (AADHip_PlanarEncodePlanRun: int16 or
+ *           float32 rows, one per channel).
  *   .aad  : the exact file image per stream - 31-byte header followed by the blocks - byte for
  *           byte what the reference writes for the same samples and parameters.
  */
@@ -70,7 +71,7 @@ const char *AADHip_ContextLastError(const struct AADHipContext *context);
 
 /* Cross-stream ordering and kernel timing without packets of their own.  `hip_start_event` / `hip_stop_event` (hipEvent_t the
  * caller owns; either may be NULL, both NULL withdraws) are recorded when the work of the NEXT AADHip_EncodePlanRun /
- * AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
+ * AADHip_PlanarEncodePlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
  * the run takes them.  An encode, decode or window decode plan run is one kernel, and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
  * stop events) instead of on barrier packets around it: a hipEventRecord behind every launch of a back-to-back sequence costs
  * the queue 2.9 us per launch on MI355X, the attached event nothing (profiles/r03_microbench_event_gap.txt), and
@@ -234,6 +235,45 @@ AADApiResult AADHip_WindowDecodePlanRun(
     struct AADHipWindowDecodePlan *plan, const uint8_t *device_data,
     uint64_t num_windows, const struct AADHipWindow *device_windows,
     uint32_t frames_per_window, int32_t sample_type, void *device_out);
+
+/* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
+
+/* The write side of the planar layout window decode reads out: one row per channel, int16 or float32 - torch's [N, C, T] - encoded
+ * by the encoder kernels themselves, with no interleaving or conversion pass in front.
+ *
+ * Definition.  For stream i (descriptor d_i), channel c < C and frame t < num_samples_i the input value is
+ *   v = x[pcm_offset_i + c * channel_stride + t]        (offsets in elements of the sample type)
+ * and the encoder sees the int16 sample q(v):
+ *   int16:    q(v) = v
+ *   float32:  q(v) = 0 if v is a NaN (quiet or signalling), else clamp(roundTiesToEven(v * 32768), -32768, 32767)
+ *             (v * 32768 is exact in float32, or overflows to +-inf and clamps; as torch:
+ *             nan_to_num(x, nan=0).mul(32768).round().clamp(-32768, 32767).to(int16).  q inverts window decode's float32 output.)
+ * The image bytes are those AADHip_EncodePlanRun writes for a plan with the same parameter, descriptor table (data_offset,
+ * data_size, num_samples), segmentation (NULL: AADHip_EncodePlanCreate, else AADHip_SegmentedEncodePlanCreate) and device_state,
+ * run on the interleaved int16 buffer P_i[t * C + c] = q(v); M/S is formed from q(L) and q(R).  So without segmentation the bytes
+ * are the reference encoder's, with it those of the segmented definition above.
+ *
+ * A planar plan is an ordinary AADHipEncodePlan: AADHip_EncodePlanDestroy destroys it, and AADHip_ContextSignalNextRun's events
+ * ride on AADHip_PlanarEncodePlanRun's one kernel.  AADHip_EncodePlanRun refuses a planar plan and AADHip_PlanarEncodePlanRun an
+ * interleaved one (AAD_APIRESULT_INVALID_ARGUMENT): neither misreads its input.  device_samples may sit at any element offset.
+ * Errors are those of AADHip_EncodePlanCreate / AADHip_SegmentedEncodePlanCreate and AADHip_EncodePlanRun, plus
+ * AAD_APIRESULT_INVALID_ARGUMENT for a null layout, an unknown sample_type or a non-zero reserved, C > 1 with channel_stride below
+ * any stream's num_samples, and a stream whose last element (pcm_offset + (C - 1) channel_stride + num_samples) or its byte offset
+ * overflows 64 bits. */
+struct AADHipPlanarLayout {
+  int32_t sample_type;     /* enum AADHipSampleType: AAD_HIP_SAMPLE_INT16 or AAD_HIP_SAMPLE_FLOAT32 */
+  uint32_t reserved;       /* 0 */
+  uint64_t channel_stride; /* elements from channel c's row of a stream to channel c + 1's (ignored for mono) */
+};
+AADApiResult AADHip_PlanarEncodePlanCreate(
+    struct AADHipContext *context, const struct AADEncodeParameter *parameter,
+    const struct AADHipPlanarLayout *layout,
+    const struct AADHipSegmentation *segmentation, /* NULL: the serial (reference-exact) encode */
+    uint32_t num_streams, const struct AADHipStreamDesc *streams,
+    struct AADHipEncodePlan **plan);
+AADApiResult AADHip_PlanarEncodePlanRun(
+    struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data,
+    struct AADHipLaneState *device_state);
 
 /* ---- host-memory convenience (stage -> run -> copy back, synchronous) ---------------------- */
 
