@@ -54,6 +54,10 @@ class AADHipPlanarLayout(C.Structure):  # include/aad_hip.h
     _fields_ = [("sample_type", C.c_int32), ("reserved", C.c_uint32), ("channel_stride", C.c_uint64)]
 
 
+class AADHipPlanarOutput(C.Structure):  # include/aad_hip.h
+    _fields_ = [("sample_type", C.c_int32), ("reserved", C.c_uint32), ("stream_stride", C.c_uint64), ("channel_stride", C.c_uint64)]
+
+
 class AADHipLaneState(C.Structure):  # include/aad_hip.h
     _fields_ = [("weight", C.c_int32 * 4), ("history", C.c_int32 * 4),
                 ("stepsize_index", C.c_int32), ("quantize_error", C.c_int32)]
@@ -90,6 +94,7 @@ HIP_SYMBOLS = [
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
+    "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -165,6 +170,12 @@ def _declare_hip(lib):
     lib.AADHip_PlanarEncodePlanCreate.restype = C.c_int
     lib.AADHip_PlanarEncodePlanRun.argtypes = [vp, vp, vp, vp]
     lib.AADHip_PlanarEncodePlanRun.restype = C.c_int
+    lib.AADHip_PlanarReconstructPlanCreate.argtypes = [vp, C.POINTER(AADEncodeParameter), C.POINTER(AADHipPlanarLayout),
+                                                       C.POINTER(AADHipPlanarOutput), C.POINTER(AADHipSegmentation), C.c_uint32, vp,
+                                                       C.POINTER(vp)]
+    lib.AADHip_PlanarReconstructPlanCreate.restype = C.c_int
+    lib.AADHip_PlanarReconstructPlanRun.argtypes = [vp, vp, vp, vp, vp]
+    lib.AADHip_PlanarReconstructPlanRun.restype = C.c_int
     lib.AADHip_EncodePlanDestroy.argtypes = [vp]
     lib.AADHip_EncodePlanDestroy.restype = None
     lib.AADHip_EncodePlanRun.argtypes = [vp, vp, vp, vp]

@@ -100,8 +100,10 @@ __device__ __forceinline__ int64_t wrapped_square(int32_t qd) { return (int64_t)
  * dequantised differences to sq (an RMSE pass of the trial search - same recurrence, no output) */
 /* PACKED: x holds eight dwords of two int16 samples each instead of sixteen widened values (the
  * subtract then reads the halves directly, v_sub_u32_sdwa) */
-template <int BITS, bool EMIT, bool PACKED = false, typename S>
-__device__ __forceinline__ void encode_chunk16(S &L, const int32_t *x, const char *lds, uint32_t *w, int32_t &qd_out, int64_t &sq)
+/* CAP: the reconstructed samples of the chunk go to yb[0..15] as well (planar reconstruct, RecRow below) */
+template <int BITS, bool EMIT, bool PACKED = false, typename S, bool CAP = false>
+__device__ __forceinline__ void encode_chunk16(S &L, const int32_t *x, const char *lds, uint32_t *w, int32_t &qd_out, int64_t &sq,
+                                               [[maybe_unused]] int32_t *yb = nullptr)
 {
   auto sample = [&](int k) -> int32_t { /* k compile-time after unrolling */
     if (PACKED) return (k & 1) ? x[k >> 1] >> 16 : (int32_t)(int16_t)x[k >> 1];
@@ -135,6 +137,7 @@ __device__ __forceinline__ void encode_chunk16(S &L, const int32_t *x, const cha
     const int32_t q = (int32_t)(uint32_t)(((uint64_t)(step9 & 0xFFFFFFu) * (uint64_t)(m21s & 0xFFFFFFu)) >> 32); /* v_mul_hi_u32_u24 */
     const int32_t qd = (q ^ m) - m;
     const int32_t y = clip16(qd + p);
+    if constexpr (CAP) yb[j] = y;
     if (EMIT) {
       uint32_t &acc = w[j / Pack<BITS>::kCodesPerWord];
       acc = (acc << BITS) | code; /* v_lshl_or_b32 */
@@ -219,9 +222,12 @@ enum { kPassRmse = 0, kPassEncode = 1, kPassBoth = 2 };
 
 /* N: samples walked (sixteen; fewer for a block's last samples, see run_block's pipelined tail - their codes end up in the LOW
  * bits of the last code word they reach) */
-template <int BITS, int PASS, int FORMAT = kWide, typename Fill = NoFill, int N = kChunk>
+/* CAP: after every fourth sample j the history shift has left y(j - t) in tap t, so the quad holds samples j - 3 .. j; each lane
+ * keeps its tap's one in ycap[j / 4] (planar reconstruct, RecRow::quad) */
+template <int BITS, int PASS, int FORMAT = kWide, typename Fill = NoFill, int N = kChunk, bool CAP = false>
 __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C, const int32_t *x, int32_t xn0,
-                                                    const char *lds, uint32_t *w, int32_t &qd_out, int64_t &sq, Fill fill = Fill())
+                                                    const char *lds, uint32_t *w, int32_t &qd_out, int64_t &sq, Fill fill = Fill(),
+                                                    [[maybe_unused]] int32_t *ycap = nullptr)
 {
   static_assert(N >= 1 && N <= kChunk, "at most a chunk");
   constexpr bool EMIT = PASS != kPassRmse, SUM = PASS != kPassEncode;
@@ -260,6 +266,7 @@ __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C,
     const int32_t qd = yq - p;
     const int32_t y = clip16(yq);
     lms_and_shift<kEncTM ? kShiftBankMask : kShiftBitSelect>(L, qd, y);
+    if constexpr (CAP && (j & 3) == 3) ycap[j >> 2] = L.h;
     /* prediction of the next sample, with the two instructions that pack this sample's code
      * placed in the wait states its DPP adds need (see decode_chunk16_quad) */
     uint32_t s = (uint32_t)L.h * (uint32_t)L.w + L.round;
@@ -354,6 +361,101 @@ struct PlanarEncodeArgs : EncodeArgs {
   uint64_t channel_stride; /* elements from one channel's row of a stream to the next */
 };
 template <int IN> using EncodeArgsFor = std::conditional_t<IN == kInInterleaved, EncodeArgs, PlanarEncodeArgs>;
+
+/* Output of encode_streams_kernel (its REC): nothing but the images, or also the decoded rows as int16 / float32 (sample / 32768,
+ * exact) - AADHip_PlanarReconstructPlanRun.  The decoder's output of an image is the encoder's own reconstruction: the history
+ * value clip16(qd + p) of every coded sample, the header's history for a block's first four, and clip16(M + S), clip16(M - S)
+ * with M/S.  So the encode pass writes the rows as it goes; the trial search's measuring passes and a segmented chain's warm-up
+ * blocks (kPassRmse) write nothing. */
+enum RecOutput { kRecNone = 0, kRecI16 = 1, kRecF32 = 2 };
+
+/* the reconstruct kernels' arguments: the output rows on top of the planar input's */
+struct RecEncodeArgs : PlanarEncodeArgs {
+  void *out;                   /* int16 or float32 rows */
+  const uint64_t *out_base;    /* per stream (SEG: per chain) the element of `out` that holds channel 0's sample of the lane's frame 0 */
+  uint64_t out_channel_stride; /* elements from one channel's row to the next */
+};
+template <int IN, int REC> using KernelArgsFor = std::conditional_t<REC == kRecNone, EncodeArgsFor<IN>, RecEncodeArgs>;
+
+struct NoRec {
+  static constexpr bool kOn = false;
+};
+
+typedef float f32x4_rec __attribute__((ext_vector_type(4), aligned(4))); /* a 16-byte store at 4-byte alignment */
+
+/* the output row of one lane (its channel, from the lane's frame 0 on).  Every store lies on a real sample of the block the pass
+ * encodes: header samples below n, whole chunks, the pipelined tail's whole units, encode_step samples before the zero padding. */
+template <int REC, bool MS, bool QUAD>
+struct RecRow {
+  static constexpr bool kOn = true;
+  using T = std::conditional_t<REC == kRecF32, float, int16_t>;
+  T *row;
+  uint32_t c, tap;
+  __device__ __forceinline__ static T convert(int32_t y)
+  {
+    if constexpr (REC == kRecF32) return (float)y * (1.0f / 32768.0f); /* exact: an int16 times a power of two */
+    else return (T)y;
+  }
+  /* the decoder's sample of this lane's channel from the reconstructed one: with M/S, L = clip16(M + S), R = clip16(M - S) from the
+   * pair's other lane (the neighbouring lane in the dense and the tap-major quad mapping - both lanes of the pair call this) */
+  __device__ __forceinline__ int32_t decoded(int32_t y) const
+  {
+    if constexpr (MS) {
+      const int32_t o = (int32_t)pair_swap<false>((uint32_t)y, c);
+      return c == 0 ? clip16(y + o) : clip16(o - y);
+    } else {
+      return y;
+    }
+  }
+  /* the first min(n, 4) samples of a block: the header's history, h3 oldest (quad: tap k stores sample k) */
+  __device__ __forceinline__ void header(uint64_t first, uint32_t n, const Lane &F) const
+  {
+    const int32_t h[kTaps] = {F.h3, F.h2, F.h1, F.h0};
+#pragma unroll
+    for (int k = 0; k < kTaps; k++) {
+      const int32_t v = decoded(h[k]);
+      if ((uint32_t)k < n && (!QUAD || tap == (uint32_t)k)) row[first + k] = convert(v);
+    }
+  }
+  /* a sample walked by encode_step: y where the history keeps the newest one (quad: tap 0 stores it); real: not zero padding */
+  __device__ __forceinline__ void one(uint64_t f, int32_t y, bool real) const
+  {
+    const int32_t v = decoded(y);
+    if (real && (!QUAD || tap == 0u)) row[f] = convert(v);
+  }
+  /* dense: a whole chunk, samples f .. f + 15, as 16-byte stores at the row's own alignment */
+  __device__ __forceinline__ void chunk(uint64_t f, const int32_t *y) const
+  {
+    int32_t v[kChunk];
+#pragma unroll
+    for (int j = 0; j < kChunk; j++) v[j] = decoded(y[j]);
+    T *p = row + f;
+    if constexpr (REC == kRecF32) {
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        *reinterpret_cast<f32x4_rec *>(p + 4 * q) = f32x4_rec{convert(v[4 * q]), convert(v[4 * q + 1]), convert(v[4 * q + 2]), convert(v[4 * q + 3])};
+    } else {
+#pragma unroll
+      for (int h = 0; h < 2; h++)
+        reinterpret_cast<U32x4 *>(p + 8 * h)->v =
+            u32x4{perm((uint32_t)v[8 * h + 1], (uint32_t)v[8 * h], 0x05040100), perm((uint32_t)v[8 * h + 3], (uint32_t)v[8 * h + 2], 0x05040100),
+                  perm((uint32_t)v[8 * h + 5], (uint32_t)v[8 * h + 4], 0x05040100), perm((uint32_t)v[8 * h + 7], (uint32_t)v[8 * h + 6], 0x05040100)};
+    }
+  }
+  /* quad: G groups of four samples from f on; yq[g] holds sample 4 g + 3 - tap (encode_chunk16_quad's CAP), so the four lanes of a
+   * recurrence store a group's four neighbouring samples with one instruction */
+  template <int G>
+  __device__ __forceinline__ void quad(uint64_t f, const int32_t *yq) const
+  {
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      const int32_t v = decoded(yq[g]);
+      row[f + 4 * g + 3 - tap] = convert(v);
+    }
+  }
+};
+__device__ __forceinline__ int32_t newest_sample(const Lane &L) { return L.h0; }
+__device__ __forceinline__ int32_t newest_sample(const QuadLane &Q) { return Q.h; } /* (in tap 0) */
 
 /* planar input at a frame: channel 0's row there, and the distance to the next row */
 template <typename T>
@@ -963,13 +1065,16 @@ constexpr bool kBurstStores = EMIT && CHF == 2 && BITS == 4;
  * the last whole unit) or like a measurement (at the last real sample) - the sum covers real samples
  * either way. */
 /* RING: the encode pass appends its bytes to the row's ByteRing (`ring`) instead of storing them under `body` */
-template <int BITS, int CHF, bool MS, bool QUAD, int PASS, bool RING = false, typename S, int IN = kInInterleaved>
+/* rec (a RecRow): the encode pass also writes the lane's decoded row (planar reconstruct) */
+template <int BITS, int CHF, bool MS, bool QUAD, int PASS, bool RING = false, typename S, int IN = kInInterleaved, typename R = NoRec>
 __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &src, uint64_t first, uint32_t n, uint32_t ch,
                                              uint32_t c, bool writer, uint8_t *body, const char *lds, int32_t &last_qd,
                                              bool defer3 = false, uint32_t deferred = 0, bool pad = true,
-                                             ByteRing<(CHF ? CHF : 1)> *ring = nullptr)
+                                             ByteRing<(CHF ? CHF : 1)> *ring = nullptr, const R *rec = nullptr)
 {
   constexpr bool EMIT = PASS != kPassRmse;
+  constexpr bool REC = R::kOn;
+  static_assert(!REC || (PASS == kPassEncode && !RING), "the decoded rows: the plain encode pass");
   static_assert(!RING || (EMIT && kRingable<BITS, CHF, QUAD>), "the byte ring serves the dense mono / stereo encode passes");
   constexpr int kPiece = BITS == 4 ? 8 : (BITS == 3 ? 12 : 4); /* RING: bytes per lane and append (3-bit: of two chunks) */
   RingSelectors ring_sel = {0, 0, 0};
@@ -1059,6 +1164,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
       const uint32_t sel_x = c ? (0x02060307u ^ 0x04040404u) : 0x02060307u, sel_y = c ? (0x00040105u ^ 0x04040404u) : 0x00040105u;
       auto one = [&](uint32_t k, const RawT &cur, const RawT &ahead, RawT &incoming) {
         uint32_t w[2] = {0, 0};
+        int32_t yq[4];
         const bool pending = kStaged && k != 0;
         if constexpr (!kStaged) { /* (the other shapes ran 1-3 % slower with their loads in the gaps: measured, same box) */
           incoming.load(rp); /* prefetch chunk k+2 (clamped to the last full one) */
@@ -1088,12 +1194,15 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
           }
         };
         if constexpr (IN == kInInterleaved) {
-          encode_chunk16_quad<BITS, PASS, FMT>(L, C, reinterpret_cast<const int32_t *>(cur.d), (int32_t)ahead.d[0], lds, w, last_qd, sq, fill);
+          encode_chunk16_quad<BITS, PASS, FMT, decltype(fill), kChunk, REC>(L, C, reinterpret_cast<const int32_t *>(cur.d), (int32_t)ahead.d[0],
+                                                                            lds, w, last_qd, sq, fill, yq);
         } else {
           uint32_t xw[8];
           cur.pack(xw);
-          encode_chunk16_quad<BITS, PASS, FMT>(L, C, reinterpret_cast<const int32_t *>(xw), ahead.sample(0), lds, w, last_qd, sq, fill);
+          encode_chunk16_quad<BITS, PASS, FMT, decltype(fill), kChunk, REC>(L, C, reinterpret_cast<const int32_t *>(xw), ahead.sample(0), lds,
+                                                                            w, last_qd, sq, fill, yq);
         }
+        if constexpr (REC) rec->template quad<4>(first + kTaps + (uint64_t)k * kChunk, yq);
         if constexpr (kStaged) {
           wp0 = w[0];
           wp1 = w[1];
@@ -1140,7 +1249,9 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
         if (k + 2 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u); /* prefetch chunk k+2 (clamped to the last full one) */
         next.load(xp, ch, c);
         uint32_t w[2] = {0, 0};
-        encode_chunk16_quad<BITS, PASS, kWide>(L, C, cur, ahead[0], lds, w, last_qd, sq);
+        int32_t yq[4];
+        encode_chunk16_quad<BITS, PASS, kWide, NoFill, kChunk, REC>(L, C, cur, ahead[0], lds, w, last_qd, sq, NoFill(), yq);
+        if constexpr (REC) rec->template quad<4>(first + kTaps + (uint64_t)k * kChunk, yq);
         next.touch();
         extract(cur);
         if (EMIT && writer) store_chunk_codes<BITS, (CHF ? CHF : 1), QUAD && !kEncTM>(body + (uint64_t)k * kOutStride * ch, w, c);
@@ -1192,7 +1303,9 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
         if (k + 1 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u); /* unconditional prefetch, see below */
         next.load(xp, ch, c);
         uint32_t w[2] = {0, 0};
-        encode_chunk16<BITS, EMIT, PK>(L, x, lds, w, last_qd, sq);
+        int32_t yb[kChunk];
+        encode_chunk16<BITS, EMIT, PK, S, REC>(L, x, lds, w, last_qd, sq, yb);
+        if constexpr (REC) rec->chunk(first + kTaps + (uint64_t)k * kChunk, yb);
         next.touch();
         /* lane 0 keeps the first half of the pair's sixteen bytes (word 0 of both channels), lane 1 the second */
         const uint32_t send = c ? w[0] : w[1], keep = c ? w[1] : w[0];
@@ -1288,8 +1401,13 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
               xb[j] = (int32_t)(j < 6 ? cur.d[10 + j] : np.d[j - 6]);
             }
             uint32_t wa[2] = {0, 0}, wb[2] = {0, 0};
-            encode_chunk16<BITS, EMIT, true>(L, xa, lds, wa, last_qd, sq);
-            encode_chunk16<BITS, EMIT, true>(L, xb, lds, wb, last_qd, sq);
+            int32_t ya[kChunk], yb[kChunk];
+            encode_chunk16<BITS, EMIT, true, S, REC>(L, xa, lds, wa, last_qd, sq, ya);
+            encode_chunk16<BITS, EMIT, true, S, REC>(L, xb, lds, wb, last_qd, sq, yb);
+            if constexpr (REC) {
+              rec->chunk(first + kTaps + (uint64_t)k0 * kChunk, ya);
+              rec->chunk(first + kTaps + (uint64_t)(k0 + 1) * kChunk, yb);
+            }
             np.touch();
 #pragma unroll
             for (int j = 0; j < 16; j++) cur.d[j] = np.d[j];
@@ -1368,7 +1486,9 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
         if (k + 1 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
         next.load(xp, ch, c);
         uint32_t w[2] = {0, 0};
-        encode_chunk16<BITS, EMIT, PK>(L, x, lds, w, last_qd, sq);
+        int32_t yb[kChunk];
+        encode_chunk16<BITS, EMIT, PK, S, REC>(L, x, lds, w, last_qd, sq, yb);
+        if constexpr (REC) rec->chunk(first + kTaps + (uint64_t)k * kChunk, yb);
         next.touch();
         if constexpr (RING && BITS == 3) {
           /* the one chunk two-chunk appends leave over (the last of its block): six bytes per lane, byte by byte */
@@ -1427,7 +1547,9 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
       EncodeCarry C;
       encode_prime_quad<BITS>(L, C, xt[0], lds);
       uint32_t w[2] = {0, 0};
-      encode_chunk16_quad<BITS, PASS, kWide, NoFill, N>(L, C, xt, 0, lds, w, last_qd, sq);
+      int32_t yq[4];
+      encode_chunk16_quad<BITS, PASS, kWide, NoFill, N, REC>(L, C, xt, 0, lds, w, last_qd, sq, NoFill(), yq);
+      if constexpr (REC) rec->template quad<N / 4>(first + kTaps + done, yq);
       if (writer) {
         uint8_t *up = body + (uint64_t)(done / US) * unit_stride + (uint64_t)c * UB;
         static_for<0, N / US>([&](auto uc) {
@@ -1472,6 +1594,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
       for (int k = 0; k < US; k++) {
         const int32_t x = i + k < coded ? src.at(first + kTaps + i + k) : 0;
         acc = (acc << BITS) | encode_step<BITS>(L, x, lds, last_qd);
+        if constexpr (REC) rec->one(first + kTaps + i + k, newest_sample(L), i + k < coded);
       }
       tail |= (uint64_t)(acc & 0xFFu) << (8 * units);
     }
@@ -1512,6 +1635,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
       for (int k = 0; k < US; k++) {
         const int32_t x = i + k < coded ? src.at(first + kTaps + i + k) : 0;
         acc = (acc << BITS) | encode_step<BITS>(L, x, lds, last_qd);
+        if constexpr (REC) rec->one(first + kTaps + i + k, newest_sample(L), i + k < coded);
       }
       if (writer) {
 #pragma unroll
@@ -1792,9 +1916,16 @@ __device__ __forceinline__ void encode_block_dual(Lane &F, int32_t &last_qd, con
  * IN (PcmLayout): interleaved int16 frames, or planar int16 / float32 rows (AADHip_PlanarEncodePlanRun; arguments
  * PlanarEncodeArgs, instantiated in aad_encode_planar.hip).  Only the reads of PCM differ; see "Input layouts" above.
  */
-template <int BITS, int CHF, bool MS, bool QUAD, bool TRIALS, bool DUAL = false, bool RING = false, bool SEG = false, int IN = kInInterleaved>
-__global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgsFor<IN> a)
+/*
+ * REC (RecOutput; arguments RecEncodeArgs, instantiated in aad_encode_reconstruct.hip): the encode pass also writes the decoded rows
+ * (RecRow) - the header samples of every kept block here, the coded samples in run_block.  Never with the dual trial search (its
+ * candidates are encoded into slots) or the byte ring: the launch policy plans neither for these kernels.
+ */
+template <int BITS, int CHF, bool MS, bool QUAD, bool TRIALS, bool DUAL = false, bool RING = false, bool SEG = false, int IN = kInInterleaved,
+          int REC = kRecNone>
+__global__ void __launch_bounds__(256) encode_streams_kernel(KernelArgsFor<IN, REC> a)
 {
+  static_assert(REC == kRecNone || (!DUAL && !RING), "the decoded rows: single-layout trial search, plain stores");
   static_assert(!QUAD || CHF != 0, "the quad mapping exists for the mono / stereo fast paths");
   static_assert(!DUAL || (QUAD && TRIALS), "the dual mapping is the trial search on the quad mapping");
   static_assert(!RING || kRingable<BITS, CHF, QUAD>, "the byte ring: dense mono / stereo encoders");
@@ -1846,6 +1977,13 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgsFor<IN> a
   const SampleSource<MS, IN> src = {x0, ch, c, sd.num_samples};
   uint8_t *out = a.data + sd.data_offset;
   const uint32_t total = sd.num_samples, spb = a.samples_per_block;
+  using Rec = std::conditional_t<REC == kRecNone, NoRec, RecRow<REC, MS, QUAD>>;
+  [[maybe_unused]] Rec rec;
+  if constexpr (REC != kRecNone) {
+    rec.row = reinterpret_cast<typename Rec::T *>(a.out) + a.out_base[s] + (uint64_t)c * a.out_channel_stride;
+    rec.c = c;
+    rec.tap = tap;
+  }
 
   /* F: the complete per-channel state, the form block headers and the state records need;
    * between block boundaries the quad mapping spreads it over four lanes (S) */
@@ -1923,6 +2061,7 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgsFor<IN> a
       if constexpr (QUAD) F = from_quad<kEncTM>(L); else F = L;
     }
     seed_history(F, src, first, n);
+    if constexpr (REC != kRecNone) rec.header(first, n, F);
     uint8_t *body = out + block_off + (uint64_t)kBlockHeaderBytesPerCh * ch;
     /* dense stereo 4-bit: code bytes 3 bytes into a 64-byte granule - the channel-1 lane holds the
      * header's last three bytes back for the first burst of code bytes (run_block) */
@@ -1944,7 +2083,8 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(EncodeArgsFor<IN> a
     const uint32_t deferred = write_block_header(F, out + block_off + (uint64_t)c * kBlockHeaderBytesPerCh, writer, defer3);
     if constexpr (QUAD) L = to_quad(F, tap); else L = F;
     AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
-    (void)run_block<BITS, CHF, MS, QUAD, true>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred);
+    if constexpr (REC == kRecNone) (void)run_block<BITS, CHF, MS, QUAD, true>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred);
+    else (void)run_block<BITS, CHF, MS, QUAD, true>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred, true, nullptr, &rec);
     if constexpr (QUAD) F = from_quad<kEncTM>(L); else F = L;
     }
     }

@@ -112,6 +112,10 @@ struct AADHipEncodePlan {
   bool planar;             /* AADHip_PlanarEncodePlanCreate: runs through AADHip_PlanarEncodePlanRun only */
   int32_t sample_type;     /* planar: enum AADHipSampleType */
   uint64_t channel_stride; /* planar: elements from one channel's row to the next */
+  bool reconstruct;            /* AADHip_PlanarReconstructPlanCreate: runs through AADHip_PlanarReconstructPlanRun only */
+  int32_t out_type;            /* reconstruct: enum AADHipSampleType of the output rows */
+  uint64_t out_channel_stride; /* reconstruct: elements from one channel's output row to the next */
+  uint64_t *d_out_base;        /* reconstruct: per stream (segmented: per chain) the output element of channel 0 at its first frame */
 };
 
 struct AADHipDecodePlan {
@@ -415,22 +419,30 @@ bool scratch_reserve(AADHipContext *ctx, T **buf, uint64_t *capacity, uint64_t b
 
 /* segmented: args.chains holds a chain table and num_streams counts chains (AADHip_SegmentedEncodePlanCreate); planar: the input is
  * rows of that sample type (enum AADHipSampleType, AADHip_PlanarEncodePlanCreate), -1 the interleaved int16 frames */
+/* rec: the decoded rows of a planar reconstruct plan (out_type: their enum AADHipSampleType), null for an encode */
 AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args, bool segmented = false, int32_t planar = -1,
-                        uint64_t channel_stride = 0)
+                        uint64_t channel_stride = 0, const aad::RecRows *rec = nullptr, int32_t out_type = 0)
 {
   if (args.num_streams == 0) return AAD_APIRESULT_OK;
   if (args.bits < 2 || args.bits > 4) return AAD_APIRESULT_INVALID_FORMAT;
   aad::EncodeArgs a = args;
   if ((reinterpret_cast<uintptr_t>(a.data) & 63u) != 0) a.ring_ok = 0;
-  const aad::EncodeLaunch p =
-      aad::plan_encode(ctx->device_info, ctx->knobs, aad::EncodeBatch{a.bits, a.channels, a.num_streams, a.trials, a.block_size, a.ring_ok != 0});
+  const aad::EncodeBatch batch{a.bits, a.channels, a.num_streams, a.trials, a.block_size, a.ring_ok != 0};
+  const aad::EncodeLaunch p = rec != nullptr ? aad::plan_reconstruct_encode(ctx->device_info, ctx->knobs, batch)
+                                             : aad::plan_encode(ctx->device_info, ctx->knobs, batch);
   a.trial_scratch = nullptr;
   a.trial_slot_bytes = p.trial_slot_bytes;
   if (p.trial_scratch_bytes != 0) {
     if (!scratch_reserve(ctx, &ctx->d_trial, &ctx->trial_capacity, p.trial_scratch_bytes, "hipMalloc trial scratch")) return AAD_APIRESULT_NG;
     a.trial_scratch = ctx->d_trial;
   }
-  if (planar == AAD_HIP_SAMPLE_FLOAT32) {
+  if (rec != nullptr) {
+    const bool in_f32 = planar == AAD_HIP_SAMPLE_FLOAT32, out_f32 = out_type == AAD_HIP_SAMPLE_FLOAT32;
+    if (in_f32 && out_f32) aad::launch_reconstruct_f32_f32(a, channel_stride, *rec, p, segmented, ctx->stream);
+    else if (in_f32) aad::launch_reconstruct_f32_i16(a, channel_stride, *rec, p, segmented, ctx->stream);
+    else if (out_f32) aad::launch_reconstruct_i16_f32(a, channel_stride, *rec, p, segmented, ctx->stream);
+    else aad::launch_reconstruct_i16_i16(a, channel_stride, *rec, p, segmented, ctx->stream);
+  } else if (planar == AAD_HIP_SAMPLE_FLOAT32) {
     aad::launch_encode_planar_f32(a, channel_stride, p, segmented, ctx->stream);
   } else if (planar == AAD_HIP_SAMPLE_INT16 && a.channels != 1) { /* mono int16 rows ARE interleaved frames: the kernels below */
     aad::launch_encode_planar_i16(a, channel_stride, p, segmented, ctx->stream);
@@ -731,6 +743,7 @@ void AADHip_EncodePlanDestroy(struct AADHipEncodePlan *plan)
     (void)hipStreamSynchronize(plan->ctx->stream);
     (void)hipFree(plan->d_streams);
     (void)hipFree(plan->d_chains);
+    (void)hipFree(plan->d_out_base);
   }
   delete plan;
 }
@@ -874,6 +887,7 @@ AADApiResult AADHip_PlanarEncodePlanRun(struct AADHipEncodePlan *plan, const voi
   DeviceGuard guard(ctx);
   if (!guard.ok) return AAD_APIRESULT_NG;
   if (!plan->planar) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* frames, not rows: AADHip_EncodePlanRun */
+  if (plan->reconstruct) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* AADHip_PlanarReconstructPlanRun */
   if (plan->segmented && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
   if (plan->args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
   aad::EncodeArgs a = plan->args;
@@ -883,6 +897,75 @@ AADApiResult AADHip_PlanarEncodePlanRun(struct AADHipEncodePlan *plan, const voi
   a.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
   aad::tl_launch_signal = signal;
   return finish_signal(ctx, signal, run_encode(ctx, a, plan->segmented, plan->sample_type, plan->channel_stride));
+}
+
+/* ------------------------------------------------------------------ planar reconstruct -- */
+
+AADApiResult AADHip_PlanarReconstructPlanCreate(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                                const struct AADHipPlanarLayout *input, const struct AADHipPlanarOutput *output,
+                                                const struct AADHipSegmentation *segmentation, uint32_t num_streams,
+                                                const struct AADHipStreamDesc *streams, struct AADHipEncodePlan **plan)
+{
+  if (ctx == nullptr || output == nullptr || plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  *plan = nullptr;
+  AADHipEncodePlan *p = nullptr;
+  const AADApiResult rc = AADHip_PlanarEncodePlanCreate(ctx, parameter, input, segmentation, num_streams, streams, &p);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  if (!aad::planar_output_ok(p->args.channels, num_streams, streams, output)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "planar reconstruct plan: output rows refused (sample type, reserved, a stride below the rows, or past 64-bit offsets)");
+    AADHip_EncodePlanDestroy(p);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  /* where each lane's frame 0 lands in `out`: stream i's row, plus a chain's first frame (the chain table's order, aad_segments.h) */
+  std::vector<uint64_t> base;
+  const uint64_t spb = p->args.samples_per_block;
+  for (uint32_t i = 0; i < num_streams; i++) {
+    const uint64_t row = (uint64_t)i * output->stream_stride;
+    if (segmentation == nullptr) {
+      base.push_back(row);
+      continue;
+    }
+    const uint64_t L = segmentation->segment_blocks, b = aad::stream_blocks(streams[i].num_samples, (uint32_t)spb);
+    const uint64_t segments = b == 0 ? 1u : (b + L - 1) / L;
+    for (uint64_t s = 0; s < segments; s++) {
+      const uint64_t kept = s * L, w = segmentation->warmup_blocks < kept ? segmentation->warmup_blocks : kept;
+      base.push_back(row + (kept - w) * spb);
+    }
+  }
+  DeviceGuard guard(ctx);
+  if (base.size() != (size_t)p->args.num_streams || !guard.ok || !upload(ctx, &p->d_out_base, base.data(), base.size())) {
+    AADHip_EncodePlanDestroy(p);
+    return AAD_APIRESULT_NG;
+  }
+  p->reconstruct = true;
+  p->out_type = output->sample_type;
+  p->out_channel_stride = output->channel_stride;
+  *plan = p;
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_PlanarReconstructPlanRun(struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data,
+                                             void *device_out, struct AADHipLaneState *device_state)
+{
+  if (plan == nullptr || device_samples == nullptr || device_data == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = plan->ctx;
+  const aad::LaunchSignal signal = take_signal(ctx);
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (!plan->reconstruct) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* AADHip_(Planar)EncodePlanRun */
+  if (plan->segmented && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  if (device_out == device_samples) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  if (plan->args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
+  if (device_out == nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  aad::EncodeArgs a = plan->args;
+  a.pcm = static_cast<const int16_t *>(device_samples); /* the kernels read it as the plan's sample type */
+  a.data = device_data;
+  a.state = reinterpret_cast<const aad::LaneStateRecord *>(device_state);
+  a.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
+  const aad::RecRows rows = {device_out, plan->d_out_base, plan->out_channel_stride};
+  aad::tl_launch_signal = signal;
+  return finish_signal(ctx, signal, run_encode(ctx, a, plan->segmented, plan->sample_type, plan->channel_stride, &rows, plan->out_type));
 }
 
 /* ------------------------------------------------------------------------------- decode -- */

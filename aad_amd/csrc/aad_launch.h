@@ -36,6 +36,18 @@ void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, bool fl
 struct EncodeArgs;
 void launch_encode_planar_i16(const EncodeArgs &args, uint64_t channel_stride, const EncodeLaunch &p, bool segmented, hipStream_t stream);
 void launch_encode_planar_f32(const EncodeArgs &args, uint64_t channel_stride, const EncodeLaunch &p, bool segmented, hipStream_t stream);
+/* aad_encode_reconstruct.hip (compiled once per input x output sample type): the planar reconstruct encoders
+ * (AADHip_PlanarReconstructPlanRun) - the planar encoders that also write the decoded rows.  base: per stream (segmented: per chain)
+ * the element of `out` that holds channel 0's sample of the lane's first frame, device memory */
+struct RecRows {
+  void *out;
+  const uint64_t *base;
+  uint64_t channel_stride;
+};
+void launch_reconstruct_i16_i16(const EncodeArgs &args, uint64_t channel_stride, const RecRows &out, const EncodeLaunch &p, bool segmented, hipStream_t stream);
+void launch_reconstruct_i16_f32(const EncodeArgs &args, uint64_t channel_stride, const RecRows &out, const EncodeLaunch &p, bool segmented, hipStream_t stream);
+void launch_reconstruct_f32_i16(const EncodeArgs &args, uint64_t channel_stride, const RecRows &out, const EncodeLaunch &p, bool segmented, hipStream_t stream);
+void launch_reconstruct_f32_f32(const EncodeArgs &args, uint64_t channel_stride, const RecRows &out, const EncodeLaunch &p, bool segmented, hipStream_t stream);
 }
 
 #define AAD_LAUNCH(kernel, grid, block, lds, stream, ...)                                                           \

@@ -180,6 +180,39 @@ inline EncodeLaunch plan_encode(const Device &d, const Knobs &k, const EncodeBat
   return p;
 }
 
+/* Planar reconstruct plans (AADHip_PlanarReconstructPlanRun): the encoders whose encode pass also writes the decoded rows.  The
+ * trial search always takes the single layout - the dual one encodes every candidate into a slot and moves the winner, so no pass
+ * knows its samples are the ones that stay - and no byte ring: the row stores ride the plain chunk loops (aad_encode.hip.h RecRow). */
+inline EncodeLaunch plan_reconstruct_encode(const Device &d, const Knobs &k, const EncodeBatch &b)
+{
+  Knobs r = k;
+  r.trial_lanes = AAD_HIP_TRIAL_LANES_SINGLE;
+  r.encode_ring = 0;
+  return plan_encode(d, r, b);
+}
+
+/* The output rows of a planar reconstruct plan (struct AADHipPlanarOutput) for a batch of `channels`-channel streams: false for an
+ * unknown sample type, a non-zero reserved, C > 1 with channel_stride below the longest stream, more than one stream with
+ * stream_stride below (C - 1) channel_stride + the longest stream (rows of different streams would overlap), or an end of the rows
+ * ((N - 1) stream_stride + (C - 1) channel_stride + the longest stream, in elements or in bytes) past 2^64. */
+inline bool planar_output_ok(uint32_t channels, uint32_t num_streams, const AADHipStreamDesc *streams, const AADHipPlanarOutput *o)
+{
+  if (o == nullptr || channels == 0) return false;
+  if ((o->sample_type != AAD_HIP_SAMPLE_INT16 && o->sample_type != AAD_HIP_SAMPLE_FLOAT32) || o->reserved != 0) return false;
+  uint64_t longest = 0;
+  for (uint32_t i = 0; i < num_streams; i++) longest = streams[i].num_samples > longest ? streams[i].num_samples : longest;
+  if (channels > 1 && o->channel_stride < longest) return false;
+  uint64_t span = 0; /* elements from a stream's first to past its last */
+  if (__builtin_mul_overflow((uint64_t)(channels - 1), o->channel_stride, &span) || __builtin_add_overflow(span, longest, &span)) return false;
+  if (num_streams > 1 && o->stream_stride < span) return false;
+  const uint64_t elem = o->sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4u : 2u;
+  uint64_t end = 0, bytes = 0;
+  if (num_streams != 0 && (__builtin_mul_overflow((uint64_t)(num_streams - 1), o->stream_stride, &end) ||
+                           __builtin_add_overflow(end, span, &end) || __builtin_mul_overflow(end, elem, &bytes)))
+    return false;
+  return true;
+}
+
 /* Round 4 (tools/size_sweep.py --mapping quad | dense, profiles/r04_decode_split_crossover.txt): the split decoder runs
  * 1024-thread workgroups of 16 recurrences, ONE to a CU (84-94 VGPRs x 16 waves), i.e. rounds of 4096 recurrences: its time is
  * about 0.025 + 0.015 ms x rounds on stereo 4-bit.  Up to two rounds (8192 recurrences) it beats the dense kernel in every

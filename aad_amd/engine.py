@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import (AADApiResult, AADHeaderInfo, AADHipPlanarLayout, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
+from .capi import (AADApiResult, AADHeaderInfo, AADHipPlanarLayout, AADHipPlanarOutput, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
                    OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
                    SAMPLE_FLOAT32, SAMPLE_INT16, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, load_library, make_parameter)
 
@@ -152,6 +152,28 @@ class Engine:
         p.segmented = segment_blocks is not None
         return p
 
+    def planar_reconstruct_plan(self, param, descs, channel_stride, dtype, out_dtype, out_stream_stride, out_channel_stride,
+                                segment_blocks=None, warmup_blocks=0):
+        """A planar encode plan that also writes the decoded rows (AADHip_PlanarReconstructPlanCreate): input as planar_encode_plan,
+        output stream i's channel c at i * out_stream_stride + c * out_channel_stride elements of a torch.int16 or torch.float32
+        tensor (float32: decoded sample / 32768).  PlanarReconstructPlan.run encodes and reconstructs in one kernel."""
+        torch = self.torch
+        if dtype not in (torch.int16, torch.float32) or out_dtype not in (torch.int16, torch.float32):
+            raise ValueError("planar reconstruct reads and writes torch.int16 or torch.float32 rows, not %s -> %s" % (dtype, out_dtype))
+        descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
+        layout = AADHipPlanarLayout(SAMPLE_FLOAT32 if dtype == torch.float32 else SAMPLE_INT16, 0, int(channel_stride))
+        output = AADHipPlanarOutput(SAMPLE_FLOAT32 if out_dtype == torch.float32 else SAMPLE_INT16, 0, int(out_stream_stride),
+                                    int(out_channel_stride))
+        seg = AADHipSegmentation(int(segment_blocks), int(warmup_blocks)) if segment_blocks is not None else None
+        plan = C.c_void_p()
+        _check("AADHip_PlanarReconstructPlanCreate",
+               self.lib.AADHip_PlanarReconstructPlanCreate(self._ctx, C.byref(param), C.byref(layout), C.byref(output),
+                                                           C.byref(seg) if seg is not None else None, len(descs), descs.ctypes.data,
+                                                           C.byref(plan)))
+        p = PlanarReconstructPlan(self, plan, param, descs, dtype, out_dtype)
+        p.segmented = segment_blocks is not None
+        return p
+
     def decode_plan(self, header, descs, has_file_header=True):
         descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
         plan = C.c_void_p()
@@ -247,6 +269,47 @@ class Engine:
         finally:
             plan.close()  # synchronises the context's stream first
         return out, [int(v) for v in sizes]
+
+    def reconstruct_planar(self, x, param, num_samples=None, dtype=None, state=None, segment_blocks=None, warmup_blocks=0,
+                           return_images=False):
+        """x: int16 or float32 cuda tensor [N, C, T] (a view with x.stride(-1) == 1 is fine) -> a new contiguous [N, C, T] tensor of
+        `dtype` (default x.dtype): x after the codec - row i is the decode of encode_planar's image of x[i, :, :num_samples[i]]
+        (float32 output: decoded sample / 32768), zero past num_samples[i].  One kernel: the encoder writes the decoded rows as it
+        encodes.  return_images=True: (y, images, image_sizes) with images and sizes in encode_planar's layout."""
+        torch = self.torch
+        if state is not None and segment_blocks is not None:
+            raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
+        if x.dim() != 3 or not x.is_cuda or x.dtype not in (torch.int16, torch.float32):
+            raise ValueError("reconstruct_planar takes an int16 or float32 cuda tensor [N, C, T]")
+        dtype = x.dtype if dtype is None else dtype
+        n, ch, t = (int(v) for v in x.shape)
+        if ch != param.num_channels:
+            raise ValueError("x has %d channels, the parameter %d" % (ch, param.num_channels))
+        if x.stride(-1) != 1:
+            raise ValueError("reconstruct_planar needs x.stride(-1) == 1 (each channel's samples contiguous); got strides %s - pass "
+                             "x.contiguous() if a copy is intended" % (tuple(x.stride()),))
+        lengths = np.full(n, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
+        if len(lengths) != n or (n and (lengths.min() < 1 or lengths.max() > t)):
+            raise ValueError("num_samples: %d lengths in [1, %d]" % (n, t))
+        sizes = np.array([self.encoded_size(param, int(v)) for v in lengths], dtype=np.uint64)
+        if n and sizes.min() == 0:
+            raise ApiError("AADHip_CalculateEncodedSize", AADApiResult.INVALID_FORMAT)
+        stride = _round_up(int(sizes.max()), 64) if n else 64
+        d = np.zeros(n, dtype=STREAM_DESC_DTYPE)
+        d["pcm_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(x.stride(0))
+        d["data_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(stride)
+        d["data_size"] = stride
+        d["num_samples"] = lengths
+        images = torch.zeros((n, stride), dtype=torch.uint8, device=x.device)
+        y = torch.zeros((n, ch, t), dtype=dtype, device=x.device)
+        plan = self.planar_reconstruct_plan(param, d, x.stride(1), x.dtype, dtype, ch * t, t, segment_blocks, warmup_blocks)
+        try:
+            plan.run(x, images, y, state)
+        finally:
+            plan.close()  # synchronises the context's stream first
+        if return_images:
+            return y, images, [int(v) for v in sizes]
+        return y
 
     def decode_uniform(self, data, image_size):
         """data: uint8 cuda tensor [streams, stride] of same-format images -> int16 [streams, samples, channels]"""
@@ -432,6 +495,28 @@ class PlanarEncodePlan(EncodePlan):
         cur = self.engine._enter() if ordered else None
         _check("AADHip_PlanarEncodePlanRun",
                self.engine.lib.AADHip_PlanarEncodePlanRun(self.handle, x.data_ptr(), data.data_ptr(), sp))
+        if ordered:
+            self.engine._exit(cur)
+
+
+class PlanarReconstructPlan(EncodePlan):
+    def __init__(self, engine, handle, param, descs, dtype, out_dtype):
+        super().__init__(engine, handle, param, descs)
+        self.dtype, self.out_dtype = dtype, out_dtype
+
+    def run(self, x, data, out, state=None, ordered=True):
+        """x: cuda rows of the plan's dtype (the table's pcm_offsets count from x.data_ptr()), data: uint8 cuda tensor for the images,
+        out: cuda tensor of the plan's out_dtype (the output strides count from out.data_ptr()), state as EncodePlan.run"""
+        if x.dtype != self.dtype or not x.is_cuda:
+            raise ValueError("this plan reads %s cuda rows, not %s" % (self.dtype, x.dtype))
+        if out.dtype != self.out_dtype or not out.is_cuda:
+            raise ValueError("this plan writes %s cuda rows, not %s" % (self.out_dtype, out.dtype))
+        if state is not None and self.segmented:
+            raise ValueError("a segmented encode plan takes no state")
+        sp = state.data_ptr() if state is not None else None
+        cur = self.engine._enter() if ordered else None
+        _check("AADHip_PlanarReconstructPlanRun",
+               self.engine.lib.AADHip_PlanarReconstructPlanRun(self.handle, x.data_ptr(), data.data_ptr(), out.data_ptr(), sp))
         if ordered:
             self.engine._exit(cur)
 
@@ -632,4 +717,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE"]

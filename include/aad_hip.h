@@ -71,7 +71,7 @@ const char *AADHip_ContextLastError(const struct AADHipContext *context);
 
 /* Cross-stream ordering and kernel timing without packets of their own.  `hip_start_event` / `hip_stop_event` (hipEvent_t the
  * caller owns; either may be NULL, both NULL withdraws) are recorded when the work of the NEXT AADHip_EncodePlanRun /
- * AADHip_PlanarEncodePlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
+ * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
  * the run takes them.  An encode, decode or window decode plan run is one kernel, and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
  * stop events) instead of on barrier packets around it: a hipEventRecord behind every launch of a back-to-back sequence costs
  * the queue 2.9 us per launch on MI355X, the attached event nothing (profiles/r03_microbench_event_gap.txt), and
@@ -273,6 +273,47 @@ AADApiResult AADHip_PlanarEncodePlanCreate(
     struct AADHipEncodePlan **plan);
 AADApiResult AADHip_PlanarEncodePlanRun(
     struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data,
+    struct AADHipLaneState *device_state);
+
+/* ---- planar reconstruct: [N, C, T] rows through the codec in one kernel ---------------------------------------------------- */
+
+/* A planar reconstruct plan is a planar encode plan with an output: "what do these rows sound like after the codec", with no
+ * second recurrence - the decoder's output of an image is the encoder's own reconstruction, so the encoder kernels write it as
+ * they encode.
+ *
+ * Definition.  Parameter, descriptor table, input layout (struct AADHipPlanarLayout), segmentation and state follow
+ * AADHip_PlanarEncodePlanCreate / AADHip_PlanarEncodePlanRun.  A run
+ *   1. writes into device_data exactly the bytes AADHip_PlanarEncodePlanRun writes for the same plan inputs, and
+ *   2. for stream i, channel c < C and frame t < num_samples_i writes
+ *        out[i * stream_stride + c * channel_stride + t] = D_i[t][c]   converted to the output sample type,
+ *      D_i being what AADHip_DecodePlanRun writes for that image: int16 output is D_i[t][c], float32 output D_i[t][c] / 32768
+ *      (exact, as window decode).
+ * No other element of `out` is touched.  Input and output sample types are independent (int16 or float32 each).  Overlap of `out`
+ * with the input or the images is undefined (device_out == device_samples is refused).
+ *
+ * The plan is an ordinary AADHipEncodePlan: AADHip_EncodePlanDestroy destroys it, and AADHip_ContextSignalNextRun's events ride on
+ * AADHip_PlanarReconstructPlanRun's one kernel.  AADHip_EncodePlanRun and AADHip_PlanarEncodePlanRun refuse it and
+ * AADHip_PlanarReconstructPlanRun refuses every other plan (AAD_APIRESULT_INVALID_ARGUMENT).  The trial search always runs on the
+ * single lane layout (AAD_HIP_OPTION_TRIAL_LANES does not apply); the bytes are the same either way.
+ * Errors are those of AADHip_PlanarEncodePlanCreate / AADHip_PlanarEncodePlanRun, plus AAD_APIRESULT_INVALID_ARGUMENT for a null
+ * `output`, an unknown output sample_type or a non-zero reserved, C > 1 with output channel_stride below the longest num_samples,
+ * more than one stream with stream_stride < (C - 1) channel_stride + the longest num_samples (rows must not overlap), an end of the
+ * rows ((N - 1) stream_stride + (C - 1) channel_stride + the longest num_samples) that overflows 64 bits in elements or bytes, and
+ * from the run device_out == device_samples or a null device_out while the plan has streams. */
+struct AADHipPlanarOutput {
+  int32_t sample_type;     /* enum AADHipSampleType: AAD_HIP_SAMPLE_INT16 or AAD_HIP_SAMPLE_FLOAT32 */
+  uint32_t reserved;       /* 0 */
+  uint64_t stream_stride;  /* elements from stream i's channel-0 row to stream i + 1's */
+  uint64_t channel_stride; /* elements from channel c's row to channel c + 1's (ignored for mono) */
+};
+AADApiResult AADHip_PlanarReconstructPlanCreate(
+    struct AADHipContext *context, const struct AADEncodeParameter *parameter,
+    const struct AADHipPlanarLayout *input, const struct AADHipPlanarOutput *output,
+    const struct AADHipSegmentation *segmentation, /* NULL: the serial (reference-exact) encode */
+    uint32_t num_streams, const struct AADHipStreamDesc *streams,
+    struct AADHipEncodePlan **plan);
+AADApiResult AADHip_PlanarReconstructPlanRun(
+    struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data, void *device_out,
     struct AADHipLaneState *device_state);
 
 /* ---- host-memory convenience (stage -> run -> copy back, synchronous) ---------------------- */
