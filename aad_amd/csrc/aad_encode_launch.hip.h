@@ -1,5 +1,6 @@
-/* aad_encode_launch.hip.h - from an encode plan (aad_launch_policy.h) to an instantiation of encode_streams_kernel, for one input
- * layout IN (aad_encode.hip.h).  aad_hip_engine.hip instantiates the interleaved kernels, aad_encode_planar.hip the planar ones,
+/* aad_encode_launch.hip.h - what one encode run is (EncodeRun) and the way from it and its launch plan (aad_launch_policy.h) to
+ * an instantiation of encode_streams_kernel: launch_encode_run<IN, REC>, one instantiation per input layout IN and output REC
+ * (aad_encode.hip.h).  aad_hip_engine.hip instantiates the interleaved kernels, aad_encode_planar.hip the planar ones,
  * aad_encode_reconstruct.hip the planar reconstruct ones (REC). */
 #ifndef AAD_ENCODE_LAUNCH_HIP_H
 #define AAD_ENCODE_LAUNCH_HIP_H
@@ -48,6 +49,59 @@ void launch_encode(const KernelArgsFor<IN, REC> &a, const EncodeLaunch &p, hipSt
     launch_encode_mapped<BITS, false, false, false, false, SEG, IN, REC>(a, p, stream);
   }
 }
+
+/* One encode run: the kernel arguments, what their table is, where the samples lie and what is written besides the images. */
+struct EncodeRun {
+  EncodeArgs args;
+  bool chain_table = false;      /* args.chains holds a chain table and args.num_streams counts chains (aad_segments.h) */
+  PcmLayout in = kInInterleaved; /* interleaved int16 frames, or one row per channel of int16 / float32 samples ... */
+  uint64_t channel_stride = 0;   /* ... channel_stride elements apart */
+  RecOutput rec = kRecNone;      /* the decoded rows of a planar reconstruct run: none, int16 or float32 ... */
+  RecRows rows = {nullptr, nullptr, 0}; /* ... and where they go */
+};
+
+/* the layout that reads rows of a sample type (enum AADHipSampleType): mono int16 rows ARE interleaved frames, see above */
+inline PcmLayout planar_layout(int32_t sample_type, uint32_t channels)
+{
+  if (sample_type == AAD_HIP_SAMPLE_FLOAT32) return kInPlanarF32;
+  return channels == 1 ? kInInterleaved : kInPlanarI16;
+}
+inline RecOutput rec_output(int32_t sample_type) { return sample_type == AAD_HIP_SAMPLE_FLOAT32 ? kRecF32 : kRecI16; }
+
+/* The kernels of one (IN, REC) by sample width and table kind.  r.in == IN and r.rec == REC: the caller has dispatched on them. */
+template <int IN, int REC>
+void launch_encode_run(const EncodeRun &r, const EncodeLaunch &p, hipStream_t stream)
+{
+  KernelArgsFor<IN, REC> a;
+  static_cast<EncodeArgs &>(a) = r.args;
+  if constexpr (IN != kInInterleaved || REC != kRecNone) a.channel_stride = r.channel_stride;
+  if constexpr (REC != kRecNone) {
+    a.out = r.rows.out;
+    a.out_base = r.rows.base;
+    a.out_channel_stride = r.rows.channel_stride;
+  }
+  auto by_bits = [&](auto seg) {
+    constexpr bool SEG = decltype(seg)::value;
+    switch (a.bits) {
+      case 4: launch_encode<4, SEG, IN, REC>(a, p, stream); break;
+      case 3: launch_encode<3, SEG, IN, REC>(a, p, stream); break;
+      default: launch_encode<2, SEG, IN, REC>(a, p, stream); break;
+    }
+  };
+  if (r.chain_table) by_bits(std::true_type{});
+  else by_bits(std::false_type{});
+}
+
+/* Every pair but the interleaved encoders is instantiated by a unit of its own (aad_encode_planar.hip,
+ * aad_encode_reconstruct.hip: one object per sample type, see the Makefile), so that the kernels build side by side. */
+extern template void launch_encode_run<kInPlanarI16, kRecNone>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+extern template void launch_encode_run<kInPlanarF32, kRecNone>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+extern template void launch_encode_run<kInInterleaved, kRecI16>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+extern template void launch_encode_run<kInInterleaved, kRecF32>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+extern template void launch_encode_run<kInPlanarI16, kRecI16>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+extern template void launch_encode_run<kInPlanarI16, kRecF32>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+extern template void launch_encode_run<kInPlanarF32, kRecI16>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+extern template void launch_encode_run<kInPlanarF32, kRecF32>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
 
 } /* namespace aad */
 

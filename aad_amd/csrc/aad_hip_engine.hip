@@ -2,9 +2,11 @@
  * aad_hip_engine.hip - host side of the batched C-ABI declared in include/aad_hip.h:
  * contexts, plans (uploaded stream tables), kernel launches and the host-memory convenience
  * calls.  Device code lives in aad_encode.hip.h / aad_decode.hip.h (shared parts: aad_device.hip.h)
- * and, for the split, sector-tiled and window decoders and the planar-input encoders, in units of their own
- * (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_planar.hip).  gfx950 only; no CPU code path -
- * every entry point that needs the GPU fails with AAD_APIRESULT_NG when HIP does.
+ * and, for the split, sector-tiled and window decoders and the planar-input and planar reconstruct encoders, in units of their own
+ * (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_planar.hip, aad_encode_reconstruct.hip).  Every
+ * kind of encode plan is made by encode_plan_create and run by encode_plan_run over one description of a run (aad::EncodeRun,
+ * aad_encode_launch.hip.h), which the host-memory paths build directly.  gfx950 only; no CPU code path - every entry point that
+ * needs the GPU fails with AAD_APIRESULT_NG when HIP does.
  */
 #include <hip/hip_runtime.h>
 
@@ -103,19 +105,19 @@ struct AADHipContext {
   StagingPool *pool;    /* staging helper threads, created on demand */
 };
 
-struct AADHipEncodePlan {
+/* which of the three ...PlanRun entry points runs a plan: they take different pointers */
+enum class EncodePlanKind {
+  Frames,     /* AADHip_EncodePlanCreate, AADHip_SegmentedEncodePlanCreate -> AADHip_EncodePlanRun */
+  Rows,       /* AADHip_PlanarEncodePlanCreate -> AADHip_PlanarEncodePlanRun */
+  Reconstruct /* AADHip_PlanarReconstructPlanCreate -> AADHip_PlanarReconstructPlanRun */
+};
+
+struct AADHipEncodePlan { /* every field is set by encode_plan_create */
   AADHipContext *ctx;
-  aad::EncodeArgs args;
-  aad::StreamDesc *d_streams;
-  aad::ChainDesc *d_chains; /* segmented plans: the chain table (args.chains), d_streams stays null */
-  bool segmented;
-  bool planar;             /* AADHip_PlanarEncodePlanCreate: runs through AADHip_PlanarEncodePlanRun only */
-  int32_t sample_type;     /* planar: enum AADHipSampleType */
-  uint64_t channel_stride; /* planar: elements from one channel's row to the next */
-  bool reconstruct;            /* AADHip_PlanarReconstructPlanCreate: runs through AADHip_PlanarReconstructPlanRun only */
-  int32_t out_type;            /* reconstruct: enum AADHipSampleType of the output rows */
-  uint64_t out_channel_stride; /* reconstruct: elements from one channel's output row to the next */
-  uint64_t *d_out_base;        /* reconstruct: per stream (segmented: per chain) the output element of channel 0 at its first frame */
+  EncodePlanKind kind;
+  aad::EncodeRun run;   /* all of a run but the caller's pointers (args.pcm / data / state / state_out, rows.out) */
+  void *d_table;        /* run.args.streams, or run.args.chains of a segmented plan */
+  uint64_t *d_out_base; /* Reconstruct: run.rows.base, else null */
 };
 
 struct AADHipDecodePlan {
@@ -417,49 +419,162 @@ bool scratch_reserve(AADHipContext *ctx, T **buf, uint64_t *capacity, uint64_t b
   return true;
 }
 
-/* segmented: args.chains holds a chain table and num_streams counts chains (AADHip_SegmentedEncodePlanCreate); planar: the input is
- * rows of that sample type (enum AADHipSampleType, AADHip_PlanarEncodePlanCreate), -1 the interleaved int16 frames */
-/* rec: the decoded rows of a planar reconstruct plan (out_type: their enum AADHipSampleType), null for an encode */
-AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeArgs &args, bool segmented = false, int32_t planar = -1,
-                        uint64_t channel_stride = 0, const aad::RecRows *rec = nullptr, int32_t out_type = 0)
+/* launch one encode run (aad_encode_launch.hip.h EncodeRun) with fully populated arguments on the context's stream */
+AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeRun &run)
 {
-  if (args.num_streams == 0) return AAD_APIRESULT_OK;
-  if (args.bits < 2 || args.bits > 4) return AAD_APIRESULT_INVALID_FORMAT;
-  aad::EncodeArgs a = args;
+  if (run.args.num_streams == 0) return AAD_APIRESULT_OK;
+  if (run.args.bits < 2 || run.args.bits > 4) return AAD_APIRESULT_INVALID_FORMAT;
+  aad::EncodeRun r = run;
+  aad::EncodeArgs &a = r.args;
   if ((reinterpret_cast<uintptr_t>(a.data) & 63u) != 0) a.ring_ok = 0;
   const aad::EncodeBatch batch{a.bits, a.channels, a.num_streams, a.trials, a.block_size, a.ring_ok != 0};
-  const aad::EncodeLaunch p = rec != nullptr ? aad::plan_reconstruct_encode(ctx->device_info, ctx->knobs, batch)
-                                             : aad::plan_encode(ctx->device_info, ctx->knobs, batch);
+  const aad::EncodeLaunch p = r.rec != aad::kRecNone ? aad::plan_reconstruct_encode(ctx->device_info, ctx->knobs, batch)
+                                                     : aad::plan_encode(ctx->device_info, ctx->knobs, batch);
   a.trial_scratch = nullptr;
   a.trial_slot_bytes = p.trial_slot_bytes;
   if (p.trial_scratch_bytes != 0) {
     if (!scratch_reserve(ctx, &ctx->d_trial, &ctx->trial_capacity, p.trial_scratch_bytes, "hipMalloc trial scratch")) return AAD_APIRESULT_NG;
     a.trial_scratch = ctx->d_trial;
   }
-  if (rec != nullptr) {
-    const bool in_f32 = planar == AAD_HIP_SAMPLE_FLOAT32, out_f32 = out_type == AAD_HIP_SAMPLE_FLOAT32;
-    if (in_f32 && out_f32) aad::launch_reconstruct_f32_f32(a, channel_stride, *rec, p, segmented, ctx->stream);
-    else if (in_f32) aad::launch_reconstruct_f32_i16(a, channel_stride, *rec, p, segmented, ctx->stream);
-    else if (out_f32) aad::launch_reconstruct_i16_f32(a, channel_stride, *rec, p, segmented, ctx->stream);
-    else aad::launch_reconstruct_i16_i16(a, channel_stride, *rec, p, segmented, ctx->stream);
-  } else if (planar == AAD_HIP_SAMPLE_FLOAT32) {
-    aad::launch_encode_planar_f32(a, channel_stride, p, segmented, ctx->stream);
-  } else if (planar == AAD_HIP_SAMPLE_INT16 && a.channels != 1) { /* mono int16 rows ARE interleaved frames: the kernels below */
-    aad::launch_encode_planar_i16(a, channel_stride, p, segmented, ctx->stream);
-  } else if (segmented) {
-    switch (a.bits) {
-      case 4: aad::launch_encode<4, true>(a, p, ctx->stream); break;
-      case 3: aad::launch_encode<3, true>(a, p, ctx->stream); break;
-      default: aad::launch_encode<2, true>(a, p, ctx->stream); break;
+  auto by_layout = [&](auto rec) {
+    constexpr int REC = decltype(rec)::value;
+    switch (r.in) {
+      case aad::kInPlanarF32: aad::launch_encode_run<aad::kInPlanarF32, REC>(r, p, ctx->stream); break;
+      case aad::kInPlanarI16: aad::launch_encode_run<aad::kInPlanarI16, REC>(r, p, ctx->stream); break;
+      case aad::kInInterleaved: aad::launch_encode_run<aad::kInInterleaved, REC>(r, p, ctx->stream); break;
     }
-  } else {
-    switch (a.bits) {
-      case 4: aad::launch_encode<4, false>(a, p, ctx->stream); break;
-      case 3: aad::launch_encode<3, false>(a, p, ctx->stream); break;
-      default: aad::launch_encode<2, false>(a, p, ctx->stream); break;
-    }
+  };
+  switch (r.rec) {
+    case aad::kRecF32: by_layout(std::integral_constant<int, aad::kRecF32>{}); break;
+    case aad::kRecI16: by_layout(std::integral_constant<int, aad::kRecI16>{}); break;
+    case aad::kRecNone: by_layout(std::integral_constant<int, aad::kRecNone>{}); break;
   }
   return hip_ok(ctx, hipGetLastError(), "encode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
+}
+
+/* The table of a run becomes a chain table of `count` chains (aad_segments.h): chains are the kernel's streams, none of them
+ * uniform, and the byte ring, which writes an image from its start (aad_encode.hip.h, SEG), is off. */
+void use_chain_table(aad::EncodeRun *run, const aad::ChainDesc *chains, uint32_t count)
+{
+  run->chain_table = true;
+  run->args.chains = chains;
+  run->args.num_streams = count;
+  run->args.ring_ok = 0;
+  run->args.uni.enabled = 0;
+}
+
+/* what the two planar ...PlanCreate entry points ask of their layout and segmentation */
+bool planar_fields_ok(const struct AADHipPlanarLayout *layout, const struct AADHipSegmentation *segmentation)
+{
+  if ((layout->sample_type != AAD_HIP_SAMPLE_INT16 && layout->sample_type != AAD_HIP_SAMPLE_FLOAT32) || layout->reserved != 0) return false;
+  return segmentation == nullptr || segmentation->segment_blocks != 0;
+}
+
+/* Every kind of encode plan.  layout: the input is rows (AADHip_PlanarEncodePlanCreate), null: interleaved frames; output: the plan
+ * also writes the decoded rows (AADHip_PlanarReconstructPlanCreate; layout non-null); segmentation: the streams are cut into
+ * chains (segment_blocks != 0), null: one lane per stream.  The callers have checked their own arguments. */
+AADApiResult encode_plan_create(AADHipContext *ctx, const struct AADEncodeParameter *parameter, const struct AADHipPlanarLayout *layout,
+                                const struct AADHipPlanarOutput *output, const struct AADHipSegmentation *segmentation,
+                                uint32_t num_streams, const struct AADHipStreamDesc *streams, struct AADHipEncodePlan **plan)
+{
+  aad::EncodeRun run;
+  const AADApiResult rc = encode_plan_init(parameter, num_streams, streams, &run.args);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  const aad::EncodeArgs &args = run.args;
+  const char *what = layout != nullptr ? "planar encode plan" : "segmented encode plan";
+  /* every row of every stream lies inside [0, 2^64) elements and bytes: the last element a stream reads is
+   * pcm_offset + (C - 1) channel_stride + num_samples - 1 */
+  const uint64_t elem = layout != nullptr && layout->sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4u : 2u;
+  for (uint32_t i = 0; layout != nullptr && i < num_streams; i++) {
+    if (args.channels > 1 && layout->channel_stride < streams[i].num_samples) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "planar encode plan: channel_stride %llu < num_samples %u of stream %u",
+               (unsigned long long)layout->channel_stride, streams[i].num_samples, i);
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    uint64_t span = 0, end = 0, bytes = 0;
+    if (__builtin_mul_overflow((uint64_t)(args.channels - 1), layout->channel_stride, &span) ||
+        __builtin_add_overflow(span, (uint64_t)streams[i].num_samples, &span) ||
+        __builtin_add_overflow(streams[i].pcm_offset, span, &end) || __builtin_mul_overflow(end, elem, &bytes)) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "planar encode plan: the rows of stream %u overflow 64-bit offsets", i);
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+  }
+  std::vector<aad::ChainDesc> chains;
+  if (segmentation != nullptr &&
+      !aad::build_segment_chains(streams, num_streams, args.channels, args.samples_per_block, args.block_size,
+                                 segmentation->segment_blocks, segmentation->warmup_blocks, &chains, layout != nullptr)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "%s: more than %u chains", what, (unsigned)UINT32_MAX);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  if (output != nullptr && !aad::planar_output_ok(args.channels, num_streams, streams, output)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "planar reconstruct plan: output rows refused (sample type, reserved, a stride below the rows, or past 64-bit offsets)");
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  AADHipEncodePlan *p = new (std::nothrow) AADHipEncodePlan();
+  if (p == nullptr) return AAD_APIRESULT_NG;
+  p->ctx = ctx;
+  p->kind = output != nullptr ? EncodePlanKind::Reconstruct : (layout != nullptr ? EncodePlanKind::Rows : EncodePlanKind::Frames);
+  p->d_table = nullptr;
+  p->d_out_base = nullptr;
+  DeviceGuard guard(ctx);
+  bool ok = guard.ok;
+  if (ok && segmentation != nullptr) {
+    aad::ChainDesc *d_chains = nullptr;
+    ok = upload(ctx, &d_chains, chains.data(), chains.size());
+    p->d_table = d_chains;
+    use_chain_table(&run, d_chains, (uint32_t)chains.size());
+  } else if (ok) {
+    aad::StreamDesc *d_streams = nullptr;
+    ok = upload(ctx, &d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams);
+    p->d_table = d_streams;
+    run.args.streams = d_streams;
+  }
+  if (ok && output != nullptr) {
+    const std::vector<uint64_t> base =
+        aad::reconstruct_output_bases(num_streams, output->stream_stride, segmentation != nullptr ? &chains : nullptr, args.samples_per_block);
+    ok = upload(ctx, &p->d_out_base, base.data(), base.size());
+    run.rec = aad::rec_output(output->sample_type);
+    run.rows = aad::RecRows{nullptr, p->d_out_base, output->channel_stride};
+  }
+  if (!ok) {
+    if (p->d_table) (void)hipFree(p->d_table);
+    if (p->d_out_base) (void)hipFree(p->d_out_base);
+    delete p;
+    return AAD_APIRESULT_NG;
+  }
+  if (layout != nullptr) {
+    run.in = aad::planar_layout(layout->sample_type, args.channels);
+    run.channel_stride = layout->channel_stride;
+  }
+  p->run = run;
+  *plan = p;
+  return AAD_APIRESULT_OK;
+}
+
+/* Run a plan for the entry point that takes plans of `kind`.  samples: interleaved int16 frames (Frames), or rows that the kernels
+ * read as the plan's sample type; out: the decoded rows, Reconstruct only. */
+AADApiResult encode_plan_run(AADHipEncodePlan *plan, EncodePlanKind kind, const void *samples, uint8_t *device_data, void *out,
+                             struct AADHipLaneState *device_state)
+{
+  if (plan == nullptr || samples == nullptr || device_data == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = plan->ctx;
+  const aad::LaunchSignal signal = take_signal(ctx);
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (plan->kind != kind) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* frames, rows, rows in and out: each its own ...PlanRun */
+  if (plan->run.chain_table && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  if (kind == EncodePlanKind::Reconstruct && out == samples) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  if (plan->run.args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
+  if (kind == EncodePlanKind::Reconstruct && out == nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  aad::EncodeRun r = plan->run;
+  r.args.pcm = static_cast<const int16_t *>(samples);
+  r.args.data = device_data;
+  r.args.state = reinterpret_cast<const aad::LaneStateRecord *>(device_state);
+  r.args.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
+  r.rows.out = out;
+  aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
+  return finish_signal(ctx, signal, run_encode(ctx, r));
 }
 
 AADApiResult run_decode(AADHipContext *ctx, const aad::DecodeArgs &a)
@@ -712,27 +827,7 @@ AADApiResult AADHip_EncodePlanCreate(struct AADHipContext *ctx, const struct AAD
   if (ctx == nullptr || parameter == nullptr || plan == nullptr || (num_streams != 0 && streams == nullptr))
     return AAD_APIRESULT_INVALID_ARGUMENT;
   *plan = nullptr;
-  aad::EncodeArgs args;
-  const AADApiResult rc = encode_plan_init(parameter, num_streams, streams, &args);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  AADHipEncodePlan *p = new (std::nothrow) AADHipEncodePlan();
-  if (p == nullptr) return AAD_APIRESULT_NG;
-  p->ctx = ctx;
-  p->d_streams = nullptr;
-  p->d_chains = nullptr;
-  p->segmented = false;
-  p->planar = false;
-  p->sample_type = 0;
-  DeviceGuard guard(ctx);
-  if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams)) {
-    if (p->d_streams) (void)hipFree(p->d_streams);
-    delete p;
-    return AAD_APIRESULT_NG;
-  }
-  p->args = args;
-  p->args.streams = p->d_streams;
-  *plan = p;
-  return AAD_APIRESULT_OK;
+  return encode_plan_create(ctx, parameter, nullptr, nullptr, nullptr, num_streams, streams, plan);
 }
 
 void AADHip_EncodePlanDestroy(struct AADHipEncodePlan *plan)
@@ -741,8 +836,7 @@ void AADHip_EncodePlanDestroy(struct AADHipEncodePlan *plan)
   DeviceGuard guard(plan->ctx);
   if (guard.ok) {
     (void)hipStreamSynchronize(plan->ctx->stream);
-    (void)hipFree(plan->d_streams);
-    (void)hipFree(plan->d_chains);
+    (void)hipFree(plan->d_table);
     (void)hipFree(plan->d_out_base);
   }
   delete plan;
@@ -756,56 +850,13 @@ AADApiResult AADHip_SegmentedEncodePlanCreate(struct AADHipContext *ctx, const s
     return AAD_APIRESULT_INVALID_ARGUMENT;
   *plan = nullptr;
   if (segmentation->segment_blocks == 0) return AAD_APIRESULT_INVALID_ARGUMENT;
-  aad::EncodeArgs args;
-  const AADApiResult rc = encode_plan_init(parameter, num_streams, streams, &args);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  std::vector<aad::ChainDesc> chains;
-  if (!aad::build_segment_chains(streams, num_streams, args.channels, args.samples_per_block, args.block_size,
-                                 segmentation->segment_blocks, segmentation->warmup_blocks, &chains)) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error), "segmented encode plan: more than %u chains", (unsigned)UINT32_MAX);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  AADHipEncodePlan *p = new (std::nothrow) AADHipEncodePlan();
-  if (p == nullptr) return AAD_APIRESULT_NG;
-  p->ctx = ctx;
-  p->d_streams = nullptr;
-  p->d_chains = nullptr;
-  p->segmented = true;
-  p->planar = false;
-  p->sample_type = 0;
-  DeviceGuard guard(ctx);
-  if (!guard.ok || !upload(ctx, &p->d_chains, chains.data(), chains.size())) {
-    if (p->d_chains) (void)hipFree(p->d_chains);
-    delete p;
-    return AAD_APIRESULT_NG;
-  }
-  p->args = args;
-  p->args.chains = p->d_chains;
-  p->args.num_streams = (uint32_t)chains.size();
-  p->args.ring_ok = 0; /* the byte ring writes an image from its start (aad_encode.hip.h, SEG) */
-  p->args.uni.enabled = 0;
-  *plan = p;
-  return AAD_APIRESULT_OK;
+  return encode_plan_create(ctx, parameter, nullptr, nullptr, segmentation, num_streams, streams, plan);
 }
 
 AADApiResult AADHip_EncodePlanRun(struct AADHipEncodePlan *plan, const int16_t *device_pcm, uint8_t *device_data,
                                   struct AADHipLaneState *device_state)
 {
-  if (plan == nullptr || device_pcm == nullptr || device_data == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = plan->ctx;
-  const aad::LaunchSignal signal = take_signal(ctx);
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (plan->segmented && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
-  if (plan->planar) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* rows, not frames: AADHip_PlanarEncodePlanRun */
-  if (plan->args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
-  aad::EncodeArgs a = plan->args;
-  a.pcm = device_pcm;
-  a.data = device_data;
-  a.state = reinterpret_cast<const aad::LaneStateRecord *>(device_state);
-  a.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
-  aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
-  return finish_signal(ctx, signal, run_encode(ctx, a, plan->segmented));
+  return encode_plan_run(plan, EncodePlanKind::Frames, device_pcm, device_data, nullptr, device_state);
 }
 
 /* ------------------------------------------------------------------------ planar encode -- */
@@ -817,86 +868,14 @@ AADApiResult AADHip_PlanarEncodePlanCreate(struct AADHipContext *ctx, const stru
   if (ctx == nullptr || parameter == nullptr || layout == nullptr || plan == nullptr || (num_streams != 0 && streams == nullptr))
     return AAD_APIRESULT_INVALID_ARGUMENT;
   *plan = nullptr;
-  if ((layout->sample_type != AAD_HIP_SAMPLE_INT16 && layout->sample_type != AAD_HIP_SAMPLE_FLOAT32) || layout->reserved != 0)
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  if (segmentation != nullptr && segmentation->segment_blocks == 0) return AAD_APIRESULT_INVALID_ARGUMENT;
-  aad::EncodeArgs args;
-  const AADApiResult rc = encode_plan_init(parameter, num_streams, streams, &args);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  /* every row of every stream lies inside [0, 2^64) elements and bytes: the last element a stream reads is
-   * pcm_offset + (C - 1) channel_stride + num_samples - 1 */
-  const uint64_t elem = layout->sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4u : 2u;
-  for (uint32_t i = 0; i < num_streams; i++) {
-    if (args.channels > 1 && layout->channel_stride < streams[i].num_samples) {
-      snprintf(ctx->last_error, sizeof(ctx->last_error), "planar encode plan: channel_stride %llu < num_samples %u of stream %u",
-               (unsigned long long)layout->channel_stride, streams[i].num_samples, i);
-      return AAD_APIRESULT_INVALID_ARGUMENT;
-    }
-    uint64_t span = 0, end = 0, bytes = 0;
-    if (__builtin_mul_overflow((uint64_t)(args.channels - 1), layout->channel_stride, &span) ||
-        __builtin_add_overflow(span, (uint64_t)streams[i].num_samples, &span) ||
-        __builtin_add_overflow(streams[i].pcm_offset, span, &end) || __builtin_mul_overflow(end, elem, &bytes)) {
-      snprintf(ctx->last_error, sizeof(ctx->last_error), "planar encode plan: the rows of stream %u overflow 64-bit offsets", i);
-      return AAD_APIRESULT_INVALID_ARGUMENT;
-    }
-  }
-  std::vector<aad::ChainDesc> chains;
-  if (segmentation != nullptr &&
-      !aad::build_segment_chains(streams, num_streams, args.channels, args.samples_per_block, args.block_size,
-                                 segmentation->segment_blocks, segmentation->warmup_blocks, &chains, true)) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error), "planar encode plan: more than %u chains", (unsigned)UINT32_MAX);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  AADHipEncodePlan *p = new (std::nothrow) AADHipEncodePlan();
-  if (p == nullptr) return AAD_APIRESULT_NG;
-  p->ctx = ctx;
-  p->d_streams = nullptr;
-  p->d_chains = nullptr;
-  p->segmented = segmentation != nullptr;
-  p->planar = true;
-  p->sample_type = layout->sample_type;
-  DeviceGuard guard(ctx);
-  const bool ok = guard.ok && (p->segmented ? upload(ctx, &p->d_chains, chains.data(), chains.size())
-                                            : upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams));
-  if (!ok) {
-    if (p->d_streams) (void)hipFree(p->d_streams);
-    if (p->d_chains) (void)hipFree(p->d_chains);
-    delete p;
-    return AAD_APIRESULT_NG;
-  }
-  p->args = args;
-  p->channel_stride = layout->channel_stride;
-  if (p->segmented) { /* as AADHip_SegmentedEncodePlanCreate */
-    p->args.chains = p->d_chains;
-    p->args.num_streams = (uint32_t)chains.size();
-    p->args.ring_ok = 0;
-    p->args.uni.enabled = 0;
-  } else {
-    p->args.streams = p->d_streams;
-  }
-  *plan = p;
-  return AAD_APIRESULT_OK;
+  if (!planar_fields_ok(layout, segmentation)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return encode_plan_create(ctx, parameter, layout, nullptr, segmentation, num_streams, streams, plan);
 }
 
 AADApiResult AADHip_PlanarEncodePlanRun(struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data,
                                         struct AADHipLaneState *device_state)
 {
-  if (plan == nullptr || device_samples == nullptr || device_data == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = plan->ctx;
-  const aad::LaunchSignal signal = take_signal(ctx);
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (!plan->planar) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* frames, not rows: AADHip_EncodePlanRun */
-  if (plan->reconstruct) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* AADHip_PlanarReconstructPlanRun */
-  if (plan->segmented && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
-  if (plan->args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
-  aad::EncodeArgs a = plan->args;
-  a.pcm = static_cast<const int16_t *>(device_samples); /* the kernels read it as the plan's sample type */
-  a.data = device_data;
-  a.state = reinterpret_cast<const aad::LaneStateRecord *>(device_state);
-  a.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
-  aad::tl_launch_signal = signal;
-  return finish_signal(ctx, signal, run_encode(ctx, a, plan->segmented, plan->sample_type, plan->channel_stride));
+  return encode_plan_run(plan, EncodePlanKind::Rows, device_samples, device_data, nullptr, device_state);
 }
 
 /* ------------------------------------------------------------------ planar reconstruct -- */
@@ -908,64 +887,15 @@ AADApiResult AADHip_PlanarReconstructPlanCreate(struct AADHipContext *ctx, const
 {
   if (ctx == nullptr || output == nullptr || plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
   *plan = nullptr;
-  AADHipEncodePlan *p = nullptr;
-  const AADApiResult rc = AADHip_PlanarEncodePlanCreate(ctx, parameter, input, segmentation, num_streams, streams, &p);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  if (!aad::planar_output_ok(p->args.channels, num_streams, streams, output)) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "planar reconstruct plan: output rows refused (sample type, reserved, a stride below the rows, or past 64-bit offsets)");
-    AADHip_EncodePlanDestroy(p);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  /* where each lane's frame 0 lands in `out`: stream i's row, plus a chain's first frame (the chain table's order, aad_segments.h) */
-  std::vector<uint64_t> base;
-  const uint64_t spb = p->args.samples_per_block;
-  for (uint32_t i = 0; i < num_streams; i++) {
-    const uint64_t row = (uint64_t)i * output->stream_stride;
-    if (segmentation == nullptr) {
-      base.push_back(row);
-      continue;
-    }
-    const uint64_t L = segmentation->segment_blocks, b = aad::stream_blocks(streams[i].num_samples, (uint32_t)spb);
-    const uint64_t segments = b == 0 ? 1u : (b + L - 1) / L;
-    for (uint64_t s = 0; s < segments; s++) {
-      const uint64_t kept = s * L, w = segmentation->warmup_blocks < kept ? segmentation->warmup_blocks : kept;
-      base.push_back(row + (kept - w) * spb);
-    }
-  }
-  DeviceGuard guard(ctx);
-  if (base.size() != (size_t)p->args.num_streams || !guard.ok || !upload(ctx, &p->d_out_base, base.data(), base.size())) {
-    AADHip_EncodePlanDestroy(p);
-    return AAD_APIRESULT_NG;
-  }
-  p->reconstruct = true;
-  p->out_type = output->sample_type;
-  p->out_channel_stride = output->channel_stride;
-  *plan = p;
-  return AAD_APIRESULT_OK;
+  if (parameter == nullptr || input == nullptr || (num_streams != 0 && streams == nullptr)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  if (!planar_fields_ok(input, segmentation)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return encode_plan_create(ctx, parameter, input, output, segmentation, num_streams, streams, plan);
 }
 
 AADApiResult AADHip_PlanarReconstructPlanRun(struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data,
                                              void *device_out, struct AADHipLaneState *device_state)
 {
-  if (plan == nullptr || device_samples == nullptr || device_data == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = plan->ctx;
-  const aad::LaunchSignal signal = take_signal(ctx);
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (!plan->reconstruct) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT); /* AADHip_(Planar)EncodePlanRun */
-  if (plan->segmented && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
-  if (device_out == device_samples) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
-  if (plan->args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
-  if (device_out == nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
-  aad::EncodeArgs a = plan->args;
-  a.pcm = static_cast<const int16_t *>(device_samples); /* the kernels read it as the plan's sample type */
-  a.data = device_data;
-  a.state = reinterpret_cast<const aad::LaneStateRecord *>(device_state);
-  a.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
-  const aad::RecRows rows = {device_out, plan->d_out_base, plan->out_channel_stride};
-  aad::tl_launch_signal = signal;
-  return finish_signal(ctx, signal, run_encode(ctx, a, plan->segmented, plan->sample_type, plan->channel_stride, &rows, plan->out_type));
+  return encode_plan_run(plan, EncodePlanKind::Reconstruct, device_samples, device_data, device_out, device_state);
 }
 
 /* ------------------------------------------------------------------------------- decode -- */
@@ -1436,6 +1366,26 @@ bool state_reserve(AADHipContext *ctx, size_t records)
   return true;
 }
 
+/* What every host-memory encode entry checks before any device work: the parameter makes a valid header (*h; its num_samples is
+ * left at the last stream's), and per stream - its image size in (*sizes)[i] - first that it is not empty (INVALID_FORMAT,
+ * src/aad_encoder.c:157-159), then, where the entry takes capacities (data_capacity non-null), that its buffer holds the image
+ * (INSUFFICIENT_BUFFER). */
+AADApiResult host_encode_check(const struct AADEncodeParameter *parameter, uint32_t num_streams, const uint32_t *num_samples,
+                               const uint64_t *data_capacity, AADHeaderInfo *h, std::vector<uint64_t> *sizes)
+{
+  if (AADFormat_ParameterToHeader(parameter, 1, AAD_HIP_MAX_NUM_CHANNELS, h) != AAD_APIRESULT_OK ||
+      !AADFormat_HeaderFieldsValid(h, AAD_HIP_MAX_NUM_CHANNELS))
+    return AAD_APIRESULT_INVALID_FORMAT;
+  sizes->resize(num_streams);
+  for (uint32_t i = 0; i < num_streams; i++) {
+    if (num_samples[i] == 0) return AAD_APIRESULT_INVALID_FORMAT;
+    h->num_samples = num_samples[i];
+    (*sizes)[i] = AADFormat_EncodedSize(h);
+    if (data_capacity != nullptr && data_capacity[i] < (*sizes)[i]) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
+  }
+  return AAD_APIRESULT_OK;
+}
+
 /*
  * Encode num_streams host streams.  fill(i, frame0, frames, dst) writes that range of stream i's
  * interleaved int16 frames, drain(i, offset, src, size) receives bytes [offset, offset + size) of
@@ -1447,17 +1397,12 @@ AADApiResult encode_host(AADHipContext *ctx, const struct AADEncodeParameter *pa
                          struct AADHipLaneState *state, Fill fill, Drain drain)
 {
   AADHeaderInfo h;
-  if (AADFormat_ParameterToHeader(parameter, 1, AAD_HIP_MAX_NUM_CHANNELS, &h) != AAD_APIRESULT_OK ||
-      !AADFormat_HeaderFieldsValid(&h, AAD_HIP_MAX_NUM_CHANNELS))
-    return AAD_APIRESULT_INVALID_FORMAT;
+  std::vector<uint64_t> sizes, blocks(num_streams);
+  const AADApiResult checked = host_encode_check(parameter, num_streams, num_samples, data_capacity, &h, &sizes);
+  if (checked != AAD_APIRESULT_OK) return checked;
   const uint32_t ch = h.num_channels, spb = h.num_samples_per_block;
-  std::vector<uint64_t> sizes(num_streams), blocks(num_streams);
   uint64_t total = 0;
   for (uint32_t i = 0; i < num_streams; i++) {
-    if (num_samples[i] == 0) return AAD_APIRESULT_INVALID_FORMAT; /* src/aad_encoder.c:157-159 */
-    h.num_samples = num_samples[i];
-    sizes[i] = AADFormat_EncodedSize(&h);
-    if (data_capacity[i] < sizes[i]) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
     blocks[i] = ((uint64_t)num_samples[i] + spb - 1) / spb;
     total += (uint64_t)num_samples[i] * ch * sizeof(int16_t) + sizes[i];
   }
@@ -1539,7 +1484,8 @@ AADApiResult encode_host(AADHipContext *ctx, const struct AADEncodeParameter *pa
     }
     f.cost[n] = data_bytes;
     fill_cost[n] = pcm_elems * sizeof(int16_t);
-    aad::EncodeArgs a;
+    aad::EncodeRun run; /* interleaved frames, a stream table, images only */
+    aad::EncodeArgs &a = run.args;
     rc = encode_plan_init(parameter, n, table.data(), &a, lead, true);
     if (rc != AAD_APIRESULT_OK) break;
     /* states live on the device while a group has tiles to go; the caller's come in with the first
@@ -1585,7 +1531,7 @@ AADApiResult encode_host(AADHipContext *ctx, const struct AADEncodeParameter *pa
     a.data = dout;
     a.state = state_in ? reinterpret_cast<const aad::LaneStateRecord *>(din + table_bytes) : (step.group_first ? nullptr : d_state);
     a.state_out = carry ? d_state : (state_back ? reinterpret_cast<aad::LaneStateRecord *>(dout + data_bytes) : nullptr);
-    if (run_encode(ctx, a) != AAD_APIRESULT_OK) break;
+    if (run_encode(ctx, run) != AAD_APIRESULT_OK) break;
     f.state_order.clear();
     if (state_back) {
       /* from the device-side records on the compute stream: the next group's first launch overwrites them */
@@ -1637,6 +1583,63 @@ bool device_block_reserve(AADHipContext *ctx, void **block, size_t *capacity, si
 /* bytes of the pinned chunks that stage a device-resident wave */
 uint64_t staging_chunk(const AADHipContext *ctx) { return ctx->tile_bytes > 0 ? (uint64_t)ctx->tile_bytes : kChunkBudget; }
 
+/* items [*a, *b) whose rows meet bytes [lo, hi) of a block; `at`: count + 1 entries, where each item's row starts and the block ends */
+void row_span(const std::vector<uint64_t> &at, uint64_t lo, uint64_t hi, uint32_t *a, uint32_t *b)
+{
+  const uint32_t count = (uint32_t)at.size() - 1;
+  *a = (uint32_t)(std::upper_bound(at.begin(), at.end(), lo) - at.begin());
+  *a = *a ? *a - 1 : 0;
+  *b = (uint32_t)(std::lower_bound(at.begin(), at.end(), hi) - at.begin());
+  if (*b > count) *b = count;
+}
+
+/* The staging of a device-resident wave, on the context's own stream through its two pinned input / output blocks.
+ * stage_up: bytes [0, bytes) of the device block d_dst in chunks; fill(lo, hi, host) writes bytes [lo, hi) to host[0 ..), and
+ * chunk k is filled while chunk k - 1 is on the bus.  `what` names the copy in an error. */
+template <class Fill>
+bool stage_up(AADHipContext *ctx, uint8_t *d_dst, uint64_t bytes, size_t chunk, const char *what, Fill fill)
+{
+  const size_t stage = bytes < chunk ? (size_t)bytes + 64 : chunk;
+  if (!staging_reserve(ctx, ctx->in[0], stage) || (bytes > chunk && !staging_reserve(ctx, ctx->in[1], stage))) return false;
+  uint32_t k = 0;
+  for (uint64_t lo = 0; lo < bytes; lo += chunk, k++) {
+    const uint64_t hi = lo + chunk < bytes ? lo + chunk : bytes;
+    /* the block's last copy, two rounds ago, has left it */
+    if (k >= 2 && !hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[k & 1]), "hipEventSynchronize")) return false;
+    uint8_t *host = static_cast<uint8_t *>(ctx->in[k & 1].host);
+    fill(lo, hi, host);
+    if (!hip_ok(ctx, hipMemcpyAsync(d_dst + lo, host, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream), what) ||
+        !hip_ok(ctx, hipEventRecord(ctx->chunk_done[k & 1], ctx->stream), "hipEventRecord"))
+      return false;
+  }
+  return true;
+}
+
+/* stage_down: bytes [lo, hi) of the device block d_src in chunks; scatter(lo, hi, host) receives bytes [lo, hi) at host[0 ..), and
+ * chunk k - 1 is scattered while chunk k is on the bus.  Nothing to bring down: no call is made. */
+template <class Scatter>
+bool stage_down(AADHipContext *ctx, const uint8_t *d_src, uint64_t lo, uint64_t hi, size_t chunk, Scatter scatter)
+{
+  if (hi <= lo) return true;
+  const size_t stage = hi - lo < chunk ? (size_t)(hi - lo) + 64 : chunk;
+  if (!staging_reserve(ctx, ctx->out[0], stage) || (hi - lo > chunk && !staging_reserve(ctx, ctx->out[1], stage))) return false;
+  /* wait for chunk k's copy, queued one round before the one that is on the bus now, and hand it over */
+  auto deliver = [&](uint32_t k, uint64_t c0, uint64_t c1) {
+    if (!hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[k & 1]), "hipEventSynchronize")) return false;
+    scatter(c0, c1, static_cast<uint8_t *>(ctx->out[k & 1].host));
+    return true;
+  };
+  uint32_t k = 0;
+  for (uint64_t c0 = lo; c0 < hi; c0 += chunk, k++) {
+    const uint64_t c1 = c0 + chunk < hi ? c0 + chunk : hi;
+    if (!hip_ok(ctx, hipMemcpyAsync(ctx->out[k & 1].host, d_src + c0, (size_t)(c1 - c0), hipMemcpyDeviceToHost, ctx->stream), "D2H block") ||
+        !hip_ok(ctx, hipEventRecord(ctx->chunk_done[k & 1], ctx->stream), "hipEventRecord"))
+      return false;
+    if (k > 0 && !deliver(k - 1, c0 - chunk, c0)) return false;
+  }
+  return deliver(k - 1, lo + (uint64_t)(k - 1) * chunk, hi);
+}
+
 /* device bytes a wave may take: what is free now plus what this context's own grow-only blocks already hold, less a quarter for
  * everybody else; a forced tile size forces small waves too (64 tiles' worth), so that the tests walk every path */
 bool wave_budget(AADHipContext *ctx, uint64_t *budget)
@@ -1671,22 +1674,13 @@ AADApiResult encode_host_segmented(AADHipContext *ctx, const struct AADEncodePar
                                    uint64_t *output_size, Fill fill, Drain drain)
 {
   AADHeaderInfo h;
-  if (AADFormat_ParameterToHeader(parameter, 1, AAD_HIP_MAX_NUM_CHANNELS, &h) != AAD_APIRESULT_OK ||
-      !AADFormat_HeaderFieldsValid(&h, AAD_HIP_MAX_NUM_CHANNELS))
-    return AAD_APIRESULT_INVALID_FORMAT;
-  const uint32_t ch = h.num_channels, spb = h.num_samples_per_block;
-  std::vector<uint64_t> sizes(num_streams);
-  for (uint32_t i = 0; i < num_streams; i++) {
-    if (num_samples[i] == 0) return AAD_APIRESULT_INVALID_FORMAT; /* src/aad_encoder.c:157-159 */
-    h.num_samples = num_samples[i];
-    sizes[i] = AADFormat_EncodedSize(&h);
-    if (data_capacity[i] < sizes[i]) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
-  }
-  aad::EncodeArgs base;
-  AADApiResult rc = encode_plan_init(parameter, 0, nullptr, &base);
+  std::vector<uint64_t> sizes;
+  AADApiResult rc = host_encode_check(parameter, num_streams, num_samples, data_capacity, &h, &sizes);
   if (rc != AAD_APIRESULT_OK) return rc;
-  base.ring_ok = 0; /* as the segmented plans: chains as streams, no byte ring */
-  base.uni.enabled = 0;
+  const uint32_t ch = h.num_channels, spb = h.num_samples_per_block;
+  aad::EncodeRun run; /* interleaved frames, each wave's chain table (use_chain_table), images only */
+  rc = encode_plan_init(parameter, 0, nullptr, &run.args);
+  if (rc != AAD_APIRESULT_OK) return rc;
   uint64_t budget;
   if (!wave_budget(ctx, &budget)) return AAD_APIRESULT_NG;
   std::vector<aad::SegmentWave> waves;
@@ -1712,91 +1706,50 @@ AADApiResult encode_host_segmented(AADHipContext *ctx, const struct AADEncodePar
     }
     row[n] = in_bytes;
     spot[n] = t.out_bytes;
-    auto span = [&](const std::vector<uint64_t> &at, uint64_t lo, uint64_t hi, uint32_t *a, uint32_t *b) { /* chains meeting [lo, hi) */
-      *a = (uint32_t)(std::upper_bound(at.begin(), at.end(), lo) - at.begin());
-      *a = *a ? *a - 1 : 0;
-      *b = (uint32_t)(std::lower_bound(at.begin(), at.end(), hi) - at.begin());
-      if (*b > n) *b = n;
-    };
     rc = AAD_APIRESULT_NG;
-    do {
-      if (!device_block_reserve(ctx, &ctx->d_rc_in, &ctx->rc_in_capacity, in_bytes + 64, "hipMalloc segmented encode input") ||
-          !device_block_reserve(ctx, &ctx->d_rc_out, &ctx->rc_out_capacity, t.out_bytes + 64, "hipMalloc segmented encode output"))
-        break;
-      const size_t stage = in_bytes < chunk ? (size_t)in_bytes + 64 : chunk;
-      if (!staging_reserve(ctx, ctx->in[0], stage) || (in_bytes > chunk && !staging_reserve(ctx, ctx->in[1], stage))) break;
-      uint8_t *d_in = static_cast<uint8_t *>(ctx->d_rc_in), *d_out = static_cast<uint8_t *>(ctx->d_rc_out);
+    if (!device_block_reserve(ctx, &ctx->d_rc_in, &ctx->rc_in_capacity, in_bytes + 64, "hipMalloc segmented encode input") ||
+        !device_block_reserve(ctx, &ctx->d_rc_out, &ctx->rc_out_capacity, t.out_bytes + 64, "hipMalloc segmented encode output"))
+      break;
+    uint8_t *d_in = static_cast<uint8_t *>(ctx->d_rc_in), *d_out = static_cast<uint8_t *>(ctx->d_rc_out);
 
-      /* ---- up: bytes [lo, hi) of the input block; chunk k is filled while chunk k - 1 is on the bus ---- */
-      bool ok = true;
-      uint32_t k = 0;
-      for (uint64_t lo = 0; lo < in_bytes && ok; lo += chunk, k++) {
-        const uint64_t hi = lo + chunk < in_bytes ? lo + chunk : in_bytes;
-        if (k >= 2) ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[k & 1]), "hipEventSynchronize"); /* the block's last copy has left it */
-        if (!ok) break;
-        uint8_t *host = static_cast<uint8_t *>(ctx->in[k & 1].host);
-        const uint64_t table_end = sizeof(aad::ChainDesc) * (uint64_t)n;
-        if (lo < table_end)
-          memcpy(host, reinterpret_cast<const uint8_t *>(t.chains.data()) + lo, (size_t)((hi < table_end ? hi : table_end) - lo));
-        uint32_t a, b;
-        span(row, lo, hi, &a, &b);
-        staged_span(ctx, a, b, row, [&](uint32_t x, uint32_t y) {
-          for (uint32_t c = x; c < y; c++) {
-            const uint64_t r0 = row[c], r1 = r0 + (uint64_t)t.chains[c].num_frames * ch * sizeof(int16_t);
-            const uint64_t c0 = r0 > lo ? r0 : lo, c1 = r1 < hi ? r1 : hi;
-            if (c1 > c0)
-              fill(t.where[c].stream, (uint64_t)t.where[c].frame0 * ch * sizeof(int16_t) + (c0 - r0), c1 - c0, host + (c0 - lo));
-          }
-        });
-        ok = hip_ok(ctx, hipMemcpyAsync(d_in + lo, host, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream), "H2D block") &&
-             hip_ok(ctx, hipEventRecord(ctx->chunk_done[k & 1], ctx->stream), "hipEventRecord");
-      }
-      if (!ok) break;
-
-      /* ---- compute: one launch over every chain of the wave ---- */
-      aad::EncodeArgs args = base;
-      args.chains = reinterpret_cast<const aad::ChainDesc *>(d_in);
-      args.num_streams = n;
-      args.pcm = reinterpret_cast<const int16_t *>(d_in + table_bytes);
-      args.data = d_out;
-      if (run_encode(ctx, args, true) != AAD_APIRESULT_OK) break;
-
-      /* ---- down: bytes [out_begin, out_bytes) of the output block; chunk k - 1 is scattered while chunk k is on the bus ---- */
-      const uint64_t down_lo = t.out_begin, down_hi = t.out_bytes;
-      const size_t dstage = down_hi - down_lo < chunk ? (size_t)(down_hi - down_lo) + 64 : chunk;
-      if (!staging_reserve(ctx, ctx->out[0], dstage) || (down_hi - down_lo > chunk && !staging_reserve(ctx, ctx->out[1], dstage))) break;
-      auto scatter = [&](uint32_t kk, uint64_t lo, uint64_t hi) { /* host block kk & 1 holds bytes [lo, hi) of the output block */
-        const uint8_t *host = static_cast<const uint8_t *>(ctx->out[kk & 1].host);
-        uint32_t a, b;
-        span(spot, lo, hi, &a, &b);
-        staged_span(ctx, a, b, spot, [&](uint32_t x, uint32_t y) {
-          for (uint32_t c = x; c < y; c++) {
-            const aad::WaveChain &w = t.where[c];
-            const uint64_t c0 = w.out_offset > lo ? w.out_offset : lo, e = w.out_offset + w.image_bytes, c1 = e < hi ? e : hi;
-            if (c1 > c0) drain(w.stream, w.image_offset + (c0 - w.out_offset), host + (c0 - lo), c1 - c0);
-          }
-        });
-      };
-      uint64_t prev_lo = 0, prev_hi = 0;
-      bool have_prev = false;
-      k = 0;
-      for (uint64_t lo = down_lo; lo < down_hi && ok; lo += chunk, k++) {
-        const uint64_t hi = lo + chunk < down_hi ? lo + chunk : down_hi;
-        ok = hip_ok(ctx, hipMemcpyAsync(ctx->out[k & 1].host, d_out + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream), "D2H block") &&
-             hip_ok(ctx, hipEventRecord(ctx->chunk_done[k & 1], ctx->stream), "hipEventRecord");
-        if (ok && have_prev) { /* the other block: its copy was queued one round ago */
-          ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[(k - 1) & 1]), "hipEventSynchronize");
-          if (ok) scatter(k - 1, prev_lo, prev_hi);
+    /* ---- up: the input block, the table's bytes and every chain's frames as they fall into a chunk ---- */
+    const bool up = stage_up(ctx, d_in, in_bytes, chunk, "H2D block", [&](uint64_t lo, uint64_t hi, uint8_t *host) {
+      const uint64_t table_end = sizeof(aad::ChainDesc) * (uint64_t)n;
+      if (lo < table_end)
+        memcpy(host, reinterpret_cast<const uint8_t *>(t.chains.data()) + lo, (size_t)((hi < table_end ? hi : table_end) - lo));
+      uint32_t a, b;
+      row_span(row, lo, hi, &a, &b);
+      staged_span(ctx, a, b, row, [&](uint32_t x, uint32_t y) {
+        for (uint32_t c = x; c < y; c++) {
+          const uint64_t r0 = row[c], r1 = r0 + (uint64_t)t.chains[c].num_frames * ch * sizeof(int16_t);
+          const uint64_t c0 = r0 > lo ? r0 : lo, c1 = r1 < hi ? r1 : hi;
+          if (c1 > c0)
+            fill(t.where[c].stream, (uint64_t)t.where[c].frame0 * ch * sizeof(int16_t) + (c0 - r0), c1 - c0, host + (c0 - lo));
         }
-        prev_lo = lo, prev_hi = hi, have_prev = true;
-      }
-      if (ok && have_prev) {
-        ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[(k - 1) & 1]), "hipEventSynchronize");
-        if (ok) scatter(k - 1, prev_lo, prev_hi);
-      }
-      if (!ok) break;
-      rc = AAD_APIRESULT_OK;
-    } while (0);
+      });
+    });
+    if (!up) break;
+
+    /* ---- compute: one launch over every chain of the wave ---- */
+    use_chain_table(&run, reinterpret_cast<const aad::ChainDesc *>(d_in), n);
+    run.args.pcm = reinterpret_cast<const int16_t *>(d_in + table_bytes);
+    run.args.data = d_out;
+    if (run_encode(ctx, run) != AAD_APIRESULT_OK) break;
+
+    /* ---- down: bytes [out_begin, out_bytes) of the output block, each chain's to its place in its stream's image ---- */
+    const bool down = stage_down(ctx, d_out, t.out_begin, t.out_bytes, chunk, [&](uint64_t lo, uint64_t hi, const uint8_t *host) {
+      uint32_t a, b;
+      row_span(spot, lo, hi, &a, &b);
+      staged_span(ctx, a, b, spot, [&](uint32_t x, uint32_t y) {
+        for (uint32_t c = x; c < y; c++) {
+          const aad::WaveChain &w = t.where[c];
+          const uint64_t c0 = w.out_offset > lo ? w.out_offset : lo, e = w.out_offset + w.image_bytes, c1 = e < hi ? e : hi;
+          if (c1 > c0) drain(w.stream, w.image_offset + (c0 - w.out_offset), host + (c0 - lo), c1 - c0);
+        }
+      });
+    });
+    if (!down) break;
+    rc = AAD_APIRESULT_OK;
   }
   if (rc != AAD_APIRESULT_OK) (void)hipStreamSynchronize(ctx->stream); /* nothing of this call stays in flight */
   if (rc == AAD_APIRESULT_OK && output_size) memcpy(output_size, sizes.data(), sizeof(uint64_t) * num_streams);
@@ -2103,8 +2056,7 @@ static AADApiResult reconstruct_plan_create(struct AADHipContext *ctx, const str
   if (p == nullptr) return AAD_APIRESULT_NG;
   memset(static_cast<void *>(p), 0, sizeof(*p));
   p->ctx = ctx;
-  AADApiResult rc = segmentation ? AADHip_SegmentedEncodePlanCreate(ctx, parameter, segmentation, num_streams, streams, &p->encode)
-                                 : AADHip_EncodePlanCreate(ctx, parameter, num_streams, streams, &p->encode);
+  AADApiResult rc = encode_plan_create(ctx, parameter, nullptr, nullptr, segmentation, num_streams, streams, &p->encode);
   if (rc == AAD_APIRESULT_OK) {
     /* the decoder sees exactly the images the encoder writes */
     AADHeaderInfo h;
@@ -2275,43 +2227,25 @@ AADApiResult reconstruct_wave(AADHipContext *ctx, const struct AADEncodeParamete
         !device_block_reserve(ctx, &ctx->d_rc_out, &ctx->rc_out_capacity, out_bytes + 64, "hipMalloc reconstruction output") ||
         !device_block_reserve(ctx, &ctx->d_scratch, &ctx->scratch_capacity, data_bytes + 64, "hipMalloc image scratch"))
       break;
-    const size_t stage = pcm_bytes < chunk ? pcm_bytes + 64 : chunk;
-    if (!staging_reserve(ctx, ctx->in[0], stage) || (pcm_bytes > chunk && !staging_reserve(ctx, ctx->in[1], stage))) break;
     uint8_t *d_in = static_cast<uint8_t *>(ctx->d_rc_in), *d_out = static_cast<uint8_t *>(ctx->d_rc_out);
 
-    /* the rows of streams [a, b) that fall into bytes [lo, hi) of the flat PCM block <-> host block `base` (which holds byte lo at 0) */
-    auto rows = [&](uint32_t a, uint32_t b, uint64_t lo, uint64_t hi, uint8_t *base, bool up) {
-      for (uint32_t i = a; i < b; i++) {
-        const uint64_t r0 = byte_prefix[i], r1 = r0 + (uint64_t)num_samples[i] * ch * sizeof(int16_t);
-        const uint64_t c0 = r0 > lo ? r0 : lo, c1 = r1 < hi ? r1 : hi;
-        if (c1 <= c0) continue;
-        if (up) memcpy(base + (c0 - lo), reinterpret_cast<const uint8_t *>(pcm[i]) + (c0 - r0), (size_t)(c1 - c0));
-        else memcpy(reinterpret_cast<uint8_t *>(out_pcm[i]) + (c0 - r0), base + (c0 - lo), (size_t)(c1 - c0));
-      }
-    };
-    auto span = [&](uint64_t lo, uint64_t hi, uint32_t *a, uint32_t *b) { /* streams whose rows meet [lo, hi) */
-      *a = (uint32_t)(std::upper_bound(byte_prefix.begin(), byte_prefix.end(), lo) - byte_prefix.begin());
-      *a = *a ? *a - 1 : 0;
-      *b = (uint32_t)(std::lower_bound(byte_prefix.begin(), byte_prefix.end(), hi) - byte_prefix.begin());
-      if (*b > count) *b = count;
+    /* the rows of the streams that fall into bytes [lo, hi) of the flat PCM block <-> host block `base` (which holds byte lo at 0) */
+    auto rows = [&](uint64_t lo, uint64_t hi, uint8_t *base, bool up) {
+      uint32_t a, b;
+      row_span(byte_prefix, lo, hi, &a, &b);
+      staged_span(ctx, a, b, byte_prefix, [&](uint32_t x, uint32_t y) {
+        for (uint32_t i = x; i < y; i++) {
+          const uint64_t r0 = byte_prefix[i], r1 = r0 + (uint64_t)num_samples[i] * ch * sizeof(int16_t);
+          const uint64_t c0 = r0 > lo ? r0 : lo, c1 = r1 < hi ? r1 : hi;
+          if (c1 <= c0) continue;
+          if (up) memcpy(base + (c0 - lo), reinterpret_cast<const uint8_t *>(pcm[i]) + (c0 - r0), (size_t)(c1 - c0));
+          else memcpy(reinterpret_cast<uint8_t *>(out_pcm[i]) + (c0 - r0), base + (c0 - lo), (size_t)(c1 - c0));
+        }
+      });
     };
 
-    /* ---- up: chunk k is filled while chunk k - 1 is on the bus ---- */
-    bool ok = true;
-    uint32_t k = 0;
-    for (uint64_t lo = 0; lo < pcm_bytes && ok; lo += chunk, k++) {
-      const uint64_t hi = lo + chunk < pcm_bytes ? lo + chunk : pcm_bytes;
-      Staging &st = ctx->in[k & 1];
-      if (k >= 2) ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[k & 1]), "hipEventSynchronize"); /* the block's last copy has left it */
-      if (!ok) break;
-      uint32_t a, b;
-      span(lo, hi, &a, &b);
-      uint8_t *host = static_cast<uint8_t *>(st.host);
-      staged_span(ctx, a, b, byte_prefix, [&](uint32_t x, uint32_t y) { rows(x, y, lo, hi, host, true); });
-      ok = hip_ok(ctx, hipMemcpyAsync(d_in + lo, host, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream), "H2D pcm") &&
-           hip_ok(ctx, hipEventRecord(ctx->chunk_done[k & 1], ctx->stream), "hipEventRecord");
-    }
-    if (!ok) break;
+    /* ---- up: the flat PCM block ---- */
+    if (!stage_up(ctx, d_in, pcm_bytes, chunk, "H2D pcm", [&](uint64_t lo, uint64_t hi, uint8_t *host) { rows(lo, hi, host, true); })) break;
 
     /* ---- compute: one run over the whole wave ---- */
     rc = AADHip_ReconstructPlanRun(plan, reinterpret_cast<const int16_t *>(d_in), static_cast<uint8_t *>(ctx->d_scratch),
@@ -2320,44 +2254,16 @@ AADApiResult reconstruct_wave(AADHipContext *ctx, const struct AADEncodeParamete
     if (rc != AAD_APIRESULT_OK) break;
     rc = AAD_APIRESULT_NG;
 
-    /* ---- down: [PCM (if wanted) | statistics] as one flat range; chunk k - 1 is scattered while chunk k is on the bus.
-     * Statistics only: nothing but 24 bytes per stream comes back. ---- */
+    /* ---- down: [PCM (if wanted) | statistics] as one flat range.  Statistics only: nothing but 24 bytes per stream comes back. ---- */
     const uint64_t down_lo = out_pcm ? 0 : stats_off, down_hi = stats ? out_bytes : (out_pcm ? pcm_bytes : down_lo);
-    if (down_hi > down_lo) {
-      const size_t dstage = (size_t)(down_hi - down_lo) < chunk ? (size_t)(down_hi - down_lo) + 64 : chunk;
-      if (!staging_reserve(ctx, ctx->out[0], dstage) || (down_hi - down_lo > chunk && !staging_reserve(ctx, ctx->out[1], dstage))) break;
-      auto scatter = [&](uint32_t kk, uint64_t lo, uint64_t hi) { /* host block kk & 1 holds bytes [lo, hi) of the output block */
-        uint8_t *host = static_cast<uint8_t *>(ctx->out[kk & 1].host);
-        if (out_pcm && lo < pcm_bytes) {
-          const uint64_t ph = hi < pcm_bytes ? hi : pcm_bytes;
-          uint32_t a, b;
-          span(lo, ph, &a, &b);
-          staged_span(ctx, a, b, byte_prefix, [&](uint32_t x, uint32_t y) { rows(x, y, lo, ph, host, false); });
-        }
-        if (stats && hi > stats_off) {
-          const uint64_t s0 = lo > stats_off ? lo : stats_off;
-          memcpy(reinterpret_cast<uint8_t *>(stats) + (s0 - stats_off), host + (s0 - lo), (size_t)(hi - s0));
-        }
-      };
-      uint64_t prev_lo = 0, prev_hi = 0;
-      bool have_prev = false;
-      k = 0;
-      for (uint64_t lo = down_lo; lo < down_hi && ok; lo += chunk, k++) {
-        const uint64_t hi = lo + chunk < down_hi ? lo + chunk : down_hi;
-        ok = hip_ok(ctx, hipMemcpyAsync(ctx->out[k & 1].host, d_out + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream), "D2H block") &&
-             hip_ok(ctx, hipEventRecord(ctx->chunk_done[k & 1], ctx->stream), "hipEventRecord");
-        if (ok && have_prev) { /* the other block: its copy was queued one round ago */
-          ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[(k - 1) & 1]), "hipEventSynchronize");
-          if (ok) scatter(k - 1, prev_lo, prev_hi);
-        }
-        prev_lo = lo, prev_hi = hi, have_prev = true;
+    const bool down = stage_down(ctx, d_out, down_lo, down_hi, chunk, [&](uint64_t lo, uint64_t hi, uint8_t *host) {
+      if (out_pcm && lo < pcm_bytes) rows(lo, hi < pcm_bytes ? hi : pcm_bytes, host, false);
+      if (stats && hi > stats_off) {
+        const uint64_t s0 = lo > stats_off ? lo : stats_off;
+        memcpy(reinterpret_cast<uint8_t *>(stats) + (s0 - stats_off), host + (s0 - lo), (size_t)(hi - s0));
       }
-      if (ok && have_prev) {
-        ok = hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[(k - 1) & 1]), "hipEventSynchronize");
-        if (ok) scatter(k - 1, prev_lo, prev_hi);
-      }
-      if (!ok) break;
-    }
+    });
+    if (!down) break;
     if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync")) break;
     rc = AAD_APIRESULT_OK;
   } while (0);
@@ -2372,21 +2278,17 @@ AADApiResult reconstruct_batch(AADHipContext *ctx, const struct AADEncodeParamet
                                const uint32_t *num_samples, int32_t output_kind, int16_t *const *out_pcm, struct AADHipErrorStats *stats)
 {
   if (num_streams == 0) return AAD_APIRESULT_OK;
-  const uint32_t ch = parameter->num_channels;
-  std::vector<uint64_t> footprint(num_streams);
-  for (uint32_t i = 0; i < num_streams; i++) { /* the whole batch is validated before the first wave runs */
+  for (uint32_t i = 0; i < num_streams; i++)
     if (pcm[i] == nullptr || (out_pcm != nullptr && out_pcm[i] == nullptr)) return AAD_APIRESULT_INVALID_ARGUMENT;
-    const uint64_t size = AADHip_CalculateEncodedSize(parameter, num_samples[i]);
-    if (size == 0) return AAD_APIRESULT_INVALID_FORMAT;
-    footprint[i] = reconstruct_footprint(num_samples[i], ch, size);
-  }
+  AADHeaderInfo h; /* the whole batch is validated before the first wave runs */
+  std::vector<uint64_t> sizes, footprint(num_streams);
+  const AADApiResult checked = host_encode_check(parameter, num_streams, num_samples, nullptr, &h, &sizes);
+  if (checked != AAD_APIRESULT_OK) return checked;
+  for (uint32_t i = 0; i < num_streams; i++) footprint[i] = reconstruct_footprint(num_samples[i], h.num_channels, sizes[i]);
   if (segmentation != nullptr) { /* the plans of the waves count chains per wave; the batch's count is refused up front */
-    AADHeaderInfo h; /* valid: CalculateEncodedSize took it */
-    (void)AADFormat_ParameterToHeader(parameter, 1, AAD_HIP_MAX_NUM_CHANNELS, &h);
-    uint64_t chains = 0;
-    for (uint32_t i = 0; i < num_streams; i++)
-      chains += (aad::stream_blocks(num_samples[i], h.num_samples_per_block) + segmentation->segment_blocks - 1) / segmentation->segment_blocks;
-    if (chains > UINT32_MAX) {
+    std::vector<AADHipStreamDesc> streams(num_streams);
+    for (uint32_t i = 0; i < num_streams; i++) streams[i] = AADHipStreamDesc{0, 0, 0, num_samples[i], 0};
+    if (aad::segment_chain_count(streams.data(), num_streams, h.num_samples_per_block, segmentation->segment_blocks) > UINT32_MAX) {
       snprintf(ctx->last_error, sizeof(ctx->last_error), "segmented reconstruction: more than %u chains", (unsigned)UINT32_MAX);
       return AAD_APIRESULT_INVALID_ARGUMENT;
     }

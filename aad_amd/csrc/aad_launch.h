@@ -31,23 +31,14 @@ void launch_decode_tiled(const DecodeArgs &args, const DecodeLaunch &p, hipStrea
 /* aad_decode_window.hip: the window decoder (AADHip_WindowDecodePlanRun), int16 or float32 rows */
 struct WindowArgs;
 void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
-/* aad_encode_planar.hip (compiled once per sample type): the planar-input encoders (AADHip_PlanarEncodePlanRun); segmented: args.chains
- * holds a chain table, as for the interleaved kernels */
-struct EncodeArgs;
-void launch_encode_planar_i16(const EncodeArgs &args, uint64_t channel_stride, const EncodeLaunch &p, bool segmented, hipStream_t stream);
-void launch_encode_planar_f32(const EncodeArgs &args, uint64_t channel_stride, const EncodeLaunch &p, bool segmented, hipStream_t stream);
-/* aad_encode_reconstruct.hip (compiled once per input x output sample type): the planar reconstruct encoders
- * (AADHip_PlanarReconstructPlanRun) - the planar encoders that also write the decoded rows.  base: per stream (segmented: per chain)
- * the element of `out` that holds channel 0's sample of the lane's first frame, device memory */
+/* the decoded rows of a planar reconstruct run (AADHip_PlanarReconstructPlanRun; launched through aad_encode_launch.hip.h).
+ * base: per stream (segmented: per chain) the element of `out` that holds channel 0's sample of the lane's first frame, device
+ * memory */
 struct RecRows {
   void *out;
   const uint64_t *base;
   uint64_t channel_stride;
 };
-void launch_reconstruct_i16_i16(const EncodeArgs &args, uint64_t channel_stride, const RecRows &out, const EncodeLaunch &p, bool segmented, hipStream_t stream);
-void launch_reconstruct_i16_f32(const EncodeArgs &args, uint64_t channel_stride, const RecRows &out, const EncodeLaunch &p, bool segmented, hipStream_t stream);
-void launch_reconstruct_f32_i16(const EncodeArgs &args, uint64_t channel_stride, const RecRows &out, const EncodeLaunch &p, bool segmented, hipStream_t stream);
-void launch_reconstruct_f32_f32(const EncodeArgs &args, uint64_t channel_stride, const RecRows &out, const EncodeLaunch &p, bool segmented, hipStream_t stream);
 }
 
 #define AAD_LAUNCH(kernel, grid, block, lds, stream, ...)                                                           \

@@ -79,6 +79,27 @@ inline bool build_segment_chains(const AADHipStreamDesc *streams, uint32_t num_s
   return true;
 }
 
+/* Where the lanes of a planar reconstruct plan (AADHip_PlanarReconstructPlanCreate) start in its output: per lane the element that
+ * holds channel 0's sample of the lane's first frame, stream i's rows starting stream_stride * i elements in.  chains == null: the
+ * lanes are the streams.  Else they are the table's chains, and the table's own records say where each starts, as for the waves
+ * below: a chain's stream (its one writes_header chain opens it) and its first frame (first_block, the first warm-up block if any). */
+inline std::vector<uint64_t> reconstruct_output_bases(uint32_t num_streams, uint64_t stream_stride, const std::vector<ChainDesc> *chains,
+                                                      uint32_t spb)
+{
+  std::vector<uint64_t> base;
+  if (chains == nullptr) {
+    for (uint32_t i = 0; i < num_streams; i++) base.push_back((uint64_t)i * stream_stride);
+    return base;
+  }
+  uint64_t stream = 0;
+  for (size_t c = 0; c < chains->size(); c++) {
+    const ChainDesc &d = (*chains)[c];
+    if (d.writes_header && c != 0) stream++;
+    base.push_back(stream * stream_stride + d.first_block * spb);
+  }
+  return base;
+}
+
 /* ---- waves of the host-memory path (AADHip_SegmentedEncodeBatch) ----------------------------------------------------------------
  *
  * A wave is a run of consecutive chains of the batch's chain table that is resident on the device at once and encoded by ONE launch,

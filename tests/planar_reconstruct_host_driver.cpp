@@ -4,12 +4,16 @@
  *              plan_reconstruct_encode and plan_encode pick the dual trial search and the byte ring over a sweep of batches,
  *              lane mappings and trial-lane / ring settings
  *   output  -> for each line "<channels> <type> <reserved> <stream_stride> <channel_stride> <n> <num_samples> ..." on stdin:
- *              "ok" or "refused" from planar_output_ok */
+ *              "ok" or "refused" from planar_output_ok
+ *   bases   -> for each line "<spb> <segment_blocks> <warmup_blocks> <stream_stride> <n> <num_samples> ..." on stdin: the plan's
+ *              per-lane output bases (reconstruct_output_bases over the chain table of build_segment_chains; segment_blocks 0: an
+ *              unsegmented plan, one lane per stream), space-separated on one line */
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "aad_launch_policy.h"
+#include "aad_segments.h"
 
 static int policy()
 {
@@ -60,10 +64,30 @@ static int output()
   return 0;
 }
 
+static int bases()
+{
+  unsigned spb, L, W, n;
+  unsigned long long ss;
+  while (scanf("%u %u %u %llu %u", &spb, &L, &W, &ss, &n) == 5) {
+    std::vector<AADHipStreamDesc> streams(n);
+    for (unsigned i = 0; i < n; i++) {
+      unsigned samples;
+      if (scanf("%u", &samples) != 1) return 1;
+      streams[i] = AADHipStreamDesc{0, 0, 0, samples, 0};
+    }
+    std::vector<aad::ChainDesc> chains;
+    if (L != 0 && !aad::build_segment_chains(streams.data(), n, 2, spb, 64, L, W, &chains, true)) return 1;
+    for (uint64_t b : aad::reconstruct_output_bases(n, ss, L != 0 ? &chains : nullptr, spb)) printf("%llu ", (unsigned long long)b);
+    printf("\n");
+  }
+  return 0;
+}
+
 int main(int argc, char **argv)
 {
   if (argc == 2 && !strcmp(argv[1], "policy")) return policy();
   if (argc == 2 && !strcmp(argv[1], "output")) return output();
-  fprintf(stderr, "usage: policy | output\n");
+  if (argc == 2 && !strcmp(argv[1], "bases")) return bases();
+  fprintf(stderr, "usage: policy | output | bases\n");
   return 2;
 }

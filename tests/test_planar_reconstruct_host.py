@@ -1,8 +1,9 @@
 """Planar reconstruct on the CPU (include/aad_hip.h "planar reconstruct"): the library exports the two entry points, the launch
 policy never plans the dual trial search or the byte ring for a reconstruct plan (aad_amd/csrc/aad_launch_policy.h
 plan_reconstruct_encode - the kernels that write the decoded rows exist for neither), and the output-layout check
-(planar_output_ok) refuses overlapping rows, bad fields and 64-bit overflow, through tests/planar_reconstruct_host_driver.cpp built
-with g++ against the policy header."""
+(planar_output_ok) refuses overlapping rows, bad fields and 64-bit overflow, and a plan's per-lane output bases
+(aad_amd/csrc/aad_segments.h reconstruct_output_bases), read off the chain table, are where the segment arithmetic puts them,
+through tests/planar_reconstruct_host_driver.cpp built with g++ against the policy and segment headers."""
 import os
 import subprocess
 
@@ -76,3 +77,33 @@ def test_output_layout_refuses_64_bit_overflow(driver):
     assert check(driver, cases) == ["refused"] * len(cases)
     ok = [(2, I16, 0, 200, (1 << 62) - 200, [100]), (2, I16, 0, (1 << 62), 100, [100, 100])]
     assert check(driver, ok) == ["ok", "ok"]
+
+
+def test_output_bases_follow_the_chain_table(driver):
+    """Lane (i, s) - stream i, segment s of L blocks with W warm-up blocks - writes its first frame, warm-up included, at
+    i * stream_stride + (s L - min(W, s L)) * spb; the segment arithmetic is written out here, the library reads the chain table."""
+    batches = [[1], [5], [63], [64], [65], [1000], [64 * 7], [64 * 7 + 1],
+               [3, 700, 64, 1, 129, 5000, 64 * 12],          # ragged, streams shorter than a block among them
+               [10, 20, 30], [4097] * 4]
+    cases = []
+    for spb in (64, 100):
+        for L in (1, 2, 3, 8, 1000):
+            for W in (0, 1, 2, 5, 9, 2000):                  # W = 0, W < L, W = L, W > L
+                for ns in batches:
+                    cases.append((spb, L, W, max(ns) + 17, ns))
+        for ns in batches:
+            cases.append((spb, 0, 0, max(ns), ns))           # unsegmented: one lane per stream
+    assert any(W > L for _, L, W, _, _ in cases) and any(min(ns) < spb for spb, _, _, _, ns in cases)
+    lines = ["%d %d %d %d %d %s" % (spb, L, W, ss, len(ns), " ".join(str(v) for v in ns)) for spb, L, W, ss, ns in cases]
+    out = subprocess.run([driver, "bases"], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(out) == len(cases)
+    for (spb, L, W, ss, ns), line in zip(cases, out):
+        want = []
+        for i, n in enumerate(ns):
+            if L == 0:
+                want.append(i * ss)
+                continue
+            blocks = -(-n // spb)
+            for s in range(-(-blocks // L)):
+                want.append(i * ss + (s * L - min(W, s * L)) * spb)
+        assert [int(v) for v in line.split()] == want, (spb, L, W, ss, ns)
