@@ -58,6 +58,10 @@ class AADHipPlanarOutput(C.Structure):  # include/aad_hip.h
     _fields_ = [("sample_type", C.c_int32), ("reserved", C.c_uint32), ("stream_stride", C.c_uint64), ("channel_stride", C.c_uint64)]
 
 
+class AADHipRowStats(C.Structure):  # include/aad_hip.h: one row of a torch int64 [N, C, 4] tensor
+    _fields_ = [("sum_sq", C.c_uint64), ("sum_abs", C.c_uint64), ("max_abs", C.c_uint64), ("count", C.c_uint64)]
+
+
 class AADHipLaneState(C.Structure):  # include/aad_hip.h
     _fields_ = [("weight", C.c_int32 * 4), ("history", C.c_int32 * 4),
                 ("stepsize_index", C.c_int32), ("quantize_error", C.c_int32)]
@@ -94,7 +98,7 @@ HIP_SYMBOLS = [
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
-    "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun",
+    "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -176,6 +180,8 @@ def _declare_hip(lib):
     lib.AADHip_PlanarReconstructPlanCreate.restype = C.c_int
     lib.AADHip_PlanarReconstructPlanRun.argtypes = [vp, vp, vp, vp, vp]
     lib.AADHip_PlanarReconstructPlanRun.restype = C.c_int
+    lib.AADHip_PlanarReconstructPlanRunStats.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.AADHip_PlanarReconstructPlanRunStats.restype = C.c_int
     lib.AADHip_EncodePlanDestroy.argtypes = [vp]
     lib.AADHip_EncodePlanDestroy.restype = None
     lib.AADHip_EncodePlanRun.argtypes = [vp, vp, vp, vp]

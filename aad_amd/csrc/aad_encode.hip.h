@@ -367,7 +367,11 @@ template <int IN> using EncodeArgsFor = std::conditional_t<IN == kInInterleaved,
  * value clip16(qd + p) of every coded sample, the header's history for a block's first four, and clip16(M + S), clip16(M - S)
  * with M/S.  So the encode pass writes the rows as it goes; the trial search's measuring passes and a segmented chain's warm-up
  * blocks (kPassRmse) write nothing. */
-enum RecOutput { kRecNone = 0, kRecI16 = 1, kRecF32 = 2 };
+enum RecOutput { kRecNone = 0, kRecI16 = 1, kRecF32 = 2, kRecI16Stats = 3, kRecF32Stats = 4, kRecStatsOnly = 5 };
+/* kRec...Stats / kRecStatsOnly (AADHip_PlanarReconstructPlanRunStats): the rows as above (kRecStatsOnly: no rows), and per row the
+ * exact error statistics of include/aad_hip.h "Planar reconstruct statistics" (RecRowStats below) */
+constexpr bool rec_has_stats(int rec) { return rec >= kRecI16Stats; }
+constexpr int rec_rows(int rec) { return rec == kRecI16Stats ? kRecI16 : (rec == kRecF32Stats ? kRecF32 : (rec == kRecStatsOnly ? kRecNone : rec)); }
 
 /* the reconstruct kernels' arguments: the output rows on top of the planar input's */
 struct RecEncodeArgs : PlanarEncodeArgs {
@@ -375,7 +379,13 @@ struct RecEncodeArgs : PlanarEncodeArgs {
   const uint64_t *out_base;    /* per stream (SEG: per chain) the element of `out` that holds channel 0's sample of the lane's frame 0 */
   uint64_t out_channel_stride; /* elements from one channel's row to the next */
 };
-template <int IN, int REC> using KernelArgsFor = std::conditional_t<REC == kRecNone, EncodeArgsFor<IN>, RecEncodeArgs>;
+/* the statistics kernels' arguments, derived once more: the three structs above keep their layout */
+struct StatsEncodeArgs : RecEncodeArgs {
+  AADHipRowStats *stats;        /* [streams][channels] records */
+  const uint32_t *stats_stream; /* SEG: per chain the index of its stream; else null (the lanes are the streams) */
+};
+template <int IN, int REC>
+using KernelArgsFor = std::conditional_t<REC == kRecNone, EncodeArgsFor<IN>, std::conditional_t<rec_has_stats(REC), StatsEncodeArgs, RecEncodeArgs>>;
 
 struct NoRec {
   static constexpr bool kOn = false;
@@ -429,7 +439,11 @@ struct RecRow {
     int32_t v[kChunk];
 #pragma unroll
     for (int j = 0; j < kChunk; j++) v[j] = decoded(y[j]);
-    T *p = row + f;
+    store_chunk(row + f, v);
+  }
+  /* sixteen decoded samples from p on */
+  __device__ __forceinline__ static void store_chunk(T *p, const int32_t *v)
+  {
     if constexpr (REC == kRecF32) {
 #pragma unroll
       for (int q = 0; q < 4; q++)
@@ -454,6 +468,7 @@ struct RecRow {
     }
   }
 };
+
 __device__ __forceinline__ int32_t newest_sample(const Lane &L) { return L.h0; }
 __device__ __forceinline__ int32_t newest_sample(const QuadLane &Q) { return Q.h; } /* (in tap 0) */
 
@@ -638,6 +653,150 @@ template <int CHF>
 __device__ __forceinline__ const int16_t *lane_row(const int16_t *x, uint32_t c) { return x + (CHF == 2 ? c : 0); }
 template <int CHF, typename T>
 __device__ __forceinline__ const T *lane_row(const PlanarRows<T> &x, uint32_t c) { return x.row(c); }
+
+/* RecRow that also accounts for every sample it stores (AADHip_PlanarReconstructPlanRunStats): e = q(x) - v, x the lane's input
+ * sample at the store position and v the decoded one, into sum e^2, sum |e| and max |e|.  REC = kRecStatsOnly stores nothing.  The
+ * interface is RecRow's, so run_block and the kernel call it at the same places - which are all the places a sample is stored -
+ * and the accumulators are mutable because run_block holds its rec as a pointer to const.
+ * The input sample is read again from the lane's row (the lines are in L2: the chunk loads fetched them a chunk or two ago), so
+ * the chunk bodies and their register sets stay as they are.  All sums are exact integers, so no order matters: the quad
+ * mapping's whole chunks are accounted for one call late (pend), when the loads issued at the previous call have long landed -
+ * a lone wave would otherwise wait out an L2 round trip per chunk.  TIN: int16_t or float (q = pcm_value). */
+template <int REC, bool MS, bool QUAD, typename TIN>
+struct RecRowStats {
+  static constexpr bool kOn = true;
+  static constexpr bool kStore = REC != kRecStatsOnly;
+  using Rows = RecRow<kStore ? rec_rows(REC) : kRecI16, MS, QUAD>;
+  using T = typename Rows::T;
+  T *row;
+  const TIN *in; /* the lane's input row, from the lane's frame 0 on */
+  uint32_t c, tap;
+  mutable uint64_t sum_sq, sum_abs;
+  mutable uint32_t max_abs;
+  mutable TIN pend_x[QUAD ? 4 : 1];
+  mutable int32_t pend_v[QUAD ? 4 : 1];
+  __device__ __forceinline__ void init(T *row_, const TIN *in_, uint32_t c_, uint32_t tap_)
+  {
+    row = row_;
+    in = in_;
+    c = c_;
+    tap = tap_;
+    sum_sq = sum_abs = 0;
+    max_abs = 0;
+    for (auto &x : pend_x) x = 0;
+    for (auto &v : pend_v) v = 0;
+  }
+  __device__ __forceinline__ int32_t decoded(int32_t y) const { return Rows{nullptr, c, tap}.decoded(y); }
+  /* |e| <= 65535: the square fits 32 bits, the sums 64 for any stream the format allows (include/aad_hip.h) */
+  __device__ __forceinline__ void add(uint32_t ae) const
+  {
+    sum_sq += (uint64_t)ae * ae; /* v_mad_u64_u32 */
+    sum_abs += ae;
+    max_abs = max(max_abs, ae);
+  }
+  __device__ __forceinline__ static uint32_t abs_error(TIN x, int32_t v)
+  {
+    const int32_t e = pcm_value(x) - v;
+    return (uint32_t)(e < 0 ? -e : e);
+  }
+  __device__ __forceinline__ void header(uint64_t first, uint32_t n, const Lane &F) const
+  {
+    const int32_t h[kTaps] = {F.h3, F.h2, F.h1, F.h0};
+#pragma unroll
+    for (int k = 0; k < kTaps; k++) {
+      const int32_t v = decoded(h[k]);
+      if ((uint32_t)k < n && (!QUAD || tap == (uint32_t)k)) {
+        if constexpr (kStore) row[first + k] = Rows::convert(v);
+        add(abs_error(in[first + k], v));
+      }
+    }
+  }
+  __device__ __forceinline__ void one(uint64_t f, int32_t y, bool real) const
+  {
+    const int32_t v = decoded(y);
+    if (real && (!QUAD || tap == 0u)) {
+      if constexpr (kStore) row[f] = Rows::convert(v);
+      add(abs_error(in[f], v));
+    }
+  }
+  __device__ __forceinline__ void chunk(uint64_t f, const int32_t *y) const
+  {
+    PlanarRaw<TIN> x;
+    x.load(in + f);
+    int32_t v[kChunk];
+#pragma unroll
+    for (int j = 0; j < kChunk; j++) v[j] = decoded(y[j]);
+    if constexpr (kStore) Rows::store_chunk(row + f, v);
+#pragma unroll
+    for (int j = 0; j < kChunk; j++) {
+      const int32_t e = x.sample(j) - v[j];
+      add((uint32_t)(e < 0 ? -e : e));
+    }
+  }
+  template <int G>
+  __device__ __forceinline__ void quad(uint64_t f, const int32_t *yq) const
+  {
+    if constexpr (G == 4) flush();
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      const int32_t v = decoded(yq[g]);
+      const uint64_t at = f + 4 * g + 3 - tap;
+      if constexpr (kStore) row[at] = Rows::convert(v);
+      if constexpr (G == 4) {
+        pend_x[g] = in[at];
+        pend_v[g] = v;
+      } else {
+        add(abs_error(in[at], v));
+      }
+    }
+  }
+  /* the samples a whole-chunk quad() call left pending (zeros - no error - before the first one) */
+  __device__ __forceinline__ void flush() const
+  {
+    if constexpr (QUAD) {
+#pragma unroll
+      for (int g = 0; g < 4; g++) add(abs_error(pend_x[g], pend_v[g]));
+      for (auto &x : pend_x) x = 0;
+      for (auto &v : pend_v) v = 0;
+    }
+  }
+  /* The end of the lane's run: its row's record.  Quad: every tap lane holds its own quarter of the row - summed over the four
+   * lanes with DPP (quad_sum's rotations), then tap 0 writes.  accumulate: several lanes feed the record (the chains of a
+   * segmented plan) - vector atomics into the table the run has zeroed; else the lane owns the record: plain stores. */
+  template <bool ACCUMULATE>
+  __device__ __forceinline__ void finish(AADHipRowStats *record, uint64_t count) const
+  {
+    flush();
+    uint64_t sq = sum_sq, ab = sum_abs;
+    uint32_t mx = max_abs;
+    if constexpr (QUAD) {
+      static_assert(kEncTM, "the rotations below are the tap-major layout's");
+      auto rot = [](uint64_t v, auto ctrl) {
+        return (uint64_t)quad_dpp<decltype(ctrl)::value>((uint32_t)v) | (uint64_t)quad_dpp<decltype(ctrl)::value>((uint32_t)(v >> 32)) << 32;
+      };
+      using R4 = std::integral_constant<int, kDppRowRor4>;
+      using R8 = std::integral_constant<int, kDppRowRor8>;
+      sq += rot(sq, R4{});
+      sq += rot(sq, R8{});
+      ab += rot(ab, R4{});
+      ab += rot(ab, R8{});
+      mx = max(mx, quad_dpp<kDppRowRor4>(mx));
+      mx = max(mx, quad_dpp<kDppRowRor8>(mx));
+      if (tap != 0u) return;
+    }
+    if constexpr (ACCUMULATE) {
+      atomicAdd(reinterpret_cast<unsigned long long *>(&record->sum_sq), (unsigned long long)sq);
+      atomicAdd(reinterpret_cast<unsigned long long *>(&record->sum_abs), (unsigned long long)ab);
+      atomicMax(reinterpret_cast<unsigned long long *>(&record->max_abs), (unsigned long long)mx);
+      atomicAdd(reinterpret_cast<unsigned long long *>(&record->count), (unsigned long long)count);
+    } else {
+      typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8))); /* the table is 8-byte aligned (host-checked) */
+      u32x4_a8 *p = reinterpret_cast<u32x4_a8 *>(record);
+      p[0] = u32x4_a8{(uint32_t)sq, (uint32_t)(sq >> 32), (uint32_t)ab, (uint32_t)(ab >> 32)};
+      p[1] = u32x4_a8{mx, 0u, (uint32_t)count, (uint32_t)(count >> 32)};
+    }
+  }
+};
 
 template <typename Src>
 __device__ __forceinline__ void seed_history(Lane &L, const Src &src, uint64_t first, uint32_t n)
@@ -1977,9 +2136,15 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(KernelArgsFor<IN, R
   const SampleSource<MS, IN> src = {x0, ch, c, sd.num_samples};
   uint8_t *out = a.data + sd.data_offset;
   const uint32_t total = sd.num_samples, spb = a.samples_per_block;
-  using Rec = std::conditional_t<REC == kRecNone, NoRec, RecRow<REC, MS, QUAD>>;
+  using Rec = std::conditional_t<REC == kRecNone, NoRec,
+                                 std::conditional_t<rec_has_stats(REC), RecRowStats<REC, MS, QUAD, PcmElem<IN>>, RecRow<rec_rows(REC), MS, QUAD>>>;
   [[maybe_unused]] Rec rec;
-  if constexpr (REC != kRecNone) {
+  if constexpr (rec_has_stats(REC)) {
+    typename Rec::T *row = nullptr;
+    if constexpr (Rec::kStore) row = reinterpret_cast<typename Rec::T *>(a.out) + a.out_base[s] + (uint64_t)c * a.out_channel_stride;
+    if constexpr (IN == kInInterleaved) rec.init(row, x0, c, tap); /* mono */
+    else rec.init(row, x0.row(c), c, tap);
+  } else if constexpr (REC != kRecNone) {
     rec.row = reinterpret_cast<typename Rec::T *>(a.out) + a.out_base[s] + (uint64_t)c * a.out_channel_stride;
     rec.c = c;
     rec.tap = tap;
@@ -2091,6 +2256,10 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(KernelArgsFor<IN, R
     AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
   }
   if constexpr (RING) ring.finish(); /* the stream's last, incomplete sector */
+  if constexpr (rec_has_stats(REC)) { /* every frame behind the lead (SEG: behind the warm-up) went through rec exactly once */
+    if constexpr (SEG) rec.template finish<true>(a.stats + (uint64_t)a.stats_stream[s] * ch + c, total - warm_end);
+    else rec.template finish<false>(a.stats + lane, total > a.lead_frames ? total - a.lead_frames : 0u);
+  }
 
   if (!SEG && a.state_out && writer) {
     LaneStateRecord r;

@@ -1,7 +1,7 @@
 /* aad_encode_launch.hip.h - what one encode run is (EncodeRun) and the way from it and its launch plan (aad_launch_policy.h) to
  * an instantiation of encode_streams_kernel: launch_encode_run<IN, REC>, one instantiation per input layout IN and output REC
  * (aad_encode.hip.h).  aad_hip_engine.hip instantiates the interleaved kernels, aad_encode_planar.hip the planar ones,
- * aad_encode_reconstruct.hip the planar reconstruct ones (REC). */
+ * aad_encode_reconstruct.hip the planar reconstruct ones (REC), aad_encode_stats.hip those with statistics. */
 #ifndef AAD_ENCODE_LAUNCH_HIP_H
 #define AAD_ENCODE_LAUNCH_HIP_H
 
@@ -58,6 +58,9 @@ struct EncodeRun {
   uint64_t channel_stride = 0;   /* ... channel_stride elements apart */
   RecOutput rec = kRecNone;      /* the decoded rows of a planar reconstruct run: none, int16 or float32 ... */
   RecRows rows = {nullptr, nullptr, 0}; /* ... and where they go */
+  /* rec with statistics (rec_has_stats, AADHip_PlanarReconstructPlanRunStats): the table, and per chain of a chain table its stream */
+  AADHipRowStats *stats = nullptr;
+  const uint32_t *stats_stream = nullptr;
 };
 
 /* the layout that reads rows of a sample type (enum AADHipSampleType): mono int16 rows ARE interleaved frames, see above */
@@ -67,6 +70,8 @@ inline PcmLayout planar_layout(int32_t sample_type, uint32_t channels)
   return channels == 1 ? kInInterleaved : kInPlanarI16;
 }
 inline RecOutput rec_output(int32_t sample_type) { return sample_type == AAD_HIP_SAMPLE_FLOAT32 ? kRecF32 : kRecI16; }
+/* the same rows with the statistics table (rows == false: the table alone) */
+inline RecOutput rec_with_stats(RecOutput rec, bool rows) { return !rows ? kRecStatsOnly : (rec == kRecF32 ? kRecF32Stats : kRecI16Stats); }
 
 /* The kernels of one (IN, REC) by sample width and table kind.  r.in == IN and r.rec == REC: the caller has dispatched on them. */
 template <int IN, int REC>
@@ -79,6 +84,10 @@ void launch_encode_run(const EncodeRun &r, const EncodeLaunch &p, hipStream_t st
     a.out = r.rows.out;
     a.out_base = r.rows.base;
     a.out_channel_stride = r.rows.channel_stride;
+  }
+  if constexpr (rec_has_stats(REC)) {
+    a.stats = r.stats;
+    a.stats_stream = r.stats_stream;
   }
   auto by_bits = [&](auto seg) {
     constexpr bool SEG = decltype(seg)::value;
@@ -102,6 +111,15 @@ extern template void launch_encode_run<kInPlanarI16, kRecI16>(const EncodeRun &,
 extern template void launch_encode_run<kInPlanarI16, kRecF32>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
 extern template void launch_encode_run<kInPlanarF32, kRecI16>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
 extern template void launch_encode_run<kInPlanarF32, kRecF32>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+/* ... and the statistics kernels (aad_encode_stats.hip): one object per input sample type and kind of output */
+#define AAD_EXTERN_STATS_RUN(REC)                                                                                  \
+  extern template void launch_encode_run<kInInterleaved, REC>(const EncodeRun &, const EncodeLaunch &, hipStream_t); \
+  extern template void launch_encode_run<kInPlanarI16, REC>(const EncodeRun &, const EncodeLaunch &, hipStream_t);   \
+  extern template void launch_encode_run<kInPlanarF32, REC>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
+AAD_EXTERN_STATS_RUN(kRecI16Stats)
+AAD_EXTERN_STATS_RUN(kRecF32Stats)
+AAD_EXTERN_STATS_RUN(kRecStatsOnly)
+#undef AAD_EXTERN_STATS_RUN
 
 } /* namespace aad */
 

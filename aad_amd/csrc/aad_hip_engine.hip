@@ -118,6 +118,8 @@ struct AADHipEncodePlan { /* every field is set by encode_plan_create */
   aad::EncodeRun run;   /* all of a run but the caller's pointers (args.pcm / data / state / state_out, rows.out) */
   void *d_table;        /* run.args.streams, or run.args.chains of a segmented plan */
   uint64_t *d_out_base; /* Reconstruct: run.rows.base, else null */
+  uint32_t *d_stats_stream; /* Reconstruct, segmented: run.stats_stream, else null */
+  uint64_t stats_records;   /* Reconstruct: streams * channels, the records of a statistics table */
 };
 
 struct AADHipDecodePlan {
@@ -445,6 +447,9 @@ AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeRun &run)
     }
   };
   switch (r.rec) {
+    case aad::kRecStatsOnly: by_layout(std::integral_constant<int, aad::kRecStatsOnly>{}); break;
+    case aad::kRecF32Stats: by_layout(std::integral_constant<int, aad::kRecF32Stats>{}); break;
+    case aad::kRecI16Stats: by_layout(std::integral_constant<int, aad::kRecI16Stats>{}); break;
     case aad::kRecF32: by_layout(std::integral_constant<int, aad::kRecF32>{}); break;
     case aad::kRecI16: by_layout(std::integral_constant<int, aad::kRecI16>{}); break;
     case aad::kRecNone: by_layout(std::integral_constant<int, aad::kRecNone>{}); break;
@@ -517,6 +522,8 @@ AADApiResult encode_plan_create(AADHipContext *ctx, const struct AADEncodeParame
   p->kind = output != nullptr ? EncodePlanKind::Reconstruct : (layout != nullptr ? EncodePlanKind::Rows : EncodePlanKind::Frames);
   p->d_table = nullptr;
   p->d_out_base = nullptr;
+  p->d_stats_stream = nullptr;
+  p->stats_records = (uint64_t)num_streams * args.channels;
   DeviceGuard guard(ctx);
   bool ok = guard.ok;
   if (ok && segmentation != nullptr) {
@@ -537,9 +544,15 @@ AADApiResult encode_plan_create(AADHipContext *ctx, const struct AADEncodeParame
     run.rec = aad::rec_output(output->sample_type);
     run.rows = aad::RecRows{nullptr, p->d_out_base, output->channel_stride};
   }
+  if (ok && output != nullptr && segmentation != nullptr) { /* a statistics run's chains add into their stream's records */
+    const std::vector<uint32_t> of = aad::chain_streams(chains);
+    ok = upload(ctx, &p->d_stats_stream, of.data(), of.size());
+    run.stats_stream = p->d_stats_stream;
+  }
   if (!ok) {
     if (p->d_table) (void)hipFree(p->d_table);
     if (p->d_out_base) (void)hipFree(p->d_out_base);
+    if (p->d_stats_stream) (void)hipFree(p->d_stats_stream);
     delete p;
     return AAD_APIRESULT_NG;
   }
@@ -553,9 +566,10 @@ AADApiResult encode_plan_create(AADHipContext *ctx, const struct AADEncodeParame
 }
 
 /* Run a plan for the entry point that takes plans of `kind`.  samples: interleaved int16 frames (Frames), or rows that the kernels
- * read as the plan's sample type; out: the decoded rows, Reconstruct only. */
+ * read as the plan's sample type; out: the decoded rows, Reconstruct only.  with_stats (AADHip_PlanarReconstructPlanRunStats): the
+ * run also writes the statistics table `stats`, and `out` may be null. */
 AADApiResult encode_plan_run(AADHipEncodePlan *plan, EncodePlanKind kind, const void *samples, uint8_t *device_data, void *out,
-                             struct AADHipLaneState *device_state)
+                             struct AADHipLaneState *device_state, bool with_stats = false, struct AADHipRowStats *stats = nullptr)
 {
   if (plan == nullptr || samples == nullptr || device_data == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
   AADHipContext *ctx = plan->ctx;
@@ -566,13 +580,29 @@ AADApiResult encode_plan_run(AADHipEncodePlan *plan, EncodePlanKind kind, const 
   if (plan->run.chain_table && device_state != nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
   if (kind == EncodePlanKind::Reconstruct && out == samples) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
   if (plan->run.args.num_streams == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
-  if (kind == EncodePlanKind::Reconstruct && out == nullptr) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  if (kind == EncodePlanKind::Reconstruct && out == nullptr && !with_stats) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  if (with_stats && (stats == nullptr || (reinterpret_cast<uintptr_t>(stats) & 7u) != 0))
+    return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
   aad::EncodeRun r = plan->run;
   r.args.pcm = static_cast<const int16_t *>(samples);
   r.args.data = device_data;
   r.args.state = reinterpret_cast<const aad::LaneStateRecord *>(device_state);
   r.args.state_out = reinterpret_cast<aad::LaneStateRecord *>(device_state);
   r.rows.out = out;
+  if (with_stats) {
+    r.rec = aad::rec_with_stats(r.rec, out != nullptr);
+    r.stats = stats;
+  }
+  if (with_stats && r.chain_table) {
+    /* several chains add into a row's record: the table is cleared first, so the run is two device operations - the start event
+     * in front of the clear, the stop event on the kernel */
+    if (signal.start != nullptr && !hip_ok(ctx, hipEventRecord(signal.start, ctx->stream), "hipEventRecord")) return AAD_APIRESULT_NG;
+    if (!hip_ok(ctx, hipMemsetAsync(stats, 0, plan->stats_records * sizeof(struct AADHipRowStats), ctx->stream), "hipMemsetAsync"))
+      return AAD_APIRESULT_NG;
+    const aad::LaunchSignal stop_only = {nullptr, signal.stop};
+    aad::tl_launch_signal = stop_only;
+    return finish_signal(ctx, stop_only, run_encode(ctx, r));
+  }
   aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
   return finish_signal(ctx, signal, run_encode(ctx, r));
 }
@@ -838,6 +868,7 @@ void AADHip_EncodePlanDestroy(struct AADHipEncodePlan *plan)
     (void)hipStreamSynchronize(plan->ctx->stream);
     (void)hipFree(plan->d_table);
     (void)hipFree(plan->d_out_base);
+    (void)hipFree(plan->d_stats_stream);
   }
   delete plan;
 }
@@ -896,6 +927,13 @@ AADApiResult AADHip_PlanarReconstructPlanRun(struct AADHipEncodePlan *plan, cons
                                              void *device_out, struct AADHipLaneState *device_state)
 {
   return encode_plan_run(plan, EncodePlanKind::Reconstruct, device_samples, device_data, device_out, device_state);
+}
+
+AADApiResult AADHip_PlanarReconstructPlanRunStats(struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data,
+                                                  void *device_out, struct AADHipLaneState *device_state,
+                                                  struct AADHipRowStats *device_stats)
+{
+  return encode_plan_run(plan, EncodePlanKind::Reconstruct, device_samples, device_data, device_out, device_state, true, device_stats);
 }
 
 /* ------------------------------------------------------------------------------- decode -- */

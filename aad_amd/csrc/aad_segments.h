@@ -100,6 +100,19 @@ inline std::vector<uint64_t> reconstruct_output_bases(uint32_t num_streams, uint
   return base;
 }
 
+/* per chain of a table the index of its stream, by the same rule (the statistics of a segmented planar reconstruct run: the
+ * chains of a stream add into that stream's records) */
+inline std::vector<uint32_t> chain_streams(const std::vector<ChainDesc> &chains)
+{
+  std::vector<uint32_t> of;
+  uint32_t stream = 0;
+  for (size_t c = 0; c < chains.size(); c++) {
+    if (chains[c].writes_header && c != 0) stream++;
+    of.push_back(stream);
+  }
+  return of;
+}
+
 /* ---- waves of the host-memory path (AADHip_SegmentedEncodeBatch) ----------------------------------------------------------------
  *
  * A wave is a run of consecutive chains of the batch's chain table that is resident on the device at once and encoded by ONE launch,

@@ -271,23 +271,47 @@ class Engine:
         return out, [int(v) for v in sizes]
 
     def reconstruct_planar(self, x, param, num_samples=None, dtype=None, state=None, segment_blocks=None, warmup_blocks=0,
-                           return_images=False):
+                           return_images=False, return_stats=False):
         """x: int16 or float32 cuda tensor [N, C, T] (a view with x.stride(-1) == 1 is fine) -> a new contiguous [N, C, T] tensor of
         `dtype` (default x.dtype): x after the codec - row i is the decode of encode_planar's image of x[i, :, :num_samples[i]]
         (float32 output: decoded sample / 32768), zero past num_samples[i].  One kernel: the encoder writes the decoded rows as it
-        encodes.  return_images=True: (y, images, image_sizes) with images and sizes in encode_planar's layout."""
+        encodes.  return_images=True: (y, images, image_sizes) with images and sizes in encode_planar's layout.
+        return_stats=True appends the int64 [N, C, 4] tensor of exact per-row error statistics (sum_sq, sum_abs, max_abs, count of
+        q(x) - decoded sample in int16 units; include/aad_hip.h), accumulated by the same kernel: see rmse / snr_db."""
+        return self._reconstruct_planar("reconstruct_planar", x, param, num_samples, dtype, state, segment_blocks, warmup_blocks,
+                                        True, return_images, return_stats)
+
+    def codec_error(self, x, param, num_samples=None, state=None, segment_blocks=None, warmup_blocks=0):
+        """The statistics of reconstruct_planar(..., return_stats=True) alone - int64 [N, C, 4] - with no rows allocated or written."""
+        return self._reconstruct_planar("codec_error", x, param, num_samples, None, state, segment_blocks, warmup_blocks,
+                                        False, False, True)
+
+    def least_bits(self, x, make_param, min_snr_db, num_samples=None):
+        """Per stream the fewest bits per sample (2, 3 or 4) at which every channel keeps an SNR of at least min_snr_db, 0 where
+        none does: int64 cuda tensor [N].  make_param(bits) returns the AADEncodeParameter to try.  The signal power is that of
+        q(x), the int16 samples the encoder sees."""
+        torch = self.torch
+        n, _, t = (int(v) for v in x.shape)
+        lengths = torch.full((n,), t, dtype=torch.int64) if num_samples is None else torch.as_tensor(np.asarray(num_samples, dtype=np.int64))
+        q = x if x.dtype == torch.int16 else torch.nan_to_num(x, nan=0.0).mul(32768.0).round().clamp(-32768, 32767)
+        live = torch.arange(t, device=x.device)[None, None, :] < lengths.to(x.device)[:, None, None]
+        signal = (q.to(torch.float64) ** 2 * live).sum(-1)  # squares below 2^30, fewer than 2^23 of them per partial sum: exact
+        return select_least_bits([snr_db(self.codec_error(x, make_param(bits), num_samples), signal) for bits in (2, 3, 4)], min_snr_db)
+
+    def _reconstruct_planar(self, what, x, param, num_samples, dtype, state, segment_blocks, warmup_blocks, rows, return_images,
+                            return_stats):
         torch = self.torch
         if state is not None and segment_blocks is not None:
             raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
         if x.dim() != 3 or not x.is_cuda or x.dtype not in (torch.int16, torch.float32):
-            raise ValueError("reconstruct_planar takes an int16 or float32 cuda tensor [N, C, T]")
+            raise ValueError("%s takes an int16 or float32 cuda tensor [N, C, T]" % what)
         dtype = x.dtype if dtype is None else dtype
         n, ch, t = (int(v) for v in x.shape)
         if ch != param.num_channels:
             raise ValueError("x has %d channels, the parameter %d" % (ch, param.num_channels))
         if x.stride(-1) != 1:
-            raise ValueError("reconstruct_planar needs x.stride(-1) == 1 (each channel's samples contiguous); got strides %s - pass "
-                             "x.contiguous() if a copy is intended" % (tuple(x.stride()),))
+            raise ValueError("%s needs x.stride(-1) == 1 (each channel's samples contiguous); got strides %s - pass "
+                             "x.contiguous() if a copy is intended" % (what, tuple(x.stride())))
         lengths = np.full(n, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
         if len(lengths) != n or (n and (lengths.min() < 1 or lengths.max() > t)):
             raise ValueError("num_samples: %d lengths in [1, %d]" % (n, t))
@@ -301,15 +325,15 @@ class Engine:
         d["data_size"] = stride
         d["num_samples"] = lengths
         images = torch.zeros((n, stride), dtype=torch.uint8, device=x.device)
-        y = torch.zeros((n, ch, t), dtype=dtype, device=x.device)
+        y = torch.zeros((n, ch, t), dtype=dtype, device=x.device) if rows else None
+        stats = torch.empty((n, ch, 4), dtype=torch.int64, device=x.device) if return_stats else None  # every record is written
         plan = self.planar_reconstruct_plan(param, d, x.stride(1), x.dtype, dtype, ch * t, t, segment_blocks, warmup_blocks)
         try:
-            plan.run(x, images, y, state)
+            plan.run(x, images, y, state, stats=stats)
         finally:
             plan.close()  # synchronises the context's stream first
-        if return_images:
-            return y, images, [int(v) for v in sizes]
-        return y
+        result = ([y] if rows else []) + ([images, [int(v) for v in sizes]] if return_images else []) + ([stats] if return_stats else [])
+        return result[0] if len(result) == 1 else tuple(result)
 
     def decode_uniform(self, data, image_size):
         """data: uint8 cuda tensor [streams, stride] of same-format images -> int16 [streams, samples, channels]"""
@@ -448,6 +472,40 @@ class Engine:
         return pcms
 
 
+def _stats_f64(stats):
+    """the fields of an int64 [..., 4] statistics tensor as float64: int64 -> float64 directly, never through float32"""
+    import torch
+    if stats.dtype != torch.int64 or stats.shape[-1] != 4:
+        raise ValueError("stats: an int64 tensor [..., 4] (sum_sq, sum_abs, max_abs, count)")
+    return stats.to(torch.float64).unbind(-1)
+
+
+def rmse(stats):
+    """sqrt(sum_sq / count) per row of an int64 [..., 4] statistics tensor, float64, in int16 units; NaN for an empty row"""
+    sum_sq, _, _, count = _stats_f64(stats)
+    return (sum_sq / count).sqrt()
+
+
+def snr_db(stats, signal_sum_sq):
+    """10 log10(signal_sum_sq / sum_sq) per row, float64; signal_sum_sq: the rows' signal power in the same int16 units (sum of
+    squared samples, any integer or float dtype).  An empty row gives NaN, a zero error +inf."""
+    import torch
+    sum_sq, _, _, count = _stats_f64(stats)
+    signal = torch.as_tensor(signal_sum_sq, device=stats.device).to(torch.float64)
+    ratio = torch.where(sum_sq == 0, torch.full_like(sum_sq, float("inf")), signal / sum_sq)
+    return torch.where(count == 0, torch.full_like(sum_sq, float("nan")), 10.0 * ratio.log10())
+
+
+def select_least_bits(snr_by_bits, min_snr_db):
+    """snr_by_bits: the [N, C] SNR tensors of 2, 3 and 4 bits -> int64 [N]: the fewest bits at which every channel of a stream
+    reaches min_snr_db, 0 where none does (a NaN - an empty row - meets no bound)"""
+    import torch
+    best = torch.zeros(snr_by_bits[0].shape[0], dtype=torch.int64, device=snr_by_bits[0].device)
+    for bits, snr in reversed(list(zip((2, 3, 4), snr_by_bits))):
+        best = torch.where((snr >= min_snr_db).all(dim=-1), torch.full_like(best, bits), best)
+    return best
+
+
 class EncodePlan:
     def __init__(self, engine, handle, param, descs):
         self.engine, self.handle, self.param, self.descs = engine, handle, param, descs
@@ -504,19 +562,33 @@ class PlanarReconstructPlan(EncodePlan):
         super().__init__(engine, handle, param, descs)
         self.dtype, self.out_dtype = dtype, out_dtype
 
-    def run(self, x, data, out, state=None, ordered=True):
+    def run(self, x, data, out, state=None, ordered=True, stats=None):
         """x: cuda rows of the plan's dtype (the table's pcm_offsets count from x.data_ptr()), data: uint8 cuda tensor for the images,
-        out: cuda tensor of the plan's out_dtype (the output strides count from out.data_ptr()), state as EncodePlan.run"""
+        out: cuda tensor of the plan's out_dtype (the output strides count from out.data_ptr()), state as EncodePlan.run.
+        stats: a contiguous int64 cuda tensor [N, C, 4] that the same run fills with the rows' error statistics
+        (AADHip_PlanarReconstructPlanRunStats; its contents before the run do not matter); with it, out=None writes no rows."""
         if x.dtype != self.dtype or not x.is_cuda:
             raise ValueError("this plan reads %s cuda rows, not %s" % (self.dtype, x.dtype))
-        if out.dtype != self.out_dtype or not out.is_cuda:
+        if out is None and stats is None:
+            raise ValueError("out=None needs stats")
+        if out is not None and (out.dtype != self.out_dtype or not out.is_cuda):
             raise ValueError("this plan writes %s cuda rows, not %s" % (self.out_dtype, out.dtype))
+        if stats is not None:
+            torch = self.engine.torch
+            shape = (len(self.descs), self.param.num_channels, 4)
+            if stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous() or tuple(stats.shape) != shape:
+                raise ValueError("stats: a contiguous int64 cuda tensor %s" % (shape,))
         if state is not None and self.segmented:
             raise ValueError("a segmented encode plan takes no state")
         sp = state.data_ptr() if state is not None else None
         cur = self.engine._enter() if ordered else None
-        _check("AADHip_PlanarReconstructPlanRun",
-               self.engine.lib.AADHip_PlanarReconstructPlanRun(self.handle, x.data_ptr(), data.data_ptr(), out.data_ptr(), sp))
+        if stats is not None:
+            _check("AADHip_PlanarReconstructPlanRunStats",
+                   self.engine.lib.AADHip_PlanarReconstructPlanRunStats(self.handle, x.data_ptr(), data.data_ptr(),
+                                                                        out.data_ptr() if out is not None else None, sp, stats.data_ptr()))
+        else:
+            _check("AADHip_PlanarReconstructPlanRun",
+                   self.engine.lib.AADHip_PlanarReconstructPlanRun(self.handle, x.data_ptr(), data.data_ptr(), out.data_ptr(), sp))
         if ordered:
             self.engine._exit(cur)
 
@@ -717,4 +789,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "select_least_bits"]

@@ -71,7 +71,7 @@ const char *AADHip_ContextLastError(const struct AADHipContext *context);
 
 /* Cross-stream ordering and kernel timing without packets of their own.  `hip_start_event` / `hip_stop_event` (hipEvent_t the
  * caller owns; either may be NULL, both NULL withdraws) are recorded when the work of the NEXT AADHip_EncodePlanRun /
- * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
+ * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
  * the run takes them.  An encode, decode or window decode plan run is one kernel, and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
  * stop events) instead of on barrier packets around it: a hipEventRecord behind every launch of a back-to-back sequence costs
  * the queue 2.9 us per launch on MI355X, the attached event nothing (profiles/r03_microbench_event_gap.txt), and
@@ -315,6 +315,50 @@ AADApiResult AADHip_PlanarReconstructPlanCreate(
 AADApiResult AADHip_PlanarReconstructPlanRun(
     struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data, void *device_out,
     struct AADHipLaneState *device_state);
+
+/* ---- planar reconstruct statistics: exact per-row codec error from the same kernel ------------------------------------------- */
+
+/* "How large is the error, per row?" - answered by the kernel that holds both operands anyway.
+ *
+ * Definition.  For a planar reconstruct plan (any input / output sample type, segmentation, state), stream i, channel c < C and
+ * frame t < num_samples_i let
+ *     e[i][c][t] = q(x[i][c][t]) - D_i[t][c]
+ * q being the planar encode's input conversion (identity for int16; the float32 rule above AADHip_PlanarEncodePlanCreate) and D_i
+ * what AADHip_DecodePlanRun gives for the image the run writes - the int16 value behind the row AADHip_PlanarReconstructPlanRun
+ * stores.  |e| <= 65535.  The record of row (i, c) is four unsigned 64-bit integers:
+ *     sum_sq = sum over t of e^2,  sum_abs = sum of |e|,  max_abs = max of |e| (0 for an empty row),  count = num_samples_i.
+ * With M/S the error is taken on L / R, after the inverse transform, as the rows are.  The warm-up blocks of a segmented chain
+ * and the trial search's measuring passes contribute nothing: every frame of a row counts exactly once.
+ * 65535^2 * (2^32 - 1) < 2^64, so nothing wraps for any stream the format allows, and every field is non-negative as int64 for
+ * rows below 2^31 frames.  The sums are integers, so they do not depend on the lane mapping, the segmentation's chains or the
+ * order of anything: two runs give the same bits.
+ *
+ * The table is N * C records, contiguous, row (i, c) at index i * C + c: a torch int64 [N, C, 4] tensor on the device IS the table
+ * (as an int64 [N, 2] tensor is the window table).
+ *
+ * AADHip_PlanarReconstructPlanRunStats is AADHip_PlanarReconstructPlanRun with the table as a further output:
+ *   - images and rows are byte for byte what AADHip_PlanarReconstructPlanRun writes for the same inputs; no other element of
+ *     `device_out` and nothing outside the N * C records is touched;
+ *   - device_out may be NULL: statistics and images only, no rows are written;
+ *   - every record is written by the run, whatever the table held before (a segmented plan's run clears it on the context's
+ *     stream first: its chains add into it);
+ *   - errors: those of AADHip_PlanarReconstructPlanRun (but for the null device_out), plus AAD_APIRESULT_INVALID_ARGUMENT for a
+ *     null device_stats or one that is not 8-byte aligned while the plan has streams.  Plans of any other kind are refused; a plan
+ *     without streams is OK and launches nothing;
+ *   - AADHip_ContextSignalNextRun: the start event sits in front of the run's first device operation and the stop event behind
+ *     its last.  An unsegmented plan's run is one kernel and both ride on it; a segmented plan's run is the clear and the kernel,
+ *     the start event recorded in front of the clear and the stop event riding on the kernel. */
+struct AADHipRowStats {
+  uint64_t sum_sq;
+  uint64_t sum_abs;
+  uint64_t max_abs;
+  uint64_t count;
+};
+AADApiResult AADHip_PlanarReconstructPlanRunStats(
+    struct AADHipEncodePlan *plan, const void *device_samples, uint8_t *device_data,
+    void *device_out,                     /* may be NULL here: statistics and images only */
+    struct AADHipLaneState *device_state,
+    struct AADHipRowStats *device_stats); /* N * C records, 8-byte aligned, every one written by the run */
 
 /* ---- host-memory convenience (stage -> run -> copy back, synchronous) ---------------------- */
 

@@ -1,10 +1,12 @@
 """Quality cost of a segmented encode (AADHip_SegmentedEncodePlanCreate), on the CPU with the oracle: for each point of a grid of
 (bits, trials, L, W), the RMSE of the decoded segmented image over the RMSE of the decoded serial encode (both against the input, as
 `aad -c` computes RMSE), and how many segments came out byte-identical to the serial encode's blocks.  The numbers are
-deterministic.  CPU only: it never touches the GPU, and bench.py, smoke() and the GPU tests do not use it.
+deterministic.  CPU only by default: it then never touches the GPU, and bench.py, smoke() and the GPU tests do not use it.
+--device adds a column with the same ratio taken on the device from exact integer sums (Engine.codec_error on the segmented and on
+the serial plan: sqrt of the quotient of the squared-error sums over all channels); the CPU columns stay as they are.
 
     python tools/segment_quality.py WAV [WAV ...] [--bits 4,2] [--trials 0,2] [--L 16,64,128,256] [--W 0,8,16,32,64]
-                                    [--max-block-size 1024] [--out FILE]
+                                    [--max-block-size 1024] [--out FILE] [--device]
 
 The image of a segmented encode is defined in include/aad_hip.h; tests/segment_oracle.py builds it from the definition."""
 import argparse
@@ -35,6 +37,11 @@ def identical_segments(serial, image, block_size, spb, frames, L):
     return count
 
 
+def device_sum_sq(engine, x, param, L=None, W=0):
+    """the squared codec error of x ([1, C, T] int16 on the device) summed over its channels, as a Python int"""
+    return int(engine.codec_error(x, param, segment_blocks=L, warmup_blocks=W)[..., 0].sum().item())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("wavs", nargs="+")
@@ -44,13 +51,20 @@ def main():
     ap.add_argument("--W", type=ints, default=[0, 8, 16, 32, 64])
     ap.add_argument("--max-block-size", type=int, default=1024)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--device", action="store_true", help="add the RMSE ratio measured on the device (Engine.codec_error)")
     args = ap.parse_args()
+    engine = None
+    if args.device:
+        import torch
+        from aad_amd.capi import make_parameter
+        from aad_amd.engine import Engine
+        engine = Engine(0)
     subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "libaad_oracle.so"], check=True)
     mbs = args.max_block_size
     lines = ["# segmented encode quality: RMSE(decoded segmented image) / RMSE(decoded serial encode), both against the input",
              "# (RMSE as `aad -c` prints it); identical = segments byte-identical to the serial encode's blocks; max block size %d" % mbs,
              "%-18s %4s %6s %5s %4s %4s %8s %12s %12s %9s" % ("file", "bits", "trials", "L", "W", "segs", "blocks", "rmse_serial",
-                                                             "rmse_seg", "ratio") + "  identical"]
+                                                             "rmse_seg", "ratio") + "  identical" + ("  dev_ratio" if engine else "")]
     print("\n".join(lines), flush=True)
     for path in args.wavs:
         pcm, rate = read_wav16(path)
@@ -61,6 +75,10 @@ def main():
             for trials in args.trials:
                 serial = ob.encode(pcm, bits, mbs, rate, False, trials)
                 rmse_serial = ob.error_stats(pcm, ob.decode(serial)[0])[0]
+                if engine:
+                    x = torch.from_numpy(pcm.T.copy()).cuda()[None]
+                    param = make_parameter(ch, bits, mbs, rate, False, trials)
+                    dev_serial = device_sum_sq(engine, x, param)
                 for L in args.L:
                     segs = -(-blocks // L)
                     for W in args.W:
@@ -70,11 +88,16 @@ def main():
                             os.path.basename(path), bits, trials, L, W, segs, blocks, rmse_serial, rmse,
                             rmse / rmse_serial if rmse_serial else float("nan"),
                             identical_segments(serial, img, block_size, spb, frames, L))
+                        if engine:
+                            dev = device_sum_sq(engine, x, param, L, W)
+                            row += "  %9.4f" % ((dev / dev_serial) ** 0.5 if dev_serial else float("nan"))
                         print(row, flush=True)
                         lines.append(row)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+    if engine:
+        engine.close()
 
 
 if __name__ == "__main__":
