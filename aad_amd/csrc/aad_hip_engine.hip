@@ -30,6 +30,7 @@
 #include "aad_encode_launch.hip.h"
 #include "aad_format.h"
 #include "aad_hip_internal.h"
+#include "aad_tiles.h"
 
 namespace aad {
 thread_local LaunchSignal tl_launch_signal = {nullptr, nullptr}; /* aad_launch.h */
@@ -1099,10 +1100,7 @@ AADApiResult AADHip_WindowDecodePlanRun(struct AADHipWindowDecodePlan *plan, con
  */
 namespace {
 
-uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
-
-constexpr uint64_t kChunkBudget = 16ull << 20; /* payload bytes (in + out) per tile of a cut batch */
-constexpr uint64_t kCutAbove = kChunkBudget;
+using aad::round_up;
 
 constexpr uint64_t kParallelStagingAbove = 1ull << 20; /* bytes in a chunk from which the helper threads pay */
 
@@ -1194,33 +1192,6 @@ void staged_span(AADHipContext *ctx, uint32_t first, uint32_t count, const std::
   p->done.wait(g, [&] { return p->pending == 0; });
 }
 
-template <class Body>
-void staged_ranges(AADHipContext *ctx, uint32_t count, const std::vector<uint64_t> &prefix, Body body)
-{
-  staged_span(ctx, 0u, count, prefix, body);
-}
-
-/* A batch that travels as ONE tile has nothing to overlap with, so its big copy is cut into pieces
- * instead: encode sends piece p up while the host fills piece p + 1, decode drains piece p while
- * piece p + 1 comes down.  Item index where each piece ends, by running bytes. */
-constexpr uint32_t kMaxPieces = 4;
-constexpr uint64_t kPieceBytes = 1ull << 20;
-
-uint32_t cut_pieces(const std::vector<uint64_t> &prefix, uint32_t count, bool wanted, uint32_t *end)
-{
-  const uint64_t total = prefix[count];
-  uint32_t pieces = wanted ? (uint32_t)(total / kPieceBytes) : 1u;
-  pieces = pieces < 1 ? 1 : (pieces > kMaxPieces ? kMaxPieces : pieces);
-  uint32_t at = 0, made = 0;
-  for (uint32_t p = 1; p < pieces; p++) {
-    const uint64_t target = total / pieces * p;
-    while (at < count && prefix[at] < target) at++;
-    if (at > (made ? end[made - 1] : 0u) && at < count) end[made++] = at;
-  }
-  end[made++] = count;
-  return made;
-}
-
 bool ensure_events(AADHipContext *ctx)
 {
   if (ctx->have_events) return true;
@@ -1267,129 +1238,12 @@ bool ensure_pipeline(AADHipContext *ctx)
   return true;
 }
 
-/* the streams a tile's three stages run on: all the context's own for a batch that goes as one
- * tile (no cross-stream hop on the latency path of small calls), three different ones for a cut batch */
-struct Route {
-  hipStream_t up, run, down;
-};
-
-Route route_for(const AADHipContext *ctx, bool piped)
-{
-  if (piped) return {ctx->up_stream, ctx->stream, ctx->down_stream};
-  return {ctx->stream, ctx->stream, ctx->stream};
-}
-
 /* make `to` wait for what `from` holds so far */
 bool hop(AADHipContext *ctx, hipEvent_t event, hipStream_t from, hipStream_t to)
 {
   if (from == to) return true;
   return hip_ok(ctx, hipEventRecord(event, from), "hipEventRecord") &&
          hip_ok(ctx, hipStreamWaitEvent(to, event, 0), "hipStreamWaitEvent");
-}
-
-void settle(const Route &r)
-{
-  (void)hipStreamSynchronize(r.up);
-  (void)hipStreamSynchronize(r.run);
-  (void)hipStreamSynchronize(r.down);
-}
-
-/*
- * How a batch is cut.  A stream's blocks are chained in the encoder (block k starts from the
- * predictor block k-1 left behind), so one launch costs about `blocks per stream` x 64 us however
- * few streams it holds: cutting a batch of long streams BY STREAM would pay that chain once per cut.
- * The batch is therefore cut both ways: consecutive streams form a GROUP until one block of each
- * fills the tile budget, and a group is walked in TILES of `budget / (streams alive x block bytes)`
- * blocks of every stream at once, the predictor state staying on the device between tiles (encode;
- * decode blocks are independent and only share the tiling).  Inside a group streams are ordered
- * longest first, so that the streams still alive at any block are a prefix of that order and a
- * stream's state record keeps its index for the whole group.
- */
-struct TileStep {
-  uint32_t alive;          /* streams in the tile: order[0 .. alive) */
-  uint64_t block0, block1; /* blocks [block0, block1) of each */
-  bool group_first, group_last;
-};
-
-struct TilePlanner {
-  const uint64_t *blocks; /* per stream: blocks to walk (0 = nothing to do) */
-  uint32_t n;
-  uint64_t block_cost, budget;
-  uint32_t next_stream = 0;
-  bool in_group = false;
-  uint64_t block0 = 0;
-  std::vector<uint32_t> order; /* the current group, longest stream first */
-
-  TilePlanner(const uint64_t *blocks_per_stream, uint32_t num_streams, uint64_t bytes_per_block, uint64_t tile_budget)
-      : blocks(blocks_per_stream), n(num_streams), block_cost(bytes_per_block ? bytes_per_block : 1), budget(tile_budget) {}
-
-  bool next(TileStep *t)
-  {
-    for (;;) {
-      bool first = false;
-      if (!in_group) {
-        if (next_stream >= n) return false;
-        order.clear();
-        uint64_t cost = 0;
-        do {
-          order.push_back(next_stream);
-          if (blocks[next_stream]) cost += block_cost;
-          next_stream++;
-        } while (next_stream < n && cost < budget);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return blocks[x] > blocks[y]; });
-        block0 = 0;
-        in_group = true;
-        first = true;
-      }
-      /* streams with more than block0 blocks: a prefix of the order */
-      uint32_t lo = 0, hi = (uint32_t)order.size();
-      while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (blocks[order[mid]] > block0) lo = mid + 1; else hi = mid;
-      }
-      if (lo == 0) { /* a group of empty streams */
-        in_group = false;
-        continue;
-      }
-      const uint64_t longest = blocks[order[0]];
-      uint64_t per_tile = budget / ((uint64_t)lo * block_cost);
-      if (per_tile == 0) per_tile = 1;
-      t->alive = lo;
-      t->block0 = block0;
-      t->block1 = longest - block0 <= per_tile ? longest : block0 + per_tile;
-      t->group_first = first;
-      t->group_last = t->block1 >= longest;
-      block0 = t->block1;
-      if (t->group_last) in_group = false;
-      return true;
-    }
-  }
-};
-
-/* what the host still has to do with a tile once its copies are back */
-struct Delivery {
-  uint32_t stream;
-  uint64_t src;   /* offset in the pair's output block (encode: bytes, decode: int16 elements) */
-  uint64_t dst;   /* encode: byte offset in the caller's image; decode: first frame */
-  uint64_t count; /* encode: bytes; decode: frames */
-};
-
-struct Flight {
-  bool active = false;
-  uint64_t sequence = 0;
-  std::vector<Delivery> items;
-  std::vector<uint64_t> cost;        /* running bytes over items: [items + 1] */
-  std::vector<uint32_t> state_order; /* encode, last tile of a group: the group's order, else empty */
-  uint64_t state_src = 0;
-  uint32_t pieces = 1, piece_end[4] = {0, 0, 0, 0}; /* decode: item index where each piece of the output copy ends */
-};
-
-bool batch_is_cut(const AADHipContext *ctx, uint64_t total_bytes) { return ctx->tile_bytes > 0 || total_bytes > kCutAbove; }
-
-uint64_t tile_budget(const AADHipContext *ctx, uint64_t total_bytes)
-{
-  if (ctx->tile_bytes > 0) return (uint64_t)ctx->tile_bytes; /* forced: tests, tuning */
-  return total_bytes > kCutAbove ? kChunkBudget : ~0ull >> 8;
 }
 
 bool state_reserve(AADHipContext *ctx, size_t records)
@@ -1402,6 +1256,96 @@ bool state_reserve(AADHipContext *ctx, size_t records)
   if (!hip_ok(ctx, hipMalloc(&ctx->d_state, sizeof(AADHipLaneState) * want), "hipMalloc lane states")) return false;
   ctx->state_capacity = want;
   return true;
+}
+
+/*
+ * The tile pipeline of the host-memory calls.  Every tile the planner hands out (aad_tiles.h) goes through one of two pairs of
+ * pinned blocks, alternately: fill and copy up (up), launch (run), copy down (down).  It is handed to the caller
+ * when its pair comes round again, or at the end, older first - so the host fills tile k + 1 and drains tile k - 1 while tile k is
+ * on the device.  Tile is aad::EncodeTile or aad::DecodeTile; the callables are all that differs between the two directions:
+ *   prepare(step, order, &tile) -> AADApiResult  lay the tile out and make its launch arguments: no device work
+ *   fill(tile, hin, first, last) -> bool          write rows [first, last) of the input block, with first == 0 also what lies before them
+ *   launch(tile, din, dout, hout) -> bool         queue the kernel, and what else belongs on the compute stream (ctx->stream)
+ *   deliver(tile, hout, first, last)              hand rows [first, last) of the output block to the caller
+ * A batch that goes as one tile has its big copy - the input's where Tile::kCutUp, else the output's - cut into pieces.  On return
+ * nothing of the call is in flight, whatever the result.
+ */
+template <class Tile, class Prepare, class Fill, class Launch, class Deliver>
+AADApiResult run_tiles(AADHipContext *ctx, aad::TilePlanner &planner, bool piped, Prepare prepare, Fill fill, Launch launch, Deliver deliver)
+{
+  if (piped && !ensure_pipeline(ctx)) return AAD_APIRESULT_NG;
+  /* the streams a tile's three stages run on: all the context's own for a batch that goes as one tile (no cross-stream hop on the
+   * latency path of small calls), three different ones for a cut batch */
+  const hipStream_t up = piped ? ctx->up_stream : ctx->stream, run = ctx->stream, down = piped ? ctx->down_stream : ctx->stream;
+  struct Flight {
+    bool active = false;
+    Tile tile;
+    uint32_t pieces = 1, piece_end[aad::kMaxPieces] = {}; /* row where each piece of the output copy ends */
+  } flight[2];
+  uint64_t sequence = 0;
+  /* recorded behind piece p of pair b's output copy */
+  auto down_event = [&](int b, uint32_t p, uint32_t pieces) { return p + 1 == pieces ? ctx->chunk_done[b] : ctx->piece_done[p]; };
+
+  /* wait for the tile on pair b and hand it to the caller */
+  auto finish = [&](int b) -> bool {
+    Flight &f = flight[b];
+    if (!f.active) return true;
+    f.active = false;
+    bool ok = true;
+    for (uint32_t p = 0, first = 0; p < f.pieces; first = f.piece_end[p++]) {
+      /* every piece is waited for, also after a failure: the buffers must be idle on return */
+      if (!hip_ok(ctx, hipEventSynchronize(down_event(b, p, f.pieces)), "hipEventSynchronize")) ok = false;
+      if (ok) deliver(f.tile, static_cast<const uint8_t *>(ctx->out[b].host), first, f.piece_end[p]);
+    }
+    return ok;
+  };
+
+  AADApiResult rc = AAD_APIRESULT_OK;
+  for (aad::TileStep step; rc == AAD_APIRESULT_OK && planner.next(&step);) {
+    const int b = (int)(sequence & 1);
+    if (!finish(b)) { rc = AAD_APIRESULT_NG; break; }
+    Flight &f = flight[b];
+    Tile &t = f.tile;
+    rc = prepare(step, planner.order, &t);
+    if (rc != AAD_APIRESULT_OK) break;
+    rc = AAD_APIRESULT_NG;
+    if (!staging_reserve(ctx, ctx->in[b], t.in_bytes + 64) || !staging_reserve(ctx, ctx->out[b], t.out_bytes + 64)) break;
+    uint8_t *hin = static_cast<uint8_t *>(ctx->in[b].host), *din = static_cast<uint8_t *>(ctx->in[b].dev);
+    uint8_t *hout = static_cast<uint8_t *>(ctx->out[b].host), *dout = static_cast<uint8_t *>(ctx->out[b].dev);
+    bool ok = true;
+    uint32_t up_end[aad::kMaxPieces];
+    const uint32_t up_pieces = aad::copy_pieces(t, true, piped, up_end);
+    size_t sent = 0, got = 0;
+    for (uint32_t p = 0, first = 0; ok && p < up_pieces; first = up_end[p++]) {
+      const size_t upto = p + 1 == up_pieces ? t.in_bytes : t.payload_off + (size_t)t.fill_cost[up_end[p]];
+      ok = fill(t, hin, first, up_end[p]) && hip_ok(ctx, hipMemcpyAsync(din + sent, hin + sent, upto - sent, hipMemcpyHostToDevice, up), "H2D block");
+      sent = upto;
+    }
+    if (!ok || !hop(ctx, ctx->uploaded[b], up, run)) break;
+    if (!launch(t, din, dout, hout) || !hop(ctx, ctx->computed[b], run, down)) break;
+    f.pieces = aad::copy_pieces(t, false, piped, f.piece_end);
+    /* piece_done[] is ONE set of events for both flights: only a batch that travels as a single tile (nothing in the other
+     * flight) may cut its copy into pieces */
+    if (piped && f.pieces != 1) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "internal: a piped decode tile was cut into %u copy pieces", f.pieces);
+      break;
+    }
+    for (uint32_t p = 0; ok && p < f.pieces; p++) {
+      const size_t upto = p + 1 == f.pieces ? t.down_bytes : (size_t)t.drain_cost[f.piece_end[p]];
+      if (upto > got) ok = hip_ok(ctx, hipMemcpyAsync(hout + got, dout + got, upto - got, hipMemcpyDeviceToHost, down), "D2H block");
+      got = upto;
+      ok = ok && hip_ok(ctx, hipEventRecord(down_event(b, p, f.pieces), down), "hipEventRecord");
+    }
+    if (!ok) break;
+    sequence++;
+    f.active = true;
+    rc = AAD_APIRESULT_OK;
+  }
+  /* drain what is still in flight, older first - the pair that would be reused next - also on failure: the buffers must be idle on return */
+  for (int b : {(int)(sequence & 1), (int)(~sequence & 1)}) rc = finish(b) ? rc : AAD_APIRESULT_NG;
+  if (rc != AAD_APIRESULT_OK) /* a tile that failed half way may have left copies queued */
+    for (hipStream_t s : {up, run, down}) (void)hipStreamSynchronize(s);
+  return rc;
 }
 
 /* What every host-memory encode entry checks before any device work: the parameter makes a valid header (*h; its num_samples is
@@ -1447,148 +1391,55 @@ AADApiResult encode_host(AADHipContext *ctx, const struct AADEncodeParameter *pa
   DeviceGuard guard(ctx);
   if (!guard.ok || !ensure_events(ctx)) return AAD_APIRESULT_NG;
 
-  TilePlanner planner(blocks.data(), num_streams, (uint64_t)spb * ch * sizeof(int16_t) + h.block_size, tile_budget(ctx, total));
-  const bool piped = batch_is_cut(ctx, total);
-  if (piped && !ensure_pipeline(ctx)) return AAD_APIRESULT_NG;
-  const Route route = route_for(ctx, piped);
-  Flight flight[2];
-  std::vector<AADHipStreamDesc> table;
-  std::vector<uint64_t> fill_cost;
-  uint64_t sequence = 0;
-
-  /* wait for the tile on pair b and hand its image bytes (and states) to the caller */
-  auto finish = [&](int b) -> bool {
-    Flight &f = flight[b];
-    if (!f.active) return true;
-    f.active = false;
-    if (!hip_ok(ctx, hipEventSynchronize(ctx->chunk_done[b]), "hipEventSynchronize")) return false;
-    const uint8_t *out = static_cast<const uint8_t *>(ctx->out[b].host);
-    staged_ranges(ctx, (uint32_t)f.items.size(), f.cost, [&](uint32_t lo, uint32_t hi) {
-      for (uint32_t k = lo; k < hi; k++) {
-        const Delivery &d = f.items[k];
-        drain(d.stream, d.dst, out + d.src, d.count);
-        if (d.dst == 0 && d.count < sizes[d.stream]) { /* first tile of a longer stream: the header carries the whole count */
-          const uint32_t all = num_samples[d.stream];
-          const uint8_t be[4] = {(uint8_t)(all >> 24), (uint8_t)(all >> 16), (uint8_t)(all >> 8), (uint8_t)all};
-          drain(d.stream, 14, be, 4);
+  aad::TilePlanner planner(blocks.data(), num_streams, (uint64_t)spb * ch * sizeof(int16_t) + h.block_size, aad::tile_budget(ctx->tile_bytes, total));
+  aad::EncodeRun run; /* interleaved frames, a stream table, images only */
+  const AADApiResult rc = run_tiles<aad::EncodeTile>(ctx, planner, aad::batch_is_cut(ctx->tile_bytes, total),
+      [&](const aad::TileStep &step, const std::vector<uint32_t> &order, aad::EncodeTile *t) {
+        aad::encode_tile_layout(step, order, num_samples, sizes.data(), blocks.data(), ch, spb, h.block_size, parameter->num_encode_trials > 0, state != nullptr, t);
+        return encode_plan_init(parameter, step.alive, t->table.data(), &run.args, t->lead, true);
+      },
+      [&](const aad::EncodeTile &t, uint8_t *hin, uint32_t first, uint32_t last) {
+        if (first == 0) {
+          if (t.carry && !state_reserve(ctx, (size_t)t.group_size * ch)) return false;
+          memcpy(hin, t.table.data(), sizeof(AADHipStreamDesc) * t.table.size());
+          for (uint32_t k = 0; t.state_in && k < t.step.alive; k++)
+            memcpy(hin + t.table_bytes + sizeof(AADHipLaneState) * (size_t)k * ch, state + (size_t)t.items[k].stream * ch, sizeof(AADHipLaneState) * ch);
         }
-      }
-    });
-    if (state) {
-      const AADHipLaneState *records = reinterpret_cast<const AADHipLaneState *>(out + f.state_src);
-      for (size_t slot = 0; slot < f.state_order.size(); slot++)
-        memcpy(state + (size_t)f.state_order[slot] * ch, records + slot * ch, sizeof(AADHipLaneState) * ch);
-    }
-    return true;
-  };
-
-  AADApiResult rc = AAD_APIRESULT_OK;
-  TileStep step;
-  while (rc == AAD_APIRESULT_OK && planner.next(&step)) {
-    const int b = (int)(sequence & 1);
-    if (!finish(b)) { rc = AAD_APIRESULT_NG; break; }
-    const uint32_t n = step.alive;
-    const std::vector<uint32_t> &order = planner.order;
-    const uint32_t group_size = (uint32_t)order.size();
-    Flight &f = flight[b];
-    /* input block: table | state | pcm ; output block: image slices | state */
-    table.resize(n);
-    f.items.resize(n);
-    f.cost.resize((size_t)n + 1);
-    fill_cost.resize((size_t)n + 1);
-    uint64_t pcm_elems = 0, data_bytes = 0;
-    /* the trial search looks one block back in the input: later tiles bring that block along */
-    const uint32_t lead = parameter->num_encode_trials > 0 && step.block0 > 0 ? spb : 0;
-    for (uint32_t k = 0; k < n; k++) {
-      const uint32_t i = order[k];
-      const uint64_t frame0 = step.block0 * spb;
-      const uint64_t frame1 = step.block1 * spb < num_samples[i] ? step.block1 * spb : num_samples[i];
-      /* file header + this tile's blocks: up to the stream's end, or whole blocks */
-      const uint64_t slice = AAD_HEADER_SIZE + (step.block1 >= blocks[i] ? sizes[i] - AAD_HEADER_SIZE - step.block0 * h.block_size
-                                                                         : (step.block1 - step.block0) * h.block_size);
-      h.num_samples = (uint32_t)(frame1 - frame0) + lead;
-      table[k].pcm_offset = pcm_elems;
-      table[k].data_offset = data_bytes;
-      table[k].data_size = slice;
-      table[k].num_samples = h.num_samples;
-      table[k].reserved = 0;
-      /* the first tile delivers the file header too; later ones only their blocks */
-      const uint64_t skip = step.block0 ? AAD_HEADER_SIZE : 0;
-      f.items[k] = {i, data_bytes + skip, step.block0 ? AAD_HEADER_SIZE + step.block0 * h.block_size : 0, slice - skip};
-      f.cost[k] = data_bytes;
-      fill_cost[k] = pcm_elems * sizeof(int16_t);
-      pcm_elems += round_up((uint64_t)h.num_samples * ch, 8);
-      data_bytes += round_up(slice, 16);
-    }
-    f.cost[n] = data_bytes;
-    fill_cost[n] = pcm_elems * sizeof(int16_t);
-    aad::EncodeRun run; /* interleaved frames, a stream table, images only */
-    aad::EncodeArgs &a = run.args;
-    rc = encode_plan_init(parameter, n, table.data(), &a, lead, true);
-    if (rc != AAD_APIRESULT_OK) break;
-    /* states live on the device while a group has tiles to go; the caller's come in with the first
-     * tile and leave with the last */
-    const bool lone = step.group_first && step.group_last; /* the group's only tile: states travel inside its blocks */
-    const bool carry = !lone;
-    const bool state_in = state != nullptr && step.group_first, state_back = state != nullptr && step.group_last;
-    const size_t table_bytes = round_up(sizeof(AADHipStreamDesc) * (size_t)n, 64);
-    const size_t state_in_bytes = state_in ? sizeof(AADHipLaneState) * (size_t)n * ch : 0;
-    const size_t state_back_bytes = state_back ? sizeof(AADHipLaneState) * (size_t)group_size * ch : 0;
-    const size_t pcm_off = table_bytes + round_up(state_in_bytes, 64);
-    const size_t in_bytes = pcm_off + pcm_elems * sizeof(int16_t);
-    const size_t out_bytes = data_bytes + state_back_bytes;
-    rc = AAD_APIRESULT_NG;
-    if (!staging_reserve(ctx, ctx->in[b], in_bytes + 64) || !staging_reserve(ctx, ctx->out[b], out_bytes + 64)) break;
-    if (carry && !state_reserve(ctx, (size_t)group_size * ch)) break;
-    uint8_t *hin = static_cast<uint8_t *>(ctx->in[b].host), *din = static_cast<uint8_t *>(ctx->in[b].dev);
-    uint8_t *dout = static_cast<uint8_t *>(ctx->out[b].dev);
-    memcpy(hin, table.data(), sizeof(AADHipStreamDesc) * (size_t)n);
-    if (state_in) /* every stream of a group is alive in its first tile: n == group_size */
-      for (uint32_t k = 0; k < n; k++)
-        memcpy(hin + table_bytes + sizeof(AADHipLaneState) * (size_t)k * ch, state + (size_t)order[k] * ch, sizeof(AADHipLaneState) * ch);
-    {
-      uint32_t piece_end[kMaxPieces];
-      const uint32_t pieces = cut_pieces(fill_cost, n, !piped, piece_end);
-      size_t sent = 0;
-      bool ok = true;
-      for (uint32_t p = 0, lo = 0; ok && p < pieces; lo = piece_end[p++]) {
-        staged_span(ctx, lo, piece_end[p], fill_cost, [&](uint32_t x, uint32_t y) {
+        staged_span(ctx, first, last, t.fill_cost, [&](uint32_t x, uint32_t y) {
           for (uint32_t k = x; k < y; k++)
-            fill(order[k], (uint32_t)(step.block0 * spb - lead), table[k].num_samples, reinterpret_cast<int16_t *>(hin + pcm_off) + table[k].pcm_offset);
+            fill(t.items[k].stream, (uint32_t)t.fill_frame0, t.table[k].num_samples, reinterpret_cast<int16_t *>(hin + t.payload_off) + t.table[k].pcm_offset);
         });
-        const size_t upto = p + 1 == pieces ? in_bytes : pcm_off + (size_t)fill_cost[piece_end[p]];
-        ok = hip_ok(ctx, hipMemcpyAsync(din + sent, hin + sent, upto - sent, hipMemcpyHostToDevice, route.up), "H2D block");
-        sent = upto;
-      }
-      if (!ok) break;
-    }
-    if (!hop(ctx, ctx->uploaded[b], route.up, route.run)) break;
-    aad::LaneStateRecord *d_state = static_cast<aad::LaneStateRecord *>(ctx->d_state);
-    a.streams = reinterpret_cast<const aad::StreamDesc *>(din);
-    a.pcm = reinterpret_cast<const int16_t *>(din + pcm_off);
-    a.data = dout;
-    a.state = state_in ? reinterpret_cast<const aad::LaneStateRecord *>(din + table_bytes) : (step.group_first ? nullptr : d_state);
-    a.state_out = carry ? d_state : (state_back ? reinterpret_cast<aad::LaneStateRecord *>(dout + data_bytes) : nullptr);
-    if (run_encode(ctx, run) != AAD_APIRESULT_OK) break;
-    f.state_order.clear();
-    if (state_back) {
-      /* from the device-side records on the compute stream: the next group's first launch overwrites them */
-      if (carry && !hip_ok(ctx, hipMemcpyAsync(static_cast<uint8_t *>(ctx->out[b].host) + data_bytes, d_state, state_back_bytes, hipMemcpyDeviceToHost, route.run), "D2H lane states")) break;
-      f.state_order = order;
-      f.state_src = data_bytes;
-    }
-    if (!hop(ctx, ctx->computed[b], route.run, route.down)) break;
-    if (!hip_ok(ctx, hipMemcpyAsync(ctx->out[b].host, dout, lone ? out_bytes : data_bytes, hipMemcpyDeviceToHost, route.down), "D2H block")) break;
-    if (!hip_ok(ctx, hipEventRecord(ctx->chunk_done[b], route.down), "hipEventRecord")) break;
-    f.sequence = sequence++;
-    f.active = true;
-    rc = AAD_APIRESULT_OK;
-  }
-  /* drain what is still in flight, oldest first (also on failure: the buffers must be idle on return) */
-  const int older = flight[0].active && flight[1].active && flight[1].sequence < flight[0].sequence ? 1 : 0;
-  if (!finish(older) && rc == AAD_APIRESULT_OK) rc = AAD_APIRESULT_NG;
-  if (!finish(older ^ 1) && rc == AAD_APIRESULT_OK) rc = AAD_APIRESULT_NG;
-  if (rc != AAD_APIRESULT_OK) settle(route); /* a tile that failed half way may have left copies queued */
+        return true;
+      },
+      [&](const aad::EncodeTile &t, uint8_t *din, uint8_t *dout, uint8_t *hout) {
+        aad::EncodeArgs &a = run.args;
+        aad::LaneStateRecord *d_state = static_cast<aad::LaneStateRecord *>(ctx->d_state);
+        a.streams = reinterpret_cast<const aad::StreamDesc *>(din);
+        a.pcm = reinterpret_cast<const int16_t *>(din + t.payload_off);
+        a.data = dout;
+        a.state = t.state_in ? reinterpret_cast<const aad::LaneStateRecord *>(din + t.table_bytes) : (t.step.group_first ? nullptr : d_state);
+        a.state_out = t.carry ? d_state : (t.state_back ? reinterpret_cast<aad::LaneStateRecord *>(dout + t.data_bytes) : nullptr);
+        if (run_encode(ctx, run) != AAD_APIRESULT_OK) return false;
+        /* from the device-side records on the compute stream: the next group's first launch overwrites them */
+        return !(t.carry && t.state_back) ||
+               hip_ok(ctx, hipMemcpyAsync(hout + t.data_bytes, d_state, t.out_bytes - t.data_bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H lane states");
+      },
+      [&](const aad::EncodeTile &t, const uint8_t *out, uint32_t first, uint32_t last) { /* one piece: the whole tile */
+        staged_span(ctx, first, last, t.drain_cost, [&](uint32_t lo, uint32_t hi) {
+          for (uint32_t k = lo; k < hi; k++) {
+            const aad::ImageSlice &d = t.items[k];
+            drain(d.stream, d.dst, out + d.src, d.bytes);
+            if (d.patch_count) { /* first tile of a longer stream: the header carries the whole count */
+              const uint32_t all = num_samples[d.stream];
+              const uint8_t be[4] = {(uint8_t)(all >> 24), (uint8_t)(all >> 16), (uint8_t)(all >> 8), (uint8_t)all};
+              drain(d.stream, 14, be, 4);
+            }
+          }
+        });
+        const AADHipLaneState *records = reinterpret_cast<const AADHipLaneState *>(out + t.data_bytes);
+        for (size_t slot = 0; slot < t.state_order.size(); slot++)
+          memcpy(state + (size_t)t.state_order[slot] * ch, records + slot * ch, sizeof(AADHipLaneState) * ch);
+      });
   if (rc == AAD_APIRESULT_OK && output_size) memcpy(output_size, sizes.data(), sizeof(uint64_t) * num_streams);
   return rc;
 }
@@ -1619,17 +1470,7 @@ bool device_block_reserve(AADHipContext *ctx, void **block, size_t *capacity, si
 }
 
 /* bytes of the pinned chunks that stage a device-resident wave */
-uint64_t staging_chunk(const AADHipContext *ctx) { return ctx->tile_bytes > 0 ? (uint64_t)ctx->tile_bytes : kChunkBudget; }
-
-/* items [*a, *b) whose rows meet bytes [lo, hi) of a block; `at`: count + 1 entries, where each item's row starts and the block ends */
-void row_span(const std::vector<uint64_t> &at, uint64_t lo, uint64_t hi, uint32_t *a, uint32_t *b)
-{
-  const uint32_t count = (uint32_t)at.size() - 1;
-  *a = (uint32_t)(std::upper_bound(at.begin(), at.end(), lo) - at.begin());
-  *a = *a ? *a - 1 : 0;
-  *b = (uint32_t)(std::lower_bound(at.begin(), at.end(), hi) - at.begin());
-  if (*b > count) *b = count;
-}
+uint64_t staging_chunk(const AADHipContext *ctx) { return ctx->tile_bytes > 0 ? (uint64_t)ctx->tile_bytes : aad::kChunkBudget; }
 
 /* The staging of a device-resident wave, on the context's own stream through its two pinned input / output blocks.
  * stage_up: bytes [0, bytes) of the device block d_dst in chunks; fill(lo, hi, host) writes bytes [lo, hi) to host[0 ..), and
@@ -1756,7 +1597,7 @@ AADApiResult encode_host_segmented(AADHipContext *ctx, const struct AADEncodePar
       if (lo < table_end)
         memcpy(host, reinterpret_cast<const uint8_t *>(t.chains.data()) + lo, (size_t)((hi < table_end ? hi : table_end) - lo));
       uint32_t a, b;
-      row_span(row, lo, hi, &a, &b);
+      aad::row_span(row, lo, hi, &a, &b);
       staged_span(ctx, a, b, row, [&](uint32_t x, uint32_t y) {
         for (uint32_t c = x; c < y; c++) {
           const uint64_t r0 = row[c], r1 = r0 + (uint64_t)t.chains[c].num_frames * ch * sizeof(int16_t);
@@ -1777,7 +1618,7 @@ AADApiResult encode_host_segmented(AADHipContext *ctx, const struct AADEncodePar
     /* ---- down: bytes [out_begin, out_bytes) of the output block, each chain's to its place in its stream's image ---- */
     const bool down = stage_down(ctx, d_out, t.out_begin, t.out_bytes, chunk, [&](uint64_t lo, uint64_t hi, const uint8_t *host) {
       uint32_t a, b;
-      row_span(spot, lo, hi, &a, &b);
+      aad::row_span(spot, lo, hi, &a, &b);
       staged_span(ctx, a, b, spot, [&](uint32_t x, uint32_t y) {
         for (uint32_t c = x; c < y; c++) {
           const aad::WaveChain &w = t.where[c];
@@ -1808,7 +1649,7 @@ AADApiResult decode_host(AADHipContext *ctx, const struct AADHeaderInfo *format,
   const uint32_t spb = format->num_samples_per_block, bs = format->block_size;
   if (ch == 0 || bs == 0 || spb == 0) return AAD_APIRESULT_INVALID_FORMAT;
   std::vector<AADHipStreamDesc> table(num_streams);
-  std::vector<uint64_t> prefix((size_t)num_streams + 1), blocks(num_streams), fill_cost, tile_blocks;
+  std::vector<uint64_t> prefix((size_t)num_streams + 1), blocks(num_streams);
   uint64_t total = 0;
   for (uint32_t i = 0; i < num_streams; i++) {
     table[i] = {0, 0, data_size[i], num_samples[i], 0};
@@ -1826,135 +1667,42 @@ AADApiResult decode_host(AADHipContext *ctx, const struct AADHeaderInfo *format,
   if (!guard.ok || !ensure_events(ctx)) return AAD_APIRESULT_NG;
   if (decoded_frames) memset(decoded_frames, 0, sizeof(uint32_t) * num_streams);
 
-  /* bytes a full block's decode touches beyond its own block_size (0 for every geometry an encoder writes) */
-  const uint64_t unit_samples = format->bits_per_sample == 3 ? 8 : (format->bits_per_sample == 4 ? 2 : 4);
-  const uint64_t unit_bytes = (uint64_t)(format->bits_per_sample == 3 ? 3 : 1) * ch;
-  const uint64_t touched = (uint64_t)AAD_BLOCK_HEADER_BYTES_PER_CH * ch + (spb > 4 ? (spb - 4 + unit_samples - 1) / unit_samples * unit_bytes : 0);
-  const uint64_t overreach = touched > bs ? touched - bs : 0;
-  TilePlanner planner(blocks.data(), num_streams, (uint64_t)spb * ch * sizeof(int16_t) + bs + overreach, tile_budget(ctx, total));
-  const bool piped = batch_is_cut(ctx, total);
-  if (piped && !ensure_pipeline(ctx)) return AAD_APIRESULT_NG;
-  const Route route = route_for(ctx, piped);
-  Flight flight[2];
-  uint64_t sequence = 0;
-
-  auto finish = [&](int b) -> bool {
-    Flight &f = flight[b];
-    if (!f.active) return true;
-    f.active = false;
-    const int16_t *out = static_cast<const int16_t *>(ctx->out[b].host);
-    bool ok = true;
-    for (uint32_t p = 0, first = 0; p < f.pieces; first = f.piece_end[p++]) {
-      /* every piece is waited for, also after a failure: the buffers must be idle on return */
-      if (!hip_ok(ctx, hipEventSynchronize(p + 1 == f.pieces ? ctx->chunk_done[b] : ctx->piece_done[p]), "hipEventSynchronize")) ok = false;
-      if (!ok) continue;
-      staged_span(ctx, first, f.piece_end[p], f.cost, [&](uint32_t lo, uint32_t hi) {
-        for (uint32_t k = lo; k < hi; k++) {
-          const Delivery &d = f.items[k];
-          if (d.count) drain(d.stream, (uint32_t)d.dst, out + d.src, (uint32_t)d.count);
-          if (decoded_frames) decoded_frames[d.stream] += (uint32_t)d.count; /* one item per stream and tile */
-        }
+  uint64_t block_cost;
+  const uint64_t overreach = aad::decode_overreach(ch, format->bits_per_sample, spb, bs, &block_cost);
+  aad::TilePlanner planner(blocks.data(), num_streams, block_cost, aad::tile_budget(ctx->tile_bytes, total));
+  aad::DecodeArgs a;
+  return run_tiles<aad::DecodeTile>(ctx, planner, aad::batch_is_cut(ctx->tile_bytes, total),
+      [&](const aad::TileStep &step, const std::vector<uint32_t> &order, aad::DecodeTile *t) {
+        aad::decode_tile_layout(step, order, data_size, num_samples, blocks.data(), ch, spb, bs, head, overreach, t);
+        prefix.resize((size_t)step.alive + 1);
+        return decode_plan_init(format, 0, step.alive, t->table.data(), prefix.data(), &a, t->tile_blocks.data());
+      },
+      [&](const aad::DecodeTile &t, uint8_t *hin, uint32_t first, uint32_t last) { /* one piece: the whole tile */
+        memcpy(hin, t.table.data(), sizeof(AADHipStreamDesc) * t.table.size());
+        memcpy(hin + t.table_bytes, prefix.data(), sizeof(uint64_t) * prefix.size());
+        staged_span(ctx, first, last, t.fill_cost, [&](uint32_t lo, uint32_t hi) {
+          for (uint32_t k = lo; k < hi; k++)
+            fill(t.items[k].stream, t.fill_byte0, t.table[k].data_size, hin + t.payload_off + t.table[k].data_offset);
+        });
+        return true;
+      },
+      [&](const aad::DecodeTile &t, uint8_t *din, uint8_t *dout, uint8_t *) {
+        a.streams = reinterpret_cast<const aad::StreamDesc *>(din);
+        a.block_prefix = reinterpret_cast<const uint64_t *>(din + t.table_bytes);
+        a.data = din + t.payload_off;
+        a.pcm = reinterpret_cast<int16_t *>(dout);
+        if ((reinterpret_cast<uintptr_t>(a.pcm) & 63u) != 0) a.stream_stores = 0;
+        return run_decode(ctx, a) == AAD_APIRESULT_OK;
+      },
+      [&](const aad::DecodeTile &t, const uint8_t *out, uint32_t first, uint32_t last) {
+        staged_span(ctx, first, last, t.drain_cost, [&](uint32_t lo, uint32_t hi) {
+          for (uint32_t k = lo; k < hi; k++) {
+            const aad::FrameRun &d = t.items[k];
+            if (d.frames) drain(d.stream, (uint32_t)d.frame0, reinterpret_cast<const int16_t *>(out) + d.src, (uint32_t)d.frames);
+            if (decoded_frames) decoded_frames[d.stream] += (uint32_t)d.frames; /* one item per stream and tile */
+          }
+        });
       });
-    }
-    return ok;
-  };
-
-  AADApiResult rc = AAD_APIRESULT_OK;
-  TileStep step;
-  while (rc == AAD_APIRESULT_OK && planner.next(&step)) {
-    const int b = (int)(sequence & 1);
-    if (!finish(b)) { rc = AAD_APIRESULT_NG; break; }
-    const uint32_t n = step.alive;
-    const std::vector<uint32_t> &order = planner.order;
-    Flight &f = flight[b];
-    table.resize(n);
-    prefix.resize((size_t)n + 1);
-    tile_blocks.resize(n);
-    f.items.resize(n);
-    f.cost.resize((size_t)n + 1);
-    fill_cost.resize((size_t)n + 1);
-    uint64_t pcm_elems = 0, data_bytes = 0;
-    for (uint32_t k = 0; k < n; k++) {
-      const uint32_t i = order[k];
-      const uint64_t payload = data_size[i] - head; /* alive: it has a block, so more than `head` bytes */
-      /* a block whose header asks for more samples than block_size holds reads on into the bytes behind it, as the reference's
-       * unbounded code walk does (src/aad_decoder.c:396-451; the header checks relate samples_per_block and block_size to
-       * nothing, :173-225): a tile carries that reach behind its last block, and a stream's last tile every byte that is left */
-      const uint64_t byte0 = step.block0 * bs;
-      const uint64_t upto = step.block1 >= blocks[i] ? payload : step.block1 * bs + overreach;
-      const uint64_t byte1 = upto < payload ? upto : payload;
-      const uint64_t frame0 = step.block0 * spb, frame1 = step.block1 * spb < num_samples[i] ? step.block1 * spb : num_samples[i];
-      /* frames the reference's block walk produces: it stops when the bytes run out (src/aad_decoder.c:514) */
-      tile_blocks[k] = (step.block1 < blocks[i] ? step.block1 : blocks[i]) - step.block0;
-      const uint64_t by_bytes = tile_blocks[k] * spb;
-      table[k].pcm_offset = pcm_elems;
-      table[k].data_offset = data_bytes;
-      table[k].data_size = byte1 - byte0;
-      table[k].num_samples = (uint32_t)(frame1 - frame0);
-      table[k].reserved = 0;
-      f.items[k] = {i, pcm_elems, frame0, by_bytes < frame1 - frame0 ? by_bytes : frame1 - frame0};
-      f.cost[k] = pcm_elems * sizeof(int16_t);
-      fill_cost[k] = data_bytes;
-      pcm_elems += round_up((frame1 - frame0) * ch, 8);
-      data_bytes += round_up(byte1 - byte0, 16);
-    }
-    f.cost[n] = pcm_elems * sizeof(int16_t);
-    fill_cost[n] = data_bytes;
-    aad::DecodeArgs a;
-    rc = decode_plan_init(format, 0, n, table.data(), prefix.data(), &a, tile_blocks.data());
-    if (rc != AAD_APIRESULT_OK) break;
-    const size_t table_bytes = round_up(sizeof(AADHipStreamDesc) * (size_t)n, 64);
-    const size_t prefix_bytes = round_up(sizeof(uint64_t) * ((size_t)n + 1), 64);
-    const size_t data_off = table_bytes + prefix_bytes;
-    const size_t in_bytes = data_off + data_bytes, out_bytes = pcm_elems * sizeof(int16_t);
-    rc = AAD_APIRESULT_NG;
-    if (!staging_reserve(ctx, ctx->in[b], in_bytes + 64) || !staging_reserve(ctx, ctx->out[b], out_bytes + 64)) break;
-    uint8_t *hin = static_cast<uint8_t *>(ctx->in[b].host), *din = static_cast<uint8_t *>(ctx->in[b].dev);
-    memcpy(hin, table.data(), sizeof(AADHipStreamDesc) * (size_t)n);
-    memcpy(hin + table_bytes, prefix.data(), sizeof(uint64_t) * ((size_t)n + 1));
-    staged_ranges(ctx, n, fill_cost, [&](uint32_t lo, uint32_t hi) {
-      for (uint32_t k = lo; k < hi; k++)
-        fill(order[k], head + step.block0 * bs, table[k].data_size, hin + data_off + table[k].data_offset);
-    });
-    if (!hip_ok(ctx, hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, route.up), "H2D block")) break;
-    if (!hop(ctx, ctx->uploaded[b], route.up, route.run)) break;
-    a.streams = reinterpret_cast<const aad::StreamDesc *>(din);
-    a.block_prefix = reinterpret_cast<const uint64_t *>(din + table_bytes);
-    a.data = din + data_off;
-    a.pcm = static_cast<int16_t *>(ctx->out[b].dev);
-    if ((reinterpret_cast<uintptr_t>(a.pcm) & 63u) != 0) a.stream_stores = 0;
-    if (run_decode(ctx, a) != AAD_APIRESULT_OK) break;
-    if (!hop(ctx, ctx->computed[b], route.run, route.down)) break;
-    {
-      f.pieces = cut_pieces(f.cost, n, !piped, f.piece_end);
-      /* piece_done[] is ONE set of events for both flights: only a batch that travels as a single tile (nothing in
-       * the other flight) may cut its copy into pieces */
-      if (piped && f.pieces != 1) {
-        snprintf(ctx->last_error, sizeof(ctx->last_error), "internal: a piped decode tile was cut into %u copy pieces", f.pieces);
-        rc = AAD_APIRESULT_NG;
-        break;
-      }
-      size_t got = 0;
-      bool ok = true;
-      for (uint32_t p = 0; ok && p < f.pieces; p++) {
-        const size_t upto = p + 1 == f.pieces ? out_bytes : (size_t)f.cost[f.piece_end[p]];
-        if (upto > got)
-          ok = hip_ok(ctx, hipMemcpyAsync(static_cast<uint8_t *>(ctx->out[b].host) + got, static_cast<uint8_t *>(ctx->out[b].dev) + got,
-                                         upto - got, hipMemcpyDeviceToHost, route.down), "D2H block");
-        got = upto;
-        ok = ok && hip_ok(ctx, hipEventRecord(p + 1 == f.pieces ? ctx->chunk_done[b] : ctx->piece_done[p], route.down), "hipEventRecord");
-      }
-      if (!ok) break;
-    }
-    f.sequence = sequence++;
-    f.active = true;
-    rc = AAD_APIRESULT_OK;
-  }
-  const int older = flight[0].active && flight[1].active && flight[1].sequence < flight[0].sequence ? 1 : 0;
-  if (!finish(older) && rc == AAD_APIRESULT_OK) rc = AAD_APIRESULT_NG;
-  if (!finish(older ^ 1) && rc == AAD_APIRESULT_OK) rc = AAD_APIRESULT_NG;
-  if (rc != AAD_APIRESULT_OK) settle(route);
-  return rc;
 }
 
 } /* namespace */
@@ -2270,7 +2018,7 @@ AADApiResult reconstruct_wave(AADHipContext *ctx, const struct AADEncodeParamete
     /* the rows of the streams that fall into bytes [lo, hi) of the flat PCM block <-> host block `base` (which holds byte lo at 0) */
     auto rows = [&](uint64_t lo, uint64_t hi, uint8_t *base, bool up) {
       uint32_t a, b;
-      row_span(byte_prefix, lo, hi, &a, &b);
+      aad::row_span(byte_prefix, lo, hi, &a, &b);
       staged_span(ctx, a, b, byte_prefix, [&](uint32_t x, uint32_t y) {
         for (uint32_t i = x; i < y; i++) {
           const uint64_t r0 = byte_prefix[i], r1 = r0 + (uint64_t)num_samples[i] * ch * sizeof(int16_t);
