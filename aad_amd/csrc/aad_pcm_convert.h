@@ -4,7 +4,7 @@
  * (torch: nan_to_num(x, nan=0).mul(32768).round().clamp(-32768, 32767).to(int16)).  v * 32768 is exact in float32 or overflows to
  * +-inf, which the clamp takes.  The encoder's chunk loads call this as the samples arrive (aad_encode.hip.h PlanarChunk /
  * PlanarRaw); device and host share the header so that a CPU test proves it over every float32 bit pattern
- * (tests/test_planar_convert.py, through tests/planar_convert_driver.cpp).
+ * (tests/test_planar_host.py, through tests/planar_host_driver.cpp).
  *
  * Written so that no hardware conversion rule decides a value: the NaN is taken out first and the clamp runs on floats, so the
  * float -> int conversion only ever sees an integer in int16 range (v_cvt_i32_f32 saturates and maps NaN to 0 on its own, C

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import aad_amd
+import crafted_pcm
 import oracle_binding as ob
 from aad_amd.synth import synth_pcm
 
@@ -15,7 +16,14 @@ def ref():
     return aad_amd.LegacyCodec(aad_amd.load_library(ob.REF_SO, hip=False))
 
 
-@pytest.mark.parametrize("kind", ["music", "noise", "nyquist"])
+def _stream(kind, n, ch, seed):
+    """the synthetic kinds of aad_amd/synth.py, or a family of tests/crafted_pcm.py (the seed picks one of its two variants)"""
+    if kind in crafted_pcm.SHORT_FAMILIES:
+        return crafted_pcm.generate(kind, n, ch, seed % 2)
+    return synth_pcm(1, n, ch, seed=seed, kind=kind)[0]
+
+
+@pytest.mark.parametrize("kind", ["music", "noise", "nyquist"] + crafted_pcm.SHORT_FAMILIES)
 @pytest.mark.parametrize("bits", [4, 3, 2])
 def test_random_streams(ref, kind, bits):
     rng = np.random.default_rng(bits * 7 + len(kind))
@@ -25,7 +33,7 @@ def test_random_streams(ref, kind, bits):
         trials = int(rng.integers(0, 3))
         mbs = int(rng.choice([64, 128, 200, 256, 1024, 4096]))
         n = int(rng.integers(1, 6000))
-        pcm = synth_pcm(1, n, ch, seed=1000 + i, kind=kind)[0]
+        pcm = _stream(kind, n, ch, 1000 + i)
         a = ref.encode(pcm, bits, mbs, 44100, ms, trials)
         assert ob.encode(pcm, bits, mbs, 44100, ms, trials) == a, (ch, ms, trials, mbs, n)
         da, _ = ref.decode(a)
