@@ -99,6 +99,7 @@ HIP_SYMBOLS = [
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
     "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
+    "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -182,6 +183,14 @@ def _declare_hip(lib):
     lib.AADHip_PlanarReconstructPlanRun.restype = C.c_int
     lib.AADHip_PlanarReconstructPlanRunStats.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.AADHip_PlanarReconstructPlanRunStats.restype = C.c_int
+    lib.AADHip_WindowReconstructPlanCreate.argtypes = [vp, C.POINTER(AADEncodeParameter), C.POINTER(AADHipPlanarLayout),
+                                                       C.POINTER(AADHipSegmentation), C.c_uint32, vp, C.POINTER(vp)]
+    lib.AADHip_WindowReconstructPlanCreate.restype = C.c_int
+    lib.AADHip_WindowReconstructPlanDestroy.argtypes = [vp]
+    lib.AADHip_WindowReconstructPlanDestroy.restype = None
+    lib.AADHip_WindowReconstructPlanRun.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, C.POINTER(AADHipPlanarOutput),
+                                                    vp, vp]
+    lib.AADHip_WindowReconstructPlanRun.restype = C.c_int
     lib.AADHip_EncodePlanDestroy.argtypes = [vp]
     lib.AADHip_EncodePlanDestroy.restype = None
     lib.AADHip_EncodePlanRun.argtypes = [vp, vp, vp, vp]

@@ -3,7 +3,8 @@
  * contexts, plans (uploaded stream tables), kernel launches and the host-memory convenience
  * calls.  Device code lives in aad_encode.hip.h / aad_decode.hip.h (shared parts: aad_device.hip.h)
  * and, for the split, sector-tiled and window decoders and the planar-input and planar reconstruct encoders, in units of their own
- * (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_planar.hip, aad_encode_reconstruct.hip).  Every
+ * (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_planar.hip, aad_encode_reconstruct.hip; the
+ * window reconstruct run's resolve kernel: aad_window_reconstruct.hip).  Every
  * kind of encode plan is made by encode_plan_create and run by encode_plan_run over one description of a run (aad::EncodeRun,
  * aad_encode_launch.hip.h), which the host-memory paths build directly.  gfx950 only; no CPU code path - every entry point that
  * needs the GPU fails with AAD_APIRESULT_NG when HIP does.
@@ -31,6 +32,7 @@
 #include "aad_format.h"
 #include "aad_hip_internal.h"
 #include "aad_tiles.h"
+#include "aad_window_reconstruct.hip.h"
 
 namespace aad {
 thread_local LaunchSignal tl_launch_signal = {nullptr, nullptr}; /* aad_launch.h */
@@ -93,6 +95,9 @@ struct AADHipContext {
    * encode_block_dual), grow-only, shared by the context's encode launches like d_residual */
   uint8_t *d_trial;
   uint64_t trial_capacity;
+  /* the images of a window reconstruct run that did not ask for them (the encoders always write images), grow-only likewise */
+  uint8_t *d_window_images;
+  uint64_t window_images_capacity;
   /* AADHip_ContextSetOption; the defaults come from the environment ONCE, at creation */
   aad::LaunchSignal signal_next; /* AADHip_ContextSignalNextRun: the events the next plan run records around its work (one-shot) */
   bool signal_refused;           /* ROC_SYSTEM_SCOPE_SIGNAL=0 at creation: an event on a dispatch packet is never seen by another queue */
@@ -108,9 +113,20 @@ struct AADHipContext {
 
 /* which of the three ...PlanRun entry points runs a plan: they take different pointers */
 enum class EncodePlanKind {
-  Frames,     /* AADHip_EncodePlanCreate, AADHip_SegmentedEncodePlanCreate -> AADHip_EncodePlanRun */
-  Rows,       /* AADHip_PlanarEncodePlanCreate -> AADHip_PlanarEncodePlanRun */
-  Reconstruct /* AADHip_PlanarReconstructPlanCreate -> AADHip_PlanarReconstructPlanRun */
+  Frames,      /* AADHip_EncodePlanCreate, AADHip_SegmentedEncodePlanCreate -> AADHip_EncodePlanRun */
+  Rows,        /* AADHip_PlanarEncodePlanCreate -> AADHip_PlanarEncodePlanRun */
+  Reconstruct, /* AADHip_PlanarReconstructPlanCreate -> AADHip_PlanarReconstructPlanRun */
+  Windows      /* AADHip_WindowReconstructPlanCreate -> AADHip_WindowReconstructPlanRun */
+};
+
+/* what a window reconstruct plan holds besides its run: the lanes are written on the device, per run, from the window table */
+struct WindowPlanPart {
+  AADHipSegmentation seg;    /* segment_blocks == 0: unsegmented */
+  AADEncodeParameter parameter;
+  AADHipStreamDesc *d_sources;
+  uint32_t num_sources;
+  uint8_t *d_lanes;          /* the lane tables of the largest run so far: table | out_base | stats_stream, grow-only */
+  uint64_t lanes_capacity;   /* in bytes */
 };
 
 struct AADHipEncodePlan { /* every field is set by encode_plan_create */
@@ -121,6 +137,7 @@ struct AADHipEncodePlan { /* every field is set by encode_plan_create */
   uint64_t *d_out_base; /* Reconstruct: run.rows.base, else null */
   uint32_t *d_stats_stream; /* Reconstruct, segmented: run.stats_stream, else null */
   uint64_t stats_records;   /* Reconstruct: streams * channels, the records of a statistics table */
+  WindowPlanPart *windows;  /* Windows (then `run` has no table, lane count, output or pointer: they come with each run), else null */
 };
 
 struct AADHipDecodePlan {
@@ -524,6 +541,7 @@ AADApiResult encode_plan_create(AADHipContext *ctx, const struct AADEncodeParame
   p->d_table = nullptr;
   p->d_out_base = nullptr;
   p->d_stats_stream = nullptr;
+  p->windows = nullptr;
   p->stats_records = (uint64_t)num_streams * args.channels;
   DeviceGuard guard(ctx);
   bool ok = guard.ok;
@@ -687,6 +705,8 @@ AADApiResult AADHip_ContextCreate(int32_t device_index, void *hip_stream, struct
   ctx->residual_capacity = 0;
   ctx->d_trial = nullptr;
   ctx->trial_capacity = 0;
+  ctx->d_window_images = nullptr;
+  ctx->window_images_capacity = 0;
   ctx->signal_next = aad::LaunchSignal{nullptr, nullptr};
   ctx->pool = nullptr;
   ctx->staging_threads = 0;
@@ -743,6 +763,7 @@ void AADHip_ContextDestroy(struct AADHipContext *ctx)
       if (ctx->d_rc_out) (void)hipFree(ctx->d_rc_out);
       if (ctx->d_residual) (void)hipFree(ctx->d_residual);
       if (ctx->d_trial) (void)hipFree(ctx->d_trial);
+      if (ctx->d_window_images) (void)hipFree(ctx->d_window_images);
       if (ctx->d_state) (void)hipFree(ctx->d_state);
       if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     }
@@ -870,7 +891,12 @@ void AADHip_EncodePlanDestroy(struct AADHipEncodePlan *plan)
     (void)hipFree(plan->d_table);
     (void)hipFree(plan->d_out_base);
     (void)hipFree(plan->d_stats_stream);
+    if (plan->windows != nullptr) {
+      (void)hipFree(plan->windows->d_sources);
+      if (plan->windows->d_lanes) (void)hipFree(plan->windows->d_lanes);
+    }
   }
+  delete plan->windows;
   delete plan;
 }
 
@@ -1082,6 +1108,151 @@ AADApiResult AADHip_WindowDecodePlanRun(struct AADHipWindowDecodePlan *plan, con
   aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
   aad::launch_decode_window(a, p, sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
   return finish_signal(ctx, signal, hip_ok(ctx, hipGetLastError(), "window decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG);
+}
+
+/* -------------------------------------------------------------------- window reconstruct -- */
+
+AADApiResult AADHip_WindowReconstructPlanCreate(struct AADHipContext *ctx, const struct AADEncodeParameter *parameter,
+                                                const struct AADHipPlanarLayout *input, const struct AADHipSegmentation *segmentation,
+                                                uint32_t num_source_streams, const struct AADHipStreamDesc *source_streams,
+                                                struct AADHipEncodePlan **plan)
+{
+  if (ctx == nullptr || plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  *plan = nullptr;
+  if (parameter == nullptr || input == nullptr || (num_source_streams != 0 && source_streams == nullptr)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  if (!planar_fields_ok(input, segmentation)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  aad::EncodeRun run;
+  const AADApiResult rc = encode_plan_init(parameter, 0, nullptr, &run.args);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  if (!aad::window_sources_ok(run.args.channels, input->channel_stride, input->sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4u : 2u,
+                              num_source_streams, source_streams)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "window reconstruct plan: source rows refused (channel_stride below a stream's num_samples, or past 64-bit offsets)");
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  AADHipEncodePlan *p = new (std::nothrow) AADHipEncodePlan(); /* every table pointer null */
+  WindowPlanPart *part = new (std::nothrow) WindowPlanPart();
+  if (p == nullptr || part == nullptr) {
+    delete p;
+    delete part;
+    return AAD_APIRESULT_NG;
+  }
+  p->ctx = ctx;
+  p->kind = EncodePlanKind::Windows;
+  p->windows = part;
+  part->seg = segmentation != nullptr ? *segmentation : AADHipSegmentation{0, 0};
+  part->parameter = *parameter;
+  part->num_sources = num_source_streams;
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &part->d_sources, source_streams, num_source_streams)) {
+    if (part->d_sources) (void)hipFree(part->d_sources);
+    delete part;
+    delete p;
+    return AAD_APIRESULT_NG;
+  }
+  run.args.ring_ok = 0; /* the byte ring stores whole sectors, past an image's last byte: a run touches the image bytes alone */
+  run.in = aad::planar_layout(input->sample_type, run.args.channels);
+  run.channel_stride = input->channel_stride;
+  p->run = run;
+  *plan = p;
+  return AAD_APIRESULT_OK;
+}
+
+void AADHip_WindowReconstructPlanDestroy(struct AADHipEncodePlan *plan) { AADHip_EncodePlanDestroy(plan); }
+
+AADApiResult AADHip_WindowReconstructPlanRun(struct AADHipEncodePlan *plan, const void *device_samples, uint64_t num_windows,
+                                             const struct AADHipWindow *device_windows, uint32_t frames_per_window,
+                                             uint64_t image_stride, uint8_t *device_data, const struct AADHipPlanarOutput *output,
+                                             void *device_out, struct AADHipRowStats *device_stats)
+{
+  if (plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = plan->ctx;
+  const aad::LaunchSignal signal = take_signal(ctx);
+  auto refuse = [&](const char *why) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "window reconstruct: %s", why);
+    return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  };
+  if (plan->kind != EncodePlanKind::Windows) return refuse("not a window reconstruct plan");
+  WindowPlanPart *part = plan->windows;
+  const aad::EncodeArgs &e = plan->run.args;
+  if (frames_per_window == 0) return refuse("frames_per_window == 0");
+  if (num_windows != 0 && device_data == nullptr && device_out == nullptr && device_stats == nullptr)
+    return refuse("no output: images, rows and statistics are all null");
+  if (device_out != nullptr && !aad::planar_output_rows_ok(e.channels, num_windows, frames_per_window, output))
+    return refuse("output rows refused (null, sample type, reserved, a stride below the rows of T elements, or past 64-bit offsets)");
+  if (device_out != nullptr && device_out == device_samples) return refuse("device_out == device_samples");
+  const uint64_t image_bytes = AADHip_CalculateEncodedSize(&part->parameter, frames_per_window);
+  if (image_bytes == 0) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_FORMAT);
+  if (device_data == nullptr) image_stride = (image_bytes + 63) / 64 * 64; /* the context's scratch: a layout of its own */
+  if (!aad::window_images_ok(num_windows, image_stride, image_bytes))
+    return refuse("image_stride below the image of a full window, or images past 64-bit offsets");
+  uint64_t lanes = 0;
+  if (!aad::window_lane_count(num_windows, frames_per_window, e.samples_per_block, part->seg.segment_blocks, &lanes))
+    return refuse("more than UINT32_MAX lanes (windows x chains per window)");
+  if (num_windows != 0 && (device_samples == nullptr || device_windows == nullptr || (reinterpret_cast<uintptr_t>(device_windows) & 7u) != 0 ||
+                           (reinterpret_cast<uintptr_t>(device_stats) & 7u) != 0))
+    return refuse("a null corpus, a null or misaligned window table, or a misaligned statistics table");
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+  if (num_windows == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
+
+  const bool segmented = part->seg.segment_blocks != 0;
+  const uint64_t entry = segmented ? sizeof(aad::ChainDesc) : sizeof(aad::StreamDesc);
+  const uint64_t base_at = lanes * entry, stats_at = base_at + lanes * sizeof(uint64_t); /* 8-byte records first: every table aligned */
+  if (!scratch_reserve(ctx, &part->d_lanes, &part->lanes_capacity, stats_at + lanes * sizeof(uint32_t), "hipMalloc window lane tables"))
+    return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+  if (device_data == nullptr) {
+    if (!scratch_reserve(ctx, &ctx->d_window_images, &ctx->window_images_capacity, (num_windows - 1) * image_stride + image_bytes,
+                         "hipMalloc window image scratch"))
+      return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+    device_data = ctx->d_window_images;
+  }
+
+  aad::WindowResolveArgs w;
+  memset(&w, 0, sizeof(w));
+  w.sources = part->d_sources;
+  w.windows = reinterpret_cast<const uint64_t *>(device_windows);
+  w.num_sources = part->num_sources;
+  w.num_windows = num_windows;
+  w.g.frames = frames_per_window;
+  w.g.spb = e.samples_per_block;
+  w.g.segment_blocks = part->seg.segment_blocks;
+  w.g.warmup_blocks = part->seg.warmup_blocks;
+  w.g.chains_per_window = (uint32_t)(lanes / num_windows);
+  w.g.image_stride = image_stride;
+  w.g.out_stream_stride = device_out != nullptr ? output->stream_stride : 0;
+  w.table = part->d_lanes;
+  w.out_base = reinterpret_cast<uint64_t *>(part->d_lanes + base_at);
+  w.stats_stream = reinterpret_cast<uint32_t *>(part->d_lanes + stats_at);
+  w.out = device_out;
+  w.out_channel_stride = device_out != nullptr ? output->channel_stride : 0;
+  w.channels = e.channels;
+  w.out_float32 = device_out != nullptr && output->sample_type == AAD_HIP_SAMPLE_FLOAT32;
+
+  aad::EncodeRun r = plan->run;
+  r.args.num_streams = (uint32_t)lanes;
+  if (segmented) use_chain_table(&r, reinterpret_cast<const aad::ChainDesc *>(part->d_lanes), (uint32_t)lanes);
+  else r.args.streams = reinterpret_cast<const aad::StreamDesc *>(part->d_lanes);
+  r.args.pcm = static_cast<const int16_t *>(device_samples);
+  r.args.data = device_data;
+  r.rows = aad::RecRows{device_out, w.out_base, w.out_channel_stride};
+  r.rec = device_out != nullptr ? aad::rec_output(output->sample_type) : aad::kRecNone;
+  if (device_stats != nullptr) {
+    r.rec = aad::rec_with_stats(r.rec, device_out != nullptr);
+    r.stats = device_stats;
+    r.stats_stream = segmented ? w.stats_stream : nullptr;
+  }
+  /* The run's device operations, in the stream's order: the resolve kernel (which also zeroes the row tails), [the clear of the
+   * statistics], the encoders.  The start event rides on the first of them and the stop event on the last (aad_launch.h). */
+  aad::tl_launch_signal = aad::LaunchSignal{signal.start, nullptr};
+  aad::launch_window_resolve(w, ctx->stream);
+  if (!hip_ok(ctx, hipGetLastError(), "window resolve launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+  if (device_stats != nullptr && segmented && /* the chains of a window add into its records */
+      !hip_ok(ctx, hipMemsetAsync(device_stats, 0, num_windows * e.channels * sizeof(struct AADHipRowStats), ctx->stream), "hipMemsetAsync"))
+    return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+  const aad::LaunchSignal stop_only = {nullptr, signal.stop};
+  aad::tl_launch_signal = stop_only;
+  return finish_signal(ctx, stop_only, run_encode(ctx, r));
 }
 
 } /* extern "C" */

@@ -195,22 +195,28 @@ inline EncodeLaunch plan_reconstruct_encode(const Device &d, const Knobs &k, con
  * unknown sample type, a non-zero reserved, C > 1 with channel_stride below the longest stream, more than one stream with
  * stream_stride below (C - 1) channel_stride + the longest stream (rows of different streams would overlap), or an end of the rows
  * ((N - 1) stream_stride + (C - 1) channel_stride + the longest stream, in elements or in bytes) past 2^64. */
-inline bool planar_output_ok(uint32_t channels, uint32_t num_streams, const AADHipStreamDesc *streams, const AADHipPlanarOutput *o)
+/* planar_output_rows_ok: for num_streams streams whose longest row has `longest` elements (a window reconstruct run: N windows,
+ * longest = T); planar_output_ok: for a plan's stream table */
+inline bool planar_output_rows_ok(uint32_t channels, uint64_t num_streams, uint64_t longest, const AADHipPlanarOutput *o)
 {
   if (o == nullptr || channels == 0) return false;
   if ((o->sample_type != AAD_HIP_SAMPLE_INT16 && o->sample_type != AAD_HIP_SAMPLE_FLOAT32) || o->reserved != 0) return false;
-  uint64_t longest = 0;
-  for (uint32_t i = 0; i < num_streams; i++) longest = streams[i].num_samples > longest ? streams[i].num_samples : longest;
   if (channels > 1 && o->channel_stride < longest) return false;
   uint64_t span = 0; /* elements from a stream's first to past its last */
   if (__builtin_mul_overflow((uint64_t)(channels - 1), o->channel_stride, &span) || __builtin_add_overflow(span, longest, &span)) return false;
   if (num_streams > 1 && o->stream_stride < span) return false;
   const uint64_t elem = o->sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4u : 2u;
   uint64_t end = 0, bytes = 0;
-  if (num_streams != 0 && (__builtin_mul_overflow((uint64_t)(num_streams - 1), o->stream_stride, &end) ||
+  if (num_streams != 0 && (__builtin_mul_overflow(num_streams - 1, o->stream_stride, &end) ||
                            __builtin_add_overflow(end, span, &end) || __builtin_mul_overflow(end, elem, &bytes)))
     return false;
   return true;
+}
+inline bool planar_output_ok(uint32_t channels, uint32_t num_streams, const AADHipStreamDesc *streams, const AADHipPlanarOutput *o)
+{
+  uint64_t longest = 0;
+  for (uint32_t i = 0; i < num_streams; i++) longest = streams[i].num_samples > longest ? streams[i].num_samples : longest;
+  return planar_output_rows_ok(channels, num_streams, longest, o);
 }
 
 /* Round 4 (tools/size_sweep.py --mapping quad | dense, profiles/r04_decode_split_crossover.txt): the split decoder runs

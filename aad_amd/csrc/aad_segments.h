@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/aad_hip.h"
+#include "aad_windows.h" /* the segment rule: segment_count, segment_cut */
 
 namespace aad {
 
@@ -35,10 +36,7 @@ inline uint64_t stream_blocks(uint32_t num_samples, uint32_t spb) { return ((uin
 inline uint64_t segment_chain_count(const AADHipStreamDesc *streams, uint32_t num_streams, uint32_t spb, uint32_t segment_blocks)
 {
   uint64_t n = 0;
-  for (uint32_t i = 0; i < num_streams; i++) {
-    const uint64_t b = stream_blocks(streams[i].num_samples, spb);
-    n += b == 0 ? 1u : (b + segment_blocks - 1) / segment_blocks;
-  }
+  for (uint32_t i = 0; i < num_streams; i++) n += segment_count(streams[i].num_samples, spb, segment_blocks);
   return n;
 }
 
@@ -56,20 +54,17 @@ inline bool build_segment_chains(const AADHipStreamDesc *streams, uint32_t num_s
   if (count > UINT32_MAX) return false;
   std::vector<ChainDesc> t;
   t.reserve((size_t)count);
-  const uint64_t L = segment_blocks;
   for (uint32_t i = 0; i < num_streams; i++) {
     const AADHipStreamDesc &sd = streams[i];
-    const uint64_t n = sd.num_samples, b = stream_blocks(sd.num_samples, spb);
-    const uint64_t segments = b == 0 ? 1u : (b + L - 1) / L;
+    const uint64_t segments = segment_count(sd.num_samples, spb, segment_blocks);
     for (uint64_t s = 0; s < segments; s++) {
-      const uint64_t kept = s * L, w = warmup_blocks < kept ? warmup_blocks : kept;
-      const uint64_t first_frame = (kept - w) * spb, end_frame = (s + 1) * L * spb < n ? (s + 1) * L * spb : n;
+      const SegmentCut cut = segment_cut(sd.num_samples, spb, segment_blocks, warmup_blocks, s);
       ChainDesc c;
-      c.pcm_offset = sd.pcm_offset + first_frame * (planar ? 1u : channels);
+      c.pcm_offset = sd.pcm_offset + cut.first_frame * (planar ? 1u : channels);
       c.data_offset = sd.data_offset;
-      c.first_block = kept - w;
-      c.num_frames = (uint32_t)(end_frame - first_frame);
-      c.warmup_blocks = (uint32_t)w;
+      c.first_block = cut.first_block;
+      c.num_frames = (uint32_t)(cut.end_frame - cut.first_frame);
+      c.warmup_blocks = cut.warmup_blocks;
       c.header_samples = sd.num_samples;
       c.writes_header = s == 0 ? 1u : 0u;
       t.push_back(c);

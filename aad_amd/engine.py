@@ -174,6 +174,26 @@ class Engine:
         p.segmented = segment_blocks is not None
         return p
 
+    def window_reconstruct_plan(self, param, source_table, channel_stride, dtype, segment_blocks=None, warmup_blocks=0):
+        """A plan over a PCM corpus on the device (AADHip_WindowReconstructPlanCreate): source stream s is num_samples frames whose
+        channel c is the row at pcm_offset + c * channel_stride elements of a torch.int16 or torch.float32 buffer (the other fields
+        of source_table are ignored).  WindowReconstructPlan.run puts crops of it, named by a window table on the device, through
+        the codec: decoded rows, exact error statistics, images, or any subset.  segment_blocks / warmup_blocks as encode_plan."""
+        torch = self.torch
+        if dtype not in (torch.int16, torch.float32):
+            raise ValueError("window reconstruct reads torch.int16 or torch.float32 rows, not %s" % dtype)
+        source_table = np.ascontiguousarray(source_table, dtype=STREAM_DESC_DTYPE)
+        layout = AADHipPlanarLayout(SAMPLE_FLOAT32 if dtype == torch.float32 else SAMPLE_INT16, 0, int(channel_stride))
+        seg = AADHipSegmentation(int(segment_blocks), int(warmup_blocks)) if segment_blocks is not None else None
+        plan = C.c_void_p()
+        _check("AADHip_WindowReconstructPlanCreate",
+               self.lib.AADHip_WindowReconstructPlanCreate(self._ctx, C.byref(param), C.byref(layout),
+                                                           C.byref(seg) if seg is not None else None, len(source_table),
+                                                           source_table.ctypes.data, C.byref(plan)))
+        p = WindowReconstructPlan(self, plan, param, source_table, dtype)
+        p.segmented = segment_blocks is not None
+        return p
+
     def decode_plan(self, header, descs, has_file_header=True):
         descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
         plan = C.c_void_p()
@@ -333,6 +353,55 @@ class Engine:
         finally:
             plan.close()  # synchronises the context's stream first
         result = ([y] if rows else []) + ([images, [int(v) for v in sizes]] if return_images else []) + ([stats] if return_stats else [])
+        return result[0] if len(result) == 1 else tuple(result)
+
+    def reconstruct_windows(self, corpus, windows, frames, param, dtype=None, return_images=False, return_stats=False,
+                            num_samples=None, segment_blocks=None, warmup_blocks=0):
+        """corpus: int16 or float32 cuda tensor [S, C, T_total] (a view with corpus.stride(-1) == 1 is fine); windows: int64 cuda
+        tensor [N, 2] of (stream, first_frame), never read on the host -> a new [N, C, frames] tensor of `dtype` (default
+        corpus.dtype): crop w = corpus[stream, :, first_frame:first_frame + frames] after the codec, as reconstruct_planar gives it
+        for the gathered crops, zero where the crop runs past its stream (num_samples: per-stream lengths <= T_total, default
+        T_total) and all zero for a stream index past S.  No gather and no copy of the batch: a kernel writes the encoders' tables
+        from the windows where they are.  The call makes a plan and closes it, which synchronises the engine's stream, as
+        reconstruct_planar does; a training loop keeps a window_reconstruct_plan and calls its run, which is asynchronous.  return_images=True: (y, images, stride) with window w's image at the
+        start of images[w] (its length follows from bytes 14..17, or from the statistics' count); return_stats=True appends the
+        int64 [N, C, 4] statistics of reconstruct_planar."""
+        return self._reconstruct_windows("reconstruct_windows", corpus, windows, frames, param, dtype, num_samples, segment_blocks,
+                                         warmup_blocks, True, return_images, return_stats)
+
+    def codec_error_windows(self, corpus, windows, frames, param, num_samples=None, segment_blocks=None, warmup_blocks=0):
+        """The statistics of reconstruct_windows(..., return_stats=True) alone - int64 [N, C, 4] - with no rows or images allocated."""
+        return self._reconstruct_windows("codec_error_windows", corpus, windows, frames, param, None, num_samples, segment_blocks,
+                                         warmup_blocks, False, False, True)
+
+    def _reconstruct_windows(self, what, corpus, windows, frames, param, dtype, num_samples, segment_blocks, warmup_blocks, rows,
+                             return_images, return_stats):
+        torch = self.torch
+        if corpus.dim() != 3 or not corpus.is_cuda or corpus.dtype not in (torch.int16, torch.float32):
+            raise ValueError("%s takes an int16 or float32 cuda tensor [S, C, T_total]" % what)
+        s, ch, t = (int(v) for v in corpus.shape)
+        if ch != param.num_channels:
+            raise ValueError("the corpus has %d channels, the parameter %d" % (ch, param.num_channels))
+        if corpus.stride(-1) != 1:
+            raise ValueError("%s needs corpus.stride(-1) == 1 (each channel's samples contiguous); got strides %s"
+                             % (what, tuple(corpus.stride())))
+        lengths = np.full(s, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
+        if len(lengths) != s or (s and (lengths.min() < 0 or lengths.max() > t)):
+            raise ValueError("num_samples: %d lengths in [0, %d]" % (s, t))
+        d = np.zeros(s, dtype=STREAM_DESC_DTYPE)
+        d["pcm_offset"] = np.arange(s, dtype=np.uint64) * np.uint64(corpus.stride(0))
+        d["num_samples"] = lengths
+        plan = self.window_reconstruct_plan(param, d, corpus.stride(1), corpus.dtype, segment_blocks, warmup_blocks)
+        try:
+            n = int(windows.shape[0])
+            stride = _round_up(self.encoded_size(param, int(frames)), 64)
+            images = torch.empty((n, stride), dtype=torch.uint8, device=corpus.device) if return_images else None
+            stats = torch.empty((n, ch, 4), dtype=torch.int64, device=corpus.device) if return_stats else None
+            y = plan.run(corpus, windows, frames, dtype=corpus.dtype if dtype is None else dtype, data=images, stats=stats) if rows \
+                else plan.run(corpus, windows, frames, out=False, data=images, stats=stats)
+        finally:
+            plan.close()  # synchronises the context's stream first
+        result = ([y] if rows else []) + ([images, stride] if return_images else []) + ([stats] if return_stats else [])
         return result[0] if len(result) == 1 else tuple(result)
 
     def decode_uniform(self, data, image_size):
@@ -591,6 +660,66 @@ class PlanarReconstructPlan(EncodePlan):
                    self.engine.lib.AADHip_PlanarReconstructPlanRun(self.handle, x.data_ptr(), data.data_ptr(), out.data_ptr(), sp))
         if ordered:
             self.engine._exit(cur)
+
+
+class WindowReconstructPlan(EncodePlan):
+    def __init__(self, engine, handle, param, source_table, dtype):
+        super().__init__(engine, handle, param, source_table)
+        self.dtype = dtype
+
+    def run(self, x, windows, frames, out=None, dtype=None, data=None, stats=None, ordered=True):
+        """x: the corpus, a cuda tensor of the plan's dtype (the source table's pcm_offsets count from x.data_ptr()); windows: int64
+        cuda tensor [N, 2] of (stream, first_frame), never read on the host; frames: T.  Returns the rows.
+        out: None allocates a contiguous [N, C, T] tensor of `dtype` (default: the plan's dtype); False writes no rows; else a
+        torch.int16 or torch.float32 cuda tensor [N, C, T] with out.stride(-1) == 1, written in place, every element of it.
+        data: None (the images stay in the engine's scratch) or a uint8 cuda tensor [N, stride >= the image of T frames];
+        stats: None or a contiguous int64 cuda tensor [N, C, 4].  At least one of the three.  ordered as EncodePlan.run."""
+        torch = self.engine.torch
+        if x.dtype != self.dtype or not x.is_cuda:
+            raise ValueError("this plan reads %s cuda rows, not %s" % (self.dtype, x.dtype))
+        if windows.dtype != torch.int64 or windows.dim() != 2 or windows.shape[1] != 2 or not windows.is_cuda:
+            raise ValueError("windows: an int64 cuda tensor [N, 2] of (stream, first_frame)")
+        windows = windows.contiguous()
+        n, ch, frames = int(windows.shape[0]), int(self.param.num_channels), int(frames)
+        if out is None:
+            out = torch.empty((n, ch, frames), dtype=self.dtype if dtype is None else dtype, device=windows.device)
+        elif out is False:
+            out = None
+        if out is not None:
+            if out.dtype not in (torch.int16, torch.float32) or (dtype is not None and out.dtype != dtype) or not out.is_cuda or \
+                    tuple(out.shape) != (n, ch, frames) or (frames > 1 and out.stride(-1) != 1):
+                raise ValueError("out: a torch.int16 or torch.float32 cuda tensor [%d, %d, %d] with stride(-1) == 1" % (n, ch, frames))
+        if out is None and data is None and stats is None:
+            raise ValueError("nothing to write: out, data and stats are all absent")
+        image_stride = 0
+        if data is not None:
+            if data.dtype != torch.uint8 or not data.is_cuda or data.dim() != 2 or int(data.shape[0]) != n or (n and data.stride(1) != 1):
+                raise ValueError("data: a uint8 cuda tensor [%d, stride]" % n)
+            if int(data.shape[1]) < self.engine.encoded_size(self.param, frames):
+                raise ValueError("data: rows of %d bytes, the image of %d frames has %d"
+                                 % (int(data.shape[1]), frames, self.engine.encoded_size(self.param, frames)))
+            image_stride = int(data.stride(0))
+        if stats is not None and (stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous() or
+                                  tuple(stats.shape) != (n, ch, 4)):
+            raise ValueError("stats: a contiguous int64 cuda tensor %s" % ((n, ch, 4),))
+        output = None
+        if out is not None:
+            output = AADHipPlanarOutput(SAMPLE_FLOAT32 if out.dtype == torch.float32 else SAMPLE_INT16, 0,
+                                        int(out.stride(0)) if n > 1 else ch * frames, int(out.stride(1)) if ch > 1 else frames)
+        cur = self.engine._enter() if ordered else None
+        _check("AADHip_WindowReconstructPlanRun",
+               self.engine.lib.AADHip_WindowReconstructPlanRun(
+                   self.handle, x.data_ptr(), n, windows.data_ptr(), frames, image_stride, data.data_ptr() if data is not None else None,
+                   C.byref(output) if output is not None else None, out.data_ptr() if out is not None else None,
+                   stats.data_ptr() if stats is not None else None))
+        if ordered:
+            self.engine._exit(cur)
+        return out
+
+    def close(self):
+        if self.handle:
+            self.engine.lib.AADHip_WindowReconstructPlanDestroy(self.handle)
+            self.handle = None
 
 
 class DecodePlan:

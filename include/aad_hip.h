@@ -71,7 +71,7 @@ const char *AADHip_ContextLastError(const struct AADHipContext *context);
 
 /* Cross-stream ordering and kernel timing without packets of their own.  `hip_start_event` / `hip_stop_event` (hipEvent_t the
  * caller owns; either may be NULL, both NULL withdraws) are recorded when the work of the NEXT AADHip_EncodePlanRun /
- * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
+ * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_WindowReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
  * the run takes them.  An encode, decode or window decode plan run is one kernel, and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
  * stop events) instead of on barrier packets around it: a hipEventRecord behind every launch of a back-to-back sequence costs
  * the queue 2.9 us per launch on MI355X, the attached event nothing (profiles/r03_microbench_event_gap.txt), and
@@ -359,6 +359,71 @@ AADApiResult AADHip_PlanarReconstructPlanRunStats(
     void *device_out,                     /* may be NULL here: statistics and images only */
     struct AADHipLaneState *device_state,
     struct AADHipRowStats *device_stats); /* N * C records, 8-byte aligned, every one written by the run */
+
+/* ---- window reconstruct: device-drawn crops of a PCM corpus through the codec ------------------------------------------------- */
+
+/* The write side of window decode: crops named by a window table IN DEVICE MEMORY (the host never reads it), read where they lie
+ * in a corpus of planar int16 / float32 rows and run through the encoder - the planar reconstruct kernels, whose per-lane tables a
+ * small kernel writes on the device from the windows.  No gather and no copy of the batch; a run is asynchronous on the context's
+ * stream (one that needs larger tables than any run of the plan before it waits for the stream once, to replace them).
+ *
+ * Definition.  A plan holds an encode parameter, an optional segmentation, the input layout (sample type and channel_stride) and a
+ * SOURCE TABLE of S streams, of which two fields are read: pcm_offset, the element that starts channel 0's row of source stream s
+ * (channel c's row channel_stride * c elements further on), and num_samples = n_s, which may be 0.  A run takes the corpus, N
+ * windows {stream, first_frame}, T = frames_per_window and its outputs.  For window w let
+ *     len_w = 0                            if stream >= S or first_frame >= n_s
+ *           = min(T, n_s - first_frame)    otherwise.
+ * Huge or "negative" (wrapped int64) values are not an error: they give len_w = 0 and read nothing.
+ *   len_w > 0:  the run writes exactly what AADHip_PlanarReconstructPlanRunStats writes for a plan with the same parameter,
+ *     segmentation and input layout and fresh encoders in which stream w has num_samples = len_w, pcm_offset = the source's
+ *     pcm_offset + first_frame, its image at data_offset = w * image_stride and its rows at
+ *     w * output->stream_stride + c * output->channel_stride: the image bytes, the rows and the AADHipRowStats records w * C + c.
+ *   len_w == 0: the image is the 31-byte file header with num_samples = 0 and no block; the four statistics fields are 0.
+ *   Every row element t in [len_w, T) is written as zero: an [N, C, T] output is fully defined, as window decode's is.
+ * Window w's length can be read from its records' `count`, or from bytes 14..17 of its image.
+ * No byte outside the 31 + blocks(len_w) image bytes, the C rows of T elements and the C records of a window is touched.
+ * Reads: no source element outside [first_frame, first_frame + len_w) of the window's C rows is read.  That is the rule of every
+ * planar plan with ragged streams, and it holds because the planar kernels have no look-ahead past a stream's end: they load whole
+ * 16-sample chunks only where all sixteen are the stream's, clamp every prefetch to the stream's last whole chunk, and read the
+ * samples behind it one by one (the trial search looks one block BACK, inside the lane's own frames).  A crop next to another
+ * stream's rows, or to the corpus's last element, is safe.
+ *
+ * Outputs.  Each of device_data, device_out and device_stats may be NULL, but not all three: images, rows, statistics or any
+ * subset.  The encoders always write images; when they are not wanted they go to scratch that the context owns (grow-only, as the
+ * trial scratch) and image_stride is ignored.  `output` may be NULL with device_out.
+ * Not supported: carried state (crops start from fresh encoders) and interleaved sources of more than one channel (mono int16 IS
+ * the interleaved layout, as elsewhere).
+ *
+ * The plan is an ordinary AADHipEncodePlan of a kind of its own: every other ...PlanRun refuses it and
+ * AADHip_WindowReconstructPlanRun refuses every other plan (AAD_APIRESULT_INVALID_ARGUMENT); AADHip_EncodePlanDestroy destroys it
+ * too.  One plan serves any N, any T and any output sample type; its device tables (one record per window and chain of the
+ * uniform launch: N * ceil(blocks(T) / L) lanes, N unsegmented) grow when needed, on the context's stream.
+ * Errors.  Create: those of AADHip_PlanarEncodePlanCreate for the parameter, layout and segmentation, AAD_APIRESULT_INVALID_ARGUMENT
+ * for C > 1 with channel_stride below the longest n_s and for a source row end (pcm_offset + (C - 1) channel_stride + n_s) that
+ * overflows 64 bits in elements or bytes.  Run: AAD_APIRESULT_INVALID_ARGUMENT for T == 0, all three outputs NULL while N > 0, with device_data
+ * an image_stride < AADHip_CalculateEncodedSize(parameter, T) while N > 1 or images past 64 bits, with device_out a null or
+ * refused `output` (sample type, reserved; rows of T elements that overlap or end past 64 bits, as the planar reconstruct plan's
+ * rule with "longest" = T), more than UINT32_MAX lanes, device_out == device_samples, and, while N > 0, a null corpus, a null or
+ * not 8-byte aligned window table or a not 8-byte aligned statistics table.  N == 0 is OK and launches nothing.
+ * AADHip_ContextSignalNextRun: a run is several device operations - the resolve kernel (which also zeroes the row tails), the
+ * clear of the statistics table (segmented, with device_stats), the encoder kernel.  The start event sits in front of the first
+ * (it rides on the resolve kernel) and the stop event rides on the last, the encoder kernel.  A run that fails leaves the events
+ * unsettled: refused arguments record neither, a HIP failure after the resolve launch may leave the start event recorded and the
+ * stop event not - wait for neither after a failed run. */
+AADApiResult AADHip_WindowReconstructPlanCreate(
+    struct AADHipContext *context, const struct AADEncodeParameter *parameter,
+    const struct AADHipPlanarLayout *input_layout,
+    const struct AADHipSegmentation *segmentation, /* NULL: the serial (reference-exact) encode */
+    uint32_t num_source_streams, const struct AADHipStreamDesc *source_streams,
+    struct AADHipEncodePlan **plan);
+void AADHip_WindowReconstructPlanDestroy(struct AADHipEncodePlan *plan);
+AADApiResult AADHip_WindowReconstructPlanRun(
+    struct AADHipEncodePlan *plan, const void *device_samples,
+    uint64_t num_windows, const struct AADHipWindow *device_windows, /* device memory, 8-byte aligned: a torch int64 [N, 2] tensor */
+    uint32_t frames_per_window,
+    uint64_t image_stride, uint8_t *device_data, /* NULL: the images go to the context's scratch */
+    const struct AADHipPlanarOutput *output, void *device_out, /* NULL (both may be): no rows */
+    struct AADHipRowStats *device_stats);        /* NULL: no statistics; else N * C records, 8-byte aligned */
 
 /* ---- host-memory convenience (stage -> run -> copy back, synchronous) ---------------------- */
 
