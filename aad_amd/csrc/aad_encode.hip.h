@@ -351,7 +351,7 @@ struct EncodeArgs {
 /* Input layouts of encode_streams_kernel (its IN): channel-interleaved int16 frames (AADHip_EncodePlanRun), or one row per
  * channel of int16 or float32 samples (AADHip_PlanarEncodePlanRun) - row c of a stream at pcm_offset + c * channel_stride.
  * Every read of PCM goes through the layout's cursor (PcmCursor) and its chunk loads (ChunkSamples / PlanarChunk, the quad
- * encoder's Raw / PlanarRaw); the chunk bodies downstream see the same packed words either way.  A float32 sample becomes the
+ * encoder's PlanarRaw); the chunk bodies downstream see the same packed words either way.  A float32 sample becomes the
  * int16 the encoder sees (pcm_from_f32, aad_pcm_convert.h) as its chunk is unpacked, off the recurrence. */
 enum PcmLayout { kInInterleaved = 0, kInPlanarI16 = 1, kInPlanarF32 = 2 };
 template <int IN> using PcmElem = std::conditional_t<IN == kInPlanarF32, float, int16_t>;
@@ -618,14 +618,15 @@ struct PlanarChunk {
   }
 };
 
-/* the quad encoder's chunk as loaded (run_block's Raw) for planar input without M/S: the lane's own row, 16 samples.  The body
- * reads them as kPairs words (pack); int16 rows are those words already. */
-template <typename T>
+/* the quad encoder's chunk as loaded (run_block) without M/S.  Planar input: the lane's own row, 16 samples; the body reads them
+ * as kPairs words (pack), int16 rows are those words already.  Interleaved input (T = int16_t): the chunk's 32 (mono) / 64
+ * (stereo) bytes, W = 8 / 16, which the body reads as they are. */
+template <typename T, int W = 16 * (int)sizeof(T) / 4>
 struct PlanarRaw {
-  static constexpr int kWords = 16 * (int)sizeof(T) / 4;
+  static constexpr int kWords = W;
   static constexpr int kParts = kWords / 4; /* 16-byte loads */
   uint32_t d[kWords];
-  __device__ __forceinline__ void load_part(const T *x, int k)
+  __device__ __forceinline__ void load_part(const T *x, int k) /* k compile-time after unrolling */
   {
     const u32x4 a = reinterpret_cast<const U32x4 *>(x + (16 / (int)sizeof(T)) * k)->v;
     d[4 * k] = a.x; d[4 * k + 1] = a.y; d[4 * k + 2] = a.z; d[4 * k + 3] = a.w;
@@ -1278,21 +1279,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
        * is left to the tail loop - its channel-1 load would read two bytes past the stream. */
       /* planar: the lane's own row, read as pairs whatever the channel count (PlanarRaw) */
       constexpr int FMT = IN != kInInterleaved || CHF == 1 ? kPairs : kFrames;
-      constexpr int kParts = IN != kInInterleaved ? PlanarRaw<PcmElem<IN>>::kParts : (CHF == 1 ? 2 : 4); /* 16-byte loads per chunk */
-      struct Raw { /* one chunk as loaded: 32 (mono) / 64 (stereo) bytes */
-        uint32_t d[CHF == 1 ? 8 : 16];
-        __device__ __forceinline__ void load_part(const int16_t *x, int k) /* k compile-time after unrolling */
-        {
-          const u32x4 a = reinterpret_cast<const U32x4 *>(x + 8 * k)->v;
-          d[4 * k] = a.x; d[4 * k + 1] = a.y; d[4 * k + 2] = a.z; d[4 * k + 3] = a.w;
-        }
-        __device__ __forceinline__ void load(const int16_t *x)
-        {
-#pragma unroll
-          for (int k = 0; k < kParts; k++) load_part(x, k);
-        }
-      };
-      using RawT = std::conditional_t<IN == kInInterleaved, Raw, PlanarRaw<PcmElem<IN>>>;
+      using RawT = std::conditional_t<IN == kInInterleaved, PlanarRaw<int16_t, (CHF == 1 ? 8 : 16)>, PlanarRaw<PcmElem<IN>>>;
       uint32_t chunks = full;
       if (IN == kInInterleaved && CHF == 2 && chunks && chunks * kChunk == coded && first + n >= (uint64_t)src.total) chunks--;
       auto rp = lane_row<CHF>(xp, c);
@@ -1332,7 +1319,7 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
         auto fill = [&](auto jc) {
           constexpr int j = decltype(jc)::value;
           if constexpr (kStaged) {
-            if constexpr (j < kParts) incoming.load_part(rp, j); /* prefetch chunk k+2 (clamped to the last full one) */
+            if constexpr (j < RawT::kParts) incoming.load_part(rp, j); /* prefetch chunk k+2 (clamped to the last full one) */
             /* lane c writes bytes 8c..8c+7 of the pair's sixteen: a0 b0 a1 b1 | a2 b2 a3 b3 of word c of both
              * channels; it has its own word c and needs the partner's */
             if constexpr (j == 4) { st_send = c ? wp0 : wp1; pin(st_send); }
@@ -1420,27 +1407,9 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
         if (k + 1 < full) one(k + 1, xn, x);
       }
       done = full * kChunk;
-    } else if constexpr (RING && CHF == 2 && BITS == 4) {
-      /* dense stereo 4-bit through the byte ring: the same chunk body as the burst path below, the lane's eight bytes appended */
-      constexpr bool PK = !MS;
-      constexpr int kN = PK ? kChunk / 2 : kChunk;
-      const uint32_t pair_sel = c ? 0x07060302u : 0x05040100u;
-      for (uint32_t k = 0; k < full; k++) {
-        int32_t x[kN];
-#pragma unroll
-        for (int j = 0; j < kN; j++) x[j] = PK ? (int32_t)next.pair(j, pair_sel) : next.get(j, c);
-        if (k + 1 < full) xp += (uint64_t)kChunk * (IN == kInInterleaved ? ch : 1u);
-        next.load(xp, ch, c);
-        uint32_t w[2] = {0, 0};
-        encode_chunk16<BITS, EMIT, PK>(L, x, lds, w, last_qd, sq);
-        next.touch();
-        uint32_t d0, d1;
-        chunk_bytes<BITS, CHF>(w, c, d0, d1);
-        ring->template append<8>(d0, d1, ring_sel);
-      }
-      done = full * kChunk;
-    } else if constexpr (kBurstStores<BITS, CHF, EMIT>) {
-      /* Dense stereo 4-bit, the saturated BASELINE shape.  A pair of lanes produces 16 code bytes per
+    } else if constexpr (kBurstStores<BITS, CHF, EMIT> && !RING) {
+      /* Dense stereo 4-bit, the saturated BASELINE shape (through the byte ring it takes the generic path below: the same chunk
+       * body, the lane's eight bytes appended).  A pair of lanes produces 16 code bytes per
        * chunk; stored chunk by chunk, the four stores that fill a 64-byte granule are a chunk's worth of
        * time apart (microseconds on a full chip), the granule leaves the L2 in between and every store
        * reaches memory as a write of its own: WRITE_SIZE was 4.0x the code bytes.  So the pieces of FOUR
@@ -1763,38 +1732,29 @@ __device__ __forceinline__ int64_t run_block(S &L, const SampleSource<MS, IN> &s
     if (burst_rest >= 1) put(burst_gp + 16 * (burst_rest - 1), burst_r2);
     uint8_t *up = body + (uint64_t)(done / US) * unit_stride + (uint64_t)c * UB;
     for (uint32_t u = 0; u < units; u++, up += unit_stride, tail >>= 8) up[0] = (uint8_t)tail;
-  } else if constexpr (PASS == kPassBoth) {
-    /* both at once: lanes that measure stop at the last real sample, lanes that encode pad the last unit
-     * with zero samples (the four taps of a recurrence agree, so the DPP traffic of a step stays whole) */
+  } else if constexpr (EMIT) { /* tail units: samples past n are zero padding - reference :592-593 */
     uint8_t *up = body + (uint64_t)(done / US) * unit_stride + (uint64_t)c * UB;
     for (uint32_t i = done; i < coded; i += US, up += unit_stride) {
       uint32_t acc = 0;
 #pragma unroll
       for (int k = 0; k < US; k++) {
-        const bool real = i + k < coded;
-        uint32_t code = 0;
-        if (real || pad) {
-          int32_t qd;
-          code = encode_step<BITS>(L, real ? src.at(first + kTaps + i + k) : 0, lds, qd);
-          last_qd = qd;
-          if (real) sq += wrapped_square(qd);
+        if constexpr (PASS == kPassBoth) {
+          /* both at once: lanes that measure stop at the last real sample, lanes that encode pad the last unit
+           * with zero samples (the four taps of a recurrence agree, so the DPP traffic of a step stays whole) */
+          const bool real = i + k < coded;
+          uint32_t code = 0;
+          if (real || pad) {
+            int32_t qd;
+            code = encode_step<BITS>(L, real ? src.at(first + kTaps + i + k) : 0, lds, qd);
+            last_qd = qd;
+            if (real) sq += wrapped_square(qd);
+          }
+          acc = (acc << BITS) | code;
+        } else {
+          const int32_t x = i + k < coded ? src.at(first + kTaps + i + k) : 0;
+          acc = (acc << BITS) | encode_step<BITS>(L, x, lds, last_qd);
+          if constexpr (REC) rec->one(first + kTaps + i + k, newest_sample(L), i + k < coded);
         }
-        acc = (acc << BITS) | code;
-      }
-      if (writer) {
-#pragma unroll
-        for (int k = 0; k < UB; k++) up[k] = (uint8_t)(acc >> (8 * (UB - 1 - k)));
-      }
-    }
-  } else if (EMIT) { /* tail units: samples past n are zero padding - reference :592-593 */
-    uint8_t *up = body + (uint64_t)(done / US) * unit_stride + (uint64_t)c * UB;
-    for (uint32_t i = done; i < coded; i += US, up += unit_stride) {
-      uint32_t acc = 0;
-#pragma unroll
-      for (int k = 0; k < US; k++) {
-        const int32_t x = i + k < coded ? src.at(first + kTaps + i + k) : 0;
-        acc = (acc << BITS) | encode_step<BITS>(L, x, lds, last_qd);
-        if constexpr (REC) rec->one(first + kTaps + i + k, newest_sample(L), i + k < coded);
       }
       if (writer) {
 #pragma unroll
@@ -1820,7 +1780,7 @@ __device__ __forceinline__ double rmse_pass(S &L, const SampleSource<MS, IN> &sr
   if (n < (uint32_t)kTaps) return 0.0;
   if constexpr (QUAD) seed_history(L, src, first, n, tap); else seed_history(L, src, first, n);
   int32_t qd_unused = 0;
-  const int64_t sum = run_block<BITS, CHF, MS, QUAD, false>(L, src, first, n, ch, c, false, nullptr, lds, qd_unused);
+  const int64_t sum = run_block<BITS, CHF, MS, QUAD, kPassRmse>(L, src, first, n, ch, c, false, nullptr, lds, qd_unused);
   return sqrt((double)sum / (double)n);
 }
 
@@ -2073,10 +2033,10 @@ __device__ __forceinline__ void encode_block_dual(Lane &F, int32_t &last_qd, con
  * segmented plans set ring_ok = 0); the dual trial search has three scratch slots per chain; no state is read or written.
  *
  * IN (PcmLayout): interleaved int16 frames, or planar int16 / float32 rows (AADHip_PlanarEncodePlanRun; arguments
- * PlanarEncodeArgs, instantiated in aad_encode_planar.hip).  Only the reads of PCM differ; see "Input layouts" above.
+ * PlanarEncodeArgs, instantiated in aad_encode_units.hip).  Only the reads of PCM differ; see "Input layouts" above.
  */
 /*
- * REC (RecOutput; arguments RecEncodeArgs, instantiated in aad_encode_reconstruct.hip): the encode pass also writes the decoded rows
+ * REC (RecOutput; arguments RecEncodeArgs, instantiated in aad_encode_units.hip): the encode pass also writes the decoded rows
  * (RecRow) - the header samples of every kept block here, the coded samples in run_block.  Never with the dual trial search (its
  * candidates are encoded into slots) or the byte ring: the launch policy plans neither for these kernels.
  */
@@ -2248,8 +2208,8 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(KernelArgsFor<IN, R
     const uint32_t deferred = write_block_header(F, out + block_off + (uint64_t)c * kBlockHeaderBytesPerCh, writer, defer3);
     if constexpr (QUAD) L = to_quad(F, tap); else L = F;
     AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
-    if constexpr (REC == kRecNone) (void)run_block<BITS, CHF, MS, QUAD, true>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred);
-    else (void)run_block<BITS, CHF, MS, QUAD, true>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred, true, nullptr, &rec);
+    if constexpr (REC == kRecNone) (void)run_block<BITS, CHF, MS, QUAD, kPassEncode>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred);
+    else (void)run_block<BITS, CHF, MS, QUAD, kPassEncode>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred, true, nullptr, &rec);
     if constexpr (QUAD) F = from_quad<kEncTM>(L); else F = L;
     }
     }

@@ -1,7 +1,7 @@
 /* aad_encode_launch.hip.h - what one encode run is (EncodeRun) and the way from it and its launch plan (aad_launch_policy.h) to
  * an instantiation of encode_streams_kernel: launch_encode_run<IN, REC>, one instantiation per input layout IN and output REC
- * (aad_encode.hip.h).  aad_hip_engine.hip instantiates the interleaved kernels, aad_encode_planar.hip the planar ones,
- * aad_encode_reconstruct.hip the planar reconstruct ones (REC), aad_encode_stats.hip those with statistics. */
+ * (aad_encode.hip.h).  aad_hip_engine.hip instantiates the interleaved kernels, aad_encode_units.hip every other pair:
+ * the planar ones, the planar reconstruct ones (REC) and those with statistics, one object per pair. */
 #ifndef AAD_ENCODE_LAUNCH_HIP_H
 #define AAD_ENCODE_LAUNCH_HIP_H
 
@@ -101,25 +101,21 @@ void launch_encode_run(const EncodeRun &r, const EncodeLaunch &p, hipStream_t st
   else by_bits(std::false_type{});
 }
 
-/* Every pair but the interleaved encoders is instantiated by a unit of its own (aad_encode_planar.hip,
- * aad_encode_reconstruct.hip: one object per sample type, see the Makefile), so that the kernels build side by side. */
+/* Every pair but the interleaved encoders is instantiated by an object of its own (aad_encode_units.hip, compiled once per input
+ * sample type and REC, see the Makefile), so that the kernels build side by side.  With a REC the int16-input objects hold
+ * IN = kInInterleaved as well. */
 extern template void launch_encode_run<kInPlanarI16, kRecNone>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
 extern template void launch_encode_run<kInPlanarF32, kRecNone>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
-extern template void launch_encode_run<kInInterleaved, kRecI16>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
-extern template void launch_encode_run<kInInterleaved, kRecF32>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
-extern template void launch_encode_run<kInPlanarI16, kRecI16>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
-extern template void launch_encode_run<kInPlanarI16, kRecF32>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
-extern template void launch_encode_run<kInPlanarF32, kRecI16>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
-extern template void launch_encode_run<kInPlanarF32, kRecF32>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
-/* ... and the statistics kernels (aad_encode_stats.hip): one object per input sample type and kind of output */
-#define AAD_EXTERN_STATS_RUN(REC)                                                                                  \
+#define AAD_EXTERN_REC_RUN(REC)                                                                                    \
   extern template void launch_encode_run<kInInterleaved, REC>(const EncodeRun &, const EncodeLaunch &, hipStream_t); \
   extern template void launch_encode_run<kInPlanarI16, REC>(const EncodeRun &, const EncodeLaunch &, hipStream_t);   \
   extern template void launch_encode_run<kInPlanarF32, REC>(const EncodeRun &, const EncodeLaunch &, hipStream_t);
-AAD_EXTERN_STATS_RUN(kRecI16Stats)
-AAD_EXTERN_STATS_RUN(kRecF32Stats)
-AAD_EXTERN_STATS_RUN(kRecStatsOnly)
-#undef AAD_EXTERN_STATS_RUN
+AAD_EXTERN_REC_RUN(kRecI16)
+AAD_EXTERN_REC_RUN(kRecF32)
+AAD_EXTERN_REC_RUN(kRecI16Stats)
+AAD_EXTERN_REC_RUN(kRecF32Stats)
+AAD_EXTERN_REC_RUN(kRecStatsOnly)
+#undef AAD_EXTERN_REC_RUN
 
 } /* namespace aad */
 

@@ -3,7 +3,7 @@
  * contexts, plans (uploaded stream tables), kernel launches and the host-memory convenience
  * calls.  Device code lives in aad_encode.hip.h / aad_decode.hip.h (shared parts: aad_device.hip.h)
  * and, for the split, sector-tiled and window decoders and the planar-input and planar reconstruct encoders, in units of their own
- * (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_planar.hip, aad_encode_reconstruct.hip; the
+ * (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_units.hip - one object per input type and REC; the
  * window reconstruct run's resolve kernel: aad_window_reconstruct.hip).  Every
  * kind of encode plan is made by encode_plan_create and run by encode_plan_run over one description of a run (aad::EncodeRun,
  * aad_encode_launch.hip.h), which the host-memory paths build directly.  gfx950 only; no CPU code path - every entry point that
