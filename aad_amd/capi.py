@@ -97,6 +97,7 @@ HIP_SYMBOLS = [
     "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate", "AADHip_SegmentedEncodeBatch",
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
+    "AADHip_MixedWindowDecodePlanCreate",
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
     "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
     "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
@@ -203,6 +204,8 @@ def _declare_hip(lib):
     lib.AADHip_DecodePlanRun.restype = C.c_int
     lib.AADHip_WindowDecodePlanCreate.argtypes = [vp, C.POINTER(AADHeaderInfo), C.c_int32, C.c_uint32, vp, C.POINTER(vp)]
     lib.AADHip_WindowDecodePlanCreate.restype = C.c_int
+    lib.AADHip_MixedWindowDecodePlanCreate.argtypes = [vp, C.c_uint32, C.c_int32, C.c_uint32, vp, vp, C.POINTER(vp)]
+    lib.AADHip_MixedWindowDecodePlanCreate.restype = C.c_int
     lib.AADHip_WindowDecodePlanDestroy.argtypes = [vp]
     lib.AADHip_WindowDecodePlanDestroy.restype = None
     lib.AADHip_WindowDecodePlanRun.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp]

@@ -20,6 +20,7 @@
 #define AAD_DECODE_WINDOW_HIP_H
 
 #include "aad_decode.hip.h"
+#include "aad_launch_policy.h" /* StreamFormat */
 
 namespace aad {
 
@@ -87,9 +88,13 @@ struct WindowRow {
   }
 };
 
-/* CHF: 1 / 2 = the mono / stereo fast paths (wide chunk loads), 0 = any channel count (byte loads) */
-template <int BITS, int CHF, bool MS, bool F32>
-__device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane)
+/* CHF: 1 / 2 = the mono / stereo fast paths (wide chunk loads), 0 = any channel count (byte loads).
+ * MIXED (aad_decode_window_mixed.hip.h): the block geometry comes from the stream's record in `formats`, not from the launch, and
+ * the lane leaves when its stream belongs to another kernel variant - a decision per window, so the lanes of a channel pair take
+ * it together.  Windows whose stream is out of range are written (as zeros) by the launch that `owns_strays`. */
+template <int BITS, int CHF, bool MS, bool F32, bool MIXED = false>
+__device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane, const StreamFormat *formats = nullptr,
+                                            uint32_t owns_strays = 0)
 {
   const uint32_t ch = CHF ? CHF : a.channels;
   const uint64_t per_window = (uint64_t)a.blocks_per_window * ch;
@@ -97,7 +102,19 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
   const uint32_t r = (uint32_t)(lane - w * per_window);
   const uint32_t k = r / ch, c = r - k * ch;
   const uint64_t stream = a.windows[2 * w], first_frame = a.windows[2 * w + 1];
-  const uint64_t spb = a.samples_per_block, frames = a.frames;
+  uint64_t spb = a.samples_per_block;
+  uint32_t block_size = a.block_size;
+  if constexpr (MIXED) {
+    if (stream < a.num_streams) {
+      const StreamFormat f = formats[stream];
+      if (f.bits != BITS || (f.mid_side != 0) != MS) return;
+      spb = f.samples_per_block;
+      block_size = f.block_size;
+    } else if (!owns_strays) {
+      return;
+    }
+  }
+  const uint64_t frames = a.frames;
   const uint64_t phase = first_frame % spb;
   const uint64_t kspb = (uint64_t)k * spb;
   if (kspb >= frames + phase) return; /* past the window's last block: lanes of one (window, block) leave together */
@@ -121,7 +138,7 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
         n = (uint32_t)(left < need ? left : need);
       }
       /* bytes of this stream still present from the start of this block */
-      const uint64_t block_off = a.header_bytes + b * a.block_size;
+      const uint64_t block_off = a.header_bytes + b * block_size;
       const uint64_t avail64 = sd.data_size > block_off ? sd.data_size - block_off : 0;
       avail = avail64 > 0x7FFFFFFFu ? 0x7FFFFFFFu : (uint32_t)avail64;
       src = a.data + sd.data_offset + block_off;

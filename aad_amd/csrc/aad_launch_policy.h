@@ -386,6 +386,81 @@ inline WindowLaunch plan_window_decode(const Device &d, const Knobs &k, const Wi
   return p;
 }
 
+/* ---- mixed-format window decode (AADHip_MixedWindowDecodePlanCreate): one launch per kernel variant of the plan ------------- */
+/* what a lane reads of its stream's format, one record per stream next to the descriptor table (device memory) */
+struct StreamFormat {
+  uint32_t samples_per_block;
+  uint16_t block_size;
+  uint8_t bits;
+  uint8_t mid_side; /* 1: the M/S instantiation decodes this stream (two channels and the M/S method), else 0 */
+};
+static_assert(sizeof(StreamFormat) == 8, "per-stream format record");
+
+/* mid/side is a kernel variant for two channels only: every other channel count runs the L/R instantiation whatever the method
+ * says, as launch_decode_window does (the plan's validation refuses M/S there anyway) */
+inline StreamFormat stream_format_of(const struct AADHeaderInfo &h, uint32_t channels)
+{
+  return StreamFormat{h.num_samples_per_block, h.block_size, (uint8_t)h.bits_per_sample,
+                      (uint8_t)(channels == 2 && h.ch_process_method == AAD_CH_PROCESS_METHOD_MS)};
+}
+
+/* a kernel variant of a plan: the template parameters its streams need, and the smallest block among them (the launch's K) */
+struct WindowVariant {
+  uint32_t bits, mid_side, min_samples_per_block, streams;
+};
+constexpr uint32_t kMaxWindowVariants = 6;
+struct WindowVariants {
+  uint32_t count;
+  WindowVariant v[kMaxWindowVariants];
+};
+
+/* The variants present in formats[0 .. n), each once, in the fixed order 4-bit L/R, 4-bit M/S, 3-bit L/R, 3-bit M/S, 2-bit L/R,
+ * 2-bit M/S.  Records with bits outside 2 .. 4 belong to no variant (plan create has refused them). */
+inline WindowVariants window_variants(const StreamFormat *formats, uint64_t n)
+{
+  WindowVariant slot[kMaxWindowVariants] = {};
+  for (uint64_t i = 0; i < n; i++) {
+    const StreamFormat &f = formats[i];
+    if (f.bits < 2 || f.bits > 4) continue;
+    WindowVariant &s = slot[(4u - f.bits) * 2u + (f.mid_side ? 1u : 0u)];
+    if (s.streams == 0 || f.samples_per_block < s.min_samples_per_block) s.min_samples_per_block = f.samples_per_block;
+    s.bits = f.bits;
+    s.mid_side = f.mid_side ? 1u : 0u;
+    s.streams++;
+  }
+  WindowVariants out = {};
+  for (const WindowVariant &s : slot)
+    if (s.streams != 0) out.v[out.count++] = s;
+  return out;
+}
+
+struct MixedWindowLaunch {
+  bool ok;        /* false: some launch's lane count, or the output's elements or bytes, overflow 64 bits - nothing is launched */
+  uint32_t count; /* launches of the run: one per variant, and ONE for a plan without variants (num_streams == 0) */
+  WindowVariant variant[kMaxWindowVariants];
+  WindowLaunch launch[kMaxWindowVariants]; /* launch[0] also writes the zeros of the windows whose stream is out of range */
+};
+
+/* Every launch walks all the windows and is planned by plan_window_decode's rules with its variant's bits and smallest block: K
+ * covers that variant's every stream, the lanes past a stream's own last covering block leave.  A plan without variants has no
+ * stream a window could name: its one launch (the 4-bit L/R kernel over blocks of `frames` frames) only writes zeros. */
+inline MixedWindowLaunch plan_mixed_window_decode(const Device &d, const Knobs &k, const WindowVariants &variants, uint64_t windows,
+                                                  uint32_t frames, uint32_t channels)
+{
+  MixedWindowLaunch m = {};
+  WindowVariants vs = variants;
+  if (vs.count == 0) vs.v[vs.count++] = WindowVariant{4, 0, frames, 0};
+  if (vs.count > kMaxWindowVariants) return m;
+  for (uint32_t i = 0; i < vs.count; i++) {
+    m.variant[i] = vs.v[i];
+    m.launch[i] = plan_window_decode(d, k, WindowBatch{windows, frames, channels, vs.v[i].bits, vs.v[i].min_samples_per_block});
+    if (!m.launch[i].ok) return m;
+  }
+  m.count = vs.count;
+  m.ok = true;
+  return m;
+}
+
 } /* namespace aad */
 
 #endif /* AAD_LAUNCH_POLICY_H */

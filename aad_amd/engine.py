@@ -212,6 +212,28 @@ class Engine:
                                                       descs.ctypes.data, C.byref(plan)))
         return WindowDecodePlan(self, plan, header, descs)
 
+    def mixed_window_decode_plan(self, headers, descs, has_file_header=True, num_channels=None):
+        """A stream table for window decodes over streams that do not share a format (AADHip_MixedWindowDecodePlanCreate):
+        headers[i] is stream i's AADHeaderInfo - bits, block size, samples per block and mid/side may differ from stream to stream,
+        the channel count may not (num_channels: default headers[0]'s; needed only for an empty table).  The WindowDecodePlan it
+        returns runs one kernel per (bits, mid/side) pair among the headers."""
+        descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
+        headers = list(headers)
+        if len(headers) != len(descs):
+            raise ValueError("%d headers for %d streams" % (len(headers), len(descs)))
+        if num_channels is None:
+            if not headers:
+                raise ValueError("an empty table needs num_channels")
+            num_channels = headers[0].num_channels
+        formats = (AADHeaderInfo * max(len(headers), 1))(*headers)
+        plan = C.c_void_p()
+        _check("AADHip_MixedWindowDecodePlanCreate",
+               self.lib.AADHip_MixedWindowDecodePlanCreate(self._ctx, int(num_channels), 1 if has_file_header else 0, len(descs),
+                                                           descs.ctypes.data, C.addressof(formats), C.byref(plan)))
+        p = WindowDecodePlan(self, plan, AADHeaderInfo(num_channels=int(num_channels)), descs)
+        p.headers = headers
+        return p
+
     # ---- uniform batches (every stream the same length) -----------------------------------
     def uniform_encode_plan(self, param, num_streams, num_samples, segment_blocks=None, warmup_blocks=0):
         """Stream table for a [streams, samples, channels] int16 tensor and a [streams, stride]
@@ -288,6 +310,49 @@ class Engine:
             plan.run(x, out, state)
         finally:
             plan.close()  # synchronises the context's stream first
+        return out, [int(v) for v in sizes]
+
+    def encode_planar_mixed(self, x, make_param, bits, num_samples=None):
+        """encode_planar with a parameter per row: bits is an int sequence or tensor [N] of 2, 3 or 4 (what least_bits returns, once
+        its zeros are decided), make_param(b) the AADEncodeParameter of the rows with bits b -> (uint8 tensor [N, stride],
+        image_sizes).  Row i starts with the image encode_planar(x[i:i + 1], make_param(bits[i])) writes, byte for byte; the rows
+        lie on 64-byte boundaries.  One planar encode plan per value of bits that occurs, its descriptor table naming that value's
+        rows where they are: no gather of x."""
+        torch = self.torch
+        if x.dim() != 3 or not x.is_cuda or x.dtype not in (torch.int16, torch.float32):
+            raise ValueError("encode_planar_mixed takes an int16 or float32 cuda tensor [N, C, T]")
+        n, ch, t = (int(v) for v in x.shape)
+        if x.stride(-1) != 1:
+            raise ValueError("encode_planar_mixed needs x.stride(-1) == 1 (each channel's samples contiguous); got strides %s"
+                             % (tuple(x.stride()),))
+        bits = (bits.detach().cpu().numpy() if isinstance(bits, torch.Tensor) else np.asarray(bits)).astype(np.int64).reshape(-1)
+        if len(bits) != n or not np.isin(bits, (2, 3, 4)).all():
+            raise ValueError("bits: %d values of 2, 3 or 4" % n)
+        lengths = np.full(n, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
+        if len(lengths) != n or (n and (lengths.min() < 1 or lengths.max() > t)):
+            raise ValueError("num_samples: %d lengths in [1, %d]" % (n, t))
+        params = {int(b): make_param(int(b)) for b in np.unique(bits)}
+        for b, param in params.items():
+            if param.num_channels != ch or param.bits_per_sample != b:
+                raise ValueError("make_param(%d): %d channels and %d bits for rows of %d channels"
+                                 % (b, param.num_channels, param.bits_per_sample, ch))
+        sizes = np.array([self.encoded_size(params[int(b)], int(v)) for b, v in zip(bits, lengths)], dtype=np.uint64)
+        if n and sizes.min() == 0:
+            raise ApiError("AADHip_CalculateEncodedSize", AADApiResult.INVALID_FORMAT)
+        stride = _round_up(int(sizes.max()), 64) if n else 64
+        out = torch.zeros((n, stride), dtype=torch.uint8, device=x.device)
+        for b, param in params.items():
+            rows = np.flatnonzero(bits == b)
+            d = np.zeros(len(rows), dtype=STREAM_DESC_DTYPE)
+            d["pcm_offset"] = rows.astype(np.uint64) * np.uint64(x.stride(0))
+            d["data_offset"] = rows.astype(np.uint64) * np.uint64(stride)
+            d["data_size"] = stride
+            d["num_samples"] = lengths[rows]
+            plan = self.planar_encode_plan(param, d, x.stride(1), x.dtype)
+            try:
+                plan.run(x, out)
+            finally:
+                plan.close()  # synchronises the context's stream first
         return out, [int(v) for v in sizes]
 
     def reconstruct_planar(self, x, param, num_samples=None, dtype=None, state=None, segment_blocks=None, warmup_blocks=0,
@@ -428,6 +493,31 @@ class Engine:
         head = bytes(data[0, :31].cpu().numpy())
         header = parse_header(head)
         plan = self.uniform_window_decode_plan(header, data.shape[0], data.shape[1], image_size)
+        try:
+            return plan.run(data, windows, frames, dtype)
+        finally:
+            plan.close()  # synchronises the context's stream first
+
+    def decode_windows_mixed(self, data, image_sizes, windows, frames, dtype=None):
+        """decode_windows over images that do not share a format (encode_planar_mixed's output): data is a uint8 cuda tensor
+        [streams, stride], row i starting with an image of image_sizes[i] bytes (an int: the same for all).  The 31-byte headers of
+        all the images come to the host in one copy and are parsed one by one (the channel counts must agree); the windows are
+        never read on the host."""
+        if data.dim() != 2 or not data.is_cuda or data.dtype != self.torch.uint8 or data.stride(1) != 1:
+            raise ValueError("data: a uint8 cuda tensor [streams, stride]")
+        s = int(data.shape[0])
+        if s == 0:
+            raise ValueError("decode_windows_mixed needs at least one image (the channel count comes from the headers)")
+        sizes = np.broadcast_to(np.asarray(image_sizes, dtype=np.uint64).reshape(-1), (s,))
+        if int(data.shape[1]) < 31:
+            raise ApiError("parse_header", AADApiResult.INVALID_FORMAT)
+        heads = data[:, :31].cpu().numpy()
+        headers = [parse_header(bytes(row)) for row in heads]
+        d = np.zeros(s, dtype=STREAM_DESC_DTYPE)
+        d["data_offset"] = np.arange(s, dtype=np.uint64) * np.uint64(data.stride(0))
+        d["data_size"] = sizes
+        d["num_samples"] = [h.num_samples for h in headers]
+        plan = self.mixed_window_decode_plan(headers, d, True)
         try:
             return plan.run(data, windows, frames, dtype)
         finally:

@@ -236,6 +236,33 @@ AADApiResult AADHip_WindowDecodePlanRun(
     uint64_t num_windows, const struct AADHipWindow *device_windows,
     uint32_t frames_per_window, int32_t sample_type, void *device_out);
 
+/* Window decode over a corpus whose streams do not share a format: files encoded at different times, or streams encoded with the
+ * bits AADHip's error statistics say each one needs.  A constructor of its own that returns an ordinary window decode plan:
+ * AADHip_WindowDecodePlanRun, AADHip_WindowDecodePlanDestroy and AADHip_ContextSignalNextRun work on it unchanged.
+ *
+ * Definition.  The one above with one change: D_s is what AADHip_DecodePlanRun writes for stream s under formats[s] (with the
+ * plan's has_file_header and the descriptor's data_offset, data_size and num_samples).  Samples past num_samples are zero, a
+ * window with stream >= num_streams is all zero, wrapped int64 values give zeros and read nothing, no byte outside
+ * [data_offset, data_offset + data_size) is read and a truncated image decodes as under AADHip_DecodePlanRun.  Per stream
+ * bits_per_sample (2 / 3 / 4), block_size, num_samples_per_block and ch_process_method may differ; the channel count may not
+ * (the output has one C), nor may has_file_header.  formats[i].num_samples is ignored: the lengths come from the table.
+ *
+ * Errors.  AAD_APIRESULT_INVALID_ARGUMENT for null pointers (streams and formats may be null while num_streams == 0),
+ * num_channels outside 1 .. AAD_HIP_MAX_NUM_CHANNELS and any formats[i].num_channels != num_channels; otherwise every formats[i]
+ * with streams[i] is validated exactly as AADHip_DecodePlanCreate validates its one format, stream by stream in order (the
+ * channel count first), and the first failing stream's error is returned.  num_streams == 0 is OK: every window is zero.
+ *
+ * A run is one kernel per (bits, mid/side) pair present in the plan - at most six for two channels, three otherwise; a plan whose
+ * streams share a format runs one kernel.  Every launch walks all the windows and writes those of its own streams; every element
+ * of the output is written exactly once per run.  The start event of AADHip_ContextSignalNextRun rides on the first kernel and
+ * the stop event on the last.  The run's errors are AADHip_WindowDecodePlanRun's; the lane count that must fit 64 bits is that of
+ * the largest launch, N * (ceil((T - 1) / spb) + 1) * C for the smallest spb of the plan. */
+AADApiResult AADHip_MixedWindowDecodePlanCreate(
+    struct AADHipContext *context, uint32_t num_channels, int32_t has_file_header,
+    uint32_t num_streams, const struct AADHipStreamDesc *streams,
+    const struct AADHeaderInfo *formats, /* host array, one per stream */
+    struct AADHipWindowDecodePlan **plan);
+
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 
 /* The write side of the planar layout window decode reads out: one row per channel, int16 or float32 - torch's [N, C, T] - encoded

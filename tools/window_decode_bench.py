@@ -13,7 +13,14 @@ Rows (kernel times from the events of AADHip_ContextSignalNextRun, median of --r
 Bit-exact: (a) auto == (a) dense; every crop of (b) and (c) == the crop gathered from (a) dense, float32 == int16 / 32768 bitwise;
 and a few windows against the oracle's decode of the whole stream (tests/oracle_binding.py, when present).
 
-Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25]"""
+--mixed (profiles/r06_window_decode_mixed.txt): the mixed-format plan (AADHip_MixedWindowDecodePlanCreate), float32 rows.
+  (a) a one-variant mixed plan against the same-format plan over the same images and windows; the same-format plan is timed twice
+      first, and the difference of its two medians is the tool's own run-to-run spread;
+  (b) a corpus of one third each 2-, 3- and 4-bit stereo streams: the mixed plan's run (three kernels) against today's composite -
+      the window table to the host, split by format, one same-format run per format over its own table, the rows scattered into
+      [N, C, T] (the three plans made beforehand).  Every row of the mixed run is compared with the composite's.
+
+Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25] [--mixed]"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -30,10 +37,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM = 8.0e12
 
 
-def build_corpus(engine, torch, streams, samples, chunk=25, seed=11):
+def build_corpus(engine, torch, streams, samples, chunk=25, seed=11, bits=4):
     from aad_amd.capi import make_parameter
     from aad_amd.synth import synth_pcm
-    param = make_parameter(2, 4, 1024)
+    param = make_parameter(2, bits, 1024)
     size = engine.encoded_size(param, samples)
     stride = (size + 63) // 64 * 64
     corpus = torch.zeros((streams, stride), dtype=torch.uint8, device="cuda")
@@ -99,6 +106,104 @@ def gather(torch, pcm_blocks, crop0, frames):
     return pcm_blocks.view(-1, 2)[idx].transpose(1, 2).contiguous()
 
 
+def mixed_main(args, say):
+    import torch
+    from aad_amd.capi import STREAM_DESC_DTYPE
+    from aad_amd.engine import Engine, HipEvent, parse_header
+    engine = Engine(0)
+    samples, frames, streams = int(round(args.seconds * 48000)), args.frames, args.streams
+    results = []
+
+    def uniform_table(count, stride, size):
+        d = np.zeros(count, dtype=STREAM_DESC_DTYPE)
+        d["data_offset"] = np.arange(count, dtype=np.uint64) * np.uint64(stride)
+        d["data_size"], d["num_samples"] = size, samples
+        return d
+
+    def draw(n, count):
+        g = torch.Generator(device="cuda")
+        g.manual_seed(args.seed + n)
+        return torch.stack([torch.randint(0, count, (n,), device="cuda", generator=g),
+                            torch.randint(0, samples - frames + 1, (n,), device="cuda", generator=g)], dim=1)
+
+    # (a) one variant: the same images and windows under both plans
+    corpus, size, stride = build_corpus(engine, torch, streams, samples, seed=args.seed)
+    hd = parse_header(bytes(corpus[0, :31].cpu().numpy()))
+    say("mixed window decode (a): %d stereo 4-bit streams x %d frames, T = %d, float32 rows, median of %d; device %s"
+        % (streams, samples, frames, args.reps, torch.cuda.get_device_name(0)))
+    same = engine.uniform_window_decode_plan(hd, streams, stride, size)
+    mixed = engine.mixed_window_decode_plan([hd] * streams, uniform_table(streams, stride, size), True)
+    for n in args.windows:
+        d_win = draw(n, streams)
+        out_s = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        out_m = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        s1 = kernel_ms(engine, HipEvent, lambda: same.run(corpus, d_win, frames, torch.float32, out=out_s), args.reps)
+        s2 = kernel_ms(engine, HipEvent, lambda: same.run(corpus, d_win, frames, torch.float32, out=out_s), args.reps)
+        m = kernel_ms(engine, HipEvent, lambda: mixed.run(corpus, d_win, frames, torch.float32, out=out_m), args.reps)
+        s3 = kernel_ms(engine, HipEvent, lambda: same.run(corpus, d_win, frames, torch.float32, out=out_s), args.reps)
+        torch.cuda.synchronize()
+        exact = bool(torch.equal(out_s.view(torch.int32), out_m.view(torch.int32)))
+        spread, base = abs(s1 - s2), min(s1, s2)
+        say("  N = %5d: same-format kernel %.4f / %.4f ms (spread %.4f; again after the mixed run: %.4f), one-variant mixed kernel "
+            "%.4f ms: %+.4f ms = %+.2f %% (more than twice the spread: %s); identical rows: %s"
+            % (n, s1, s2, spread, s3, m, m - base, 100 * (m - base) / base, m - base > 2 * spread, exact))
+        results.append(dict(part="a", windows=n, same_ms=[s1, s2, s3], mixed_ms=m, identical=exact))
+        del out_s, out_m
+    same.close()
+    mixed.close()
+    del corpus
+    torch.cuda.empty_cache()
+
+    # (b) three variants: one third each of 2-, 3- and 4-bit streams (stream i has bits (2, 3, 4)[i % 3])
+    third = streams // 3
+    parts = {b: build_corpus(engine, torch, third, samples, seed=args.seed + b, bits=b) for b in (2, 3, 4)}
+    stride = max(p[2] for p in parts.values())
+    corpus = torch.zeros((3 * third, stride), dtype=torch.uint8, device="cuda")
+    table = np.zeros(3 * third, dtype=STREAM_DESC_DTYPE)
+    table["data_offset"] = np.arange(3 * third, dtype=np.uint64) * np.uint64(stride)
+    table["num_samples"] = samples
+    headers, plans = [None] * (3 * third), {}
+    for j, b in enumerate((2, 3, 4)):
+        img, size_b, stride_b = parts[b]
+        corpus[j::3, :stride_b] = img
+        table["data_size"][j::3] = size_b
+        h = parse_header(bytes(img[0, :31].cpu().numpy()))
+        headers[j::3] = [h] * third
+        plans[j] = engine.window_decode_plan(h, table[j::3], True)  # the format's own streams: stream s of the corpus is s // 3 here
+    del parts
+    mixed = engine.mixed_window_decode_plan(headers, table, True)
+    say("")
+    say("mixed window decode (b): %d streams, one third each 2-, 3- and 4-bit stereo (spb %s), T = %d, float32 rows"
+        % (3 * third, "/".join(str(headers[j].num_samples_per_block) for j in range(3)), frames))
+    for n in args.windows:
+        d_win = draw(n, 3 * third)
+        out_m = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        out_c = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+
+        def composite():
+            w = d_win.cpu()  # the host synchronisation the mixed plan removes
+            for j in range(3):
+                idx = torch.nonzero(w[:, 0] % 3 == j).flatten()
+                sub = torch.stack([w[idx, 0] // 3, w[idx, 1]], dim=1).cuda()
+                out_c[idx.cuda()] = plans[j].run(corpus, sub, frames, torch.float32)
+
+        km = kernel_ms(engine, HipEvent, lambda: mixed.run(corpus, d_win, frames, torch.float32, out=out_m), args.reps)
+        cm = call_ms(torch, lambda: mixed.run(corpus, d_win, frames, torch.float32, out=out_m), args.reps)
+        cc = call_ms(torch, composite, args.reps)
+        torch.cuda.synchronize()
+        exact = bool(torch.equal(out_m.view(torch.int32), out_c.view(torch.int32)))
+        say("  N = %5d: mixed plan, three kernels: first start to last stop %.4f ms, call %.4f ms; composite (three runs over "
+            "host-split tables + scatter) call %.4f ms: %.2fx; identical rows: %s" % (n, km, cm, cc, cc / cm, exact))
+        results.append(dict(part="b", windows=n, mixed_kernels_ms=km, mixed_call_ms=cm, composite_call_ms=cc, identical=exact))
+        del out_m, out_c
+    say("")
+    say("json " + json.dumps(results))
+    mixed.close()
+    for p in plans.values():
+        p.close()
+    engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=1000)
@@ -108,6 +213,7 @@ def main():
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--seed", type=int, default=11)
     ap.add_argument("--out", default=None, help="also write the report here")
+    ap.add_argument("--mixed", action="store_true", help="the mixed-format plan's two measurements instead (see above)")
     args = ap.parse_args()
 
     import torch
@@ -117,6 +223,14 @@ def main():
     def say(s=""):
         print(s, flush=True)
         lines.append(s)
+
+    if args.mixed:
+        mixed_main(args, say)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
 
     engine = Engine(0)
     samples = int(round(args.seconds * 48000))
