@@ -97,7 +97,7 @@ HIP_SYMBOLS = [
     "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate", "AADHip_SegmentedEncodeBatch",
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
-    "AADHip_MixedWindowDecodePlanCreate",
+    "AADHip_MixedWindowDecodePlanCreate", "AADHip_ChannelMixWindowDecodePlanCreate",
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
     "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
     "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
@@ -206,6 +206,8 @@ def _declare_hip(lib):
     lib.AADHip_WindowDecodePlanCreate.restype = C.c_int
     lib.AADHip_MixedWindowDecodePlanCreate.argtypes = [vp, C.c_uint32, C.c_int32, C.c_uint32, vp, vp, C.POINTER(vp)]
     lib.AADHip_MixedWindowDecodePlanCreate.restype = C.c_int
+    lib.AADHip_ChannelMixWindowDecodePlanCreate.argtypes = [vp, C.c_uint32, C.c_int32, C.c_uint32, vp, vp, C.POINTER(vp)]
+    lib.AADHip_ChannelMixWindowDecodePlanCreate.restype = C.c_int
     lib.AADHip_WindowDecodePlanDestroy.argtypes = [vp]
     lib.AADHip_WindowDecodePlanDestroy.restype = None
     lib.AADHip_WindowDecodePlanRun.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp]

@@ -44,21 +44,30 @@ struct WindowArgs {
 
 typedef float f32x4_u4 __attribute__((ext_vector_type(4), aligned(4))); /* a 16-byte store at 4-byte alignment */
 
-/* one row segment of a lane: output element t = base + i for sample i of the block, kept where lo <= t < hi */
-template <bool F32>
+/* how a lane's samples reach the output's channels (aad_decode_window_channel_mix.hip.h); kMixNone: channel c into row c */
+enum WindowMix { kMixNone = 0, kMixTwin = 1 /* mono source, two rows */, kMixDown = 2 /* stereo source, one row */ };
+
+/* one row segment of a lane: output element t = base + i for sample i of the block, kept where lo <= t < hi.
+ * kMixTwin: every store goes to the row `twin` elements on as well.  kMixDown: y is L + R as float32, (L + R) >> 1 as int16. */
+template <bool F32, int MIX = kMixNone>
 struct WindowRow {
   using T = std::conditional_t<F32, float, int16_t>;
   T *row;
   int64_t base, lo, hi;
+  int64_t twin; /* kMixTwin alone */
   __device__ __forceinline__ static T convert(int32_t y)
   {
-    if constexpr (F32) return (float)y * (1.0f / 32768.0f); /* exact: an int16 times a power of two */
+    /* exact: an int16 (kMixDown: a sum of two, at most 17 bits) times a power of two */
+    if constexpr (F32) return (float)y * (MIX == kMixDown ? 1.0f / 65536.0f : 1.0f / 32768.0f);
     else return (T)y;
   }
   __device__ __forceinline__ void one(uint32_t i, int32_t y) const
   {
     const int64_t t = base + (int64_t)i;
-    if (t >= lo && t < hi) row[t] = convert(y);
+    if (t >= lo && t < hi) {
+      row[t] = convert(y);
+      if constexpr (MIX == kMixTwin) row[t + twin] = convert(y);
+    }
   }
   /* samples i0 .. i0 + 15 */
   __device__ __forceinline__ void chunk(uint32_t i0, const int32_t *y) const
@@ -69,12 +78,19 @@ struct WindowRow {
       T *p = row + t0;
       if constexpr (F32) {
 #pragma unroll
-        for (int q = 0; q < 4; q++)
-          *reinterpret_cast<f32x4_u4 *>(p + 4 * q) = f32x4_u4{convert(y[4 * q]), convert(y[4 * q + 1]), convert(y[4 * q + 2]), convert(y[4 * q + 3])};
+        for (int q = 0; q < 4; q++) {
+          const f32x4_u4 v = f32x4_u4{convert(y[4 * q]), convert(y[4 * q + 1]), convert(y[4 * q + 2]), convert(y[4 * q + 3])};
+          *reinterpret_cast<f32x4_u4 *>(p + 4 * q) = v;
+          if constexpr (MIX == kMixTwin) *reinterpret_cast<f32x4_u4 *>(p + twin + 4 * q) = v;
+        }
       } else {
         const ChunkPcm o = pack_chunk_pcm<1, false>(y, 0);
         store_u32x4<false>(p, o.v[0]);
         store_u32x4<false>(p + 8, o.v[1]);
+        if constexpr (MIX == kMixTwin) {
+          store_u32x4<false>(p + twin, o.v[0]);
+          store_u32x4<false>(p + twin + 8, o.v[1]);
+        }
       }
       return;
     }
@@ -84,18 +100,26 @@ struct WindowRow {
   /* zeros over [from, hi) */
   __device__ __forceinline__ void zeros(int64_t from) const
   {
-    for (int64_t t = from > lo ? from : lo; t < hi; t++) row[t] = (T)0;
+    for (int64_t t = from > lo ? from : lo; t < hi; t++) {
+      row[t] = (T)0;
+      if constexpr (MIX == kMixTwin) row[t + twin] = (T)0;
+    }
   }
 };
 
 /* CHF: 1 / 2 = the mono / stereo fast paths (wide chunk loads), 0 = any channel count (byte loads).
  * MIXED (aad_decode_window_mixed.hip.h): the block geometry comes from the stream's record in `formats`, not from the launch, and
  * the lane leaves when its stream belongs to another kernel variant - a decision per window, so the lanes of a channel pair take
- * it together.  Windows whose stream is out of range are written (as zeros) by the launch that `owns_strays`. */
-template <int BITS, int CHF, bool MS, bool F32, bool MIXED = false>
-__device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane, const StreamFormat *formats = nullptr,
+ * it together.  Windows whose stream is out of range are written (as zeros) by the launch that `owns_strays`.
+ * OUTC (aad_decode_window_channel_mix.hip.h; 0: as many as the source has): the rows a window has in the output.  The lanes, the
+ * block geometry and every read stay the SOURCE's (CHF); a mono source stores into both rows, a stereo pair exchanges the finished
+ * L / R samples once more and lane c == 0 stores the mix into the one row. */
+template <int BITS, int CHF, bool MS, bool F32, bool MIXED = false, int OUTC = 0, class FORMAT = StreamFormat>
+__device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane, const FORMAT *formats = nullptr,
                                             uint32_t owns_strays = 0)
 {
+  static_assert(OUTC == 0 || ((CHF == 1 || CHF == 2) && (OUTC == 1 || OUTC == 2)), "a channel mix is between one and two channels");
+  constexpr int MIX = OUTC == 0 || OUTC == CHF ? kMixNone : OUTC == 2 ? kMixTwin : kMixDown;
   const uint32_t ch = CHF ? CHF : a.channels;
   const uint64_t per_window = (uint64_t)a.blocks_per_window * ch;
   const uint64_t w = lane / per_window;
@@ -106,8 +130,12 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
   uint32_t block_size = a.block_size;
   if constexpr (MIXED) {
     if (stream < a.num_streams) {
-      const StreamFormat f = formats[stream];
-      if (f.bits != BITS || (f.mid_side != 0) != MS) return;
+      const FORMAT f = formats[stream];
+      if constexpr (std::is_same_v<FORMAT, StreamFormat>) {
+        if (f.bits != BITS || (f.mid_side != 0) != MS) return;
+      } else {
+        if (f.bits != BITS || f.source != (CHF == 1 ? kSourceMono : MS ? kSourceMidSide : kSourceStereo)) return;
+      }
       spb = f.samples_per_block;
       block_size = f.block_size;
     } else if (!owns_strays) {
@@ -119,8 +147,13 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
   const uint64_t kspb = (uint64_t)k * spb;
   if (kspb >= frames + phase) return; /* past the window's last block: lanes of one (window, block) leave together */
 
-  WindowRow<F32> out;
-  out.row = reinterpret_cast<typename WindowRow<F32>::T *>(a.out) + (w * ch + c) * frames;
+  WindowRow<F32, MIX> out;
+  if constexpr (MIX == kMixNone) {
+    out.row = reinterpret_cast<typename WindowRow<F32>::T *>(a.out) + (w * ch + c) * frames;
+  } else {
+    out.row = reinterpret_cast<typename WindowRow<F32>::T *>(a.out) + w * OUTC * frames;
+    out.twin = (int64_t)frames;
+  }
   out.base = (int64_t)kspb - (int64_t)phase;
   out.lo = out.base > 0 ? out.base : 0;
   out.hi = out.base + (int64_t)spb < (int64_t)frames ? out.base + (int64_t)spb : (int64_t)frames;
@@ -146,6 +179,10 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
     }
   }
 
+  /* the R lane of a down-mixed pair decodes and exchanges, and stores nothing (`n` above came from the segment both lanes share) */
+  if constexpr (MIX == kMixDown)
+    if (c) out.lo = out.hi = INT64_MIN;
+
   Lane L = {0, 0, 0, 0, 0, 0, 0, 0, kIdxBias};
   if (n) { /* block header - reference src/aad_decoder.c:364-380 */
     const uint8_t *hp = src + c * kBlockHeaderBytesPerCh;
@@ -164,11 +201,19 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
 
   /* inverse mid/side: the partner channel is the neighbouring lane, of the same window and block, with the same trip counts */
   auto finish = [&](int32_t y) -> int32_t {
-    if (MS) {
+    if constexpr (MIX == kMixDown) {
+      /* the mix is taken on the finished samples: with mid/side L = clip16(M + S) and R = clip16(M - S), both from the one
+       * exchange; right on lane c == 0, which alone stores */
       const int32_t other = (int32_t)pair_swap<false>((uint32_t)y, c);
-      return c == 0 ? clip16(y + other) : clip16(other - y);
+      const int32_t sum = MS ? clip16(y + other) + clip16(y - other) : y + other;
+      return F32 ? sum : sum >> 1; /* float32 keeps the half step (WindowRow::convert), int16 is the floor */
+    } else {
+      if (MS) {
+        const int32_t other = (int32_t)pair_swap<false>((uint32_t)y, c);
+        return c == 0 ? clip16(y + other) : clip16(other - y);
+      }
+      return y;
     }
-    return y;
   };
 
   constexpr int US = Pack<BITS>::kUnitSamples, UB = Pack<BITS>::kUnitBytes;

@@ -28,6 +28,7 @@
 #include "aad_decode.hip.h"
 #include "aad_decode_window.hip.h"
 #include "aad_decode_window_mixed.hip.h"
+#include "aad_decode_window_channel_mix.hip.h"
 #include "aad_encode.hip.h"
 #include "aad_encode_launch.hip.h"
 #include "aad_format.h"
@@ -156,6 +157,10 @@ struct AADHipWindowDecodePlan {
   bool mixed;
   aad::StreamFormat *d_formats; /* one record per stream */
   aad::WindowVariants variants;
+  /* AADHip_ChannelMixWindowDecodePlanCreate: `args` as for a mixed plan with the OUTPUT's channel count, the formats are these */
+  bool channel_mix;
+  aad::ChannelStreamFormat *d_mix_formats; /* one record per stream */
+  aad::ChannelMixVariants mix_variants;
 };
 
 struct AADHipReconstructPlan {
@@ -1052,6 +1057,8 @@ AADApiResult AADHip_WindowDecodePlanCreate(struct AADHipContext *ctx, const stru
   p->mixed = false;
   p->d_formats = nullptr;
   p->variants = aad::WindowVariants{};
+  p->channel_mix = false;
+  p->d_mix_formats = nullptr;
   DeviceGuard guard(ctx);
   if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams)) {
     if (p->d_streams) (void)hipFree(p->d_streams);
@@ -1089,6 +1096,8 @@ AADApiResult AADHip_MixedWindowDecodePlanCreate(struct AADHipContext *ctx, uint3
   p->mixed = true;
   p->d_formats = nullptr;
   p->variants = aad::window_variants(records.data(), num_streams);
+  p->channel_mix = false;
+  p->d_mix_formats = nullptr;
   DeviceGuard guard(ctx);
   if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams) ||
       !upload(ctx, &p->d_formats, records.data(), num_streams)) {
@@ -1106,6 +1115,46 @@ AADApiResult AADHip_MixedWindowDecodePlanCreate(struct AADHipContext *ctx, uint3
   return AAD_APIRESULT_OK;
 }
 
+AADApiResult AADHip_ChannelMixWindowDecodePlanCreate(struct AADHipContext *ctx, uint32_t out_channels, int32_t has_file_header,
+                                                     uint32_t num_streams, const struct AADHipStreamDesc *streams,
+                                                     const struct AADHeaderInfo *formats, struct AADHipWindowDecodePlan **plan)
+{
+  if (ctx == nullptr || plan == nullptr || (num_streams != 0 && (streams == nullptr || formats == nullptr)))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *plan = nullptr;
+  if (out_channels < 1 || out_channels > 2) return AAD_APIRESULT_INVALID_ARGUMENT;
+  /* stream by stream what AADHip_DecodePlanCreate checks of its one format and table; the first failing stream's error */
+  std::vector<aad::ChannelStreamFormat> records(num_streams);
+  for (uint32_t i = 0; i < num_streams; i++) {
+    if (formats[i].num_channels < 1 || formats[i].num_channels > 2) return AAD_APIRESULT_INVALID_ARGUMENT;
+    uint64_t prefix[2];
+    aad::DecodeArgs one;
+    const AADApiResult rc = decode_plan_init(&formats[i], has_file_header, 1, &streams[i], prefix, &one);
+    if (rc != AAD_APIRESULT_OK) return rc;
+    records[i] = aad::channel_stream_format_of(formats[i]);
+  }
+  AADHipWindowDecodePlan *p = new (std::nothrow) AADHipWindowDecodePlan(); /* every pointer null, no other kind */
+  if (p == nullptr) return AAD_APIRESULT_NG;
+  p->ctx = ctx;
+  p->channel_mix = true;
+  p->mix_variants = aad::channel_mix_variants(records.data(), num_streams);
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams) ||
+      !upload(ctx, &p->d_mix_formats, records.data(), num_streams)) {
+    if (p->d_streams) (void)hipFree(p->d_streams);
+    if (p->d_mix_formats) (void)hipFree(p->d_mix_formats);
+    delete p;
+    return AAD_APIRESULT_NG;
+  }
+  memset(&p->args, 0, sizeof(p->args));
+  p->args.streams = p->d_streams;
+  p->args.num_streams = num_streams;
+  p->args.channels = out_channels;
+  p->args.header_bytes = has_file_header ? AAD_HEADER_SIZE : 0;
+  *plan = p;
+  return AAD_APIRESULT_OK;
+}
+
 void AADHip_WindowDecodePlanDestroy(struct AADHipWindowDecodePlan *plan)
 {
   if (plan == nullptr) return;
@@ -1114,6 +1163,7 @@ void AADHip_WindowDecodePlanDestroy(struct AADHipWindowDecodePlan *plan)
     (void)hipStreamSynchronize(plan->ctx->stream);
     (void)hipFree(plan->d_streams);
     if (plan->d_formats) (void)hipFree(plan->d_formats);
+    if (plan->d_mix_formats) (void)hipFree(plan->d_mix_formats);
   }
   delete plan;
 }
@@ -1163,6 +1213,51 @@ AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::La
   }
   return finish_signal(ctx, last, AAD_APIRESULT_OK);
 }
+
+/* ... and of a channel-mix run: one per (source channels, bits, mid/side) of the plan, d.channels rows per window */
+AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &signal, const uint8_t *device_data,
+                                           uint64_t num_windows, const struct AADHipWindow *device_windows,
+                                           uint32_t frames_per_window, int32_t sample_type, void *device_out)
+{
+  AADHipContext *ctx = plan->ctx;
+  const aad::DecodeArgs &d = plan->args;
+  const aad::ChannelMixWindowLaunch m =
+      aad::plan_channel_mix_window_decode(ctx->device_info, ctx->knobs, plan->mix_variants, num_windows, frames_per_window, d.channels);
+  if (!m.ok) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "window decode: %llu windows x %u channels x %u frames overflow 64 bits",
+             (unsigned long long)num_windows, d.channels, frames_per_window);
+    return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+  if (num_windows == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
+  aad::LaunchSignal last = signal;
+  for (uint32_t i = 0; i < m.count; i++) {
+    aad::ChannelMixWindowArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w.streams = d.streams;
+    a.w.data = device_data;
+    a.w.windows = reinterpret_cast<const uint64_t *>(device_windows);
+    a.w.out = device_out;
+    a.w.lanes = m.launch[i].lanes;
+    a.w.blocks_per_window = m.launch[i].blocks_per_window;
+    a.w.frames = frames_per_window;
+    a.w.num_streams = d.num_streams;
+    a.w.channels = m.variant[i].channels;
+    a.w.samples_per_block = m.variant[i].min_samples_per_block;
+    a.w.header_bytes = d.header_bytes;
+    a.w.mid_side = m.variant[i].mid_side;
+    a.w.bits = m.variant[i].bits;
+    a.formats = plan->d_mix_formats;
+    a.owns_strays = i == 0;
+    a.out_channels = d.channels;
+    last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
+    aad::tl_launch_signal = last;
+    aad::launch_decode_window_channel_mix(a, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+    if (!hip_ok(ctx, hipGetLastError(), "channel-mix window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+  }
+  return finish_signal(ctx, last, AAD_APIRESULT_OK);
+}
 } /* namespace */
 
 AADApiResult AADHip_WindowDecodePlanRun(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
@@ -1177,6 +1272,9 @@ AADApiResult AADHip_WindowDecodePlanRun(struct AADHipWindowDecodePlan *plan, con
     return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
   if (plan->mixed)
     return run_mixed_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out);
+  if (plan->channel_mix)
+    return run_channel_mix_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type,
+                                         device_out);
   const aad::DecodeArgs &d = plan->args;
   const aad::WindowLaunch p =
       aad::plan_window_decode(ctx->device_info, ctx->knobs, aad::WindowBatch{num_windows, frames_per_window, d.channels, d.bits, d.samples_per_block});

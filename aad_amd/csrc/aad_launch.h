@@ -34,6 +34,9 @@ void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, bool fl
 /* aad_decode_window_mixed.hip: one launch (one kernel variant: args.w.bits, args.w.mid_side) of a mixed-format window decode run */
 struct MixedWindowArgs;
 void launch_decode_window_mixed(const MixedWindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
+/* aad_decode_window_channel_mix.hip: one launch (args.w.channels, args.w.bits, args.w.mid_side: the variant) of a channel-mix run */
+struct ChannelMixWindowArgs;
+void launch_decode_window_channel_mix(const ChannelMixWindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
 /* the decoded rows of a planar reconstruct run (AADHip_PlanarReconstructPlanRun; launched through aad_encode_launch.hip.h).
  * base: per stream (segmented: per chain) the element of `out` that holds channel 0's sample of the lane's first frame, device
  * memory */

@@ -366,14 +366,16 @@ constexpr uint64_t kWindowMaxGrid = 1ull << 20;
 
 /* The window kernel is the per-lane dense decoder with predicated stores: the dense decoder's workgroup rule (one-wave workgroups
  * while the batch has at most one wave per SIMD) and its occupancy cap (dense_decode_lds_pad) */
-inline WindowLaunch plan_window_decode(const Device &d, const Knobs &k, const WindowBatch &b)
+/* out_channels: the rows a window has in the output (`elements`), b.channels: the channels a window's lanes decode.  They differ
+ * in a channel-mix run alone (plan_channel_mix_window_decode). */
+inline WindowLaunch plan_window_decode_into(const Device &d, const Knobs &k, const WindowBatch &b, uint32_t out_channels)
 {
   WindowLaunch p = {};
-  if (b.frames == 0 || b.samples_per_block == 0 || b.channels == 0) return p;
+  if (b.frames == 0 || b.samples_per_block == 0 || b.channels == 0 || out_channels == 0) return p;
   const uint64_t kb = window_blocks_spanned(b.frames, b.samples_per_block);
   uint64_t per_window = 0, elements = 0, bytes = 0;
   if (__builtin_mul_overflow(kb, (uint64_t)b.channels, &per_window) || __builtin_mul_overflow(b.windows, per_window, &p.lanes)) return p;
-  if (__builtin_mul_overflow(b.windows, (uint64_t)b.channels * b.frames, &elements) || __builtin_mul_overflow(elements, (uint64_t)4, &bytes))
+  if (__builtin_mul_overflow(b.windows, (uint64_t)out_channels * b.frames, &elements) || __builtin_mul_overflow(elements, (uint64_t)4, &bytes))
     return p;
   p.ok = true;
   p.blocks_per_window = (uint32_t)kb;
@@ -384,6 +386,10 @@ inline WindowLaunch plan_window_decode(const Device &d, const Knobs &k, const Wi
   p.grid = (uint32_t)(groups < kWindowMaxGrid ? groups : kWindowMaxGrid);
   if (p.workgroup == 256u) p.lds = dense_decode_lds_pad(d, k, p.lanes, b.channels, b.bits);
   return p;
+}
+inline WindowLaunch plan_window_decode(const Device &d, const Knobs &k, const WindowBatch &b)
+{
+  return plan_window_decode_into(d, k, b, b.channels);
 }
 
 /* ---- mixed-format window decode (AADHip_MixedWindowDecodePlanCreate): one launch per kernel variant of the plan ------------- */
@@ -454,6 +460,89 @@ inline MixedWindowLaunch plan_mixed_window_decode(const Device &d, const Knobs &
   for (uint32_t i = 0; i < vs.count; i++) {
     m.variant[i] = vs.v[i];
     m.launch[i] = plan_window_decode(d, k, WindowBatch{windows, frames, channels, vs.v[i].bits, vs.v[i].min_samples_per_block});
+    if (!m.launch[i].ok) return m;
+  }
+  m.count = vs.count;
+  m.ok = true;
+  return m;
+}
+
+/* ---- channel-mix window decode (AADHip_ChannelMixWindowDecodePlanCreate): mono and stereo streams into one channel count ---- */
+/* which decoder a stream needs: the source channel count, and for two channels the inverse mid/side */
+enum StreamSource : uint8_t { kSourceMono = 0, kSourceStereo = 1, kSourceMidSide = 2, kSourceNone = 3 };
+/* StreamFormat with the source in the place of mid_side */
+struct ChannelStreamFormat {
+  uint32_t samples_per_block;
+  uint16_t block_size;
+  uint8_t bits;
+  uint8_t source; /* a StreamSource; kSourceNone: a channel count other than 1 or 2 (plan create has refused it) */
+};
+static_assert(sizeof(ChannelStreamFormat) == 8, "per-stream format record");
+
+/* a mono stream is kSourceMono whatever its method says (the plan's validation refuses M/S there anyway) */
+inline ChannelStreamFormat channel_stream_format_of(const struct AADHeaderInfo &h)
+{
+  const uint8_t source = h.num_channels == 1   ? kSourceMono
+                         : h.num_channels != 2 ? kSourceNone
+                         : h.ch_process_method == AAD_CH_PROCESS_METHOD_MS ? kSourceMidSide
+                                                                           : kSourceStereo;
+  return ChannelStreamFormat{h.num_samples_per_block, h.block_size, (uint8_t)h.bits_per_sample, source};
+}
+
+/* a kernel variant of a channel-mix plan: WindowVariant with the source channel count in front */
+struct ChannelMixVariant {
+  uint32_t channels, bits, mid_side, min_samples_per_block, streams;
+};
+constexpr uint32_t kMaxChannelMixVariants = 9;
+struct ChannelMixVariants {
+  uint32_t count;
+  ChannelMixVariant v[kMaxChannelMixVariants];
+};
+
+/* The variants present in formats[0 .. n), each once: window_variants' six stereo ones in its order, then mono 4-, 3- and 2-bit.
+ * Records with bits outside 2 .. 4 or without a source belong to no variant. */
+inline ChannelMixVariants channel_mix_variants(const ChannelStreamFormat *formats, uint64_t n)
+{
+  ChannelMixVariant slot[kMaxChannelMixVariants] = {};
+  for (uint64_t i = 0; i < n; i++) {
+    const ChannelStreamFormat &f = formats[i];
+    if (f.bits < 2 || f.bits > 4 || f.source >= kSourceNone) continue;
+    const bool mono = f.source == kSourceMono, ms = f.source == kSourceMidSide;
+    ChannelMixVariant &s = slot[mono ? 6u + (4u - f.bits) : (4u - f.bits) * 2u + (ms ? 1u : 0u)];
+    if (s.streams == 0 || f.samples_per_block < s.min_samples_per_block) s.min_samples_per_block = f.samples_per_block;
+    s.channels = mono ? 1u : 2u;
+    s.bits = f.bits;
+    s.mid_side = ms ? 1u : 0u;
+    s.streams++;
+  }
+  ChannelMixVariants out = {};
+  for (const ChannelMixVariant &s : slot)
+    if (s.streams != 0) out.v[out.count++] = s;
+  return out;
+}
+
+struct ChannelMixWindowLaunch {
+  bool ok;        /* false: some launch's lane count, or the output's elements or bytes, overflow 64 bits - nothing is launched */
+  uint32_t count; /* launches of the run: one per variant, and ONE for a plan without variants (num_streams == 0) */
+  ChannelMixVariant variant[kMaxChannelMixVariants];
+  WindowLaunch launch[kMaxChannelMixVariants]; /* launch[0] also writes the zeros of the windows whose stream is out of range */
+};
+
+/* plan_mixed_window_decode with two channel counts: a launch's lanes are (window, block, SOURCE channel) of its variant - planned
+ * by plan_window_decode's rules for that channel count, bits and smallest block - and `elements` is the output's,
+ * windows * out_channels * frames, whose overflow refuses the run whatever the sources.  A plan without variants: the mono 4-bit
+ * kernel over blocks of `frames` frames writes the zeros (one lane per window and block covers out_channels rows). */
+inline ChannelMixWindowLaunch plan_channel_mix_window_decode(const Device &d, const Knobs &k, const ChannelMixVariants &variants,
+                                                             uint64_t windows, uint32_t frames, uint32_t out_channels)
+{
+  ChannelMixWindowLaunch m = {};
+  ChannelMixVariants vs = variants;
+  if (vs.count == 0) vs.v[vs.count++] = ChannelMixVariant{1, 4, 0, frames, 0};
+  if (vs.count > kMaxChannelMixVariants || out_channels < 1 || out_channels > 2) return m;
+  for (uint32_t i = 0; i < vs.count; i++) {
+    m.variant[i] = vs.v[i];
+    m.launch[i] = plan_window_decode_into(d, k, WindowBatch{windows, frames, vs.v[i].channels, vs.v[i].bits, vs.v[i].min_samples_per_block},
+                                          out_channels);
     if (!m.launch[i].ok) return m;
   }
   m.count = vs.count;

@@ -234,6 +234,25 @@ class Engine:
         p.headers = headers
         return p
 
+    def channel_mix_window_decode_plan(self, headers, descs, out_channels, has_file_header=True):
+        """A stream table for window decodes over mono and stereo streams into rows of one channel count
+        (AADHip_ChannelMixWindowDecodePlanCreate): headers[i] is stream i's AADHeaderInfo - the channel count (1 or 2), bits, block
+        size, samples per block and mid/side may differ from stream to stream.  out_channels = 2 writes a mono stream into both
+        rows; out_channels = 1 writes a stereo stream's mean, (L + R) >> 1 as int16 and (L + R) / 65536 as float32.  The
+        WindowDecodePlan it returns runs one kernel per (channels, bits, mid/side) among the headers."""
+        descs = np.ascontiguousarray(descs, dtype=STREAM_DESC_DTYPE)
+        headers = list(headers)
+        if len(headers) != len(descs):
+            raise ValueError("%d headers for %d streams" % (len(headers), len(descs)))
+        formats = (AADHeaderInfo * max(len(headers), 1))(*headers)
+        plan = C.c_void_p()
+        _check("AADHip_ChannelMixWindowDecodePlanCreate",
+               self.lib.AADHip_ChannelMixWindowDecodePlanCreate(self._ctx, int(out_channels), 1 if has_file_header else 0, len(descs),
+                                                                descs.ctypes.data, C.addressof(formats), C.byref(plan)))
+        p = WindowDecodePlan(self, plan, AADHeaderInfo(num_channels=int(out_channels)), descs)
+        p.headers = headers
+        return p
+
     # ---- uniform batches (every stream the same length) -----------------------------------
     def uniform_encode_plan(self, param, num_streams, num_samples, segment_blocks=None, warmup_blocks=0):
         """Stream table for a [streams, samples, channels] int16 tensor and a [streams, stride]
@@ -498,11 +517,12 @@ class Engine:
         finally:
             plan.close()  # synchronises the context's stream first
 
-    def decode_windows_mixed(self, data, image_sizes, windows, frames, dtype=None):
+    def decode_windows_mixed(self, data, image_sizes, windows, frames, dtype=None, channels=None):
         """decode_windows over images that do not share a format (encode_planar_mixed's output): data is a uint8 cuda tensor
         [streams, stride], row i starting with an image of image_sizes[i] bytes (an int: the same for all).  The 31-byte headers of
         all the images come to the host in one copy and are parsed one by one (the channel counts must agree); the windows are
-        never read on the host."""
+        never read on the host.  channels = 1 or 2: mono and stereo images may share the tensor and the result has that many rows
+        per window (channel_mix_window_decode_plan)."""
         if data.dim() != 2 or not data.is_cuda or data.dtype != self.torch.uint8 or data.stride(1) != 1:
             raise ValueError("data: a uint8 cuda tensor [streams, stride]")
         s = int(data.shape[0])
@@ -517,7 +537,8 @@ class Engine:
         d["data_offset"] = np.arange(s, dtype=np.uint64) * np.uint64(data.stride(0))
         d["data_size"] = sizes
         d["num_samples"] = [h.num_samples for h in headers]
-        plan = self.mixed_window_decode_plan(headers, d, True)
+        plan = self.mixed_window_decode_plan(headers, d, True) if channels is None \
+            else self.channel_mix_window_decode_plan(headers, d, channels, True)
         try:
             return plan.run(data, windows, frames, dtype)
         finally:

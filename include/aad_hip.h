@@ -263,6 +263,41 @@ AADApiResult AADHip_MixedWindowDecodePlanCreate(
     const struct AADHeaderInfo *formats, /* host array, one per stream */
     struct AADHipWindowDecodePlan **plan);
 
+/* Window decode over a corpus that mixes mono and stereo streams, into rows of one channel count.  A constructor of its own that
+ * returns an ordinary window decode plan: AADHip_WindowDecodePlanRun, AADHip_WindowDecodePlanDestroy and
+ * AADHip_ContextSignalNextRun work on it unchanged.
+ *
+ * Definition.  D_s is what AADHip_DecodePlanRun writes for stream s under formats[s] - after the inverse mid/side, so D_s[t][0]
+ * is L and D_s[t][1] is R.  Per stream bits_per_sample, block_size, num_samples_per_block, ch_process_method and the channel
+ * count C_s (1 or 2) may differ; has_file_header may not.  With C = out_channels, for window w = {stream, first_frame}, t < T
+ * and f = first_frame + t, out[(w * C + c) * T + t] is
+ *   C_s == C:                    D_s[f][c] - the mixed-format plan's rule;
+ *   C_s == 1, C == 2:            D_s[f][0] in both rows;
+ *   C_s == 2, C == 1, int16:     (L + R) >> 1 with an arithmetic shift, i.e. the floor of the mean: L = R = -32768 gives -32768,
+ *                                a sum of -3 gives -2;
+ *   C_s == 2, C == 1, float32:   (float)(L + R) * 2^-16, the exact mean (|L + R| <= 65536 is exact in float32).  It is NOT the
+ *                                int16 down-mix divided by 32768: the half step is kept.
+ * Samples with f >= num_samples are zero, a window with stream >= num_streams is all zero in all C rows, wrapped int64 values
+ * give zeros and read nothing, no byte outside [data_offset, data_offset + data_size) is read, and a truncated image decodes as
+ * under AADHip_DecodePlanRun before the mix is taken.  formats[i].num_samples is ignored: the lengths come from the table.
+ *
+ * Errors.  AAD_APIRESULT_INVALID_ARGUMENT for null pointers (streams and formats may be null while num_streams == 0),
+ * out_channels outside {1, 2} and any formats[i].num_channels outside {1, 2}; otherwise every formats[i] with streams[i] is
+ * validated exactly as AADHip_DecodePlanCreate validates its one format, stream by stream in order (the channel count first),
+ * and the first failing stream's error is returned.  num_streams == 0 is OK: every window is zero.
+ *
+ * A run is one kernel per (source channels, bits, mid/side) present in the plan, in the order of the mixed-format plan's six
+ * two-channel kernels, then mono 4-, 3- and 2-bit: at most nine.  Every launch walks all the windows, with lanes for its SOURCE
+ * channel count, and writes those of its own streams; every element of the output is written exactly once per run.  The start
+ * event of AADHip_ContextSignalNextRun rides on the first kernel and the stop event on the last.  The run's errors are
+ * AADHip_WindowDecodePlanRun's with N * out_channels * T elements; the lane count that must fit 64 bits is that of the largest
+ * launch, N * (ceil((T - 1) / spb) + 1) * C_s for a variant's source channel count and smallest spb. */
+AADApiResult AADHip_ChannelMixWindowDecodePlanCreate(
+    struct AADHipContext *context, uint32_t out_channels /* 1 or 2 */, int32_t has_file_header,
+    uint32_t num_streams, const struct AADHipStreamDesc *streams,
+    const struct AADHeaderInfo *formats, /* host array, one per stream; num_channels 1 or 2 each */
+    struct AADHipWindowDecodePlan **plan);
+
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 
 /* The write side of the planar layout window decode reads out: one row per channel, int16 or float32 - torch's [N, C, T] - encoded

@@ -20,7 +20,18 @@ and a few windows against the oracle's decode of the whole stream (tests/oracle_
       the window table to the host, split by format, one same-format run per format over its own table, the rows scattered into
       [N, C, T] (the three plans made beforehand).  Every row of the mixed run is compared with the composite's.
 
-Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25] [--mixed]"""
+--channel-mix (profiles/r07_window_decode_channel_mix.txt): the channel-mix plan (AADHip_ChannelMixWindowDecodePlanCreate) down to
+one float32 row per window, on an all-stereo corpus and on one whose every second stream is mono (4-bit, the tool's shapes):
+  (a) the channel-mix plan with out_channels = 1: call time, and first kernel start to last kernel stop;
+  (b) what a caller has without it.  All stereo: the mixed-format plan into [N, 2, T], then (y[:, 0] + y[:, 1]) * 0.5 in torch.
+      Half mono: the mixed-format plan refuses the corpus, so the window table goes to the host and is split by channel count, a
+      mono and a stereo mixed-format plan (made beforehand) run over their own tables, the stereo rows are mixed in torch and both
+      parts scattered into [N, 1, T].
+  Both are warmed up, then timed in alternating rounds of --reps calls; a figure is the median of the rounds' medians and its spread
+  the range of the rounds' medians.  Every row of (a) is compared with (b)'s bitwise.
+
+Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25]
+       [--mixed | --channel-mix]"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -37,15 +48,15 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM = 8.0e12
 
 
-def build_corpus(engine, torch, streams, samples, chunk=25, seed=11, bits=4):
+def build_corpus(engine, torch, streams, samples, chunk=25, seed=11, bits=4, channels=2):
     from aad_amd.capi import make_parameter
     from aad_amd.synth import synth_pcm
-    param = make_parameter(2, bits, 1024)
+    param = make_parameter(channels, bits, 1024)
     size = engine.encoded_size(param, samples)
     stride = (size + 63) // 64 * 64
     corpus = torch.zeros((streams, stride), dtype=torch.uint8, device="cuda")
     starts = list(range(0, streams, chunk))
-    gen = lambda s0: synth_pcm(min(chunk, streams - s0), samples, 2, seed=seed, first_stream=s0)
+    gen = lambda s0: synth_pcm(min(chunk, streams - s0), samples, channels, seed=seed, first_stream=s0)
     with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         for s0, pcm in zip(starts, pool.map(gen, starts)):
             img, got = engine.encode_uniform(torch.from_numpy(pcm).cuda(), param, segment_blocks=16, warmup_blocks=1)
@@ -204,6 +215,108 @@ def mixed_main(args, say):
     engine.close()
 
 
+def channel_mix_main(args, say):
+    import torch
+    from aad_amd.capi import STREAM_DESC_DTYPE
+    from aad_amd.engine import Engine, HipEvent, parse_header
+    engine = Engine(0)
+    samples, frames, streams = int(round(args.seconds * 48000)), args.frames, args.streams
+    rounds, results = 5, []
+
+    def draw(n, count):
+        g = torch.Generator(device="cuda")
+        g.manual_seed(args.seed + n)
+        return torch.stack([torch.randint(0, count, (n,), device="cuda", generator=g),
+                            torch.randint(0, samples - frames + 1, (n,), device="cuda", generator=g)], dim=1)
+
+    def alternate(fa, fb):
+        """warm both up, then rounds of (a), (b): per side the median of the rounds' medians and their range"""
+        for _ in range(3):
+            fa()
+            fb()
+        torch.cuda.synchronize()
+        ta, tb = [], []
+        for _ in range(rounds):
+            ta.append(call_ms(torch, fa, args.reps))
+            tb.append(call_ms(torch, fb, args.reps))
+        return (float(np.median(ta)), max(ta) - min(ta)), (float(np.median(tb)), max(tb) - min(tb))
+
+    say("channel-mix window decode to one float32 row per window: %d 4-bit streams x %d frames, T = %d; %d alternating rounds of %d "
+        "calls, median of the rounds' medians (range of the rounds' medians); device %s"
+        % (streams, samples, frames, rounds, args.reps, torch.cuda.get_device_name(0)))
+    for name in ("all stereo", "half mono"):
+        half = streams // 2
+        stereo, size2, stride2 = build_corpus(engine, torch, streams if name == "all stereo" else half, samples, seed=args.seed)
+        h2 = parse_header(bytes(stereo[0, :31].cpu().numpy()))
+        if name == "all stereo":
+            count, corpus, stride = streams, stereo, stride2
+            headers, sizes = [h2] * count, np.full(count, size2, dtype=np.uint64)
+        else:  # stream i is mono for even i, stereo for odd i
+            mono, size1, stride1 = build_corpus(engine, torch, half, samples, seed=args.seed + 1, channels=1)
+            h1 = parse_header(bytes(mono[0, :31].cpu().numpy()))
+            count, stride = 2 * half, max(stride1, stride2)
+            corpus = torch.zeros((count, stride), dtype=torch.uint8, device="cuda")
+            corpus[0::2, :stride1] = mono
+            corpus[1::2, :stride2] = stereo
+            headers, sizes = [h1, h2] * half, np.array([size1, size2] * half, dtype=np.uint64)
+            del mono
+        del stereo
+        table = np.zeros(count, dtype=STREAM_DESC_DTYPE)
+        table["data_offset"] = np.arange(count, dtype=np.uint64) * np.uint64(stride)
+        table["data_size"], table["num_samples"] = sizes, samples
+        mix = engine.channel_mix_window_decode_plan(headers, table, 1, True)
+        if name == "all stereo":
+            plans = {2: engine.mixed_window_decode_plan(headers, table, True)}
+        else:  # the channel count's own streams: stream s of the corpus is s // 2 there
+            plans = {1: engine.mixed_window_decode_plan(headers[0::2], table[0::2], True),
+                     2: engine.mixed_window_decode_plan(headers[1::2], table[1::2], True)}
+        say("")
+        say("%s: %d streams (%s), %.2f GB of images" % (name, count, "spb %d" % h2.num_samples_per_block if name == "all stereo" else
+                                                         "mono spb %d, stereo spb %d" % (h1.num_samples_per_block, h2.num_samples_per_block),
+                                                         count * stride / 1e9))
+        for n in args.windows:
+            d_win = draw(n, count)
+            out_a = torch.empty((n, 1, frames), dtype=torch.float32, device="cuda")
+            out_b = torch.empty((n, 1, frames), dtype=torch.float32, device="cuda")
+            wide = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+
+            def new_plan():
+                mix.run(corpus, d_win, frames, torch.float32, out=out_a)
+
+            def parent_stereo():
+                y = plans[2].run(corpus, d_win, frames, torch.float32, out=wide)
+                torch.mul(y[:, 0] + y[:, 1], 0.5, out=out_b[:, 0])
+
+            def parent_half_mono():
+                w = d_win.cpu()  # the host synchronisation the channel-mix plan removes
+                for c in (1, 2):
+                    idx = torch.nonzero(w[:, 0] % 2 == c - 1).flatten()
+                    sub = torch.stack([w[idx, 0] // 2, w[idx, 1]], dim=1).cuda()
+                    y = plans[c].run(corpus, sub, frames, torch.float32)
+                    out_b[idx.cuda()] = y if c == 1 else ((y[:, 0] + y[:, 1]) * 0.5)[:, None]
+
+            parent = parent_stereo if name == "all stereo" else parent_half_mono
+            (a, a_range), (b, b_range) = alternate(new_plan, parent)
+            ka = kernel_ms(engine, HipEvent, new_plan, args.reps)
+            torch.cuda.synchronize()
+            exact = bool(torch.equal(out_a.view(torch.int32), out_b.view(torch.int32)))
+            say("  N = %5d: (a) channel-mix plan, out_channels = 1: call %.4f ms (range %.4f), kernels first start to last stop %.4f ms; "
+                "(b) %s: call %.4f ms (range %.4f); (b) / (a) = %.2fx; (a) no slower than (b): %s; identical rows: %s"
+                % (n, a, a_range, ka, "mixed-format plan into [N, 2, T] + torch mix" if name == "all stereo" else
+                   "host split + two mixed-format plans + torch mix + scatter", b, b_range, b / a, a <= b, exact))
+            results.append(dict(corpus=name, windows=n, a_call_ms=a, a_range_ms=a_range, a_kernels_ms=ka, b_call_ms=b, b_range_ms=b_range,
+                                identical=exact))
+            del out_a, out_b, wide
+        mix.close()
+        for p in plans.values():
+            p.close()
+        del corpus
+        torch.cuda.empty_cache()
+    say("")
+    say("json " + json.dumps(results))
+    engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=1000)
@@ -214,6 +327,7 @@ def main():
     ap.add_argument("--seed", type=int, default=11)
     ap.add_argument("--out", default=None, help="also write the report here")
     ap.add_argument("--mixed", action="store_true", help="the mixed-format plan's two measurements instead (see above)")
+    ap.add_argument("--channel-mix", action="store_true", help="the channel-mix plan against what a caller has without it (see above)")
     args = ap.parse_args()
 
     import torch
@@ -224,8 +338,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    if args.mixed:
-        mixed_main(args, say)
+    if args.mixed or args.channel_mix:
+        (mixed_main if args.mixed else channel_mix_main)(args, say)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
