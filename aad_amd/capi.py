@@ -97,7 +97,7 @@ HIP_SYMBOLS = [
     "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate", "AADHip_SegmentedEncodeBatch",
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
-    "AADHip_MixedWindowDecodePlanCreate", "AADHip_ChannelMixWindowDecodePlanCreate",
+    "AADHip_WindowDecodePlanRunStats", "AADHip_MixedWindowDecodePlanCreate", "AADHip_ChannelMixWindowDecodePlanCreate",
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
     "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
     "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
@@ -212,6 +212,8 @@ def _declare_hip(lib):
     lib.AADHip_WindowDecodePlanDestroy.restype = None
     lib.AADHip_WindowDecodePlanRun.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp]
     lib.AADHip_WindowDecodePlanRun.restype = C.c_int
+    lib.AADHip_WindowDecodePlanRunStats.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, vp]
+    lib.AADHip_WindowDecodePlanRunStats.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

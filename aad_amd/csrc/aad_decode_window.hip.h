@@ -47,10 +47,23 @@ typedef float f32x4_u4 __attribute__((ext_vector_type(4), aligned(4))); /* a 16-
 /* how a lane's samples reach the output's channels (aad_decode_window_channel_mix.hip.h); kMixNone: channel c into row c */
 enum WindowMix { kMixNone = 0, kMixTwin = 1 /* mono source, two rows */, kMixDown = 2 /* stereo source, one row */ };
 
+/* the level statistics of a lane's samples inside its window (AADHip_WindowDecodePlanRunStats): 64-bit sums from the first sample
+ * on - one 16-sample chunk at full scale is 2^34 in sum_sq, one long block 2^32 in sum_abs.  Empty without STATS. */
+template <bool STATS>
+struct WindowLevels {
+};
+template <>
+struct WindowLevels<true> {
+  uint64_t sum_sq, sum_abs;
+  uint32_t max_abs;
+  bool store; /* false: a statistics-only run, `row` is not written (uniform over the run) */
+};
+
 /* one row segment of a lane: output element t = base + i for sample i of the block, kept where lo <= t < hi.
- * kMixTwin: every store goes to the row `twin` elements on as well.  kMixDown: y is L + R as float32, (L + R) >> 1 as int16. */
-template <bool F32, int MIX = kMixNone>
-struct WindowRow {
+ * kMixTwin: every store goes to the row `twin` elements on as well.  kMixDown: y is L + R as float32, (L + R) >> 1 as int16.
+ * STATS: every kept sample is added to the lane's WindowLevels as the int16 value the row holds, zeros() adds nothing. */
+template <bool F32, int MIX = kMixNone, bool STATS = false>
+struct WindowRow : WindowLevels<STATS> {
   using T = std::conditional_t<F32, float, int16_t>;
   T *row;
   int64_t base, lo, hi;
@@ -61,20 +74,42 @@ struct WindowRow {
     if constexpr (F32) return (float)y * (MIX == kMixDown ? 1.0f / 65536.0f : 1.0f / 32768.0f);
     else return (T)y;
   }
-  __device__ __forceinline__ void one(uint32_t i, int32_t y) const
+  /* STATS only.  The float32 down-mix carries L + R: its statistic is the int16 floor mix's */
+  __device__ __forceinline__ void level(int32_t y)
+  {
+    const int32_t v = F32 && MIX == kMixDown ? y >> 1 : y;
+    const uint32_t m = (uint32_t)(v < 0 ? -v : v); /* at most 32768 */
+    this->sum_sq += (uint64_t)m * m;
+    this->sum_abs += m;
+    this->max_abs = m > this->max_abs ? m : this->max_abs;
+  }
+  __device__ __forceinline__ bool stores() const
+  {
+    if constexpr (STATS) return this->store;
+    else return true;
+  }
+  __device__ __forceinline__ void one(uint32_t i, int32_t y)
   {
     const int64_t t = base + (int64_t)i;
     if (t >= lo && t < hi) {
-      row[t] = convert(y);
-      if constexpr (MIX == kMixTwin) row[t + twin] = convert(y);
+      if (stores()) {
+        row[t] = convert(y);
+        if constexpr (MIX == kMixTwin) row[t + twin] = convert(y);
+      }
+      if constexpr (STATS) level(y);
     }
   }
   /* samples i0 .. i0 + 15 */
-  __device__ __forceinline__ void chunk(uint32_t i0, const int32_t *y) const
+  __device__ __forceinline__ void chunk(uint32_t i0, const int32_t *y)
   {
     const int64_t t0 = base + (int64_t)i0;
     if (t0 + kChunk <= lo || t0 >= hi) return;
     if (t0 >= lo && t0 + kChunk <= hi) {
+      if constexpr (STATS) {
+#pragma unroll
+        for (int j = 0; j < kChunk; j++) level(y[j]);
+        if (!this->store) return;
+      }
       T *p = row + t0;
       if constexpr (F32) {
 #pragma unroll
@@ -100,6 +135,7 @@ struct WindowRow {
   /* zeros over [from, hi) */
   __device__ __forceinline__ void zeros(int64_t from) const
   {
+    if (!stores()) return;
     for (int64_t t = from > lo ? from : lo; t < hi; t++) {
       row[t] = (T)0;
       if constexpr (MIX == kMixTwin) row[t + twin] = (T)0;
@@ -113,10 +149,12 @@ struct WindowRow {
  * it together.  Windows whose stream is out of range are written (as zeros) by the launch that `owns_strays`.
  * OUTC (aad_decode_window_channel_mix.hip.h; 0: as many as the source has): the rows a window has in the output.  The lanes, the
  * block geometry and every read stay the SOURCE's (CHF); a mono source stores into both rows, a stereo pair exchanges the finished
- * L / R samples once more and lane c == 0 stores the mix into the one row. */
-template <int BITS, int CHF, bool MS, bool F32, bool MIXED = false, int OUTC = 0, class FORMAT = StreamFormat>
+ * L / R samples once more and lane c == 0 stores the mix into the one row.
+ * STATS (aad_decode_window_stats.hip.h): the lane also sums the levels of the samples it keeps and ends by adding them into its
+ * row's record of `stats`, which the run cleared; a.out may then be null - nothing is stored, the ranges stay. */
+template <int BITS, int CHF, bool MS, bool F32, bool MIXED = false, int OUTC = 0, class FORMAT = StreamFormat, bool STATS = false>
 __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane, const FORMAT *formats = nullptr,
-                                            uint32_t owns_strays = 0)
+                                            uint32_t owns_strays = 0, unsigned long long *stats = nullptr)
 {
   static_assert(OUTC == 0 || ((CHF == 1 || CHF == 2) && (OUTC == 1 || OUTC == 2)), "a channel mix is between one and two channels");
   constexpr int MIX = OUTC == 0 || OUTC == CHF ? kMixNone : OUTC == 2 ? kMixTwin : kMixDown;
@@ -147,7 +185,12 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
   const uint64_t kspb = (uint64_t)k * spb;
   if (kspb >= frames + phase) return; /* past the window's last block: lanes of one (window, block) leave together */
 
-  WindowRow<F32, MIX> out;
+  WindowRow<F32, MIX, STATS> out;
+  if constexpr (STATS) {
+    out.sum_sq = out.sum_abs = 0;
+    out.max_abs = 0;
+    out.store = a.out != nullptr;
+  }
   if constexpr (MIX == kMixNone) {
     out.row = reinterpret_cast<typename WindowRow<F32>::T *>(a.out) + (w * ch + c) * frames;
   } else {
@@ -160,10 +203,13 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
 
   /* samples of this block the window needs, as far as the stream has them (n = 0: none) */
   uint32_t n = 0, avail = 0;
+  [[maybe_unused]] uint64_t count = 0; /* STATS: frames of the window the stream's table has, from the lane of the window's first block */
   const uint8_t *src = a.data;
   if (stream < a.num_streams) {
     const StreamDesc sd = a.streams[stream];
     if (first_frame < sd.num_samples) {
+      if constexpr (STATS)
+        if (k == 0) count = sd.num_samples - first_frame < frames ? sd.num_samples - first_frame : frames;
       const uint64_t b = first_frame / spb + k;
       const uint64_t first = b * spb;
       if (first < sd.num_samples) {
@@ -302,6 +348,22 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
     }
   }
   out.zeros(out.base + (int64_t)n);
+
+  if constexpr (STATS) {
+    /* the lanes of a row's K blocks meet in its record: integer adds and a max, so any order gives the same bits.  The R lane of a
+     * down-mixed pair kept nothing; a lane without a non-zero sample and the records of stray windows leave the cleared zeros */
+    if (MIX == kMixDown && c) return;
+    unsigned long long *rec = stats + 4 * (MIX == kMixNone ? w * ch + c : w * OUTC);
+#pragma unroll
+    for (int twin = 0; twin < (MIX == kMixTwin ? 2 : 1); twin++, rec += 4) {
+      if (out.sum_abs) {
+        atomicAdd(rec, (unsigned long long)out.sum_sq);
+        atomicAdd(rec + 1, (unsigned long long)out.sum_abs);
+        atomicMax(rec + 2, (unsigned long long)out.max_abs);
+      }
+      if (count) atomicAdd(rec + 3, (unsigned long long)count);
+    }
+  }
 }
 
 template <int BITS, int CHF, bool MS, bool F32>

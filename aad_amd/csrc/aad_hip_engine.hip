@@ -422,7 +422,8 @@ aad::LaunchSignal take_signal(AADHipContext *ctx)
   return s;
 }
 /* ... and settled when it ends: a run that launched its kernel has handed the events to it (aad_launch.h); one that launched
- * nothing (an empty plan) records them behind whatever the stream holds; a failed run leaves them unrecorded */
+ * nothing (an empty plan) records them behind whatever the stream holds; a failed run leaves them unrecorded - but for the
+ * start event of a statistics run whose clear itself failed to enqueue (clear_window_stats: the event goes in front of the clear) */
 AADApiResult finish_signal(AADHipContext *ctx, const aad::LaunchSignal &signal, AADApiResult rc)
 {
   const bool taken = aad::tl_launch_signal.start == nullptr && aad::tl_launch_signal.stop == nullptr;
@@ -1169,12 +1170,24 @@ void AADHip_WindowDecodePlanDestroy(struct AADHipWindowDecodePlan *plan)
 }
 
 namespace {
-/* The launches of a mixed-format run, in the stream's order: one per kernel variant of the plan, each over all the windows.  The
- * start event rides on the first and the stop event on the last (aad_launch.h); a plan with one variant is one kernel. */
-AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &signal, const uint8_t *device_data,
-                                     uint64_t num_windows, const struct AADHipWindow *device_windows, uint32_t frames_per_window,
-                                     int32_t sample_type, void *device_out)
+/* AADHip_WindowDecodePlanRunStats: the lanes add into the table, so the run clears it in front of its first launch - the start
+ * event recorded in front of the clear, and the launches carry the stop event alone (as a segmented reconstruct's statistics) */
+bool clear_window_stats(AADHipContext *ctx, aad::LaunchSignal *signal, struct AADHipRowStats *stats, uint64_t bytes)
 {
+  if (signal->start != nullptr && !hip_ok(ctx, hipEventRecord(signal->start, ctx->stream), "hipEventRecord")) return false;
+  signal->start = nullptr;
+  return hip_ok(ctx, hipMemsetAsync(stats, 0, bytes, ctx->stream), "hipMemsetAsync");
+}
+
+/* The launches of a mixed-format run, in the stream's order: one per kernel variant of the plan, each over all the windows.  The
+ * start event rides on the first and the stop event on the last (aad_launch.h); a plan with one variant is one kernel.
+ * stats (AADHip_WindowDecodePlanRunStats; stats_bytes: the table's size), else null: the launches also fill the table, and
+ * device_out may be null. */
+AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &run_signal, const uint8_t *device_data,
+                                     uint64_t num_windows, const struct AADHipWindow *device_windows, uint32_t frames_per_window,
+                                     int32_t sample_type, void *device_out, struct AADHipRowStats *stats, uint64_t stats_bytes)
+{
+  aad::LaunchSignal signal = run_signal;
   AADHipContext *ctx = plan->ctx;
   const aad::DecodeArgs &d = plan->args;
   const aad::MixedWindowLaunch m =
@@ -1187,6 +1200,7 @@ AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::La
   DeviceGuard guard(ctx);
   if (!guard.ok) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   if (num_windows == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
+  if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   aad::LaunchSignal last = signal;
   for (uint32_t i = 0; i < m.count; i++) {
     aad::MixedWindowArgs a;
@@ -1208,17 +1222,20 @@ AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::La
     a.owns_strays = i == 0;
     last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
     aad::tl_launch_signal = last;
-    aad::launch_decode_window_mixed(a, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+    if (stats != nullptr) aad::launch_decode_window_mixed_stats(a, stats, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+    else aad::launch_decode_window_mixed(a, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
     if (!hip_ok(ctx, hipGetLastError(), "mixed window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   }
   return finish_signal(ctx, last, AAD_APIRESULT_OK);
 }
 
 /* ... and of a channel-mix run: one per (source channels, bits, mid/side) of the plan, d.channels rows per window */
-AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &signal, const uint8_t *device_data,
+AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &run_signal, const uint8_t *device_data,
                                            uint64_t num_windows, const struct AADHipWindow *device_windows,
-                                           uint32_t frames_per_window, int32_t sample_type, void *device_out)
+                                           uint32_t frames_per_window, int32_t sample_type, void *device_out,
+                                           struct AADHipRowStats *stats, uint64_t stats_bytes)
 {
+  aad::LaunchSignal signal = run_signal;
   AADHipContext *ctx = plan->ctx;
   const aad::DecodeArgs &d = plan->args;
   const aad::ChannelMixWindowLaunch m =
@@ -1231,6 +1248,7 @@ AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const a
   DeviceGuard guard(ctx);
   if (!guard.ok) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   if (num_windows == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
+  if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   aad::LaunchSignal last = signal;
   for (uint32_t i = 0; i < m.count; i++) {
     aad::ChannelMixWindowArgs a;
@@ -1253,28 +1271,44 @@ AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const a
     a.out_channels = d.channels;
     last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
     aad::tl_launch_signal = last;
-    aad::launch_decode_window_channel_mix(a, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+    if (stats != nullptr)
+      aad::launch_decode_window_channel_mix_stats(a, stats, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+    else aad::launch_decode_window_channel_mix(a, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
     if (!hip_ok(ctx, hipGetLastError(), "channel-mix window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   }
   return finish_signal(ctx, last, AAD_APIRESULT_OK);
 }
-} /* namespace */
 
-AADApiResult AADHip_WindowDecodePlanRun(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
-                                        const struct AADHipWindow *device_windows, uint32_t frames_per_window, int32_t sample_type,
-                                        void *device_out)
+/* AADHip_WindowDecodePlanRun, and with_stats AADHip_WindowDecodePlanRunStats: the table as a further output, device_out optional */
+AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
+                               const struct AADHipWindow *device_windows, uint32_t frames_per_window, int32_t sample_type,
+                               void *device_out, bool with_stats, struct AADHipRowStats *stats)
 {
   if (plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
   AADHipContext *ctx = plan->ctx;
-  const aad::LaunchSignal signal = take_signal(ctx);
+  aad::LaunchSignal signal = take_signal(ctx);
   if (frames_per_window == 0 || (sample_type != AAD_HIP_SAMPLE_INT16 && sample_type != AAD_HIP_SAMPLE_FLOAT32) ||
-      (num_windows != 0 && (device_data == nullptr || device_windows == nullptr || device_out == nullptr)))
+      (num_windows != 0 && (device_data == nullptr || device_windows == nullptr || (device_out == nullptr && !with_stats))))
     return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+  uint64_t stats_bytes = 0;
+  if (with_stats) {
+    const aad::WindowStatsTable t = aad::window_stats_table(num_windows, plan->args.channels, (uint64_t)reinterpret_cast<uintptr_t>(stats));
+    if (!t.ok) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error),
+               "window decode statistics: a null or unaligned table, or %llu windows x %u channels x 32 bytes overflow 64 bits",
+               (unsigned long long)num_windows, plan->args.channels);
+      return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+    }
+    stats_bytes = t.bytes;
+  } else {
+    stats = nullptr;
+  }
   if (plan->mixed)
-    return run_mixed_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out);
+    return run_mixed_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out,
+                                   stats, stats_bytes);
   if (plan->channel_mix)
     return run_channel_mix_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type,
-                                         device_out);
+                                         device_out, stats, stats_bytes);
   const aad::DecodeArgs &d = plan->args;
   const aad::WindowLaunch p =
       aad::plan_window_decode(ctx->device_info, ctx->knobs, aad::WindowBatch{num_windows, frames_per_window, d.channels, d.bits, d.samples_per_block});
@@ -1303,9 +1337,27 @@ AADApiResult AADHip_WindowDecodePlanRun(struct AADHipWindowDecodePlan *plan, con
   a.header_bytes = d.header_bytes;
   a.mid_side = d.mid_side;
   a.bits = d.bits;
+  if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
-  aad::launch_decode_window(a, p, sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+  if (stats != nullptr) aad::launch_decode_window_stats(a, stats, p, sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+  else aad::launch_decode_window(a, p, sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
   return finish_signal(ctx, signal, hip_ok(ctx, hipGetLastError(), "window decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG);
+}
+} /* namespace */
+
+AADApiResult AADHip_WindowDecodePlanRun(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
+                                        const struct AADHipWindow *device_windows, uint32_t frames_per_window, int32_t sample_type,
+                                        void *device_out)
+{
+  return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out, false, nullptr);
+}
+
+AADApiResult AADHip_WindowDecodePlanRunStats(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
+                                             const struct AADHipWindow *device_windows, uint32_t frames_per_window,
+                                             int32_t sample_type, void *device_out, struct AADHipRowStats *device_stats)
+{
+  return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out, true,
+                           device_stats);
 }
 
 /* -------------------------------------------------------------------- window reconstruct -- */

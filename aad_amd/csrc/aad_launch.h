@@ -37,6 +37,15 @@ void launch_decode_window_mixed(const MixedWindowArgs &args, const WindowLaunch 
 /* aad_decode_window_channel_mix.hip: one launch (args.w.channels, args.w.bits, args.w.mid_side: the variant) of a channel-mix run */
 struct ChannelMixWindowArgs;
 void launch_decode_window_channel_mix(const ChannelMixWindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
+/* aad_decode_window_stats.hip, aad_decode_window_mixed_stats.hip, aad_decode_window_channel_mix_stats.hip: the same launches of
+ * AADHip_WindowDecodePlanRunStats - the rows (args' out, which may be null) and the level statistics of every row added into
+ * `stats`, which the run cleared */
+void launch_decode_window_stats(const WindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, bool float32,
+                                hipStream_t stream);
+void launch_decode_window_mixed_stats(const MixedWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, bool float32,
+                                      hipStream_t stream);
+void launch_decode_window_channel_mix_stats(const ChannelMixWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p,
+                                            bool float32, hipStream_t stream);
 /* the decoded rows of a planar reconstruct run (AADHip_PlanarReconstructPlanRun; launched through aad_encode_launch.hip.h).
  * base: per stream (segmented: per chain) the element of `out` that holds channel 0's sample of the lane's first frame, device
  * memory */

@@ -392,6 +392,25 @@ inline WindowLaunch plan_window_decode(const Device &d, const Knobs &k, const Wi
   return plan_window_decode_into(d, k, b, b.channels);
 }
 
+/* ---- window decode statistics (AADHip_WindowDecodePlanRunStats): the table of a run ------------------------------------------ */
+struct WindowStatsTable {
+  bool ok;        /* false: the pointer is null or not 8-byte aligned while the run has windows, or windows * channels * 32 bytes
+                   * overflow 64 bits - with frames < 8 that can happen where the rows' bytes do not */
+  uint64_t bytes; /* windows * out_channels * sizeof(AADHipRowStats): what the run clears in front of its first launch */
+};
+inline WindowStatsTable window_stats_table(uint64_t windows, uint32_t out_channels, uint64_t stats_address)
+{
+  WindowStatsTable t = {};
+  uint64_t records = 0;
+  if (__builtin_mul_overflow(windows, (uint64_t)out_channels, &records) ||
+      __builtin_mul_overflow(records, (uint64_t)sizeof(struct AADHipRowStats), &t.bytes)) {
+    t.bytes = 0;
+    return t;
+  }
+  t.ok = windows == 0 || (stats_address != 0 && (stats_address & 7u) == 0);
+  return t;
+}
+
 /* ---- mixed-format window decode (AADHip_MixedWindowDecodePlanCreate): one launch per kernel variant of the plan ------------- */
 /* what a lane reads of its stream's format, one record per stream next to the descriptor table (device memory) */
 struct StreamFormat {

@@ -505,24 +505,43 @@ class Engine:
         d["num_samples"] = header.num_samples
         return self.window_decode_plan(header, d, True)
 
-    def decode_windows(self, data, image_size, windows, frames, dtype=None):
+    def decode_windows(self, data, image_size, windows, frames, dtype=None, return_stats=False):
         """data: uint8 cuda tensor [streams, stride] of same-format images (encode_uniform's output); windows: int64 cuda tensor
         [N, 2] of (stream, first_frame) -> [N, channels, frames] tensor of `dtype` (torch.float32 = sample / 32768, or torch.int16).
-        The header is read once, from the first image; the windows are never read on the host."""
+        The header is read once, from the first image; the windows are never read on the host.
+        return_stats: -> (rows, int64 [N, channels, 4] level statistics of the rows), see WindowDecodePlan.run."""
         head = bytes(data[0, :31].cpu().numpy())
         header = parse_header(head)
         plan = self.uniform_window_decode_plan(header, data.shape[0], data.shape[1], image_size)
         try:
-            return plan.run(data, windows, frames, dtype)
+            return plan.run(data, windows, frames, dtype, stats=True if return_stats else None)
         finally:
             plan.close()  # synchronises the context's stream first
 
-    def decode_windows_mixed(self, data, image_sizes, windows, frames, dtype=None, channels=None):
+    def decode_windows_mixed(self, data, image_sizes, windows, frames, dtype=None, channels=None, return_stats=False):
         """decode_windows over images that do not share a format (encode_planar_mixed's output): data is a uint8 cuda tensor
         [streams, stride], row i starting with an image of image_sizes[i] bytes (an int: the same for all).  The 31-byte headers of
         all the images come to the host in one copy and are parsed one by one (the channel counts must agree); the windows are
         never read on the host.  channels = 1 or 2: mono and stereo images may share the tensor and the result has that many rows
-        per window (channel_mix_window_decode_plan)."""
+        per window (channel_mix_window_decode_plan).  return_stats: -> (rows, int64 [N, channels, 4] level statistics)."""
+        plan = self._corpus_window_plan(data, image_sizes, channels)
+        try:
+            return plan.run(data, windows, frames, dtype, stats=True if return_stats else None)
+        finally:
+            plan.close()  # synchronises the context's stream first
+
+    def window_levels(self, data, image_sizes, windows, frames, channels=None):
+        """The level statistics of decode_windows_mixed's rows without the rows: int64 [N, channels, 4] of (sum_sq, sum_abs,
+        max_abs, count) per row, in int16 units (rmse, level_dbfs).  Nothing is stored but the table - what a rejection sampler
+        asks of its candidates before it decodes the ones it keeps.  channels=None: the images share a channel count."""
+        plan = self._corpus_window_plan(data, image_sizes, channels)
+        try:
+            return plan.run(data, windows, frames, stats=True, rows=False)
+        finally:
+            plan.close()  # synchronises the context's stream first
+
+    def _corpus_window_plan(self, data, image_sizes, channels):
+        """the window decode plan over the images in the rows of `data`: mixed-format, or channel-mix when `channels` is given"""
         if data.dim() != 2 or not data.is_cuda or data.dtype != self.torch.uint8 or data.stride(1) != 1:
             raise ValueError("data: a uint8 cuda tensor [streams, stride]")
         s = int(data.shape[0])
@@ -537,12 +556,8 @@ class Engine:
         d["data_offset"] = np.arange(s, dtype=np.uint64) * np.uint64(data.stride(0))
         d["data_size"] = sizes
         d["num_samples"] = [h.num_samples for h in headers]
-        plan = self.mixed_window_decode_plan(headers, d, True) if channels is None \
+        return self.mixed_window_decode_plan(headers, d, True) if channels is None \
             else self.channel_mix_window_decode_plan(headers, d, channels, True)
-        try:
-            return plan.run(data, windows, frames, dtype)
-        finally:
-            plan.close()  # synchronises the context's stream first
 
     # ---- reconstruction modes (the reference CLI's -r / -g / -c, src/main.c:275-503) ----------
     def reconstruct_uniform(self, pcm, param, residual=False, want_stats=True, segment_blocks=None, warmup_blocks=0):
@@ -664,6 +679,15 @@ def rmse(stats):
     """sqrt(sum_sq / count) per row of an int64 [..., 4] statistics tensor, float64, in int16 units; NaN for an empty row"""
     sum_sq, _, _, count = _stats_f64(stats)
     return (sum_sq / count).sqrt()
+
+
+def level_dbfs(stats):
+    """20 log10(rmse / 32768) per row of an int64 [..., 4] statistics tensor, float64: the row's RMS level against full scale;
+    -inf for an all-zero or empty row"""
+    import torch
+    sum_sq, _, _, count = _stats_f64(stats)
+    mean = torch.where(count == 0, torch.zeros_like(sum_sq), sum_sq / count.clamp(min=1.0))
+    return 20.0 * (mean.sqrt() / 32768.0).log10()
 
 
 def snr_db(stats, signal_sum_sq):
@@ -860,10 +884,13 @@ class WindowDecodePlan:
     def __init__(self, engine, handle, header, descs):
         self.engine, self.handle, self.header, self.descs = engine, handle, header, descs
 
-    def run(self, data, windows, frames, dtype=None, out=None, ordered=True):
+    def run(self, data, windows, frames, dtype=None, out=None, ordered=True, stats=None, rows=True):
         """data: uint8 cuda tensor of the images; windows: int64 cuda tensor [N, 2] of (stream, first_frame) ->
         `out` ([N, channels, frames] of dtype torch.float32 - sample / 32768 - or torch.int16; allocated when None).
-        Asynchronous on the engine's stream, ordered against torch's current one; the windows stay on the device."""
+        Asynchronous on the engine's stream, ordered against torch's current one; the windows stay on the device.
+        stats (AADHip_WindowDecodePlanRunStats): True, or a contiguous cuda int64 tensor [N, channels, 4] - the exact level
+        statistics of every row (sum_sq, sum_abs, max_abs in int16 units, count = the frames the stream had), from the same
+        kernels -> (out, stats).  rows=False: statistics only, no row is written -> stats."""
         torch = self.engine.torch
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.int16):
@@ -872,18 +899,39 @@ class WindowDecodePlan:
             raise ValueError("windows: an int64 cuda tensor [N, 2] of (stream, first_frame)")
         windows = windows.contiguous()
         n, ch, frames = int(windows.shape[0]), int(self.header.num_channels), int(frames)
-        if out is None:
+        if stats is None or stats is False:
+            stats = None
+            if not rows:
+                raise ValueError("rows=False is a statistics-only run: pass stats=True or a table")
+        elif stats is True:
+            stats = torch.empty((n, ch, 4), dtype=torch.int64, device=windows.device)
+        elif (not torch.is_tensor(stats) or stats.dtype != torch.int64 or tuple(stats.shape) != (n, ch, 4) or not stats.is_cuda
+              or not stats.is_contiguous()):
+            raise ValueError("stats: True or a contiguous cuda int64 tensor [%d, %d, 4]" % (n, ch))
+        elif stats.device != windows.device:
+            raise ValueError("stats: on %s, the windows are on %s" % (stats.device, windows.device))
+        if not rows:
+            if out is not None:
+                raise ValueError("rows=False writes no rows: pass no `out`")
+        elif out is None:
             out = torch.empty((n, ch, frames), dtype=dtype, device=windows.device)
-        elif out.dtype != dtype or tuple(out.shape) != (n, ch, frames) or not out.is_contiguous():
-            raise ValueError("out: a contiguous %s tensor [%d, %d, %d]" % (dtype, n, ch, frames))
+        elif out.dtype != dtype or tuple(out.shape) != (n, ch, frames) or not out.is_contiguous() or out.device != windows.device:
+            raise ValueError("out: a contiguous %s tensor [%d, %d, %d] on %s" % (dtype, n, ch, frames, windows.device))
         kind = SAMPLE_FLOAT32 if dtype == torch.float32 else SAMPLE_INT16
         cur = self.engine._enter() if ordered else None
-        _check("AADHip_WindowDecodePlanRun",
-               self.engine.lib.AADHip_WindowDecodePlanRun(self.handle, data.data_ptr(), n, windows.data_ptr(), frames, kind,
-                                                          out.data_ptr()))
+        if stats is None:
+            _check("AADHip_WindowDecodePlanRun",
+                   self.engine.lib.AADHip_WindowDecodePlanRun(self.handle, data.data_ptr(), n, windows.data_ptr(), frames, kind,
+                                                              out.data_ptr()))
+        else:
+            _check("AADHip_WindowDecodePlanRunStats",
+                   self.engine.lib.AADHip_WindowDecodePlanRunStats(self.handle, data.data_ptr(), n, windows.data_ptr(), frames, kind,
+                                                                   out.data_ptr() if rows else None, stats.data_ptr()))
         if ordered:
             self.engine._exit(cur)
-        return out
+        if stats is None:
+            return out
+        return (out, stats) if rows else stats
 
     def close(self):
         if self.handle:
@@ -1029,4 +1077,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "select_least_bits"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "select_least_bits"]

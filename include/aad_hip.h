@@ -71,8 +71,10 @@ const char *AADHip_ContextLastError(const struct AADHipContext *context);
 
 /* Cross-stream ordering and kernel timing without packets of their own.  `hip_start_event` / `hip_stop_event` (hipEvent_t the
  * caller owns; either may be NULL, both NULL withdraws) are recorded when the work of the NEXT AADHip_EncodePlanRun /
- * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_WindowReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
- * the run takes them.  An encode, decode or window decode plan run is one kernel, and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
+ * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_WindowReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_WindowDecodePlanRunStats / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
+ * the run takes them.  An encode, decode or window decode plan run is one kernel (a mixed-format or channel-mix window decode several: start on the first, stop on
+ * the last; a run that first clears a statistics table - AADHip_WindowDecodePlanRunStats, a segmented AADHip_PlanarReconstructPlanRunStats - records the
+ * start event with hipEventRecord in front of the clear and its last kernel carries the stop event), and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
  * stop events) instead of on barrier packets around it: a hipEventRecord behind every launch of a back-to-back sequence costs
  * the queue 2.9 us per launch on MI355X, the attached event nothing (profiles/r03_microbench_event_gap.txt), and
  * hipEventElapsedTime between the two is the kernel's own duration.  Another stream waits for the stop event with
@@ -297,6 +299,46 @@ AADApiResult AADHip_ChannelMixWindowDecodePlanCreate(
     uint32_t num_streams, const struct AADHipStreamDesc *streams,
     const struct AADHeaderInfo *formats, /* host array, one per stream; num_channels 1 or 2 each */
     struct AADHipWindowDecodePlan **plan);
+
+/* Window decode with exact per-row level statistics, from the decode kernels themselves: what a data loader asks of a crop (is
+ * it silent, what is its RMS, how many of its frames did the stream have) without a second pass over the rows - and, with
+ * device_out == NULL, without the rows.  For all three kinds of window decode plan.
+ *
+ * Definition.  Let C be the plan's output channel count (num_channels; out_channels of a channel-mix plan).  For window
+ * w = {stream, first_frame}, row r < C and t < T let v[w][r][t] be the int16 value that AADHip_WindowDecodePlanRun with
+ * AAD_HIP_SAMPLE_INT16 writes to out[(w * C + r) * T + t] for the same plan, data and windows.  The record of row (w, r) is the
+ * AADHipRowStats (below) at index w * C + r - a torch int64 [N, C, 4] tensor on the device IS the table - with
+ *   sum_sq  = sum over t of v * v,   sum_abs = sum over t of |v|,   max_abs = max over t of |v| (0 when nothing contributes;
+ *             32768 is reachable),
+ *   count   = the number of t < T with stream < num_streams and first_frame + t < num_samples[stream], that is
+ *             min(T, num_samples - first_frame): 0 for a stray window or a wrapped value and where first_frame >= num_samples.
+ *             It comes from the stream table alone - a truncated image does not change it - and is the row's padding mask.
+ * Consequences:
+ *   - the statistics do not depend on sample_type.  A float32 row is v / 32768 exactly, with one exception: the float32 down-mix
+ *     (C_s = 2, C = 1) keeps the half step in the row, and its statistics are still those of the int16 floor mix (L + R) >> 1;
+ *   - a mono stream decoded into two rows gives two equal records;
+ *   - |v| <= 32768 and T < 2^32, so sum_sq <= 2^62: nothing wraps and every field is non-negative as int64;
+ *   - the sums are integers, so two runs give the same bits whatever order the lanes finish in.
+ *
+ * Outputs.  The rows are byte for byte what AADHip_WindowDecodePlanRun writes; no other element of device_out and nothing outside
+ * the N * C records is touched; every record is written, whatever the table held before.  device_out may be NULL: statistics only,
+ * no row is written (and nothing is stored but the records).
+ *
+ * Errors.  AADHip_WindowDecodePlanRun's, except that a null device_out is allowed (sample_type is validated all the same), plus
+ * AAD_APIRESULT_INVALID_ARGUMENT for a device_stats that is null or not 8-byte aligned while num_windows > 0 and for N * C * 32
+ * bytes overflowing 64 bits (with T < 8 that can happen where N * C * T * 4 does not).  num_windows == 0 is OK and launches
+ * nothing.
+ *
+ * The lanes of a row's blocks add into its record, so the run first clears the table on the context's stream and then launches
+ * AADHip_WindowDecodePlanRun's kernels (same lanes, same variants).  AADHip_ContextSignalNextRun: the start event is recorded in
+ * front of the clear - the run's first device operation - and the stop event rides on the run's last kernel. */
+struct AADHipRowStats;
+AADApiResult AADHip_WindowDecodePlanRunStats(
+    struct AADHipWindowDecodePlan *plan, const uint8_t *device_data,
+    uint64_t num_windows, const struct AADHipWindow *device_windows,
+    uint32_t frames_per_window, int32_t sample_type,
+    void *device_out,                     /* may be NULL: statistics only, no row is written */
+    struct AADHipRowStats *device_stats); /* N * C records, 8-byte aligned, every one written by the run */
 
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 

@@ -30,8 +30,18 @@ one float32 row per window, on an all-stereo corpus and on one whose every secon
   Both are warmed up, then timed in alternating rounds of --reps calls; a figure is the median of the rounds' medians and its spread
   the range of the rounds' medians.  Every row of (a) is compared with (b)'s bitwise.
 
+--stats (profiles/r08_window_decode_stats.txt): the level statistics of the rows (AADHip_WindowDecodePlanRunStats) on the tool's
+corpus - stereo 4-bit, float32 rows, same-format plan:
+  (a) AADHip_WindowDecodePlanRun alone;
+  (b) rows and the statistics table in one run;
+  (c) the table alone (device_out = NULL: nothing is stored but the records);
+  (d) what a caller has without it: (a), then y.square().sum(-1), y.abs().sum(-1) and y.abs().amax(-1) over the float32 rows.
+  All four are warmed up, then timed in alternating rounds of --reps calls (wall clock with a device synchronise); a figure is
+  the median of the rounds' medians and its spread the range of the rounds' medians.  (b)'s rows are compared with (a)'s bitwise,
+  (b)'s table with (c)'s, and the table with int64 sums over the int16 rows taken in torch.
+
 Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25]
-       [--mixed | --channel-mix]"""
+       [--mixed | --channel-mix | --stats]"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -317,6 +327,75 @@ def channel_mix_main(args, say):
     engine.close()
 
 
+def stats_main(args, say):
+    import torch
+    from aad_amd.engine import Engine, parse_header
+    engine = Engine(0)
+    samples, frames, streams = int(round(args.seconds * 48000)), args.frames, args.streams
+    rounds, results = 5, []
+    corpus, size, stride = build_corpus(engine, torch, streams, samples, seed=args.seed)
+    hd = parse_header(bytes(corpus[0, :31].cpu().numpy()))
+    plan = engine.uniform_window_decode_plan(hd, streams, stride, size)
+    say("window decode statistics: %d stereo 4-bit streams x %d frames (spb %d), T = %d, float32 rows; %d alternating rounds of %d "
+        "calls, median of the rounds' medians (range of the rounds' medians); device %s"
+        % (streams, samples, hd.num_samples_per_block, frames, rounds, args.reps, torch.cuda.get_device_name(0)))
+    for n in args.windows:
+        g = torch.Generator(device="cuda")
+        g.manual_seed(args.seed + n)
+        d_win = torch.stack([torch.randint(0, streams, (n,), device="cuda", generator=g),
+                             torch.randint(0, samples - frames + 1, (n,), device="cuda", generator=g)], dim=1)
+        out_a = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        out_b = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        st_b = torch.empty((n, 2, 4), dtype=torch.int64, device="cuda")
+        st_c = torch.empty((n, 2, 4), dtype=torch.int64, device="cuda")
+        keep = {}
+
+        def rows_alone():
+            plan.run(corpus, d_win, frames, torch.float32, out=out_a)
+
+        def rows_and_stats():
+            plan.run(corpus, d_win, frames, torch.float32, out=out_b, stats=st_b)
+
+        def stats_alone():
+            plan.run(corpus, d_win, frames, torch.float32, stats=st_c, rows=False)
+
+        def rows_then_torch():
+            y = plan.run(corpus, d_win, frames, torch.float32, out=out_a)
+            keep["d"] = (y.square().sum(-1), y.abs().sum(-1), y.abs().amax(-1))
+
+        sides = [rows_alone, rows_and_stats, stats_alone, rows_then_torch]
+        for _ in range(3):
+            for f in sides:
+                f()
+        torch.cuda.synchronize()
+        times = [[] for _ in sides]
+        for _ in range(rounds):
+            for t, f in zip(times, sides):
+                t.append(call_ms(torch, f, args.reps))
+        med = [float(np.median(t)) for t in times]
+        rng = [max(t) - min(t) for t in times]
+        torch.cuda.synchronize()
+        same_rows = bool(torch.equal(out_a.view(torch.int32), out_b.view(torch.int32)))
+        same_table = bool(torch.equal(st_b, st_c))
+        y16 = plan.run(corpus, d_win, frames, torch.int16).to(torch.int64).abs()
+        ref = torch.stack([(y16 * y16).sum(-1), y16.sum(-1), y16.amax(-1), torch.full_like(y16[:, :, 0], frames)], dim=-1)
+        exact = bool(torch.equal(st_b, ref))
+        del y16, ref
+        a, b, c, d = med
+        say("  N = %5d: (a) rows %.4f ms (range %.4f); (b) rows + statistics %.4f ms (range %.4f), (b) / (a) = %.3f; (c) statistics "
+            "alone %.4f ms (range %.4f), (c) / (a) = %.3f; (d) rows + torch reductions %.4f ms (range %.4f), (d) / (b) = %.2fx; "
+            "rows of (b) == (a): %s; table of (b) == (c): %s; table == int64 sums over the int16 rows: %s"
+            % (n, a, rng[0], b, rng[1], b / a, c, rng[2], c / a, d, rng[3], d / b, same_rows, same_table, exact))
+        results.append(dict(windows=n, a_ms=a, b_ms=b, c_ms=c, d_ms=d, ranges_ms=rng, same_rows=same_rows, same_table=same_table,
+                            exact=exact))
+        del out_a, out_b, st_b, st_c, keep
+        torch.cuda.empty_cache()
+    say("")
+    say("json " + json.dumps(results))
+    plan.close()
+    engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=1000)
@@ -328,6 +407,7 @@ def main():
     ap.add_argument("--out", default=None, help="also write the report here")
     ap.add_argument("--mixed", action="store_true", help="the mixed-format plan's two measurements instead (see above)")
     ap.add_argument("--channel-mix", action="store_true", help="the channel-mix plan against what a caller has without it (see above)")
+    ap.add_argument("--stats", action="store_true", help="the statistics run against the row run and torch reductions (see above)")
     args = ap.parse_args()
 
     import torch
@@ -338,8 +418,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    if args.mixed or args.channel_mix:
-        (mixed_main if args.mixed else channel_mix_main)(args, say)
+    if args.mixed or args.channel_mix or args.stats:
+        (mixed_main if args.mixed else channel_mix_main if args.channel_mix else stats_main)(args, say)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
