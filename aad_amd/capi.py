@@ -76,6 +76,8 @@ RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL = 0, 1  # enum AADHipReconstructOutput
 OPTION_LANE_MAPPING, OPTION_TRIAL_LANES, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_COMPARE_ORDER = 0, 1, 2, 3, 4  # enum AADHipOption
 LANE_MAPPINGS = {"auto": 0, "dense": 1, "quad": 2, "quad-fused": 3, "dense-tiled": 4}  # enum AADHipLaneMapping
 TRIAL_LANES = {"dual": 0, "single": 1}  # enum AADHipTrialLanes
+OPTION_SIMD_ROLE = 5  # enum AADHipOption; value: SIMD_ROLE_OFF or the SIMD (0..3) that runs the context's latency-bound waves
+SIMD_ROLE_OFF = -1
 LANE_STATE_DTYPE = np.dtype([("weight", "<i4", (4,)), ("history", "<i4", (4,)),
                              ("stepsize_index", "<i4"), ("quantize_error", "<i4")])
 

@@ -37,7 +37,10 @@ struct SplitDecodeArgs {
   DecodeArgs d;
   int32_t *residual;        /* [total_blocks * channels][residual_stride] */
   uint32_t residual_stride; /* int32 per recurrence, a multiple of kChunk */
-  uint32_t reserved;
+  /* ROLE instantiations (DecodeLaunch::simd_role): the SIMD of the recurrence wave and the dwords of a residual row in dynamic
+   * LDS (LDSRES) - packed so that the arguments keep their size */
+  uint8_t simd, reserved;
+  uint16_t lds_row;
 };
 
 /* where block g of the batch lives (the same arithmetic as decode_blocks_kernel) */
@@ -422,13 +425,29 @@ __device__ __forceinline__ void predict_for_quad(const SplitDecodeArgs &a, uint6
  * buffer in device memory otherwise.
  */
 
-template <int BITS, int CHF, bool MS, bool LDSRES>
+/*
+ * ROLE (AAD_HIP_OPTION_SIMD_ROLE, plan_decode): the recurrence wave is the one ELECTED by SIMD (elect_worker_wave,
+ * aad_device.hip.h) instead of wave 0 - a sixteen-wave workgroup has four waves on every SIMD of its CU, so the role's SIMD
+ * always has one - and the LDS residual rows are sized to the block (a.lds_row dwords each, dynamic LDS) instead of to 2048
+ * coded samples, so that the quad encoder's workgroups fit beside this one on a CU: the encoder's busy wave on its SIMD, this
+ * kernel's on another.  Strand (1) then runs only on the waves that sit on this decoder's SIMD pair {simd, simd ^ 2} - the pair
+ * that the roles of step pipelines (aad_amd/engine.py SimdRoleAllocator) keep free of encoders - each taking every P-th
+ * recurrence, P = those waves' count (8 as the dispatcher places them; any count works, none: all sixteen waves, one each).
+ * The scan on all sixteen waves is 4 us shorter for this kernel and costs a co-resident encoder 2-3 us, which is what bounds
+ * the pipelined step (tools/experiments/README.md "SIMD roles: the decoder's scan on all sixteen waves").
+ */
+template <int BITS, int CHF, bool MS, bool LDSRES, bool ROLE = false>
 __global__ void __launch_bounds__(1024) decode_split_kernel(SplitDecodeArgs a)
 {
   __shared__ uint32_t s_step[AAD_STEP_TABLE_LEN];
   __shared__ int32_t s_delta[8];
-  __shared__ __attribute__((aligned(16))) int32_t s_res[LDSRES ? 16 * kLdsResidualRow : 4];
+  __shared__ __attribute__((aligned(16))) int32_t s_res_static[LDSRES && !ROLE ? 16 * kLdsResidualRow : 4];
+  extern __shared__ __attribute__((aligned(16))) int32_t s_res_dynamic[]; /* ROLE && LDSRES: sixteen rows of a.lds_row dwords */
   __shared__ __attribute__((aligned(16))) uint32_t s_stage[2 * 16 * 8]; /* stereo output staging of the recurrence wave */
+  __shared__ uint32_t s_wave_simd[ROLE ? 16 : 1];
+  int32_t *const s_res = ROLE && LDSRES ? s_res_dynamic : s_res_static;
+  const uint32_t res_row = ROLE ? a.lds_row : kLdsResidualRow;
+  if constexpr (ROLE) publish_wave_simd(s_wave_simd);
   AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
   for (uint32_t i = threadIdx.x; i < AAD_STEP_TABLE_LEN; i += blockDim.x) s_step[i] = c_step_table[i];
   if (threadIdx.x < 8) {
@@ -438,23 +457,44 @@ __global__ void __launch_bounds__(1024) decode_split_kernel(SplitDecodeArgs a)
   AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
   __syncthreads();
   AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
-  {
-    const uint32_t w = threadIdx.x >> 6;
+  uint32_t first = threadIdx.x >> 6, stride = 16; /* this wave's recurrences of the workgroup's sixteen: first, first + stride, .. */
+  if constexpr (ROLE) {
+    uint32_t rank = 0, count = 0;
+    bool mine = false;
+    for (uint32_t w = 0; w < 16u; w++) {
+      const bool on_pair = ((s_wave_simd[w] ^ a.simd) & 1u) == 0; /* simd or simd ^ 2 */
+      if (w == (threadIdx.x >> 6)) {
+        mine = on_pair;
+        rank = count;
+      }
+      count += on_pair;
+    }
+    if (count) {
+      first = mine ? rank : 16u;
+      stride = count;
+    }
+  }
+  for (uint32_t w = first; w < 16u; w += stride) {
     const uint64_t rec = (uint64_t)blockIdx.x * 16u + w;
     if (rec < a.d.total_blocks * CHF)
       residuals_for_recurrence<BITS>(a, rec, threadIdx.x & 63u, s_step, s_delta,
-                                     LDSRES ? s_res + w * kLdsResidualRow : a.residual + rec * a.residual_stride);
+                                     LDSRES ? s_res + w * res_row : a.residual + rec * a.residual_stride);
   }
   AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
   /* the residuals are in LDS / in memory before wave 0 reads them (workgroup-scope release/acquire) */
   __syncthreads();
   AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
-  if (threadIdx.x >= 64) return;
-  const uint64_t thread = (uint64_t)blockIdx.x * 64u + threadIdx.x;
+  if constexpr (ROLE) {
+    if ((threadIdx.x >> 6) != elected_worker_wave(a.simd, s_wave_simd)) return;
+  } else {
+    if (threadIdx.x >= 64) return;
+  }
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t thread = (uint64_t)blockIdx.x * 64u + lane;
   const uint64_t rec = thread >> 2;
   const bool active = rec < a.d.total_blocks * CHF;
   predict_for_quad<CHF, MS>(a, thread,
-                            LDSRES ? s_res + (threadIdx.x >> 2) * kLdsResidualRow
+                            LDSRES ? s_res + (lane >> 2) * res_row
                                    : a.residual + (active ? rec : 0) * a.residual_stride,
                             s_stage);
 }

@@ -166,6 +166,37 @@ struct Pack {
   static constexpr int pos(int j) { return BITS * (kCodesPerWord - 1 - j); }
 };
 
+/* ---- SIMD roles (AAD_HIP_OPTION_SIMD_ROLE, DESIGN.md "SIMD roles") -----------------------------------------------------------
+ * A lane-starved launch keeps ONE wave per workgroup busy for its whole life, and a SIMD issues the forms these recurrences are
+ * made of one at a time, whatever its wave count: two such waves on one SIMD run at half speed each.  Which SIMD a one-wave
+ * workgroup gets is the dispatcher's choice; the waves of a four-wave workgroup go to the CU's four SIMDs one each (a
+ * sixteen-wave workgroup's four each).  So a workgroup of four waves (or more) can pick its worker BY SIMD, and kernels that
+ * run side by side can be told different SIMDs.
+ * Every wave publishes the SIMD it sits on (HW_REG_HW_ID bits 5:4, read-only) to its slot of `slot` (one dword per wave of the
+ * workgroup, LDS); after ONE workgroup barrier every wave computes the same answer: the lowest-numbered wave on `wanted_simd`,
+ * or wave 0 if there is none.  Exactly one worker, always - a missed placement costs speed, never a result.  No spinning,
+ * nothing crosses a workgroup, no hardware register is written. */
+__device__ __forceinline__ uint32_t wave_simd_id() { return __builtin_amdgcn_s_getreg(4 | (4 << 6) | (1 << 11)); /* hwreg(HW_REG_HW_ID, 4, 2) */ }
+/* the two halves of elect_worker_wave, for kernels that have a barrier of their own between them (the table staging's) */
+__device__ __forceinline__ void publish_wave_simd(uint32_t *slot)
+{
+  if ((threadIdx.x & 63u) == 0) slot[threadIdx.x >> 6] = wave_simd_id();
+}
+__device__ __forceinline__ uint32_t elected_worker_wave(uint32_t wanted_simd, const uint32_t *slot)
+{
+  const uint32_t waves = blockDim.x >> 6;
+  uint32_t worker = 0;
+  for (uint32_t w = waves; w-- > 0;)
+    if (slot[w] == wanted_simd) worker = w;
+  return worker;
+}
+__device__ __forceinline__ uint32_t elect_worker_wave(uint32_t wanted_simd, uint32_t *slot)
+{
+  publish_wave_simd(slot);
+  __syncthreads();
+  return elected_worker_wave(wanted_simd, slot);
+}
+
 /* stage the tables into LDS; every thread of the workgroup must call this */
 template <int BITS, bool QUAD, int WIDE_STEP_SHIFT = 0, bool WIDE4 = false>
 __device__ __forceinline__ void stage_tables(char *lds)

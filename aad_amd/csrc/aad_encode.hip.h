@@ -344,6 +344,7 @@ struct EncodeArgs {
   /* dual trial search (encode_block_dual): three block-sized slots per stream, device memory of the context */
   uint8_t *trial_scratch;
   uint32_t trial_slot_bytes;
+  uint32_t simd_role; /* quad encoders without the dual search: 0, or 1 + the SIMD whose wave of a four-wave workgroup does the work (EncodeLaunch) */
   UniformLayout uni;
   alignas(4) uint8_t header_template[32]; /* 31-byte file header with num_samples = 0 */
 };
@@ -2051,12 +2052,26 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(KernelArgsFor<IN, R
   static_assert(!(SEG && RING), "segmented plans never take the byte ring");
   __shared__ __attribute__((aligned(16))) char lds[kLdsBytesEncoderStatic<BITS, CHF, QUAD, RING>]; /* dense and quad encoders share the wide table; dense: + code staging */
   extern __shared__ __attribute__((aligned(16))) char ring_lds[]; /* RING: the rows' byte rings, kLdsRingBytesPerWave per wave (then the occupancy pad, unused) */
+  /* SIMD role (the quad encoders of a lane-starved batch, plan_encode): the workgroup is four waves for the sixteen recurrences
+   * of one.  All four stage the tables, the one on the role's SIMD goes on as today's one-wave workgroup did (elect_worker_wave,
+   * aad_device.hip.h: published in front of the staging's barrier, read behind it), the other three leave. */
+  constexpr bool kRoles = QUAD && !DUAL;
+  __shared__ uint32_t s_wave_simd[kRoles ? 4 : 1];
   AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
+  if constexpr (kRoles) {
+    if (a.simd_role) publish_wave_simd(s_wave_simd);
+  }
   stage_tables<BITS, true, kWideStepShift, true>(lds);
   AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
 
   const uint32_t ch = CHF ? CHF : a.channels;
-  const uint64_t thread = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t thread = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (kRoles) {
+    if (a.simd_role) {
+      if ((threadIdx.x >> 6) != elected_worker_wave(a.simd_role - 1u, s_wave_simd)) return;
+      thread = (uint64_t)blockIdx.x * 64u + (threadIdx.x & 63u);
+    }
+  }
   /* dual: with trials on the quad mapping every stream owns 2 x CHF recurrence slots, laid out
    * [role 0: ch 0 .. CHF-1][role 1: ch 0 .. CHF-1] so that a stereo pair stays adjacent */
   constexpr uint32_t kQuadsPerStream = DUAL ? 2u * (CHF ? CHF : 1) : 1u;

@@ -463,6 +463,7 @@ AADApiResult run_encode(AADHipContext *ctx, const aad::EncodeRun &run)
                                                      : aad::plan_encode(ctx->device_info, ctx->knobs, batch);
   a.trial_scratch = nullptr;
   a.trial_slot_bytes = p.trial_slot_bytes;
+  a.simd_role = p.simd_role;
   if (p.trial_scratch_bytes != 0) {
     if (!scratch_reserve(ctx, &ctx->d_trial, &ctx->trial_capacity, p.trial_scratch_bytes, "hipMalloc trial scratch")) return AAD_APIRESULT_NG;
     a.trial_scratch = ctx->d_trial;
@@ -854,6 +855,10 @@ AADApiResult AADHip_ContextSetOption(struct AADHipContext *ctx, int32_t option, 
     case AAD_HIP_OPTION_TRIAL_LANES:
       if (value != AAD_HIP_TRIAL_LANES_DUAL && value != AAD_HIP_TRIAL_LANES_SINGLE) return AAD_APIRESULT_INVALID_ARGUMENT;
       ctx->knobs.trial_lanes = value;
+      return AAD_APIRESULT_OK;
+    case AAD_HIP_OPTION_SIMD_ROLE:
+      if (value < AAD_HIP_SIMD_ROLE_OFF || value > AAD_HIP_SIMD_ROLE_3) return AAD_APIRESULT_INVALID_ARGUMENT;
+      ctx->knobs.simd_role = value;
       return AAD_APIRESULT_OK;
     case AAD_HIP_OPTION_COMPARE_ORDER:
       if (value != 0 && value != 1) return AAD_APIRESULT_INVALID_ARGUMENT;

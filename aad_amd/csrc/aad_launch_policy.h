@@ -23,6 +23,7 @@ struct Knobs {
   int32_t encode_lds_pad = -1; /* AAD_HIP_ENCODE_LDS_PAD bytes; < 0: by policy */
   int32_t decode_lds_pad = -1; /* AAD_HIP_DECODE_LDS_PAD bytes; < 0: by policy */
   uint64_t decode_nt_min = 0;  /* AAD_HIP_DECODE_NT_MIN lanes */
+  int32_t simd_role = AAD_HIP_SIMD_ROLE_OFF; /* AAD_HIP_OPTION_SIMD_ROLE: off, or the SIMD (0..3) of the context's busy waves */
 };
 
 struct EncodeBatch {
@@ -42,6 +43,7 @@ struct EncodeLaunch {
   bool trials; /* the TRIALS instantiation */
   uint32_t workgroup, grid, lds, trial_slot_bytes;
   uint64_t trial_scratch_bytes; /* 0: none */
+  uint32_t simd_role; /* Quad: 0, or 1 + SIMD - four-wave workgroups of sixteen recurrences whose wave on that SIMD works (plan_simd_role) */
 };
 
 enum class DecodeKernel { SplitLds, SplitScratch, QuadFused, Tiled, Dense };
@@ -50,6 +52,9 @@ struct DecodeLaunch {
   bool stream_stores; /* Dense: the streamed-store (NT) instantiation */
   uint32_t workgroup, grid, lds, residual_stride;
   uint64_t residual_bytes; /* SplitScratch */
+  /* SplitLds / SplitScratch under a role: 1 + SIMD of the recurrence wave, else 0.  SplitLds then keeps its residual rows in
+   * dynamic LDS (`lds` bytes, sixteen rows of lds_row dwords sized to the block) */
+  uint32_t simd_role, lds_row;
 };
 
 constexpr uint32_t kSimdsPerCu = 4, kWaveLanes = 64;
@@ -64,6 +69,21 @@ inline uint64_t one_wave_per_simd(const Device &d) { return (uint64_t)d.cus * kS
 inline uint32_t pick_workgroup(const Device &d, uint64_t threads) { return threads <= one_wave_per_simd(d) ? 64u : 256u; }
 
 inline uint32_t grid_for(uint64_t threads, uint32_t workgroup) { return (uint32_t)((threads + workgroup - 1) / workgroup); }
+
+/* SIMD roles (AAD_HIP_OPTION_SIMD_ROLE; the election: aad_device.hip.h).  A role applies to the launches that keep ONE wave per
+ * workgroup busy - the quad encoder in one-wave workgroups, the split decoder - and only while every workgroup can have a CU of
+ * its own: the workgroups of one launch elect the SAME SIMD, so two of them on one CU would share it, where today's one-wave
+ * workgroups spread over the CU's SIMDs.  -> 0 (no role), or 1 + SIMD. */
+inline uint32_t plan_simd_role(const Device &d, const Knobs &k, uint32_t workgroups)
+{
+  if (k.simd_role < 0 || k.simd_role >= (int32_t)kSimdsPerCu || workgroups > d.cus) return 0;
+  return 1u + (uint32_t)k.simd_role;
+}
+
+/* The split decoder's residual rows under a role: the block's coded samples rounded up to a chunk, + 4 dwords (a row length of
+ * 4 or 20 mod 32 dwords: the sixteen rows a wave reads at the same sample offset spread over the banks, as kLdsResidualRow's do).
+ * Every read of the recurrence wave stays inside: whole chunks up to the rounded length, the tail's one wide load included. */
+inline uint32_t split_lds_row(uint32_t coded) { return (coded + (uint32_t)kChunk - 1u) / (uint32_t)kChunk * (uint32_t)kChunk + 4u; }
 
 /* On the quad mapping the trial search's probe strand gets lanes of its own ("dual"): one pass of
  * latency less per block with a predecessor, nothing lost otherwise (tools/trial_probe.py).
@@ -162,6 +182,10 @@ inline EncodeLaunch plan_encode(const Device &d, const Knobs &k, const EncodeBat
      * profiles/r04_trial_search_size_sweep.txt.  One-wave workgroups spread over the SIMDs.) */
     p.workgroup = dual && threads <= 128ull * d.cus ? 128u : pick_workgroup(d, threads);
     p.grid = grid_for(threads, p.workgroup);
+    if (!dual && p.workgroup == 64u) { /* lane-starved: one wave per sixteen recurrences */
+      p.simd_role = plan_simd_role(d, k, p.grid);
+      if (p.simd_role) p.workgroup = 256u; /* the same grid: three of a workgroup's four waves only help to stage the tables */
+    }
     return p;
   }
   /* the dense encoders, with and without the trial search: one-wave workgroups only while their LDS lets all of them be resident */
@@ -314,8 +338,13 @@ inline DecodeLaunch plan_decode(const Device &d, const Knobs &k, const DecodeBat
     if (row <= kMaxResidualBytes / sizeof(int32_t) && lanes * row * sizeof(int32_t) <= kMaxResidualBytes) {
       p.workgroup = 1024; /* 16 recurrences per workgroup */
       p.grid = grid_for(lanes, 16);
+      p.simd_role = plan_simd_role(d, k, p.grid);
       if (decode_split_fits_lds(d, b)) {
         p.kernel = DecodeKernel::SplitLds;
+        if (p.simd_role) {
+          p.lds_row = split_lds_row((uint32_t)coded);
+          p.lds = 16u * p.lds_row * (uint32_t)sizeof(int32_t);
+        }
       } else {
         p.kernel = DecodeKernel::SplitScratch;
         p.residual_stride = (uint32_t)row;

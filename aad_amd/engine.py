@@ -9,8 +9,8 @@ import ctypes as C
 import numpy as np
 
 from .capi import (AADApiResult, AADHeaderInfo, AADHipPlanarLayout, AADHipPlanarOutput, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
-                   OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
-                   SAMPLE_FLOAT32, SAMPLE_INT16, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, load_library, make_parameter)
+                   OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_SIMD_ROLE, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
+                   SAMPLE_FLOAT32, SAMPLE_INT16, SIMD_ROLE_OFF, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, load_library, make_parameter)
 
 
 def _check(where, rc):
@@ -107,6 +107,13 @@ class Engine:
         (bit-identical doubles; AAD_HIP_OPTION_COMPARE_ORDER)"""
         _check("AADHip_ContextSetOption",
                self.lib.AADHip_ContextSetOption(self._ctx, OPTION_COMPARE_ORDER, 1 if sequential else 0))
+
+    def set_simd_role(self, simd=None):
+        """The SIMD (0..3) of a CU that runs the one busy wave of this context's lane-starved launches (the quad encoder, the
+        split decoder's recurrence wave), None = off: today's launches.  Contexts whose kernels run side by side take different
+        SIMDs (EncodeDecodePipeline does); the bytes never depend on it (AAD_HIP_OPTION_SIMD_ROLE)."""
+        _check("AADHip_ContextSetOption",
+               self.lib.AADHip_ContextSetOption(self._ctx, OPTION_SIMD_ROLE, SIMD_ROLE_OFF if simd is None else int(simd)))
 
     def synchronize(self):
         _check("AADHip_ContextSynchronize", self.lib.AADHip_ContextSynchronize(self._ctx))
@@ -1010,6 +1017,57 @@ class HipEvent:
             pass
 
 
+# whether an EncodeDecodePipeline gives its engines SIMD roles by default (DESIGN.md "SIMD roles")
+PIPELINE_SIMD_ROLES = True
+
+
+class SimdRoleAllocator:
+    """Free-slot allocator of the SIMD roles of one device's pipelines.  A pipeline takes one slot = (encoder SIMD, decoder SIMD);
+    the two slots are (0, 1) and (2, 3), so that the four engines of two live pipelines hold four different SIMDs and the two
+    encoders sit on different halves of the CU's LDS path ({0, 1} and {2, 3}).  A third live pipeline gets None: no roles.
+    The roles are IN FORCE only while both slots are taken: a pipeline that runs alone keeps today's launches - its two kernels
+    cannot share a CU then (their LDS does not fit), let alone a SIMD, and under roles they would (measured: one pipeline alone
+    2.5 % slower with roles, DESIGN.md "SIMD roles").  `apply` of every holder is called whenever that changes."""
+    SLOTS = ((0, 1), (2, 3))
+
+    def __init__(self):
+        self.taken = [False] * len(self.SLOTS)
+        self.holders = [None] * len(self.SLOTS)  # per slot: apply(encoder SIMD or None, decoder SIMD or None)
+
+    def in_force(self):
+        return all(self.taken)
+
+    def acquire(self, apply=None):
+        """-> slot index, or None when every slot is taken.  apply(enc_simd, dec_simd): sets the holder's roles"""
+        for i, t in enumerate(self.taken):
+            if not t:
+                self.taken[i] = True
+                self.holders[i] = apply
+                self._apply_all()
+                return i
+        return None
+
+    def release(self, slot):
+        if slot is not None and self.taken[slot]:
+            apply = self.holders[slot]
+            self.taken[slot], self.holders[slot] = False, None
+            if apply is not None:
+                apply(None, None)
+            self._apply_all()
+
+    def roles(self, slot):
+        """-> (encoder SIMD, decoder SIMD) of a slot while the roles are in force, else (None, None)"""
+        return self.SLOTS[slot] if slot is not None and self.taken[slot] and self.in_force() else (None, None)
+
+    def _apply_all(self):
+        for i, apply in enumerate(self.holders):
+            if self.taken[i] and apply is not None:
+                apply(*self.roles(i))
+
+
+_simd_roles = {}  # device index -> SimdRoleAllocator
+
+
 class EncodeDecodePipeline:
     """Encode on one context, decode on another: the encode of step k+1 runs while step k decodes.
 
@@ -1022,12 +1080,15 @@ class EncodeDecodePipeline:
     Every step encodes its whole batch and decodes exactly what it encoded; `pcm` and `out`
     are the caller's and must stay untouched until the step's kernels have run."""
 
-    def __init__(self, enc_engine, dec_engine, param, streams, samples, ring=8):
+    def __init__(self, enc_engine, dec_engine, param, streams, samples, ring=8, simd_roles=PIPELINE_SIMD_ROLES):
         assert ring >= 2 and ring % 2 == 0
         assert enc_engine.stream.cuda_stream != dec_engine.stream.cuda_stream, "the two contexts need streams of their own"
         torch = enc_engine.torch
         self.torch, self.ring, self.k = torch, ring, 0
         self.enc_engine, self.dec_engine = enc_engine, dec_engine
+        # Two pipelines that are alive together run their kernels side by side: each gives its two engines SIMDs of their own
+        # (SimdRoleAllocator), so that the one busy wave of every such kernel finds a SIMD no other kernel's busy wave uses.
+        self._take_simd_roles(_simd_roles.setdefault(enc_engine.device, SimdRoleAllocator()) if simd_roles else None)
         self.enc = enc_engine.uniform_encode_plan(param, streams, samples)
         self.images = [torch.zeros((streams, self.enc.stride), dtype=torch.uint8, device="cuda:%d" % enc_engine.device)
                        for _ in range(ring)]
@@ -1065,6 +1126,21 @@ class EncodeDecodePipeline:
         self.dec.close()
         for e in self.encoded:
             e.close()
+        self._release_simd_roles()
+
+    def _take_simd_roles(self, allocator):
+        """allocator: the device's SimdRoleAllocator, None: no roles"""
+        self._roles = allocator
+        self._role_slot = allocator.acquire(self._set_simd_roles) if allocator is not None else None
+
+    def _set_simd_roles(self, enc_simd, dec_simd):
+        self.enc_engine.set_simd_role(enc_simd)
+        self.dec_engine.set_simd_role(dec_simd)
+
+    def _release_simd_roles(self):
+        if getattr(self, "_role_slot", None) is not None:
+            self._roles.release(self._role_slot)
+            self._role_slot = None
 
 
 def parse_header(data):
@@ -1077,4 +1153,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "select_least_bits"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "select_least_bits"]

@@ -112,7 +112,16 @@ enum AADHipOption {
    * to a rounding boundary of the six decimals `aad -c` prints that the order could show (the printed line is the
    * reference's either way); 1 = always the reference's order (bit-identical doubles, one lane per stream: slow).
    * Default from AAD_HIP_COMPARE_ORDER (auto | sequential). */
-  AAD_HIP_OPTION_COMPARE_ORDER = 4
+  AAD_HIP_OPTION_COMPARE_ORDER = 4,
+  /* enum AADHipSimdRole: the SIMD of a compute unit that runs the one busy wave per workgroup of this context's lane-starved
+   * launches (the quad encoder of up to 16 recurrences per compute unit of the device, the split decoder's recurrence wave).
+   * Contexts whose kernels run side by side on one device - the engines of step pipelines - take different SIMDs, so that no two
+   * of those waves share one.  Off (the default): the launches as they are without the option.  The bytes never depend on it. */
+  AAD_HIP_OPTION_SIMD_ROLE = 5
+};
+enum AADHipSimdRole {
+  AAD_HIP_SIMD_ROLE_OFF = -1,
+  AAD_HIP_SIMD_ROLE_0 = 0, AAD_HIP_SIMD_ROLE_1 = 1, AAD_HIP_SIMD_ROLE_2 = 2, AAD_HIP_SIMD_ROLE_3 = 3
 };
 enum AADHipLaneMapping {
   AAD_HIP_LANE_MAPPING_AUTO = 0,      /* by batch size (the default) */
