@@ -1,6 +1,7 @@
 /* Prints aad_launch_policy.h's plans for the batches on stdin, one line each (tests/test_launch_policy.py).
  *   E cus lds_per_cu | mapping trial_lanes encode_ring encode_lds_pad decode_lds_pad decode_nt_min | bits channels streams trials block_size ring_ok
  *     -> kernel trials workgroup grid lds trial_slot_bytes trial_scratch_bytes
+ *   R (an E row's fields): the same batch under plan_reconstruct_encode (planar and window reconstruct runs) -> as E
  *   D cus lds_per_cu | (knobs as above) | blocks streams channels bits samples_per_block block_size pcm_aligned16 pcm_base_aligned16
  *     code_phase_uniform stream_stores
  *     -> kernel stream_stores workgroup grid lds residual_bytes residual_stride */
@@ -21,12 +22,12 @@ int main()
               &k.decode_lds_pad, &nt_min) != 8)
       return 1;
     k.decode_nt_min = nt_min;
-    if (kind == 'E') {
+    if (kind == 'E' || kind == 'R') {
       aad::EncodeBatch b;
       unsigned ring_ok;
       if (scanf("%u %u %u %u %u %u", &b.bits, &b.channels, &b.streams, &b.trials, &b.block_size, &ring_ok) != 6) return 1;
       b.ring_ok = ring_ok != 0;
-      const aad::EncodeLaunch p = aad::plan_encode(d, k, b);
+      const aad::EncodeLaunch p = kind == 'R' ? aad::plan_reconstruct_encode(d, k, b) : aad::plan_encode(d, k, b);
       printf("%s %d %u %u %u %u %llu\n", kEncode[(int)p.kernel], (int)p.trials, p.workgroup, p.grid, p.lds, p.trial_slot_bytes,
              (unsigned long long)p.trial_scratch_bytes);
     } else {
