@@ -402,6 +402,7 @@ struct RecRow {
   using T = std::conditional_t<REC == kRecF32, float, int16_t>;
   T *row;
   uint32_t c, tap;
+  mutable bool mute = false; /* the pass's samples are not the decoder's (rec_wrapped_block has written the block): one / chunk / quad leave */
   __device__ __forceinline__ static T convert(int32_t y)
   {
     if constexpr (REC == kRecF32) return (float)y * (1.0f / 32768.0f); /* exact: an int16 times a power of two */
@@ -431,12 +432,14 @@ struct RecRow {
   /* a sample walked by encode_step: y where the history keeps the newest one (quad: tap 0 stores it); real: not zero padding */
   __device__ __forceinline__ void one(uint64_t f, int32_t y, bool real) const
   {
+    if (mute) return;
     const int32_t v = decoded(y);
     if (real && (!QUAD || tap == 0u)) row[f] = convert(v);
   }
   /* dense: a whole chunk, samples f .. f + 15, as 16-byte stores at the row's own alignment */
   __device__ __forceinline__ void chunk(uint64_t f, const int32_t *y) const
   {
+    if (mute) return;
     int32_t v[kChunk];
 #pragma unroll
     for (int j = 0; j < kChunk; j++) v[j] = decoded(y[j]);
@@ -462,6 +465,7 @@ struct RecRow {
   template <int G>
   __device__ __forceinline__ void quad(uint64_t f, const int32_t *yq) const
   {
+    if (mute) return;
 #pragma unroll
     for (int g = 0; g < G; g++) {
       const int32_t v = decoded(yq[g]);
@@ -677,8 +681,10 @@ struct RecRowStats {
   mutable uint32_t max_abs;
   mutable TIN pend_x[QUAD ? 4 : 1];
   mutable int32_t pend_v[QUAD ? 4 : 1];
+  mutable bool mute; /* as RecRow's */
   __device__ __forceinline__ void init(T *row_, const TIN *in_, uint32_t c_, uint32_t tap_)
   {
+    mute = false;
     row = row_;
     in = in_;
     c = c_;
@@ -715,6 +721,7 @@ struct RecRowStats {
   }
   __device__ __forceinline__ void one(uint64_t f, int32_t y, bool real) const
   {
+    if (mute) return;
     const int32_t v = decoded(y);
     if (real && (!QUAD || tap == 0u)) {
       if constexpr (kStore) row[f] = Rows::convert(v);
@@ -723,6 +730,7 @@ struct RecRowStats {
   }
   __device__ __forceinline__ void chunk(uint64_t f, const int32_t *y) const
   {
+    if (mute) return;
     PlanarRaw<TIN> x;
     x.load(in + f);
     int32_t v[kChunk];
@@ -738,6 +746,7 @@ struct RecRowStats {
   template <int G>
   __device__ __forceinline__ void quad(uint64_t f, const int32_t *yq) const
   {
+    if (mute) return;
     if constexpr (G == 4) flush();
 #pragma unroll
     for (int g = 0; g < G; g++) {
@@ -826,11 +835,14 @@ __device__ __forceinline__ void store_be16(uint8_t *p, uint32_t v)
 /* defer3: leave the last three bytes (low byte of weight 3, history 3) unwritten and return them, lowest
  * address in the low byte - the dense stereo encoder writes them with the first code bytes, which
  * share their 64-byte granule (see run_block) */
-__device__ __forceinline__ uint32_t write_block_header(Lane &L, uint8_t *p, bool do_store, bool defer3 = false, uint32_t *words = nullptr)
+/* shift_out: receives the weight shift (the header's 4-bit field keeps shift & 15) */
+__device__ __forceinline__ uint32_t write_block_header(Lane &L, uint8_t *p, bool do_store, bool defer3 = false, uint32_t *words = nullptr,
+                                                       int32_t *shift_out = nullptr)
 {
   auto wabs = [](int32_t w) { const int32_t m = w >> 31; return (int32_t)(((uint32_t)w ^ (uint32_t)m) - (uint32_t)m); };
   const int32_t maxabs = max(max(max(wabs(L.w0), wabs(L.w1)), max(wabs(L.w2), wabs(L.w3))), 0);
   const int32_t shift = max(17 - (int32_t)__clz(maxabs), 0); /* smallest shift with maxabs >> shift <= 32767 */
+  if (shift_out != nullptr) *shift_out = shift;
   const int32_t mask = (int32_t)~((1u << shift) - 1u);
   L.w0 &= mask;
   L.w1 &= mask;
@@ -864,6 +876,20 @@ __device__ __forceinline__ uint32_t write_block_header(Lane &L, uint8_t *p, bool
     store_be16(p + 16, h3);
   }
   return last3;
+}
+
+/* a weight of a lane behind write_block_header as a decoder reads it from that header: the 16-bit field, sign-extended, at the
+ * 4-bit field's shift */
+__device__ __forceinline__ int32_t header_weight_read(int32_t w, int32_t shift)
+{
+  return (int32_t)((uint32_t)(int32_t)(int16_t)(w >> shift) << (shift & 15));
+}
+/* does the header hold the lane's weights?  Not where the shift passes 15 (a magnitude of 2^30 or more) and not for INT32_MIN,
+ * which write_block_header leaves out of the largest magnitude: its field reads back as 0 */
+__device__ __forceinline__ bool header_holds_weights(const Lane &L, int32_t shift)
+{
+  return header_weight_read(L.w0, shift) == L.w0 && header_weight_read(L.w1, shift) == L.w1 && header_weight_read(L.w2, shift) == L.w2 &&
+         header_weight_read(L.w3, shift) == L.w3;
 }
 
 /* Write the packed codes of one 16-sample chunk.  w[]: big-endian code words of this lane's
@@ -2041,6 +2067,36 @@ __device__ __forceinline__ void encode_block_dual(Lane &F, int32_t &last_qd, con
  * (RecRow) - the header samples of every kept block here, the coded samples in run_block.  Never with the dual trial search (its
  * candidates are encoded into slots) or the byte ring: the launch policy plans neither for these kernels.
  */
+/*
+ * REC, a block whose header cannot hold the weights (header_holds_weights): a magnitude of 2^30 or more needs a weight shift of 16
+ * and the header's 4-bit field keeps shift & 15 (reference src/aad_encoder.c:644-646 built with NDEBUG), and INT32_MIN stays out of
+ * the largest magnitude, so its 16-bit field reads 0; the image stays the reference's.  A decoder then
+ * runs the block on other weights, so the decode of the image - what the rows and statistics are defined as - is
+ * not the encoder's reconstruction for this block.  The block's coded samples are walked here once more, sample by sample, with the
+ * encoder's recurrence (E: the codes' dequantised differences, which depend on the codes and the step index alone and so are the
+ * decoder's too) beside the decoder's (D: the header's weights as a decoder reads them, the same history), and the decoder's
+ * samples go to rec; the caller mutes rec for the encode pass proper.  F: the lane's state behind write_block_header (every lane of
+ * a quad recurrence holds all of it and walks the block; tap 0 stores).  With M/S both lanes of a pair come here together
+ * (RecRow::decoded trades the samples).
+ */
+template <int BITS, bool MS, int IN, typename R>
+__device__ __forceinline__ void rec_wrapped_block(const Lane &F, int32_t shift, const SampleSource<MS, IN> &src, uint64_t first, uint32_t n,
+                                                  const char *lds, const R &rec)
+{
+  Lane E = F, D = F;
+  D.w0 = header_weight_read(F.w0, shift);
+  D.w1 = header_weight_read(F.w1, shift);
+  D.w2 = header_weight_read(F.w2, shift);
+  D.w3 = header_weight_read(F.w3, shift);
+  for (uint32_t k = kTaps; k < n; k++) {
+    int32_t qd;
+    (void)encode_step<BITS>(E, src.at(first + k), lds, qd);
+    const int32_t y = clip16(qd + predict(D));
+    lms_and_shift(D, qd, y);
+    rec.one(first + k, y, true);
+  }
+}
+
 template <int BITS, int CHF, bool MS, bool QUAD, bool TRIALS, bool DUAL = false, bool RING = false, bool SEG = false, int IN = kInInterleaved,
           int REC = kRecNone>
 __global__ void __launch_bounds__(256) encode_streams_kernel(KernelArgsFor<IN, REC> a)
@@ -2220,11 +2276,22 @@ __global__ void __launch_bounds__(256) encode_streams_kernel(KernelArgsFor<IN, R
       F = L;
     } else {
     const bool defer3 = !QUAD && kBurstStores<BITS, CHF, true> && c == 1 && (reinterpret_cast<uintptr_t>(body) & 63u) == 3u;
-    const uint32_t deferred = write_block_header(F, out + block_off + (uint64_t)c * kBlockHeaderBytesPerCh, writer, defer3);
+    [[maybe_unused]] int32_t hshift = 0;
+    const uint32_t deferred = write_block_header(F, out + block_off + (uint64_t)c * kBlockHeaderBytesPerCh, writer, defer3, nullptr,
+                                                 REC != kRecNone ? &hshift : nullptr);
+    if constexpr (REC != kRecNone) { /* a header that cannot hold the weights: the decoder's samples, see rec_wrapped_block */
+      uint32_t wrapped = header_holds_weights(F, hshift) ? 0u : 1u;
+      if constexpr (MS) wrapped |= pair_swap<false>(wrapped, c); /* both lanes of the pair trade the flag, then go together */
+      if (wrapped != 0u) {
+        rec_wrapped_block<BITS>(F, hshift, src, first, n, lds, rec);
+        rec.mute = true;
+      }
+    }
     if constexpr (QUAD) L = to_quad(F, tap); else L = F;
     AAD_PHASE_MARK(blockIdx.x == 0 && threadIdx.x == 0);
     if constexpr (REC == kRecNone) (void)run_block<BITS, CHF, MS, QUAD, kPassEncode>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred);
     else (void)run_block<BITS, CHF, MS, QUAD, kPassEncode>(L, src, first, n, ch, c, writer, body, lds, last_qd, defer3, deferred, true, nullptr, &rec);
+    if constexpr (REC != kRecNone) rec.mute = false;
     if constexpr (QUAD) F = from_quad<kEncTM>(L); else F = L;
     }
     }

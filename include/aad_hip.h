@@ -45,7 +45,20 @@ struct AADHipStreamDesc {
 };
 
 /* Predictor state of one stream x channel, carried across calls exactly like the reference's
- * struct AADEncodeProcessor (src/aad_encoder.c:10-15) inside a reused encoder handle. */
+ * struct AADEncodeProcessor (src/aad_encoder.c:10-15) inside a reused encoder handle.
+ *
+ * What a run does with a record it is handed (every entry point that takes state; tests/test_gpu_crafted_state.py):
+ *   - stepsize_index is clamped to [0, 4080] on load: a run given an index outside that range computes exactly what it computes
+ *     given the clamped index.  (The reference keeps the index in an int16 and asserts the range.)
+ *   - weight[] is taken as it is, any int32.  The first block header carries weight >> shift with the smallest shift that brings
+ *     the largest magnitude to 16 bits and the shifted-out bits cleared in the carried weights too; the header's 4-bit field holds
+ *     shift & 15, so magnitudes from 2^30 on (shift 16) wrap it, as in the reference built with NDEBUG.  INT32_MIN, whose
+ *     magnitude does not exist in int32, never becomes the largest magnitude: next to smaller weights its header field reads 0.
+ *   - history[] is overwritten at every block start with the block's first four samples (taps that no sample seeds: 0), so its
+ *     contents before a run do not matter.
+ *   - quantize_error is the dequantised difference of the last coded sample.  The first four samples of a block travel in its
+ *     header and are not coded: a run that codes no sample of a stream (1 .. 4 samples) passes quantize_error through untouched.
+ * The record written back holds the weights, history and index the next block would start from. */
 struct AADHipLaneState {
   int32_t weight[4];
   int32_t history[4];
@@ -403,6 +416,12 @@ AADApiResult AADHip_PlanarEncodePlanRun(
  *      (exact, as window decode).
  * No other element of `out` is touched.  Input and output sample types are independent (int16 or float32 each).  Overlap of `out`
  * with the input or the images is undefined (device_out == device_samples is refused).
+ * 2. also holds where a block header cannot carry the encoder's weights: a magnitude of 2^30 or more at a block start (a carried
+ * record that starts there, or weights that grow past it) needs a weight shift of 16 and the header's 4-bit field wraps, as in the
+ * reference built with NDEBUG; and a weight of INT32_MIN, which the shift ignores, reads back from its 16-bit field as 0.  A
+ * decoder runs that block on the weights it reads, so D_i there is not the encoder's own reconstruction; the run compares every
+ * header it writes with what a decoder reads back from it, walks such a block with the decoder's recurrence beside the encoder's
+ * and writes D_i (and accounts for it in the statistics below).  tests/test_gpu_crafted_state.py.
  *
  * The plan is an ordinary AADHipEncodePlan: AADHip_EncodePlanDestroy destroys it, and AADHip_ContextSignalNextRun's events ride on
  * AADHip_PlanarReconstructPlanRun's one kernel.  AADHip_EncodePlanRun and AADHip_PlanarEncodePlanRun refuse it and

@@ -268,9 +268,11 @@ static uint8_t *emit_unit(uint8_t *p, const uint32_t *codes, uint32_t count, uin
   return put_be(p, acc, (int)bytes);
 }
 
-/* one block: reference src/aad_encoder.c:565-727.  x[c] planar, n <= spb valid samples at x[c][0..n). */
+/* one block: reference src/aad_encoder.c:565-727.  x[c] planar, n <= spb valid samples at x[c][0..n).
+ * rec (may be NULL): n interleaved frames that receive the ENCODER's own reconstruction of the block, per lane (mid / side as
+ * they are): the header samples, then the newest history sample behind every coded one. */
 static size_t encode_block(AadoLane *lanes, const int32_t *const *x, uint32_t n, uint32_t channels,
-                           uint32_t bits, uint8_t *out)
+                           uint32_t bits, uint8_t *out, int16_t *rec)
 {
   const PackUnit u = pack_unit(bits);
   uint8_t *p = out;
@@ -296,12 +298,15 @@ static size_t encode_block(AadoLane *lanes, const int32_t *const *x, uint32_t n,
       p = put_be(p, (uint32_t)(l->w[k] >> shift) & 0xFFFFu, 2);
       p = put_be(p, (uint32_t)l->h[k] & 0xFFFFu, 2);
     }
+    for (uint32_t k = 0; rec && k < AADO_TAPS && k < n; k++) rec[(size_t)k * channels + c] = (int16_t)x[c][k];
   }
   for (uint32_t s = AADO_TAPS; s < n; s += u.unit_samples) {
     for (uint32_t c = 0; c < channels; c++) {
       uint32_t codes[8];
-      for (uint32_t k = 0; k < u.unit_samples; k++) /* samples past n are zero padding (:592-593) */
+      for (uint32_t k = 0; k < u.unit_samples; k++) { /* samples past n are zero padding (:592-593) */
         codes[k] = aado_encode_step(&lanes[c], s + k < n ? x[c][s + k] : 0, bits);
+        if (rec && s + k < n) rec[(size_t)(s + k) * channels + c] = (int16_t)lanes[c].h[0];
+      }
       p = emit_unit(p, codes, u.unit_samples, bits, u.unit_bytes_per_ch);
     }
   }
@@ -340,6 +345,15 @@ int aado_encode_stream(const int16_t *pcm, uint32_t num_samples, uint32_t channe
                        uint32_t ch_process_method, uint32_t trials, AadoLane *lanes,
                        uint8_t *out, size_t cap, size_t *out_size)
 {
+  return aado_encode_stream_recon(pcm, num_samples, channels, sampling_rate, bits, max_block_size, ch_process_method, trials, lanes,
+                                  out, cap, out_size, NULL);
+}
+
+int aado_encode_stream_recon(const int16_t *pcm, uint32_t num_samples, uint32_t channels,
+                             uint32_t sampling_rate, uint32_t bits, uint32_t max_block_size,
+                             uint32_t ch_process_method, uint32_t trials, AadoLane *lanes,
+                             uint8_t *out, size_t cap, size_t *out_size, int16_t *recon)
+{
   if (!pcm || !lanes || !out || !out_size) return AADO_INVALID_ARGUMENT;
   AadoHeader hd;
   memset(&hd, 0, sizeof(hd));
@@ -366,7 +380,13 @@ int aado_encode_stream(const int16_t *pcm, uint32_t num_samples, uint32_t channe
       if (trials) search_best_lane(&lanes[c], x[c], progress, n, spb, bits, trials);
       cur[c] = x[c] + progress;
     }
-    p += encode_block(lanes, cur, n, channels, bits, p);
+    int16_t *rec = recon ? recon + (size_t)progress * channels : NULL;
+    p += encode_block(lanes, cur, n, channels, bits, p, rec);
+    for (uint32_t s = 0; rec && ch_process_method == 1 && s < n; s++) { /* to L/R as a decoder does (src/aad_decoder.c:458-470) */
+      const int32_t m = rec[(size_t)s * channels], sd = rec[(size_t)s * channels + 1];
+      rec[(size_t)s * channels] = (int16_t)clip16(m + sd);
+      rec[(size_t)s * channels + 1] = (int16_t)clip16(m - sd);
+    }
     progress += n;
   }
   free_planar(x, channels);

@@ -97,6 +97,15 @@ int aado_decode_stream(const uint8_t *data, size_t size, uint32_t max_channels,
 int aado_decode_block(const AadoHeader *hd, const uint8_t *block, size_t size,
                       int16_t *pcm, uint32_t want_frames, uint32_t *got_frames);
 
+/* aado_encode_stream that also writes the ENCODER's own reconstruction (recon: num_samples interleaved frames, L/R; may be NULL):
+ * what the encoder's recurrence holds as the decoded sample behind every sample it codes.  It equals aado_decode_stream of the
+ * image wherever every block header can carry the encoder's weights; a weight the header's 16-bit field and 4-bit shift cannot
+ * hold (a magnitude of 2^30 or more, INT32_MIN) makes a decoder run that block on other weights, and the two part ways. */
+int aado_encode_stream_recon(const int16_t *pcm, uint32_t num_samples, uint32_t channels,
+                             uint32_t sampling_rate, uint32_t bits, uint32_t max_block_size,
+                             uint32_t ch_process_method, uint32_t trials, AadoLane *lanes,
+                             uint8_t *out, size_t cap, size_t *out_size, int16_t *recon);
+
 /* single steps, exported for white-box tests and the quantiser-equivalence check */
 uint32_t aado_encode_step(AadoLane *lane, int32_t x, uint32_t bits);
 int32_t aado_decode_step(AadoLane *lane, uint32_t code, uint32_t bits);

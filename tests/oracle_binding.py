@@ -41,6 +41,8 @@ def lib():
                                          C.POINTER(sz)]
         l.aado_decode_stream.argtypes = [vp, sz, u32, vp, u32, C.POINTER(AadoHeader)]
         l.aado_decode_block.argtypes = [C.POINTER(AadoHeader), vp, sz, vp, u32, C.POINTER(u32)]
+        l.aado_encode_stream_recon.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, C.POINTER(AadoLane), vp, sz,
+                                               C.POINTER(sz), vp]
         l.aado_encode_step.argtypes = [C.POINTER(AadoLane), C.c_int32, u32]
         l.aado_encode_step.restype = u32
         l.aado_decode_step.argtypes = [C.POINTER(AadoLane), u32, u32]
@@ -69,8 +71,9 @@ def fresh_lanes(channels=8):
     return (AadoLane * channels)()
 
 
-def encode(pcm, bits=4, max_block_size=1024, rate=48000, ms=False, trials=0, lanes=None, reset_idx=True):
-    """pcm: int16 [samples, channels] -> bytes.  lanes: carried state (AadoLane array) or None."""
+def encode(pcm, bits=4, max_block_size=1024, rate=48000, ms=False, trials=0, lanes=None, reset_idx=True, recon=None):
+    """pcm: int16 [samples, channels] -> bytes.  lanes: carried state (AadoLane array) or None.  recon: an int16 array of pcm's
+    shape that receives the encoder's own reconstruction (aado_encode_stream_recon)."""
     pcm = np.ascontiguousarray(pcm, dtype=np.int16)
     n, ch = pcm.shape
     if lanes is None:
@@ -81,8 +84,10 @@ def encode(pcm, bits=4, max_block_size=1024, rate=48000, ms=False, trials=0, lan
     cap = encoded_size(n, ch, bits, max_block_size) + 64
     out = np.zeros(cap, dtype=np.uint8)
     got = C.c_size_t(0)
-    rc = lib().aado_encode_stream(pcm.ctypes.data, n, ch, rate, bits, max_block_size, 1 if ms else 0, trials,
-                                  lanes, out.ctypes.data, cap, C.byref(got))
+    if recon is not None:
+        assert recon.dtype == np.int16 and recon.shape == pcm.shape and recon.flags["C_CONTIGUOUS"]
+    rc = lib().aado_encode_stream_recon(pcm.ctypes.data, n, ch, rate, bits, max_block_size, 1 if ms else 0, trials,
+                                        lanes, out.ctypes.data, cap, C.byref(got), recon.ctypes.data if recon is not None else None)
     if rc != 0:
         raise RuntimeError("oracle encode rc=%d" % rc)
     return out[:got.value].tobytes()

@@ -277,6 +277,16 @@ def test_staging_threads_do_not_change_bytes(engine):
         engine.set_staging_threads(9)
 
 
+def _record(r):
+    """every field of a LANE_STATE_DTYPE record"""
+    return ([int(v) for v in r["weight"]], [int(v) for v in r["history"]], int(r["stepsize_index"]), int(r["quantize_error"]))
+
+
+def _lane(l):
+    """every field of an oracle lane, in _record's order"""
+    return (list(l.w), list(l.h), int(l.idx), int(l.qerr))
+
+
 @pytest.mark.parametrize("kbytes", [1, 24, 200])
 @pytest.mark.parametrize("bits,channels,ms,trials,mbs", [(4, 2, False, 0, 256), (4, 2, True, 1, 128), (3, 1, False, 0, 64),
                                                          (2, 3, False, 2, 96), (4, 8, False, 0, 256)])
@@ -309,8 +319,7 @@ def test_tiled_host_path_is_tile_size_independent(engine, kbytes, bits, channels
             for i, p in enumerate(pcms):
                 assert images[i] == ob.encode(p, bits, mbs, 48000, ms, trials, lanes=lanes[i], reset_idx=True), (k, i)
                 for c in range(channels):
-                    assert list(state[i * channels + c]["weight"]) == list(lanes[i][c].w), (k, i, c)
-                    assert int(state[i * channels + c]["stepsize_index"]) == lanes[i][c].idx
+                    assert _record(state[i * channels + c]) == _lane(lanes[i][c]), (k, i, c)
         # images that end early: inside a block header is an error, anywhere else the walk stops
         from aad_amd.engine import parse_header
         head, bs = 18 * channels, parse_header(want[0][:31]).block_size
@@ -344,8 +353,7 @@ def test_state_carry_matches_oracle(engine, mapping):
         for s in range(streams):
             assert images[s] == ob.encode(pcms[s], 4, 1024, 48000, False, 1, lanes=lanes[s], reset_idx=True), (k, s)
             for c in range(ch):
-                assert list(state[s * ch + c]["weight"]) == list(lanes[s][c].w)
-                assert int(state[s * ch + c]["stepsize_index"]) == lanes[s][c].idx
+                assert _record(state[s * ch + c]) == _lane(lanes[s][c]), (k, s, c)
 
 
 def test_legacy_handle_reuse_and_decode_block(legacy):
@@ -357,6 +365,12 @@ def test_legacy_handle_reuse_and_decode_block(legacy):
             pcm = synth_pcm(1, 2100 + k, 2, seed=70 + k)[0]
             img = legacy.encode(pcm, 4, 1024, 48000, True, 2, encoder=enc)
             assert img == ob.encode(pcm, 4, 1024, 48000, True, 2, lanes=lanes, reset_idx=True)
+        # a third call with no AADEncoder_SetEncodeParameter in front: the step index is carried as well as the weights
+        import crafted_state as cs
+        pcm = synth_pcm(1, 1777, 2, seed=72)[0]
+        carried = cs.api_encode(lib, enc, {"bits": 4, "max_block_size": 1024, "ms": True, "trials": 2}, pcm, set_parameter=False)
+        assert any(l.idx for l in lanes)
+        assert carried == ob.encode(pcm, 4, 1024, 48000, True, 2, lanes=lanes, reset_idx=False)
     finally:
         lib.AADEncoder_Destroy(enc)
     hd = legacy.decode_header(img)
