@@ -486,6 +486,30 @@ __device__ __forceinline__ int32_t predict(const QuadLane &Q)
   return (int32_t)s >> 15;
 }
 __device__ __forceinline__ void lms_first(QuadLane &Q, int32_t qd) { Q.w += mad_i24(qd, Q.h, 16384) >> 18; }
+/* The same update as ONE 64-bit multiply-add.  A lane of a quad owns one tap, so the addend's upper dword can carry the
+ * weight itself:
+ *   w' = hi32( q14 * h + {lo: 2^28, hi: w} ),   q14 = qd << 14 (lms_q14; |qd| <= 61438, so q14 fits 31 bits)
+ * q14 * h + 2^28 = (qd * h + 16384) * 2^14 as for lms_tap, and adding w << 32 touches the upper dword only: the result is
+ * w + ((qd * h + 16384) >> 18) mod 2^32, the reference's int32 wraparound, for any int16 h and any int32 w
+ * (tests/lms_fused_equiv.c).  The multiply-add overwrites its register pair, so the pair `wa` = {2^28, w} is the carried
+ * form of the weight and its lower dword is loaded again after every update - one v_mov_b32, which the caller places
+ * (lms_addend_reload) where a slot is free: the chunk bodies put it into a DPP gap, in place of an s_nop.  The constant is
+ * pinned so that the move stays where it is written and lands in the pair's own lower register (handed to the compiler as a
+ * literal it becomes a 64-bit add of 2^28 behind the multiply-add and a copy of the weight: four instructions). */
+constexpr uint32_t kLmsHalf = 1u << 28;
+__device__ __forceinline__ uint32_t lms_half()
+{
+  uint32_t v = kLmsHalf;
+  pin(v);
+  return v;
+}
+__device__ __forceinline__ uint64_t lms_addend(int32_t w, uint32_t half) { return ((uint64_t)(uint32_t)w << 32) | half; }
+__device__ __forceinline__ void lms_addend_reload(uint64_t &wa) { wa = (wa & 0xFFFFFFFF00000000ull) | lms_half(); }
+__device__ __forceinline__ void lms_first_fused(QuadLane &Q, uint64_t &wa, int32_t qd)
+{
+  wa = (uint64_t)((int64_t)lms_q14(qd) * (int64_t)Q.h + (int64_t)wa); /* v_mad_i64_i32 */
+  Q.w = (int32_t)(wa >> 32);
+}
 /* History shift: every tap takes the next-newer tap's sample, tap 0 the reconstructed one.
  *   kShiftBankMask  tap-major layout only, ONE instruction: v_mov_b32_dpp row_shr:4 with bank_mask
  *                   0xE - the DPP write is switched off for bank 0 of every row (= the tap-0 lanes),

@@ -182,6 +182,7 @@ struct EncodeCarry {
   float f;         /* (float)d */
   int32_t j;       /* kIdxScale * (biased step index): the chunk bodies' own form of L.idxb */
   uint32_t copy;   /* byte offset of this lane's copy of the wide records inside a slot (wide_copy_offset) */
+  uint32_t half;   /* 2^28 in a register: the lower dword of the fused LMS update's addend, loaded by the previous sample (lms_half) */
 };
 
 template <int BITS>
@@ -189,6 +190,7 @@ __device__ __forceinline__ void encode_prime_quad(QuadLane &L, EncodeCarry &C, i
 {
   C.j = L.idxb * kIdxScale;
   C.copy = wide_copy_offset();
+  C.half = lms_half();
   C.e = *reinterpret_cast<const u32x3 *>(lds + kLdsWideOff + wide4_addr(C.j, C.copy));
   C.p = predict<kEncTM>(L);
   C.d = x0 - C.p;
@@ -224,7 +226,13 @@ enum { kPassRmse = 0, kPassEncode = 1, kPassBoth = 2 };
  * bits of the last code word they reach) */
 /* CAP: after every fourth sample j the history shift has left y(j - t) in tap t, so the quad holds samples j - 3 .. j; each lane
  * keeps its tap's one in ycap[j / 4] (planar reconstruct, RecRow::quad) */
-template <int BITS, int PASS, int FORMAT = kWide, typename Fill = NoFill, int N = kChunk, bool CAP = false>
+/* FUSED: the tap update is the one 64-bit multiply-add of lms_first_fused, its addend's lower dword loaded again in the second
+ * DPP gap.  On by default where it measured faster, the encode pass: there the move takes the place of an s_nop (486 -> 471
+ * slots per chunk of the headline body, 61.5 -> 60.4 us per launch).  The bodies that also sum the squares (kPassRmse, kPassBoth)
+ * lose slots as well (dual search 528 -> 518) but did not get faster - the dual trial search measured 0.4 % slower, a second
+ * 64-bit multiply-add per sample costing a lone wave what the slot saves - so they keep lms_first
+ * (profiles/r10_quad_lms_fused.txt). */
+template <int BITS, int PASS, int FORMAT = kWide, typename Fill = NoFill, int N = kChunk, bool CAP = false, bool FUSED = PASS == kPassEncode>
 __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C, const int32_t *x, int32_t xn0,
                                                     const char *lds, uint32_t *w, int32_t &qd_out, int64_t &sq, Fill fill = Fill(),
                                                     [[maybe_unused]] int32_t *ycap = nullptr)
@@ -243,6 +251,7 @@ __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C,
   int32_t p = C.p, d = C.d, m = C.m, idxj = C.j;
   const uint32_t copy = C.copy;
   float f = C.f;
+  uint64_t wa = lms_addend(L.w, C.half); /* the weight as the fused LMS update carries it (lms_first_fused) */
   static_for<0, N>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
     /* A */
@@ -265,7 +274,9 @@ __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C,
     const int32_t yq = (int32_t)((uint64_t)((int64_t)(int32_t)step9_j * (int64_t)(int32_t)g + (int64_t)mp) >> 32); /* v_mad_i64_i32 */
     const int32_t qd = yq - p;
     const int32_t y = clip16(yq);
-    lms_and_shift<kEncTM ? kShiftBankMask : kShiftBitSelect>(L, qd, y);
+    if constexpr (FUSED) lms_first_fused(L, wa, qd); /* w' = hi32(q14 * h + {2^28, w}) */
+    else lms_first(L, qd);
+    lms_rest_and_shift<kEncTM ? kShiftBankMask : kShiftBitSelect>(L, qd, y);
     if constexpr (CAP && (j & 3) == 3) ycap[j >> 2] = L.h;
     /* prediction of the next sample, with the two instructions that pack this sample's code
      * placed in the wait states its DPP adds need (see decode_chunk16_quad) */
@@ -297,6 +308,9 @@ __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C,
      * launch of the bench batch with the wait in the first gap, 70.4 in front of the quantiser,
      * 68.6 here). */
     __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0) */
+    /* the weight's addend gets its lower dword back (the update overwrote it): an independent instruction in the second
+     * DPP gap, where an s_nop stood */
+    if constexpr (FUSED) lms_addend_reload(wa);
     s += quad_dpp<kEncTM ? kDppRowRor8 : 0x4E>(s);
     p = (int32_t)s >> 15;
     d = sample(j + 1) - p;
@@ -314,6 +328,7 @@ __device__ __forceinline__ void encode_chunk16_quad(QuadLane &L, EncodeCarry &C,
   C.m = m;
   C.f = f;
   C.j = idxj;
+  C.half = (uint32_t)wa;
   L.idxb = idxj >> kIdxScaleLog2; /* the unscaled form everything outside the chunk bodies uses; dead code unless read */
 }
 

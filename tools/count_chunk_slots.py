@@ -22,14 +22,15 @@ SAMPLES = 16
 
 def kernel_symbol(bits, chf, ms, quad, trials, dual, ring):
     b = lambda v: "Lb1E" if v else "Lb0E"
-    return "_ZN3aad21encode_streams_kernelILi%dELi%dE%s%s%s%s%sEEvNS_10EncodeArgsE" % (
+    # <BITS, CHF, MS, QUAD, TRIALS, DUAL, RING, SEG = false, IN = interleaved, REC = none>; the argument type follows
+    return "_ZN3aad21encode_streams_kernelILi%dELi%dE%s%s%s%s%sLb0ELi0ELi0EEEv" % (
         bits, chf, b(ms), b(quad), b(trials), b(dual), b(ring))
 
 
 def kernel_lines(lines, sym):
     start = None
     for i, l in enumerate(lines):
-        if l.startswith(sym + ":"):
+        if l.startswith(sym) and re.match(r"^\w+:", l):
             start = i + 1
         elif start is not None and (l.startswith(".Lfunc_end") or re.match(r"^_Z\w*:", l)):
             return lines[start:i]
