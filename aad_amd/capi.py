@@ -72,6 +72,7 @@ STREAM_DESC_DTYPE = np.dtype([("pcm_offset", "<u8"), ("data_offset", "<u8"), ("d
 ERROR_STATS_DTYPE = np.dtype([("rms_error", "<f8"), ("mean_abs_error", "<f8"), ("max_abs_error", "<f8")])  # AADHipErrorStats
 WINDOW_DTYPE = np.dtype([("stream", "<i8"), ("first_frame", "<i8")])  # struct AADHipWindow: an int64 pair, a torch int64 [N, 2] row
 SAMPLE_INT16, SAMPLE_FLOAT32 = 0, 1  # enum AADHipSampleType
+SAMPLE_FLOAT16, SAMPLE_BFLOAT16 = 4, 5  # window decode rows alone (WindowDecodePlan.run)
 RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL = 0, 1  # enum AADHipReconstructOutput
 OPTION_LANE_MAPPING, OPTION_TRIAL_LANES, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_COMPARE_ORDER = 0, 1, 2, 3, 4  # enum AADHipOption
 LANE_MAPPINGS = {"auto": 0, "dense": 1, "quad": 2, "quad-fused": 3, "dense-tiled": 4}  # enum AADHipLaneMapping

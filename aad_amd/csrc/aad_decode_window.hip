@@ -4,32 +4,35 @@
 
 namespace aad {
 
-template <int BITS, bool F32>
+template <int BITS, int ST>
 static void launch_bits(const WindowArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
 {
   if (a.channels == 1)
-    AAD_LAUNCH((decode_window_kernel<BITS, 1, false, F32>), grid, block, lds, stream, a);
+    AAD_LAUNCH((decode_window_kernel<BITS, 1, false, ST>), grid, block, lds, stream, a);
   else if (a.channels == 2 && a.mid_side)
-    AAD_LAUNCH((decode_window_kernel<BITS, 2, true, F32>), grid, block, lds, stream, a);
+    AAD_LAUNCH((decode_window_kernel<BITS, 2, true, ST>), grid, block, lds, stream, a);
   else if (a.channels == 2)
-    AAD_LAUNCH((decode_window_kernel<BITS, 2, false, F32>), grid, block, lds, stream, a);
+    AAD_LAUNCH((decode_window_kernel<BITS, 2, false, ST>), grid, block, lds, stream, a);
   else
-    AAD_LAUNCH((decode_window_kernel<BITS, 0, false, F32>), grid, block, lds, stream, a);
+    AAD_LAUNCH((decode_window_kernel<BITS, 0, false, ST>), grid, block, lds, stream, a);
 }
 
-template <bool F32>
+template <int ST>
 static void launch_type(const WindowArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
 {
-  if (a.bits == 4) launch_bits<4, F32>(a, grid, block, lds, stream);
-  else if (a.bits == 3) launch_bits<3, F32>(a, grid, block, lds, stream);
-  else launch_bits<2, F32>(a, grid, block, lds, stream);
+  if (a.bits == 4) launch_bits<4, ST>(a, grid, block, lds, stream);
+  else if (a.bits == 3) launch_bits<3, ST>(a, grid, block, lds, stream);
+  else launch_bits<2, ST>(a, grid, block, lds, stream);
 }
 
-void launch_decode_window(const WindowArgs &a, const WindowLaunch &p, bool float32, hipStream_t stream)
+template <>
+void launch_decode_window_unit<AAD_WINDOW_HALF != 0>(
+    const WindowArgs &a, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
 {
+  using T = WindowUnitTypes<AAD_WINDOW_HALF != 0>;
   const dim3 grid(p.grid), block(p.workgroup);
-  if (float32) launch_type<true>(a, grid, block, p.lds, stream);
-  else launch_type<false>(a, grid, block, p.lds, stream);
+  if (sample_type == T::second) launch_type<T::second>(a, grid, block, p.lds, stream);
+  else launch_type<T::first>(a, grid, block, p.lds, stream);
 }
 
 } /* namespace aad */

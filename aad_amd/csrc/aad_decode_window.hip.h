@@ -1,6 +1,6 @@
 /*
  * aad_decode_window.hip.h - window decode (AADHip_WindowDecodePlanRun): sample-accurate crops of many streams, straight into
- * planar [windows, channels, frames] rows of int16 or float32.
+ * planar [windows, channels, frames] rows of int16, float32, float16 or bfloat16.
  *
  * Every block header carries the decoder's whole state (reference src/aad_decoder.c:364-380), so the frames of a crop come from the
  * blocks that cover it alone.  One lane per (window, block-in-window, channel): a window of T frames touches at most
@@ -9,8 +9,10 @@
  * header on - the samples in front of the crop carry the state - with the per-lane dense decoder's pieces (aad_decode.hip.h: header
  * parse, code fetch one chunk ahead, decode_chunk16, byte-load tail, M/S finish through pair_swap), stops after the last sample the
  * window needs, and stores only the samples inside the window: whole 16-sample chunks as 16-byte vectors at the row's own
- * (2- or 4-byte) alignment, the head and tail of a row sample by sample.  Frames the stream does not produce (past num_samples,
- * past the bytes that are there, a stream index out of range) are written as zeros by the lane whose block holds them.
+ * (2- or 4-byte) alignment, the head and tail of a row sample by sample.  The float16 and bfloat16 rows are the float32 value
+ * rounded to nearest even, two samples per v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32, and leave by the int16 row's stores.  Frames the
+ * stream does not produce (past num_samples, past the bytes that are there, a stream index out of range) are written as zeros by
+ * the lane whose block holds them.
  *
  * Reads: the 18-byte channel headers only when that many bytes are present, chunk loads only while they lie inside the stream's
  * bytes, the tail byte by byte against the same bound - exactly decode_blocks_kernel's `avail` rule, so no byte outside
@@ -28,7 +30,7 @@ struct WindowArgs {
   const StreamDesc *streams;
   const uint8_t *data;
   const uint64_t *windows; /* [num_windows][2]: stream, first_frame (struct AADHipWindow) */
-  void *out;               /* [num_windows][channels][frames] int16 or float32 */
+  void *out;               /* [num_windows][channels][frames] of the sample type */
   uint64_t lanes;          /* num_windows * blocks_per_window * channels */
   uint32_t blocks_per_window;
   uint32_t frames;
@@ -43,6 +45,28 @@ struct WindowArgs {
 };
 
 typedef float f32x4_u4 __attribute__((ext_vector_type(4), aligned(4))); /* a 16-byte store at 4-byte alignment */
+
+/* the sample type of the rows, by its number in the C ABI (enum AADHipSampleType) */
+enum WindowSample {
+  kRowI16 = AAD_HIP_SAMPLE_INT16,
+  kRowF32 = AAD_HIP_SAMPLE_FLOAT32,
+  kRowF16 = AAD_HIP_SAMPLE_FLOAT16,
+  kRowBF16 = AAD_HIP_SAMPLE_BFLOAT16
+};
+
+/* two float32 values as one word of two float16 / bfloat16, the first in the low half: round to nearest even in hardware, one
+ * v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32 (the kernels keep 16-bit subnormals: .amdhsa_float_denorm_mode_16_64 3).  With hi = 0 - a
+ * single sample - hipcc folds the float16 case and the scale in front of it into v_fma_mixlo_f16: the product in float32, exact,
+ * and the same one rounding */
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+template <int ST>
+__device__ __forceinline__ uint32_t pack_half2(float lo, float hi)
+{
+  static_assert(ST == kRowF16 || ST == kRowBF16, "the 2-byte float types");
+  if constexpr (ST == kRowF16) return __builtin_bit_cast(uint32_t, f16x2{(_Float16)lo, (_Float16)hi});
+  else return __builtin_bit_cast(uint32_t, bf16x2{(__bf16)lo, (__bf16)hi});
+}
 
 /* how a lane's samples reach the output's channels (aad_decode_window_channel_mix.hip.h); kMixNone: channel c into row c */
 enum WindowMix { kMixNone = 0, kMixTwin = 1 /* mono source, two rows */, kMixDown = 2 /* stereo source, one row */ };
@@ -60,24 +84,32 @@ struct WindowLevels<true> {
 };
 
 /* one row segment of a lane: output element t = base + i for sample i of the block, kept where lo <= t < hi.
- * kMixTwin: every store goes to the row `twin` elements on as well.  kMixDown: y is L + R as float32, (L + R) >> 1 as int16.
+ * kMixTwin: every store goes to the row `twin` elements on as well.  kMixDown: y is L + R for the float types, (L + R) >> 1 as int16.
+ * float16 / bfloat16 rows hold the bits (uint16_t): the float32 value, exact, then the one rounding of the type.
  * STATS: every kept sample is added to the lane's WindowLevels as the int16 value the row holds, zeros() adds nothing. */
-template <bool F32, int MIX = kMixNone, bool STATS = false>
+template <int ST, int MIX = kMixNone, bool STATS = false>
 struct WindowRow : WindowLevels<STATS> {
-  using T = std::conditional_t<F32, float, int16_t>;
+  static_assert(ST == kRowI16 || ST == kRowF32 || ST == kRowF16 || ST == kRowBF16, "a sample type of window decode");
+  static constexpr bool F32 = ST == kRowF32, HALF = ST == kRowF16 || ST == kRowBF16;
+  using T = std::conditional_t<F32, float, std::conditional_t<HALF, uint16_t, int16_t>>;
   T *row;
   int64_t base, lo, hi;
   int64_t twin; /* kMixTwin alone */
+  /* exact: an int16 (kMixDown: a sum of two, at most 17 bits) times a power of two */
+  __device__ __forceinline__ static float scaled(int32_t y)
+  {
+    return (float)y * (MIX == kMixDown ? 1.0f / 65536.0f : 1.0f / 32768.0f);
+  }
   __device__ __forceinline__ static T convert(int32_t y)
   {
-    /* exact: an int16 (kMixDown: a sum of two, at most 17 bits) times a power of two */
-    if constexpr (F32) return (float)y * (MIX == kMixDown ? 1.0f / 65536.0f : 1.0f / 32768.0f);
+    if constexpr (F32) return scaled(y);
+    else if constexpr (HALF) return (T)pack_half2<ST>(scaled(y), 0.0f);
     else return (T)y;
   }
-  /* STATS only.  The float32 down-mix carries L + R: its statistic is the int16 floor mix's */
+  /* STATS only.  The float down-mix carries L + R: its statistic is the int16 floor mix's */
   __device__ __forceinline__ void level(int32_t y)
   {
-    const int32_t v = F32 && MIX == kMixDown ? y >> 1 : y;
+    const int32_t v = ST != kRowI16 && MIX == kMixDown ? y >> 1 : y;
     const uint32_t m = (uint32_t)(v < 0 ? -v : v); /* at most 32768 */
     this->sum_sq += (uint64_t)m * m;
     this->sum_abs += m;
@@ -118,6 +150,21 @@ struct WindowRow : WindowLevels<STATS> {
           *reinterpret_cast<f32x4_u4 *>(p + 4 * q) = v;
           if constexpr (MIX == kMixTwin) *reinterpret_cast<f32x4_u4 *>(p + twin + 4 * q) = v;
         }
+      } else if constexpr (HALF) {
+        ChunkPcm o;
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+          o.v[h] = u32x4{pack_half2<ST>(scaled(y[8 * h]), scaled(y[8 * h + 1])),
+                         pack_half2<ST>(scaled(y[8 * h + 2]), scaled(y[8 * h + 3])),
+                         pack_half2<ST>(scaled(y[8 * h + 4]), scaled(y[8 * h + 5])),
+                         pack_half2<ST>(scaled(y[8 * h + 6]), scaled(y[8 * h + 7]))};
+        int16_t *h16 = reinterpret_cast<int16_t *>(p); /* the int16 row's stores: 16 bytes at 2-byte alignment */
+        store_u32x4<false>(h16, o.v[0]);
+        store_u32x4<false>(h16 + 8, o.v[1]);
+        if constexpr (MIX == kMixTwin) {
+          store_u32x4<false>(h16 + twin, o.v[0]);
+          store_u32x4<false>(h16 + twin + 8, o.v[1]);
+        }
       } else {
         const ChunkPcm o = pack_chunk_pcm<1, false>(y, 0);
         store_u32x4<false>(p, o.v[0]);
@@ -152,7 +199,7 @@ struct WindowRow : WindowLevels<STATS> {
  * L / R samples once more and lane c == 0 stores the mix into the one row.
  * STATS (aad_decode_window_stats.hip.h): the lane also sums the levels of the samples it keeps and ends by adding them into its
  * row's record of `stats`, which the run cleared; a.out may then be null - nothing is stored, the ranges stay. */
-template <int BITS, int CHF, bool MS, bool F32, bool MIXED = false, int OUTC = 0, class FORMAT = StreamFormat, bool STATS = false>
+template <int BITS, int CHF, bool MS, int ST, bool MIXED = false, int OUTC = 0, class FORMAT = StreamFormat, bool STATS = false>
 __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane, const FORMAT *formats = nullptr,
                                             uint32_t owns_strays = 0, unsigned long long *stats = nullptr)
 {
@@ -185,16 +232,16 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
   const uint64_t kspb = (uint64_t)k * spb;
   if (kspb >= frames + phase) return; /* past the window's last block: lanes of one (window, block) leave together */
 
-  WindowRow<F32, MIX, STATS> out;
+  WindowRow<ST, MIX, STATS> out;
   if constexpr (STATS) {
     out.sum_sq = out.sum_abs = 0;
     out.max_abs = 0;
     out.store = a.out != nullptr;
   }
   if constexpr (MIX == kMixNone) {
-    out.row = reinterpret_cast<typename WindowRow<F32>::T *>(a.out) + (w * ch + c) * frames;
+    out.row = reinterpret_cast<typename WindowRow<ST>::T *>(a.out) + (w * ch + c) * frames;
   } else {
-    out.row = reinterpret_cast<typename WindowRow<F32>::T *>(a.out) + w * OUTC * frames;
+    out.row = reinterpret_cast<typename WindowRow<ST>::T *>(a.out) + w * OUTC * frames;
     out.twin = (int64_t)frames;
   }
   out.base = (int64_t)kspb - (int64_t)phase;
@@ -252,7 +299,7 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
        * exchange; right on lane c == 0, which alone stores */
       const int32_t other = (int32_t)pair_swap<false>((uint32_t)y, c);
       const int32_t sum = MS ? clip16(y + other) + clip16(y - other) : y + other;
-      return F32 ? sum : sum >> 1; /* float32 keeps the half step (WindowRow::convert), int16 is the floor */
+      return ST != kRowI16 ? sum : sum >> 1; /* the float types keep the half step (WindowRow::scaled), int16 is the floor */
     } else {
       if (MS) {
         const int32_t other = (int32_t)pair_swap<false>((uint32_t)y, c);
@@ -366,7 +413,7 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
   }
 }
 
-template <int BITS, int CHF, bool MS, bool F32>
+template <int BITS, int CHF, bool MS, int ST>
 __global__ void __launch_bounds__(256) decode_window_kernel(WindowArgs a)
 {
   __shared__ __attribute__((aligned(16))) char lds[kLdsBytesDenseDec];
@@ -374,7 +421,7 @@ __global__ void __launch_bounds__(256) decode_window_kernel(WindowArgs a)
   stage_dense_decode_tables<BITS>(lds);
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x; /* a multiple of 64: the lanes of a channel pair stay neighbours */
   for (uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; lane < a.lanes; lane += stride)
-    window_lane<BITS, CHF, MS, F32>(a, lds, lane);
+    window_lane<BITS, CHF, MS, ST>(a, lds, lane);
 }
 
 } /* namespace aad */

@@ -31,7 +31,7 @@ struct ChannelMixWindowArgs {
   uint32_t out_channels;              /* 1 or 2: the rows of a window */
 };
 
-template <int BITS, int CHF, bool MS, bool F32, int OUTC>
+template <int BITS, int CHF, bool MS, int ST, int OUTC>
 __global__ void __launch_bounds__(256) decode_window_channel_mix_kernel(ChannelMixWindowArgs a)
 {
   __shared__ __attribute__((aligned(16))) char lds[kLdsBytesDenseDec];
@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(256) decode_window_channel_mix_kernel(ChannelM
   stage_dense_decode_tables<BITS>(lds);
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x; /* a multiple of 64: the lanes of a channel pair stay neighbours */
   for (uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; lane < a.w.lanes; lane += stride)
-    window_lane<BITS, CHF, MS, F32, true, OUTC>(a.w, lds, lane, a.formats, a.owns_strays);
+    window_lane<BITS, CHF, MS, ST, true, OUTC>(a.w, lds, lane, a.formats, a.owns_strays);
 }
 
 } /* namespace aad */

@@ -27,7 +27,7 @@ struct MixedWindowArgs {
   uint32_t reserved;
 };
 
-template <int BITS, int CHF, bool MS, bool F32>
+template <int BITS, int CHF, bool MS, int ST>
 __global__ void __launch_bounds__(256) decode_window_mixed_kernel(MixedWindowArgs a)
 {
   __shared__ __attribute__((aligned(16))) char lds[kLdsBytesDenseDec];
@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256) decode_window_mixed_kernel(MixedWindowArg
   stage_dense_decode_tables<BITS>(lds);
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x; /* a multiple of 64: the lanes of a channel pair stay neighbours */
   for (uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; lane < a.w.lanes; lane += stride)
-    window_lane<BITS, CHF, MS, F32, true>(a.w, lds, lane, a.formats, a.owns_strays);
+    window_lane<BITS, CHF, MS, ST, true>(a.w, lds, lane, a.formats, a.owns_strays);
 }
 
 } /* namespace aad */

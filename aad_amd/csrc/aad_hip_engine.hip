@@ -1227,8 +1227,8 @@ AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::La
     a.owns_strays = i == 0;
     last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
     aad::tl_launch_signal = last;
-    if (stats != nullptr) aad::launch_decode_window_mixed_stats(a, stats, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
-    else aad::launch_decode_window_mixed(a, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+    if (stats != nullptr) aad::launch_decode_window_mixed_stats(a, stats, m.launch[i], sample_type, ctx->stream);
+    else aad::launch_decode_window_mixed(a, m.launch[i], sample_type, ctx->stream);
     if (!hip_ok(ctx, hipGetLastError(), "mixed window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   }
   return finish_signal(ctx, last, AAD_APIRESULT_OK);
@@ -1277,11 +1277,18 @@ AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const a
     last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
     aad::tl_launch_signal = last;
     if (stats != nullptr)
-      aad::launch_decode_window_channel_mix_stats(a, stats, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
-    else aad::launch_decode_window_channel_mix(a, m.launch[i], sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+      aad::launch_decode_window_channel_mix_stats(a, stats, m.launch[i], sample_type, ctx->stream);
+    else aad::launch_decode_window_channel_mix(a, m.launch[i], sample_type, ctx->stream);
     if (!hip_ok(ctx, hipGetLastError(), "channel-mix window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   }
   return finish_signal(ctx, last, AAD_APIRESULT_OK);
+}
+
+/* the sample types of window decode rows: 2 and 3 are no type, and float16 / bfloat16 exist for window decode alone */
+bool window_sample_type_ok(int32_t sample_type)
+{
+  return sample_type == AAD_HIP_SAMPLE_INT16 || sample_type == AAD_HIP_SAMPLE_FLOAT32 || sample_type == AAD_HIP_SAMPLE_FLOAT16 ||
+         sample_type == AAD_HIP_SAMPLE_BFLOAT16;
 }
 
 /* AADHip_WindowDecodePlanRun, and with_stats AADHip_WindowDecodePlanRunStats: the table as a further output, device_out optional */
@@ -1292,7 +1299,7 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
   if (plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
   AADHipContext *ctx = plan->ctx;
   aad::LaunchSignal signal = take_signal(ctx);
-  if (frames_per_window == 0 || (sample_type != AAD_HIP_SAMPLE_INT16 && sample_type != AAD_HIP_SAMPLE_FLOAT32) ||
+  if (frames_per_window == 0 || !window_sample_type_ok(sample_type) ||
       (num_windows != 0 && (device_data == nullptr || device_windows == nullptr || (device_out == nullptr && !with_stats))))
     return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
   uint64_t stats_bytes = 0;
@@ -1344,8 +1351,8 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
   a.bits = d.bits;
   if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
-  if (stats != nullptr) aad::launch_decode_window_stats(a, stats, p, sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
-  else aad::launch_decode_window(a, p, sample_type == AAD_HIP_SAMPLE_FLOAT32, ctx->stream);
+  if (stats != nullptr) aad::launch_decode_window_stats(a, stats, p, sample_type, ctx->stream);
+  else aad::launch_decode_window(a, p, sample_type, ctx->stream);
   return finish_signal(ctx, signal, hip_ok(ctx, hipGetLastError(), "window decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG);
 }
 } /* namespace */

@@ -28,24 +28,89 @@ extern thread_local LaunchSignal tl_launch_signal; /* defined in aad_hip_engine.
 struct DecodeArgs;
 void launch_decode_split(const DecodeArgs &args, const DecodeLaunch &p, int32_t *residual, hipStream_t stream);
 void launch_decode_tiled(const DecodeArgs &args, const DecodeLaunch &p, hipStream_t stream);
-/* aad_decode_window.hip: the window decoder (AADHip_WindowDecodePlanRun), int16 or float32 rows */
+/* The window decoders (AADHip_WindowDecodePlanRun, AADHip_WindowDecodePlanRunStats).  Each of their six translation units is
+ * compiled twice (Makefile): with AAD_WINDOW_HALF=0 its kernels write int16 and float32 rows, with AAD_WINDOW_HALF=1 (the _half
+ * objects) float16 and bfloat16 rows.  A unit defines launch_..._unit<AAD_WINDOW_HALF>; the launch_... below pick the unit by the
+ * run's sample_type (enum AADHipSampleType, validated by the entry point). */
+#ifndef AAD_WINDOW_HALF
+#define AAD_WINDOW_HALF 0
+#endif
+template <bool HALF>
+struct WindowUnitTypes { /* a unit's two sample types: sample_type == second runs the second, anything else the first */
+  static constexpr int32_t first = HALF ? AAD_HIP_SAMPLE_FLOAT16 : AAD_HIP_SAMPLE_INT16;
+  static constexpr int32_t second = HALF ? AAD_HIP_SAMPLE_BFLOAT16 : AAD_HIP_SAMPLE_FLOAT32;
+};
+/* the unit's launch function: declared with both explicit specialisations, one defined by each object of the unit */
+#define AAD_WINDOW_UNIT(name, ...)     \
+  template <bool HALF>                 \
+  void name(__VA_ARGS__);              \
+  template <>                          \
+  void name<false>(__VA_ARGS__);       \
+  template <>                          \
+  void name<true>(__VA_ARGS__)
+inline bool window_half_type(int32_t sample_type)
+{
+  return sample_type == AAD_HIP_SAMPLE_FLOAT16 || sample_type == AAD_HIP_SAMPLE_BFLOAT16;
+}
+/* aad_decode_window.hip: the same-format window decoder */
 struct WindowArgs;
-void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_unit,
+                const WindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
 /* aad_decode_window_mixed.hip: one launch (one kernel variant: args.w.bits, args.w.mid_side) of a mixed-format window decode run */
 struct MixedWindowArgs;
-void launch_decode_window_mixed(const MixedWindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_mixed_unit,
+                const MixedWindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
 /* aad_decode_window_channel_mix.hip: one launch (args.w.channels, args.w.bits, args.w.mid_side: the variant) of a channel-mix run */
 struct ChannelMixWindowArgs;
-void launch_decode_window_channel_mix(const ChannelMixWindowArgs &args, const WindowLaunch &p, bool float32, hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_channel_mix_unit,
+                const ChannelMixWindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
 /* aad_decode_window_stats.hip, aad_decode_window_mixed_stats.hip, aad_decode_window_channel_mix_stats.hip: the same launches of
  * AADHip_WindowDecodePlanRunStats - the rows (args' out, which may be null) and the level statistics of every row added into
  * `stats`, which the run cleared */
-void launch_decode_window_stats(const WindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, bool float32,
-                                hipStream_t stream);
-void launch_decode_window_mixed_stats(const MixedWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, bool float32,
-                                      hipStream_t stream);
-void launch_decode_window_channel_mix_stats(const ChannelMixWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p,
-                                            bool float32, hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_stats_unit,
+                const WindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, int32_t sample_type,
+                hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_mixed_stats_unit,
+                const MixedWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, int32_t sample_type,
+                hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_channel_mix_stats_unit,
+                const ChannelMixWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, int32_t sample_type,
+                hipStream_t stream);
+
+inline void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_unit<true>(args, p, sample_type, stream);
+  else launch_decode_window_unit<false>(args, p, sample_type, stream);
+}
+inline void launch_decode_window_mixed(const MixedWindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_mixed_unit<true>(args, p, sample_type, stream);
+  else launch_decode_window_mixed_unit<false>(args, p, sample_type, stream);
+}
+inline void launch_decode_window_channel_mix(const ChannelMixWindowArgs &args, const WindowLaunch &p, int32_t sample_type,
+                                             hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_channel_mix_unit<true>(args, p, sample_type, stream);
+  else launch_decode_window_channel_mix_unit<false>(args, p, sample_type, stream);
+}
+inline void launch_decode_window_stats(const WindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p,
+                                       int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_stats_unit<true>(args, stats, p, sample_type, stream);
+  else launch_decode_window_stats_unit<false>(args, stats, p, sample_type, stream);
+}
+inline void launch_decode_window_mixed_stats(const MixedWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p,
+                                             int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_mixed_stats_unit<true>(args, stats, p, sample_type, stream);
+  else launch_decode_window_mixed_stats_unit<false>(args, stats, p, sample_type, stream);
+}
+inline void launch_decode_window_channel_mix_stats(const ChannelMixWindowArgs &args, struct AADHipRowStats *stats,
+                                                   const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_channel_mix_stats_unit<true>(args, stats, p, sample_type, stream);
+  else launch_decode_window_channel_mix_stats_unit<false>(args, stats, p, sample_type, stream);
+}
 /* the decoded rows of a planar reconstruct run (AADHip_PlanarReconstructPlanRun; launched through aad_encode_launch.hip.h).
  * base: per stream (segmented: per chain) the element of `out` that holds channel 0's sample of the lane's first frame, device
  * memory */

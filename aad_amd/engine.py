@@ -10,7 +10,7 @@ import numpy as np
 
 from .capi import (AADApiResult, AADHeaderInfo, AADHipPlanarLayout, AADHipPlanarOutput, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
                    OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_SIMD_ROLE, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
-                   SAMPLE_FLOAT32, SAMPLE_INT16, SIMD_ROLE_OFF, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, load_library, make_parameter)
+                   SAMPLE_BFLOAT16, SAMPLE_FLOAT16, SAMPLE_FLOAT32, SAMPLE_INT16, SIMD_ROLE_OFF, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, load_library, make_parameter)
 
 
 def _check(where, rc):
@@ -514,7 +514,8 @@ class Engine:
 
     def decode_windows(self, data, image_size, windows, frames, dtype=None, return_stats=False):
         """data: uint8 cuda tensor [streams, stride] of same-format images (encode_uniform's output); windows: int64 cuda tensor
-        [N, 2] of (stream, first_frame) -> [N, channels, frames] tensor of `dtype` (torch.float32 = sample / 32768, or torch.int16).
+        [N, 2] of (stream, first_frame) -> [N, channels, frames] tensor of `dtype` (torch.float32 = sample / 32768, torch.int16, or
+        torch.float16 / torch.bfloat16 = the float32 row rounded to nearest even).
         The header is read once, from the first image; the windows are never read on the host.
         return_stats: -> (rows, int64 [N, channels, 4] level statistics of the rows), see WindowDecodePlan.run."""
         head = bytes(data[0, :31].cpu().numpy())
@@ -894,14 +895,17 @@ class WindowDecodePlan:
     def run(self, data, windows, frames, dtype=None, out=None, ordered=True, stats=None, rows=True):
         """data: uint8 cuda tensor of the images; windows: int64 cuda tensor [N, 2] of (stream, first_frame) ->
         `out` ([N, channels, frames] of dtype torch.float32 - sample / 32768 - or torch.int16; allocated when None).
+        dtype torch.float16 / torch.bfloat16: the float32 row rounded once to nearest even, bit for bit row_float32.to(dtype),
+        from the kernel's own stores - what a model under autocast takes without a cast pass.
         Asynchronous on the engine's stream, ordered against torch's current one; the windows stay on the device.
         stats (AADHip_WindowDecodePlanRunStats): True, or a contiguous cuda int64 tensor [N, channels, 4] - the exact level
         statistics of every row (sum_sq, sum_abs, max_abs in int16 units, count = the frames the stream had), from the same
         kernels -> (out, stats).  rows=False: statistics only, no row is written -> stats."""
         torch = self.engine.torch
         dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.int16):
-            raise ValueError("window decode writes torch.float32 or torch.int16, not %s" % dtype)
+        kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
+        if dtype not in kinds:
+            raise ValueError("window decode writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % dtype)
         if windows.dtype != torch.int64 or windows.dim() != 2 or windows.shape[1] != 2 or not windows.is_cuda:
             raise ValueError("windows: an int64 cuda tensor [N, 2] of (stream, first_frame)")
         windows = windows.contiguous()
@@ -924,7 +928,7 @@ class WindowDecodePlan:
             out = torch.empty((n, ch, frames), dtype=dtype, device=windows.device)
         elif out.dtype != dtype or tuple(out.shape) != (n, ch, frames) or not out.is_contiguous() or out.device != windows.device:
             raise ValueError("out: a contiguous %s tensor [%d, %d, %d] on %s" % (dtype, n, ch, frames, windows.device))
-        kind = SAMPLE_FLOAT32 if dtype == torch.float32 else SAMPLE_INT16
+        kind = kinds[dtype]
         cur = self.engine._enter() if ordered else None
         if stats is None:
             _check("AADHip_WindowDecodePlanRun",

@@ -245,9 +245,29 @@ struct AADHipWindow {
   uint64_t stream;      /* index into the plan's stream table */
   uint64_t first_frame; /* first frame of the window */
 };
+/* AAD_HIP_SAMPLE_FLOAT16 and AAD_HIP_SAMPLE_BFLOAT16: 2-byte float rows for a model under autocast, without a cast pass over a
+ * float32 batch.  They are sample types of AADHip_WindowDecodePlanRun and AADHip_WindowDecodePlanRunStats alone, for plans of all
+ * three constructors; the planar encode, planar reconstruct and window reconstruct entry points refuse them, and 2 and 3 are no
+ * sample type anywhere.
+ *
+ * Definition.  Let f be the float32 value an AAD_HIP_SAMPLE_FLOAT32 run writes to the element: the int16 sample * 2^-15, and for
+ * the stereo-to-mono down-mix of a channel-mix plan (L + R) * 2^-16 - both exact in float32.  FLOAT16 writes f rounded to IEEE
+ * binary16, round to nearest even, subnormals kept; BFLOAT16 writes f rounded to bfloat16, round to nearest even.  One rounding,
+ * taken from f: bit for bit torch's row_float32.to(torch.float16) and .to(torch.bfloat16).  Zeros are +0 (frames past num_samples,
+ * stray windows, wrapped values).  Consequences, checked over all 65 536 int16 values:
+ *   - sample 1 is binary16 0x0200, a subnormal, and -1 is 0x8200; no non-zero value rounds to zero, the smallest down-mix sum
+ *     (2^-16, binary16 0x0100) included;
+ *   - 32767 rounds to +1.0 in both types; -32768 and -32767 both give -1.0 in float16;
+ *   - float16 is exact for 12 288 of the 65 536 values (|sample| <= 2048, then the multiples of 2, 4, 8, 16), bfloat16 for 2 304;
+ *   - float16 has a tie at every odd |sample| in [2048, 4096): 2049 goes to 2048 and 2051 to 2052; bfloat16 has one at every
+ *     odd |sample| in [256, 512): 257 goes to 256 and 259 to 260.
+ * The statistics of AADHip_WindowDecodePlanRunStats are those of the int16 values, whatever the sample type.  Errors, the
+ * alignment of device_out and the 64-bit size rule are those of int16: 2-byte elements. */
 enum AADHipSampleType {
-  AAD_HIP_SAMPLE_INT16 = 0,  /* the decoded sample */
-  AAD_HIP_SAMPLE_FLOAT32 = 1 /* the decoded sample / 32768.0f (exact) */
+  AAD_HIP_SAMPLE_INT16 = 0,   /* the decoded sample */
+  AAD_HIP_SAMPLE_FLOAT32 = 1, /* the decoded sample / 32768.0f (exact) */
+  AAD_HIP_SAMPLE_FLOAT16 = 4, /* window decode only: the float32 value rounded to binary16, nearest even */
+  AAD_HIP_SAMPLE_BFLOAT16 = 5 /* window decode only: the float32 value rounded to bfloat16, nearest even */
 };
 struct AADHipWindowDecodePlan;
 AADApiResult AADHip_WindowDecodePlanCreate(

@@ -40,8 +40,14 @@ corpus - stereo 4-bit, float32 rows, same-format plan:
   the median of the rounds' medians and its spread the range of the rounds' medians.  (b)'s rows are compared with (a)'s bitwise,
   (b)'s table with (c)'s, and the table with int64 sums over the int16 rows taken in torch.
 
+--half (profiles/window_decode_half.txt): the run's kernel per sample type - int16, float32, float16 and bfloat16, those the
+loaded library has (AAD_HIP_LIBRARY names another build, e.g. the parent commit's, which refuses the last two) - on the tool's
+corpus, same-format plan.  Kernel times from the events of AADHip_ContextSignalNextRun: per type the median of --reps, in
+alternating rounds over the types; a figure is the median of the rounds' medians and its spread the range of the rounds' medians.
+float16 and bfloat16 rows are compared bitwise with torch's conversion of the float32 rows.
+
 Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25]
-       [--mixed | --channel-mix | --stats]"""
+       [--mixed | --channel-mix | --stats | --half]"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -396,6 +402,69 @@ def stats_main(args, say):
     engine.close()
 
 
+def half_main(args, say):
+    import torch
+    from aad_amd.capi import LIBRARY_PATH, ApiError
+    from aad_amd.engine import Engine, HipEvent, parse_header
+    engine = Engine(0)
+    samples, frames, streams = int(round(args.seconds * 48000)), args.frames, args.streams
+    rounds, results = 5, []
+    corpus, size, stride = build_corpus(engine, torch, streams, samples, seed=args.seed)
+    hd = parse_header(bytes(corpus[0, :31].cpu().numpy()))
+    plan = engine.uniform_window_decode_plan(hd, streams, stride, size)
+    dtypes = []
+    for dtype in (torch.int16, torch.float32, torch.float16, torch.bfloat16):
+        try:
+            plan.run(corpus, torch.zeros((1, 2), dtype=torch.int64, device="cuda"), 16, dtype)
+            dtypes.append(dtype)
+        except ApiError:
+            pass  # a library from before the type
+    torch.cuda.synchronize()
+    say("window decode by sample type: library %s; %d stereo 4-bit streams x %d frames (spb %d), T = %d; kernel times, %d alternating "
+        "rounds of %d runs, median of the rounds' medians (range of the rounds' medians); device %s"
+        % (os.path.relpath(LIBRARY_PATH, ROOT), streams, samples, hd.num_samples_per_block, frames, rounds, args.reps,
+           torch.cuda.get_device_name(0)))
+    for n in args.windows:
+        g = torch.Generator(device="cuda")
+        g.manual_seed(args.seed + n)
+        d_win = torch.stack([torch.randint(0, streams, (n,), device="cuda", generator=g),
+                             torch.randint(0, samples - frames + 1, (n,), device="cuda", generator=g)], dim=1)
+        outs = {d: torch.empty((n, 2, frames), dtype=d, device="cuda") for d in dtypes}
+        runs = {d: (lambda d=d: plan.run(corpus, d_win, frames, d, out=outs[d])) for d in dtypes}
+        for _ in range(3):
+            for d in dtypes:
+                runs[d]()
+        torch.cuda.synchronize()
+        times = {d: [] for d in dtypes}
+        for _ in range(rounds):
+            for d in dtypes:
+                times[d].append(kernel_ms(engine, HipEvent, runs[d], args.reps))
+        torch.cuda.synchronize()
+        say("")
+        say("N = %d windows x T = %d" % (n, frames))
+        row = {"windows": n, "frames": frames, "library": os.path.relpath(LIBRARY_PATH, ROOT)}
+        for d in dtypes:
+            med, spread = float(np.median(times[d])), max(times[d]) - min(times[d])
+            nbytes = outs[d].numel() * outs[d].element_size()
+            exact = None
+            if d in (torch.float16, torch.bfloat16):
+                exact = bool(torch.equal(outs[d].view(torch.int16), outs[torch.float32].to(d).view(torch.int16)))
+            elif d == torch.float32:
+                exact = bool(torch.equal(outs[d], outs[torch.int16].float() / 32768))
+            name = str(d).replace("torch.", "")
+            say("  %-9s kernel %8.4f ms (range %.4f)   %6.1f MB out   %7.1f GB/s (%.3f of 8 TB/s)   rounds %s%s"
+                % (name, med, spread, nbytes / 1e6, nbytes / (med * 1e-3) / 1e9, nbytes / (med * 1e-3) / HBM,
+                   " ".join("%.4f" % t for t in times[d]), "" if exact is None else "   bit-exact: %s" % exact))
+            row[name] = dict(kernel_ms=med, range_ms=spread, rounds_ms=times[d], out_bytes=nbytes, bit_exact=exact)
+        results.append(row)
+        del outs, runs
+        torch.cuda.empty_cache()
+    say("")
+    say("json " + json.dumps(results))
+    plan.close()
+    engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=1000)
@@ -408,6 +477,7 @@ def main():
     ap.add_argument("--mixed", action="store_true", help="the mixed-format plan's two measurements instead (see above)")
     ap.add_argument("--channel-mix", action="store_true", help="the channel-mix plan against what a caller has without it (see above)")
     ap.add_argument("--stats", action="store_true", help="the statistics run against the row run and torch reductions (see above)")
+    ap.add_argument("--half", action="store_true", help="the run's kernel per sample type, float16 and bfloat16 included (see above)")
     args = ap.parse_args()
 
     import torch
@@ -418,11 +488,11 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    if args.mixed or args.channel_mix or args.stats:
-        (mixed_main if args.mixed else channel_mix_main if args.channel_mix else stats_main)(args, say)
+    if args.mixed or args.channel_mix or args.stats or args.half:
+        (mixed_main if args.mixed else channel_mix_main if args.channel_mix else stats_main if args.stats else half_main)(args, say)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "w") as fh:
+            with open(args.out, "a" if args.half else "w") as fh:  # --half: one report per library, appended
                 fh.write("\n".join(lines) + "\n")
         return
 
