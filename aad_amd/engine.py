@@ -22,6 +22,44 @@ def _round_up(v, a):
     return (v + a - 1) // a * a
 
 
+def tensor_span(t):
+    """Elements from t.data_ptr() to the end of the tensor's own storage span: 1 + sum((size - 1) * stride), 0 for an empty tensor.
+    What lies behind it in the same storage belongs to somebody else as far as a run is concerned."""
+    if any(int(s) == 0 for s in t.shape):
+        return 0
+    return 1 + sum((int(s) - 1) * int(st) for s, st in zip(t.shape, t.stride()))
+
+
+def run_extent(kind, descs=None, channels=1, channel_stride=0, stream_stride=0, rows=0, frames=0):
+    """Elements, counted from the pointer a run is handed, that the run may read or write, as include/aad_hip.h defines each
+    call's reads and writes over the plan's table (`descs`, STREAM_DESC_DTYPE; a stream without samples or bytes touches nothing):
+      "interleaved"  max(pcm_offset + num_samples * C)                          int16 frames of EncodePlan / DecodePlan runs
+      "planar"       max(pcm_offset + (C - 1) * channel_stride + num_samples)   input rows of the planar and window reconstruct plans
+      "images"       max(data_offset + data_size)                               bytes of every plan's images
+      "planar_out"   (N - 1) * stream_stride + (C - 1) * channel_stride + the longest num_samples
+      "window_rows"  rows * C * frames                                          [N, C, T] of the window plans
+      "stats"        rows * C * 4                                               int64 [N, C, 4]
+      "state"        rows * C * 10                                              int32 [N * C, 10]
+    Python integers throughout: an offset past 2^63 does not wrap."""
+    c = int(channels)
+    if kind == "window_rows":
+        return int(rows) * c * int(frames)
+    if kind == "stats":
+        return int(rows) * c * 4
+    if kind == "state":
+        return int(rows) * c * 10
+    n = [int(v) for v in descs["num_samples"]]
+    if kind == "interleaved":
+        return max([int(o) + v * c for o, v in zip(descs["pcm_offset"], n) if v], default=0)
+    if kind == "planar":
+        return max([int(o) + (c - 1) * int(channel_stride) + v for o, v in zip(descs["pcm_offset"], n) if v], default=0)
+    if kind == "images":
+        return max([int(o) + int(s) for o, s in zip(descs["data_offset"], descs["data_size"]) if int(s)], default=0)
+    if kind == "planar_out":
+        return (len(n) - 1) * int(stream_stride) + (c - 1) * int(channel_stride) + max(n) if n and max(n) else 0
+    raise ValueError("unknown extent kind %r" % (kind,))
+
+
 class Engine:
     """One HIP context (device + stream).  By default it rides on torch's current stream so that
     torch.cuda.Event timing and tensor lifetimes line up with the kernels."""
@@ -34,6 +72,7 @@ class Engine:
         self.lib = lib or load_library()
         self.device = int(device)
         torch.cuda.set_device(self.device)
+        self.tensor_device = torch.device("cuda", self.device)  # where every tensor argument must live (tensor)
         # The C context launches on an explicit stream.  Use torch's current stream when it is a
         # real one; the legacy null stream cannot be named through a pointer, so in that case the
         # engine owns a torch side stream and orders it against the caller's stream around every
@@ -58,6 +97,105 @@ class Engine:
     def _exit(self, cur):
         if cur.cuda_stream != self.stream.cuda_stream:
             cur.wait_stream(self.stream)
+
+    # ---- the one check of a tensor argument ---------------------------------------------------
+    def tensor(self, name, t, dtypes, extent=0, dims=None, shape=None, rows_in_place=False, contiguous=False, memo=None):
+        """The C ABI takes raw pointers, so what a tensor is gets checked here, before any library call: dtype (one or several),
+        device (this engine's), rank (`dims`) or shape (None: any size), strides - rows_in_place: stride(-1) == 1, the rows are read
+        or written where they lie; contiguous: the C call has no stride to give - and extent: the elements the run touches from
+        data_ptr() (run_extent) against the tensor's own span (tensor_span).  ValueError names the argument, the need and the given.
+        memo: a plan's dict.  The verdict depends on the tensor's shape, strides, dtype and device alone (the rules of one argument
+        of one plan never change), so a run that is handed the same layout again - a training loop's every step - skips the rest."""
+        torch = self.torch
+        if not torch.is_tensor(t):
+            raise ValueError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
+        if memo is not None:
+            key = (t.shape, t.stride(), t.dtype, t.device)
+            if memo.get(name) == key:
+                return t
+        dtypes = tuple(dtypes) if isinstance(dtypes, (tuple, list)) else (dtypes,)
+        if t.dtype not in dtypes:
+            raise ValueError("%s: dtype %s is needed, got %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+        if t.device != self.tensor_device:
+            raise ValueError("%s: a tensor on the engine's device %s is needed, got one on %s" % (name, self.tensor_device, t.device))
+        if dims is not None and t.dim() != dims:
+            raise ValueError("%s: %d dimensions are needed, got shape %s" % (name, dims, tuple(t.shape)))
+        if shape is not None and (t.dim() != len(shape) or any(w is not None and int(w) != int(g) for w, g in zip(shape, t.shape))):
+            raise ValueError("%s: shape [%s] is needed, got %s" % (name, ", ".join("*" if w is None else str(int(w)) for w in shape),
+                                                                 tuple(t.shape)))
+        if rows_in_place and t.dim() and int(t.shape[-1]) > 1 and t.stride(-1) != 1:
+            raise ValueError("%s: stride(-1) == 1 is needed (its rows are read or written where they lie); got strides %s - pass "
+                             "%s.contiguous() if a copy is intended" % (name, tuple(t.stride()), name))
+        if contiguous and not t.is_contiguous():
+            raise ValueError("%s: a contiguous tensor is needed (the C call takes no strides for it); got shape %s with strides %s - "
+                             "pass %s.contiguous() if a copy is intended" % (name, tuple(t.shape), tuple(t.stride()), name))
+        if tensor_span(t) < extent:
+            raise ValueError("%s: the run touches %d elements from data_ptr(), the tensor spans %d (shape %s, strides %s)"
+                             % (name, extent, tensor_span(t), tuple(t.shape), tuple(t.stride())))
+        if memo is not None:
+            memo[name] = key
+        return t
+
+    def state_tensor(self, state, streams, channels, memo=None):
+        """state: None, or the contiguous int32 [streams * channels, 10] table of AADHipLaneState records a run reads and writes"""
+        if state is not None:
+            lanes = int(streams) * int(channels)
+            self.tensor("state", state, self.torch.int32, run_extent("state", rows=streams, channels=channels), shape=(lanes, 10),
+                        contiguous=True, memo=memo)
+        return state
+
+    def planar_input(self, what, name, x, param, num_samples, shortest=1):
+        """x: the int16 or float32 [N, C, T] view a planar entry point reads in place; num_samples: per-row lengths in
+        [shortest, T], default T -> (N, C, T, lengths)"""
+        torch = self.torch
+        self.tensor(name, x, (torch.int16, torch.float32), dims=3, rows_in_place=True)
+        n, ch, t = (int(v) for v in x.shape)
+        if param is not None and ch != param.num_channels:
+            raise ValueError("%s: %s has %d channels, the parameter %d" % (what, name, ch, param.num_channels))
+        lengths = np.full(n, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
+        if len(lengths) != n or (n and (lengths.min() < shortest or lengths.max() > t)):
+            raise ValueError("num_samples: %d lengths in [%d, %d]" % (n, shortest, t))
+        if ch > 1 and n and x.stride(1) < int(lengths.max()):
+            raise ValueError("%s: %s has channel stride %d (stride(1)) below its longest row of %d samples - the channels' rows would "
+                             "overlap; pass %s.contiguous() if a copy is intended" % (what, name, x.stride(1), int(lengths.max()), name))
+        return n, ch, t, lengths
+
+    def window_table(self, windows, ordered):
+        """windows: int64 [N, 2] of (stream, first_frame) on the device -> the contiguous table the C call takes.
+        A non-contiguous one is copied.  The copy is a temporary that goes back to torch's caching allocator when the run
+        returns, while the kernel may not have read it yet.  With ordered=True that is safe: the allocator hands a block out again
+        to work on the stream it was allocated on, torch's current stream, and _exit has made that stream wait for the engine's, so
+        whatever reuses the block is queued behind the kernel.  With ordered=False nothing orders the two streams and the
+        kernel could read a table that has been handed out again: refused, the caller keeps a contiguous table alive."""
+        self.tensor("windows", windows, self.torch.int64, shape=(None, 2))
+        if not windows.is_contiguous():
+            if not ordered:
+                raise ValueError("windows: a contiguous tensor is needed with ordered=False (a temporary copy could be freed and "
+                                 "reused while the kernel still reads it); got strides %s - keep windows.contiguous() alive until "
+                                 "the run is done" % (tuple(windows.stride()),))
+            windows = windows.contiguous()
+        return windows
+
+    def interleaved_input(self, what, pcm, param):
+        """pcm: the contiguous int16 [streams, samples, channels] tensor of the uniform entry points -> (streams, samples, channels).
+        The interleaved C calls take one offset per stream and no stride, so a view cannot be read in place."""
+        self.tensor("pcm", pcm, self.torch.int16, dims=3, contiguous=True)
+        streams, samples, ch = (int(v) for v in pcm.shape)
+        if ch != param.num_channels:
+            raise ValueError("%s: pcm has %d channels, the parameter %d" % (what, ch, param.num_channels))
+        return streams, samples, ch
+
+    def image_rows(self, name, data, image_sizes):
+        """data: uint8 [streams, pitch] whose rows start with an image each, read in place -> the per-row image sizes (uint64)"""
+        self.tensor(name, data, self.torch.uint8, dims=2, rows_in_place=True)
+        s, width = int(data.shape[0]), int(data.shape[1])
+        if s == 0:
+            raise ValueError("%s: at least one image is needed (the format comes from the headers), got shape %s" % (name, tuple(data.shape)))
+        sizes = np.broadcast_to(np.asarray(image_sizes, dtype=np.uint64).reshape(-1), (s,))
+        if int(sizes.max()) > width:
+            raise ValueError("%s: an image of %d bytes is needed in every row, the rows have %d (shape %s)"
+                             % (name, int(sizes.max()), width, tuple(data.shape)))
+        return sizes
 
     def close(self):
         if self._ctx:
@@ -155,7 +293,7 @@ class Engine:
         _check("AADHip_PlanarEncodePlanCreate",
                self.lib.AADHip_PlanarEncodePlanCreate(self._ctx, C.byref(param), C.byref(layout), C.byref(seg) if seg is not None else None,
                                                       len(descs), descs.ctypes.data, C.byref(plan)))
-        p = PlanarEncodePlan(self, plan, param, descs, dtype)
+        p = PlanarEncodePlan(self, plan, param, descs, dtype, int(channel_stride))
         p.segmented = segment_blocks is not None
         return p
 
@@ -177,7 +315,8 @@ class Engine:
                self.lib.AADHip_PlanarReconstructPlanCreate(self._ctx, C.byref(param), C.byref(layout), C.byref(output),
                                                            C.byref(seg) if seg is not None else None, len(descs), descs.ctypes.data,
                                                            C.byref(plan)))
-        p = PlanarReconstructPlan(self, plan, param, descs, dtype, out_dtype)
+        p = PlanarReconstructPlan(self, plan, param, descs, dtype, out_dtype, int(channel_stride), int(out_stream_stride),
+                                  int(out_channel_stride))
         p.segmented = segment_blocks is not None
         return p
 
@@ -197,7 +336,7 @@ class Engine:
                self.lib.AADHip_WindowReconstructPlanCreate(self._ctx, C.byref(param), C.byref(layout),
                                                            C.byref(seg) if seg is not None else None, len(source_table),
                                                            source_table.ctypes.data, C.byref(plan)))
-        p = WindowReconstructPlan(self, plan, param, source_table, dtype)
+        p = WindowReconstructPlan(self, plan, param, source_table, dtype, int(channel_stride))
         p.segmented = segment_blocks is not None
         return p
 
@@ -295,8 +434,8 @@ class Engine:
         torch = self.torch
         if state is not None and segment_blocks is not None:
             raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
-        streams, samples, ch = pcm.shape
-        assert ch == param.num_channels and pcm.dtype == torch.int16 and pcm.is_contiguous()
+        streams, samples, ch = self.interleaved_input("encode_uniform", pcm, param)
+        self.state_tensor(state, streams, ch)
         plan = self.uniform_encode_plan(param, streams, samples, segment_blocks, warmup_blocks)
         out = torch.zeros((streams, plan.stride), dtype=torch.uint8, device=pcm.device)
         plan.run(pcm, out, state)
@@ -310,17 +449,8 @@ class Engine:
         torch = self.torch
         if state is not None and segment_blocks is not None:
             raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
-        if x.dim() != 3 or not x.is_cuda or x.dtype not in (torch.int16, torch.float32):
-            raise ValueError("encode_planar takes an int16 or float32 cuda tensor [N, C, T]")
-        n, ch, t = (int(v) for v in x.shape)
-        if ch != param.num_channels:
-            raise ValueError("x has %d channels, the parameter %d" % (ch, param.num_channels))
-        if x.stride(-1) != 1:
-            raise ValueError("encode_planar needs x.stride(-1) == 1 (each channel's samples contiguous); got strides %s - pass "
-                             "x.contiguous() if a copy is intended" % (tuple(x.stride()),))
-        lengths = np.full(n, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
-        if len(lengths) != n or (n and (lengths.min() < 1 or lengths.max() > t)):
-            raise ValueError("num_samples: %d lengths in [1, %d]" % (n, t))
+        n, ch, t, lengths = self.planar_input("encode_planar", "x", x, param, num_samples)
+        self.state_tensor(state, n, ch)
         sizes = np.array([self.encoded_size(param, int(v)) for v in lengths], dtype=np.uint64)
         if n and sizes.min() == 0:
             raise ApiError("AADHip_CalculateEncodedSize", AADApiResult.INVALID_FORMAT)
@@ -345,18 +475,10 @@ class Engine:
         lie on 64-byte boundaries.  One planar encode plan per value of bits that occurs, its descriptor table naming that value's
         rows where they are: no gather of x."""
         torch = self.torch
-        if x.dim() != 3 or not x.is_cuda or x.dtype not in (torch.int16, torch.float32):
-            raise ValueError("encode_planar_mixed takes an int16 or float32 cuda tensor [N, C, T]")
-        n, ch, t = (int(v) for v in x.shape)
-        if x.stride(-1) != 1:
-            raise ValueError("encode_planar_mixed needs x.stride(-1) == 1 (each channel's samples contiguous); got strides %s"
-                             % (tuple(x.stride()),))
+        n, ch, t, lengths = self.planar_input("encode_planar_mixed", "x", x, None, num_samples)  # the channels: per parameter, below
         bits = (bits.detach().cpu().numpy() if isinstance(bits, torch.Tensor) else np.asarray(bits)).astype(np.int64).reshape(-1)
         if len(bits) != n or not np.isin(bits, (2, 3, 4)).all():
             raise ValueError("bits: %d values of 2, 3 or 4" % n)
-        lengths = np.full(n, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
-        if len(lengths) != n or (n and (lengths.min() < 1 or lengths.max() > t)):
-            raise ValueError("num_samples: %d lengths in [1, %d]" % (n, t))
         params = {int(b): make_param(int(b)) for b in np.unique(bits)}
         for b, param in params.items():
             if param.num_channels != ch or param.bits_per_sample != b:
@@ -414,18 +536,9 @@ class Engine:
         torch = self.torch
         if state is not None and segment_blocks is not None:
             raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
-        if x.dim() != 3 or not x.is_cuda or x.dtype not in (torch.int16, torch.float32):
-            raise ValueError("%s takes an int16 or float32 cuda tensor [N, C, T]" % what)
+        n, ch, t, lengths = self.planar_input(what, "x", x, param, num_samples)
+        self.state_tensor(state, n, ch)
         dtype = x.dtype if dtype is None else dtype
-        n, ch, t = (int(v) for v in x.shape)
-        if ch != param.num_channels:
-            raise ValueError("x has %d channels, the parameter %d" % (ch, param.num_channels))
-        if x.stride(-1) != 1:
-            raise ValueError("%s needs x.stride(-1) == 1 (each channel's samples contiguous); got strides %s - pass "
-                             "x.contiguous() if a copy is intended" % (what, tuple(x.stride())))
-        lengths = np.full(n, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
-        if len(lengths) != n or (n and (lengths.min() < 1 or lengths.max() > t)):
-            raise ValueError("num_samples: %d lengths in [1, %d]" % (n, t))
         sizes = np.array([self.encoded_size(param, int(v)) for v in lengths], dtype=np.uint64)
         if n and sizes.min() == 0:
             raise ApiError("AADHip_CalculateEncodedSize", AADApiResult.INVALID_FORMAT)
@@ -468,17 +581,8 @@ class Engine:
     def _reconstruct_windows(self, what, corpus, windows, frames, param, dtype, num_samples, segment_blocks, warmup_blocks, rows,
                              return_images, return_stats):
         torch = self.torch
-        if corpus.dim() != 3 or not corpus.is_cuda or corpus.dtype not in (torch.int16, torch.float32):
-            raise ValueError("%s takes an int16 or float32 cuda tensor [S, C, T_total]" % what)
-        s, ch, t = (int(v) for v in corpus.shape)
-        if ch != param.num_channels:
-            raise ValueError("the corpus has %d channels, the parameter %d" % (ch, param.num_channels))
-        if corpus.stride(-1) != 1:
-            raise ValueError("%s needs corpus.stride(-1) == 1 (each channel's samples contiguous); got strides %s"
-                             % (what, tuple(corpus.stride())))
-        lengths = np.full(s, t, dtype=np.int64) if num_samples is None else np.asarray(num_samples, dtype=np.int64).reshape(-1)
-        if len(lengths) != s or (s and (lengths.min() < 0 or lengths.max() > t)):
-            raise ValueError("num_samples: %d lengths in [0, %d]" % (s, t))
+        s, ch, t, lengths = self.planar_input(what, "corpus", corpus, param, num_samples, shortest=0)
+        self.tensor("windows", windows, torch.int64, shape=(None, 2))
         d = np.zeros(s, dtype=STREAM_DESC_DTYPE)
         d["pcm_offset"] = np.arange(s, dtype=np.uint64) * np.uint64(corpus.stride(0))
         d["num_samples"] = lengths
@@ -496,11 +600,13 @@ class Engine:
         return result[0] if len(result) == 1 else tuple(result)
 
     def decode_uniform(self, data, image_size):
-        """data: uint8 cuda tensor [streams, stride] of same-format images -> int16 [streams, samples, channels]"""
+        """data: uint8 cuda tensor [streams, pitch] of same-format images, image_size <= pitch bytes each; a view is fine as long as
+        data.stride(1) == 1: row i is read where it lies, at i * data.stride(0) -> int16 [streams, samples, channels]"""
         torch = self.torch
+        self.image_rows("data", data, image_size)
         head = bytes(data[0, :31].cpu().numpy())
         header = parse_header(head)
-        plan = self.uniform_decode_plan(header, data.shape[0], data.shape[1], image_size)
+        plan = self.uniform_decode_plan(header, data.shape[0], data.stride(0), image_size)  # the row pitch: the view's, not its width
         pcm = torch.zeros((data.shape[0], header.num_samples, header.num_channels), dtype=torch.int16, device=data.device)
         plan.run(data, pcm)
         return pcm, header
@@ -513,14 +619,16 @@ class Engine:
         return self.window_decode_plan(header, d, True)
 
     def decode_windows(self, data, image_size, windows, frames, dtype=None, return_stats=False):
-        """data: uint8 cuda tensor [streams, stride] of same-format images (encode_uniform's output); windows: int64 cuda tensor
+        """data: uint8 cuda tensor [streams, pitch] of same-format images (encode_uniform's output, or a view of it with
+        data.stride(1) == 1: row i is read where it lies, at i * data.stride(0)); windows: int64 cuda tensor
         [N, 2] of (stream, first_frame) -> [N, channels, frames] tensor of `dtype` (torch.float32 = sample / 32768, torch.int16, or
         torch.float16 / torch.bfloat16 = the float32 row rounded to nearest even).
         The header is read once, from the first image; the windows are never read on the host.
         return_stats: -> (rows, int64 [N, channels, 4] level statistics of the rows), see WindowDecodePlan.run."""
+        self.image_rows("data", data, image_size)
         head = bytes(data[0, :31].cpu().numpy())
         header = parse_header(head)
-        plan = self.uniform_window_decode_plan(header, data.shape[0], data.shape[1], image_size)
+        plan = self.uniform_window_decode_plan(header, data.shape[0], data.stride(0), image_size)  # the view's row pitch
         try:
             return plan.run(data, windows, frames, dtype, stats=True if return_stats else None)
         finally:
@@ -550,12 +658,8 @@ class Engine:
 
     def _corpus_window_plan(self, data, image_sizes, channels):
         """the window decode plan over the images in the rows of `data`: mixed-format, or channel-mix when `channels` is given"""
-        if data.dim() != 2 or not data.is_cuda or data.dtype != self.torch.uint8 or data.stride(1) != 1:
-            raise ValueError("data: a uint8 cuda tensor [streams, stride]")
+        sizes = self.image_rows("data", data, image_sizes)
         s = int(data.shape[0])
-        if s == 0:
-            raise ValueError("decode_windows_mixed needs at least one image (the channel count comes from the headers)")
-        sizes = np.broadcast_to(np.asarray(image_sizes, dtype=np.uint64).reshape(-1), (s,))
         if int(data.shape[1]) < 31:
             raise ApiError("parse_header", AADApiResult.INVALID_FORMAT)
         heads = data[:, :31].cpu().numpy()
@@ -574,8 +678,7 @@ class Engine:
         the comparison run back to back on the device; the images stay in a scratch tensor.
         segment_blocks / warmup_blocks: over the images of a segmented encode (see encode_plan)."""
         torch = self.torch
-        streams, samples, ch = pcm.shape
-        assert ch == param.num_channels and pcm.dtype == torch.int16 and pcm.is_contiguous()
+        streams, samples, ch = self.interleaved_input("reconstruct_uniform", pcm, param)
         size = self.encoded_size(param, samples)
         if size == 0:
             raise ApiError("AADHip_CalculateEncodedSize", AADApiResult.INVALID_FORMAT)
@@ -614,7 +717,7 @@ class Engine:
         ERROR_STATS_DTYPE array [streams] or None) through AADHip_ReconstructBatch, or with segment_blocks
         AADHip_SegmentedReconstructBatch (the images of a segmented encode, see encode_plan)."""
         n = len(pcm_list)
-        pcm_list = [np.ascontiguousarray(p, dtype=np.int16) for p in pcm_list]
+        pcm_list = _host_pcm("reconstruct_host", pcm_list, param)
         nsamp = np.array([p.shape[0] for p in pcm_list], dtype=np.uint32)
         outs = [np.zeros_like(p) for p in pcm_list] if want_pcm else None
         stats = np.zeros(n, dtype=ERROR_STATS_DTYPE) if want_stats else None
@@ -640,7 +743,12 @@ class Engine:
         if state is not None and segment_blocks is not None:
             raise ValueError("a segmented encode starts from fresh encoders: state and segment_blocks exclude each other")
         n = len(pcm_list)
-        pcm_list = [np.ascontiguousarray(p, dtype=np.int16) for p in pcm_list]
+        pcm_list = _host_pcm("encode_host", pcm_list, param)
+        if state is not None and (not isinstance(state, np.ndarray) or state.dtype != LANE_STATE_DTYPE or state.ndim != 1
+                                  or len(state) != n * param.num_channels or not state.flags["C_CONTIGUOUS"]):
+            raise ValueError("encode_host: state: a contiguous LANE_STATE_DTYPE array [%d] (streams * channels) is needed, got %s"
+                             % (n * param.num_channels, "%s %s" % (state.dtype, state.shape) if isinstance(state, np.ndarray)
+                                else type(state).__name__))
         nsamp = np.array([p.shape[0] for p in pcm_list], dtype=np.uint32)
         caps = np.array([max(self.encoded_size(param, int(s)), 64) for s in nsamp], dtype=np.uint64)
         outs = [np.zeros(int(c), dtype=np.uint8) for c in caps]
@@ -673,6 +781,20 @@ class Engine:
         _check("AADHip_DecodeBatch",
                self.lib.AADHip_DecodeBatch(self._ctx, n, dp, sizes.ctypes.data, pp, caps.ctypes.data, got.ctypes.data))
         return pcms
+
+
+def _host_pcm(what, pcm_list, param):
+    """the host entry points' input: int16 arrays [samples, channels] of the parameter's channel count (mono: 1-D is fine too),
+    contiguous - the C call reads samples * channels values behind each pointer"""
+    ch = int(param.num_channels)
+    out = []
+    for i, p in enumerate(pcm_list):
+        p = np.ascontiguousarray(p, dtype=np.int16)
+        if not ((p.ndim == 2 and p.shape[1] == ch) or (p.ndim == 1 and ch == 1)):
+            raise ValueError("%s: pcm_list[%d]: an array [samples, %d] is needed (the parameter's channels%s), got shape %s"
+                             % (what, i, ch, "; mono may be 1-D" if ch == 1 else "", p.shape))
+        out.append(p)
+    return out
 
 
 def _stats_f64(stats):
@@ -723,13 +845,26 @@ class EncodePlan:
         self.engine, self.handle, self.param, self.descs = engine, handle, param, descs
         self.image_size = self.stride = None
         self.segmented = False
+        self._extents, self._memo = {}, {}  # per run argument: the elements a run touches; the layout that passed the check last
+
+    def extent(self, kind, **layout):
+        """run_extent of this plan's table, computed once (the table never changes)"""
+        if kind not in self._extents:
+            self._extents[kind] = run_extent(kind, self.descs, self.param.num_channels, **layout)
+        return self._extents[kind]
 
     def run(self, pcm, data, state=None, ordered=True):
-        """pcm: int16 cuda tensor, data: uint8 cuda tensor, state: int32 cuda tensor [lanes, 10] or None.
+        """pcm: int16 cuda tensor that holds every stream's frames at its pcm_offset, data: uint8 cuda tensor that holds every
+        image's data_size bytes at its data_offset (both counted from data_ptr(), stride(-1) == 1), state: int32 cuda tensor
+        [lanes, 10] or None.
         ordered=False: launch on the engine's stream without ordering it against torch's current stream
         (the caller orders the streams itself, with events - see bench.py's pipelined step)."""
         if state is not None and self.segmented:
             raise ValueError("a segmented encode plan takes no state")
+        e = self.engine
+        e.tensor("pcm", pcm, e.torch.int16, self.extent("interleaved"), rows_in_place=True, memo=self._memo)
+        e.tensor("data", data, e.torch.uint8, self.extent("images"), rows_in_place=True, memo=self._memo)
+        e.state_tensor(state, len(self.descs), self.param.num_channels, self._memo)
         sp = state.data_ptr() if state is not None else None
         cur = self.engine._enter() if ordered else None
         _check("AADHip_EncodePlanRun",
@@ -750,17 +885,19 @@ class EncodePlan:
 
 
 class PlanarEncodePlan(EncodePlan):
-    def __init__(self, engine, handle, param, descs, dtype):
+    def __init__(self, engine, handle, param, descs, dtype, channel_stride):
         super().__init__(engine, handle, param, descs)
-        self.dtype = dtype
+        self.dtype, self.channel_stride = dtype, channel_stride
 
     def run(self, x, data, state=None, ordered=True):
-        """x: cuda tensor of the plan's dtype whose data_ptr() the table's pcm_offsets count from (elements), data: uint8 cuda
-        tensor, state: int32 cuda tensor [lanes, 10] or None; ordered as EncodePlan.run"""
-        if x.dtype != self.dtype or not x.is_cuda:
-            raise ValueError("this plan reads %s cuda rows, not %s" % (self.dtype, x.dtype))
+        """x: cuda tensor of the plan's dtype whose data_ptr() the table's pcm_offsets count from (elements; it spans every row the
+        table names), data: uint8 cuda tensor, state: int32 cuda tensor [lanes, 10] or None; ordered as EncodePlan.run"""
         if state is not None and self.segmented:
             raise ValueError("a segmented encode plan takes no state")
+        e = self.engine
+        e.tensor("x", x, self.dtype, self.extent("planar", channel_stride=self.channel_stride), rows_in_place=True, memo=self._memo)
+        e.tensor("data", data, e.torch.uint8, self.extent("images"), rows_in_place=True, memo=self._memo)
+        e.state_tensor(state, len(self.descs), self.param.num_channels, self._memo)
         sp = state.data_ptr() if state is not None else None
         cur = self.engine._enter() if ordered else None
         _check("AADHip_PlanarEncodePlanRun",
@@ -770,28 +907,29 @@ class PlanarEncodePlan(EncodePlan):
 
 
 class PlanarReconstructPlan(EncodePlan):
-    def __init__(self, engine, handle, param, descs, dtype, out_dtype):
+    def __init__(self, engine, handle, param, descs, dtype, out_dtype, channel_stride, out_stream_stride, out_channel_stride):
         super().__init__(engine, handle, param, descs)
-        self.dtype, self.out_dtype = dtype, out_dtype
+        self.dtype, self.out_dtype, self.channel_stride = dtype, out_dtype, channel_stride
+        self.out_stream_stride, self.out_channel_stride = out_stream_stride, out_channel_stride
 
     def run(self, x, data, out, state=None, ordered=True, stats=None):
         """x: cuda rows of the plan's dtype (the table's pcm_offsets count from x.data_ptr()), data: uint8 cuda tensor for the images,
         out: cuda tensor of the plan's out_dtype (the output strides count from out.data_ptr()), state as EncodePlan.run.
         stats: a contiguous int64 cuda tensor [N, C, 4] that the same run fills with the rows' error statistics
         (AADHip_PlanarReconstructPlanRunStats; its contents before the run do not matter); with it, out=None writes no rows."""
-        if x.dtype != self.dtype or not x.is_cuda:
-            raise ValueError("this plan reads %s cuda rows, not %s" % (self.dtype, x.dtype))
         if out is None and stats is None:
             raise ValueError("out=None needs stats")
-        if out is not None and (out.dtype != self.out_dtype or not out.is_cuda):
-            raise ValueError("this plan writes %s cuda rows, not %s" % (self.out_dtype, out.dtype))
-        if stats is not None:
-            torch = self.engine.torch
-            shape = (len(self.descs), self.param.num_channels, 4)
-            if stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous() or tuple(stats.shape) != shape:
-                raise ValueError("stats: a contiguous int64 cuda tensor %s" % (shape,))
         if state is not None and self.segmented:
             raise ValueError("a segmented encode plan takes no state")
+        e, n, ch = self.engine, len(self.descs), self.param.num_channels
+        e.tensor("x", x, self.dtype, self.extent("planar", channel_stride=self.channel_stride), rows_in_place=True, memo=self._memo)
+        e.tensor("data", data, e.torch.uint8, self.extent("images"), rows_in_place=True, memo=self._memo)
+        if out is not None:
+            e.tensor("out", out, self.out_dtype, self.extent("planar_out", stream_stride=self.out_stream_stride,
+                                                             channel_stride=self.out_channel_stride), rows_in_place=True, memo=self._memo)
+        if stats is not None:
+            e.tensor("stats", stats, e.torch.int64, self.extent("stats", rows=n), shape=(n, ch, 4), contiguous=True, memo=self._memo)
+        e.state_tensor(state, n, ch, self._memo)
         sp = state.data_ptr() if state is not None else None
         cur = self.engine._enter() if ordered else None
         if stats is not None:
@@ -806,9 +944,9 @@ class PlanarReconstructPlan(EncodePlan):
 
 
 class WindowReconstructPlan(EncodePlan):
-    def __init__(self, engine, handle, param, source_table, dtype):
+    def __init__(self, engine, handle, param, source_table, dtype, channel_stride):
         super().__init__(engine, handle, param, source_table)
-        self.dtype = dtype
+        self.dtype, self.channel_stride = dtype, channel_stride
 
     def run(self, x, windows, frames, out=None, dtype=None, data=None, stats=None, ordered=True):
         """x: the corpus, a cuda tensor of the plan's dtype (the source table's pcm_offsets count from x.data_ptr()); windows: int64
@@ -817,34 +955,29 @@ class WindowReconstructPlan(EncodePlan):
         torch.int16 or torch.float32 cuda tensor [N, C, T] with out.stride(-1) == 1, written in place, every element of it.
         data: None (the images stay in the engine's scratch) or a uint8 cuda tensor [N, stride >= the image of T frames];
         stats: None or a contiguous int64 cuda tensor [N, C, 4].  At least one of the three.  ordered as EncodePlan.run."""
-        torch = self.engine.torch
-        if x.dtype != self.dtype or not x.is_cuda:
-            raise ValueError("this plan reads %s cuda rows, not %s" % (self.dtype, x.dtype))
-        if windows.dtype != torch.int64 or windows.dim() != 2 or windows.shape[1] != 2 or not windows.is_cuda:
-            raise ValueError("windows: an int64 cuda tensor [N, 2] of (stream, first_frame)")
-        windows = windows.contiguous()
+        e, torch = self.engine, self.engine.torch
+        e.tensor("x", x, self.dtype, self.extent("planar", channel_stride=self.channel_stride), rows_in_place=True)
+        windows = e.window_table(windows, ordered)
         n, ch, frames = int(windows.shape[0]), int(self.param.num_channels), int(frames)
         if out is None:
             out = torch.empty((n, ch, frames), dtype=self.dtype if dtype is None else dtype, device=windows.device)
         elif out is False:
             out = None
-        if out is not None:
-            if out.dtype not in (torch.int16, torch.float32) or (dtype is not None and out.dtype != dtype) or not out.is_cuda or \
-                    tuple(out.shape) != (n, ch, frames) or (frames > 1 and out.stride(-1) != 1):
-                raise ValueError("out: a torch.int16 or torch.float32 cuda tensor [%d, %d, %d] with stride(-1) == 1" % (n, ch, frames))
+        if out is not None:  # its own strides go to the library, so its own span is what the run writes
+            e.tensor("out", out, (torch.int16, torch.float32), shape=(n, ch, frames), rows_in_place=True)
+            if dtype is not None and out.dtype != dtype:
+                raise ValueError("out: dtype %s was asked for, the tensor has %s" % (dtype, out.dtype))
         if out is None and data is None and stats is None:
             raise ValueError("nothing to write: out, data and stats are all absent")
         image_stride = 0
         if data is not None:
-            if data.dtype != torch.uint8 or not data.is_cuda or data.dim() != 2 or int(data.shape[0]) != n or (n and data.stride(1) != 1):
-                raise ValueError("data: a uint8 cuda tensor [%d, stride]" % n)
-            if int(data.shape[1]) < self.engine.encoded_size(self.param, frames):
+            e.tensor("data", data, torch.uint8, shape=(n, None), rows_in_place=True)
+            if int(data.shape[1]) < e.encoded_size(self.param, frames):
                 raise ValueError("data: rows of %d bytes, the image of %d frames has %d"
-                                 % (int(data.shape[1]), frames, self.engine.encoded_size(self.param, frames)))
+                                 % (int(data.shape[1]), frames, e.encoded_size(self.param, frames)))
             image_stride = int(data.stride(0))
-        if stats is not None and (stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous() or
-                                  tuple(stats.shape) != (n, ch, 4)):
-            raise ValueError("stats: a contiguous int64 cuda tensor %s" % ((n, ch, 4),))
+        if stats is not None:
+            e.tensor("stats", stats, torch.int64, run_extent("stats", rows=n, channels=ch), shape=(n, ch, 4), contiguous=True)
         output = None
         if out is not None:
             output = AADHipPlanarOutput(SAMPLE_FLOAT32 if out.dtype == torch.float32 else SAMPLE_INT16, 0,
@@ -868,8 +1001,16 @@ class WindowReconstructPlan(EncodePlan):
 class DecodePlan:
     def __init__(self, engine, handle, header, descs):
         self.engine, self.handle, self.header, self.descs = engine, handle, header, descs
+        self._memo = {}
+        self.data_extent = run_extent("images", descs)
+        self.pcm_extent = run_extent("interleaved", descs, header.num_channels)
 
     def run(self, data, pcm, ordered=True):
+        """data: uint8 cuda tensor that holds every image's data_size bytes at its data_offset, pcm: int16 cuda tensor that holds
+        every stream's num_samples frames at its pcm_offset (both counted from data_ptr(), stride(-1) == 1); ordered as EncodePlan.run"""
+        e = self.engine
+        e.tensor("data", data, e.torch.uint8, self.data_extent, rows_in_place=True, memo=self._memo)
+        e.tensor("pcm", pcm, e.torch.int16, self.pcm_extent, rows_in_place=True, memo=self._memo)
         cur = self.engine._enter() if ordered else None
         _check("AADHip_DecodePlanRun",
                self.engine.lib.AADHip_DecodePlanRun(self.handle, data.data_ptr(), pcm.data_ptr()))
@@ -891,6 +1032,8 @@ class DecodePlan:
 class WindowDecodePlan:
     def __init__(self, engine, handle, header, descs):
         self.engine, self.handle, self.header, self.descs = engine, handle, header, descs
+        self._memo = {}
+        self.data_extent = run_extent("images", descs)
 
     def run(self, data, windows, frames, dtype=None, out=None, ordered=True, stats=None, rows=True):
         """data: uint8 cuda tensor of the images; windows: int64 cuda tensor [N, 2] of (stream, first_frame) ->
@@ -906,9 +1049,9 @@ class WindowDecodePlan:
         kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
         if dtype not in kinds:
             raise ValueError("window decode writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % dtype)
-        if windows.dtype != torch.int64 or windows.dim() != 2 or windows.shape[1] != 2 or not windows.is_cuda:
-            raise ValueError("windows: an int64 cuda tensor [N, 2] of (stream, first_frame)")
-        windows = windows.contiguous()
+        e = self.engine
+        e.tensor("data", data, torch.uint8, self.data_extent, rows_in_place=True, memo=self._memo)
+        windows = e.window_table(windows, ordered)
         n, ch, frames = int(windows.shape[0]), int(self.header.num_channels), int(frames)
         if stats is None or stats is False:
             stats = None
@@ -916,18 +1059,16 @@ class WindowDecodePlan:
                 raise ValueError("rows=False is a statistics-only run: pass stats=True or a table")
         elif stats is True:
             stats = torch.empty((n, ch, 4), dtype=torch.int64, device=windows.device)
-        elif (not torch.is_tensor(stats) or stats.dtype != torch.int64 or tuple(stats.shape) != (n, ch, 4) or not stats.is_cuda
-              or not stats.is_contiguous()):
-            raise ValueError("stats: True or a contiguous cuda int64 tensor [%d, %d, 4]" % (n, ch))
-        elif stats.device != windows.device:
-            raise ValueError("stats: on %s, the windows are on %s" % (stats.device, windows.device))
+        else:
+            e.tensor("stats", stats, torch.int64, run_extent("stats", rows=n, channels=ch), shape=(n, ch, 4), contiguous=True)
         if not rows:
             if out is not None:
                 raise ValueError("rows=False writes no rows: pass no `out`")
         elif out is None:
             out = torch.empty((n, ch, frames), dtype=dtype, device=windows.device)
-        elif out.dtype != dtype or tuple(out.shape) != (n, ch, frames) or not out.is_contiguous() or out.device != windows.device:
-            raise ValueError("out: a contiguous %s tensor [%d, %d, %d] on %s" % (dtype, n, ch, frames, windows.device))
+        else:
+            e.tensor("out", out, dtype, run_extent("window_rows", rows=n, channels=ch, frames=frames), shape=(n, ch, frames),
+                     contiguous=True)
         kind = kinds[dtype]
         cur = self.engine._enter() if ordered else None
         if stats is None:
@@ -1101,7 +1242,7 @@ class EncodeDecodePipeline:
         self.enc.run(zero, self.images[0])
         torch.cuda.synchronize()
         self.header = parse_header(bytes(self.images[0][0, :31].cpu().numpy()))
-        self.dec = dec_engine.uniform_decode_plan(self.header, streams, self.enc.stride, self.enc.image_size)
+        self.dec = dec_engine.uniform_decode_plan(self.header, streams, self.images[0].stride(0), self.enc.image_size)
         self.encoded = [HipEvent() for _ in range(ring)]
         self.decoded = [torch.cuda.Event() for _ in range(ring)]
 
@@ -1157,4 +1298,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "select_least_bits"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "select_least_bits", "run_extent", "tensor_span"]
