@@ -73,6 +73,7 @@ ERROR_STATS_DTYPE = np.dtype([("rms_error", "<f8"), ("mean_abs_error", "<f8"), (
 WINDOW_DTYPE = np.dtype([("stream", "<i8"), ("first_frame", "<i8")])  # struct AADHipWindow: an int64 pair, a torch int64 [N, 2] row
 SAMPLE_INT16, SAMPLE_FLOAT32 = 0, 1  # enum AADHipSampleType
 SAMPLE_FLOAT16, SAMPLE_BFLOAT16 = 4, 5  # window decode rows alone (WindowDecodePlan.run)
+WINDOW_GAIN_STORE, WINDOW_GAIN_ADD = 0, 1  # enum AADHipWindowGainMode (WindowDecodePlan.run with gain / accumulate)
 RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL = 0, 1  # enum AADHipReconstructOutput
 OPTION_LANE_MAPPING, OPTION_TRIAL_LANES, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_COMPARE_ORDER = 0, 1, 2, 3, 4  # enum AADHipOption
 LANE_MAPPINGS = {"auto": 0, "dense": 1, "quad": 2, "quad-fused": 3, "dense-tiled": 4}  # enum AADHipLaneMapping
@@ -100,7 +101,7 @@ HIP_SYMBOLS = [
     "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate", "AADHip_SegmentedEncodeBatch",
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
-    "AADHip_WindowDecodePlanRunStats", "AADHip_MixedWindowDecodePlanCreate", "AADHip_ChannelMixWindowDecodePlanCreate",
+    "AADHip_WindowDecodePlanRunStats", "AADHip_WindowDecodePlanRunGain", "AADHip_MixedWindowDecodePlanCreate", "AADHip_ChannelMixWindowDecodePlanCreate",
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
     "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
     "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
@@ -217,6 +218,8 @@ def _declare_hip(lib):
     lib.AADHip_WindowDecodePlanRun.restype = C.c_int
     lib.AADHip_WindowDecodePlanRunStats.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, vp]
     lib.AADHip_WindowDecodePlanRunStats.restype = C.c_int
+    lib.AADHip_WindowDecodePlanRunGain.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, vp, C.c_int32]
+    lib.AADHip_WindowDecodePlanRunGain.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

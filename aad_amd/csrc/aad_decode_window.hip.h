@@ -83,13 +83,27 @@ struct WindowLevels<true> {
   bool store; /* false: a statistics-only run, `row` is not written (uniform over the run) */
 };
 
+/* the gain of a lane's window (AADHip_WindowDecodePlanRunGain, aad_decode_window_gain.hip.h).  Empty without GAIN. */
+template <bool GAIN>
+struct WindowGain {
+};
+template <>
+struct WindowGain<true> {
+  float g;  /* device_gain[w], 1 with a null table */
+  bool add; /* AAD_HIP_WINDOW_GAIN_ADD: the element becomes old + g * f (uniform over the run) */
+};
+
 /* one row segment of a lane: output element t = base + i for sample i of the block, kept where lo <= t < hi.
  * kMixTwin: every store goes to the row `twin` elements on as well.  kMixDown: y is L + R for the float types, (L + R) >> 1 as int16.
  * float16 / bfloat16 rows hold the bits (uint16_t): the float32 value, exact, then the one rounding of the type.
- * STATS: every kept sample is added to the lane's WindowLevels as the int16 value the row holds, zeros() adds nothing. */
-template <int ST, int MIX = kMixNone, bool STATS = false>
-struct WindowRow : WindowLevels<STATS> {
+ * STATS: every kept sample is added to the lane's WindowLevels as the int16 value the row holds, zeros() adds nothing.
+ * GAIN (the float types): with f the float32 value above, the element becomes p = fl32(g * f), under `add` fl32(old + p) - two
+ * roundings, never one fma - and then the one rounding of the type; zeros() writes g * 0 / old + g * 0 likewise.  The twin rows of
+ * kMixTwin hold different old values: each is loaded, added and stored on its own. */
+template <int ST, int MIX = kMixNone, bool STATS = false, bool GAIN = false>
+struct WindowRow : WindowLevels<STATS>, WindowGain<GAIN> {
   static_assert(ST == kRowI16 || ST == kRowF32 || ST == kRowF16 || ST == kRowBF16, "a sample type of window decode");
+  static_assert(!GAIN || (ST != kRowI16 && !STATS), "a gain is for float rows, and has no statistics variant");
   static constexpr bool F32 = ST == kRowF32, HALF = ST == kRowF16 || ST == kRowBF16;
   using T = std::conditional_t<F32, float, std::conditional_t<HALF, uint16_t, int16_t>>;
   T *row;
@@ -105,6 +119,87 @@ struct WindowRow : WindowLevels<STATS> {
     if constexpr (F32) return scaled(y);
     else if constexpr (HALF) return (T)pack_half2<ST>(scaled(y), 0.0f);
     else return (T)y;
+  }
+  /* GAIN only.  p = fl32(g * f): one multiply that no add may contract into an fma and no float16 pack into a mixed-precision
+   * one - the empty asm makes the product a float32 register value of its own */
+  __device__ __forceinline__ float gained(float f) const
+  {
+#pragma clang fp contract(off)
+    float p = this->g * f;
+    asm("" : "+v"(p));
+    return p;
+  }
+  __device__ __forceinline__ static float sum(float old, float p)
+  {
+#pragma clang fp contract(off)
+    float s = old + p;
+    asm("" : "+v"(s));
+    return s;
+  }
+  /* the float32 value of a row element / the element of a float32 value */
+  __device__ __forceinline__ static float widen(T e)
+  {
+    if constexpr (F32) return e;
+    else if constexpr (ST == kRowF16) return (float)__builtin_bit_cast(_Float16, e);
+    else return __builtin_bit_cast(float, (uint32_t)e << 16);
+  }
+  __device__ __forceinline__ static T narrow(float v)
+  {
+    if constexpr (F32) return v;
+    else return (T)pack_half2<ST>(v, 0.0f);
+  }
+  /* element *q from the float32 value f */
+  __device__ __forceinline__ void put(T *q, float f) const
+  {
+    const float p = gained(f);
+    *q = narrow(this->add ? sum(widen(*q), p) : p);
+  }
+  /* GAIN only.  The old content of a whole chunk under `add`, as the 16-byte vectors it is loaded in at the row's own alignment
+   * (float32: four, the 16-bit types: two; `twin`: the second row's under kMixTwin).  window_lane fetches it in front of the
+   * chunk's decode, so the loads are in flight while the lane decodes, and hands it to chunk() */
+  struct Old {
+    static constexpr int NV = F32 ? 4 : 2, PER = kChunk / NV; /* vectors of a chunk, elements of a vector */
+    u32x4 v[NV];
+    u32x4 twin[MIX == kMixTwin ? NV : 1];
+  };
+  __device__ __forceinline__ bool whole(int64_t t0) const { return t0 >= lo && t0 + kChunk <= hi; }
+  __device__ __forceinline__ void fetch(uint32_t i0, Old &o) const
+  {
+    const int64_t t0 = base + (int64_t)i0;
+    if (!this->add || !whole(t0)) return;
+    const T *p = row + t0;
+#pragma unroll
+    for (int q = 0; q < Old::NV; q++) {
+      o.v[q] = reinterpret_cast<const U32x4 *>(p + Old::PER * q)->v;
+      if constexpr (MIX == kMixTwin) o.twin[q] = reinterpret_cast<const U32x4 *>(p + twin + Old::PER * q)->v;
+    }
+  }
+  /* 8 elements at q from f[0 .. 7], under `add` on top of the old ones in old[0] (float32: old[0], old[1]): 16-byte stores at the
+   * row's own alignment */
+  __device__ __forceinline__ void put8(T *q, const float *f, const u32x4 *old) const
+  {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = gained(f[j]);
+    if constexpr (F32) {
+      if (this->add) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = sum(__builtin_bit_cast(float, (uint32_t)old[j / 4][j % 4]), v[j]);
+      }
+#pragma unroll
+      for (int h = 0; h < 2; h++)
+        *reinterpret_cast<f32x4_u4 *>(q + 4 * h) = f32x4_u4{v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]};
+    } else {
+      if (this->add) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          v[2 * j] = sum(widen((T)(old[0][j] & 0xFFFFu)), v[2 * j]);
+          v[2 * j + 1] = sum(widen((T)(old[0][j] >> 16)), v[2 * j + 1]);
+        }
+      }
+      store_u32x4<false>(reinterpret_cast<int16_t *>(q), u32x4{pack_half2<ST>(v[0], v[1]), pack_half2<ST>(v[2], v[3]),
+                                                               pack_half2<ST>(v[4], v[5]), pack_half2<ST>(v[6], v[7])});
+    }
   }
   /* STATS only.  The float down-mix carries L + R: its statistic is the int16 floor mix's */
   __device__ __forceinline__ void level(int32_t y)
@@ -124,15 +219,18 @@ struct WindowRow : WindowLevels<STATS> {
   {
     const int64_t t = base + (int64_t)i;
     if (t >= lo && t < hi) {
-      if (stores()) {
+      if constexpr (GAIN) {
+        put(row + t, scaled(y));
+        if constexpr (MIX == kMixTwin) put(row + t + twin, scaled(y));
+      } else if (stores()) {
         row[t] = convert(y);
         if constexpr (MIX == kMixTwin) row[t + twin] = convert(y);
       }
       if constexpr (STATS) level(y);
     }
   }
-  /* samples i0 .. i0 + 15 */
-  __device__ __forceinline__ void chunk(uint32_t i0, const int32_t *y)
+  /* samples i0 .. i0 + 15; GAIN: old = what fetch(i0, ...) loaded */
+  __device__ __forceinline__ void chunk(uint32_t i0, const int32_t *y, [[maybe_unused]] const Old *old = nullptr)
   {
     const int64_t t0 = base + (int64_t)i0;
     if (t0 + kChunk <= lo || t0 >= hi) return;
@@ -143,7 +241,18 @@ struct WindowRow : WindowLevels<STATS> {
         if (!this->store) return;
       }
       T *p = row + t0;
-      if constexpr (F32) {
+      if constexpr (GAIN) {
+        float f[kChunk];
+#pragma unroll
+        for (int j = 0; j < kChunk; j++) f[j] = scaled(y[j]);
+        constexpr int H = Old::NV / 2; /* vectors of 8 elements */
+        put8(p, f, old->v);
+        put8(p + 8, f + 8, old->v + H);
+        if constexpr (MIX == kMixTwin) {
+          put8(p + twin, f, old->twin);
+          put8(p + twin + 8, f + 8, old->twin + H);
+        }
+      } else if constexpr (F32) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           const f32x4_u4 v = f32x4_u4{convert(y[4 * q]), convert(y[4 * q + 1]), convert(y[4 * q + 2]), convert(y[4 * q + 3])};
@@ -184,8 +293,13 @@ struct WindowRow : WindowLevels<STATS> {
   {
     if (!stores()) return;
     for (int64_t t = from > lo ? from : lo; t < hi; t++) {
-      row[t] = (T)0;
-      if constexpr (MIX == kMixTwin) row[t + twin] = (T)0;
+      if constexpr (GAIN) {
+        put(row + t, 0.0f);
+        if constexpr (MIX == kMixTwin) put(row + t + twin, 0.0f);
+      } else {
+        row[t] = (T)0;
+        if constexpr (MIX == kMixTwin) row[t + twin] = (T)0;
+      }
     }
   }
 };
@@ -198,10 +312,14 @@ struct WindowRow : WindowLevels<STATS> {
  * block geometry and every read stay the SOURCE's (CHF); a mono source stores into both rows, a stereo pair exchanges the finished
  * L / R samples once more and lane c == 0 stores the mix into the one row.
  * STATS (aad_decode_window_stats.hip.h): the lane also sums the levels of the samples it keeps and ends by adding them into its
- * row's record of `stats`, which the run cleared; a.out may then be null - nothing is stored, the ranges stay. */
-template <int BITS, int CHF, bool MS, int ST, bool MIXED = false, int OUTC = 0, class FORMAT = StreamFormat, bool STATS = false>
+ * row's record of `stats`, which the run cleared; a.out may then be null - nothing is stored, the ranges stay.
+ * GAIN (aad_decode_window_gain.hip.h): the lane reads its window's gain from `gain` (null: 1) and its row writer stores g * f, or
+ * with `add` adds it to what the row holds (WindowRow). */
+template <int BITS, int CHF, bool MS, int ST, bool MIXED = false, int OUTC = 0, class FORMAT = StreamFormat, bool STATS = false,
+          bool GAIN = false>
 __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane, const FORMAT *formats = nullptr,
-                                            uint32_t owns_strays = 0, unsigned long long *stats = nullptr)
+                                            uint32_t owns_strays = 0, unsigned long long *stats = nullptr,
+                                            const float *gain = nullptr, uint32_t add = 0)
 {
   static_assert(OUTC == 0 || ((CHF == 1 || CHF == 2) && (OUTC == 1 || OUTC == 2)), "a channel mix is between one and two channels");
   constexpr int MIX = OUTC == 0 || OUTC == CHF ? kMixNone : OUTC == 2 ? kMixTwin : kMixDown;
@@ -232,11 +350,15 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
   const uint64_t kspb = (uint64_t)k * spb;
   if (kspb >= frames + phase) return; /* past the window's last block: lanes of one (window, block) leave together */
 
-  WindowRow<ST, MIX, STATS> out;
+  WindowRow<ST, MIX, STATS, GAIN> out;
   if constexpr (STATS) {
     out.sum_sq = out.sum_abs = 0;
     out.max_abs = 0;
     out.store = a.out != nullptr;
+  }
+  if constexpr (GAIN) {
+    out.g = gain != nullptr ? gain[w] : 1.0f;
+    out.add = add != 0;
   }
   if constexpr (MIX == kMixNone) {
     out.row = reinterpret_cast<typename WindowRow<ST>::T *>(a.out) + (w * ch + c) * frames;
@@ -345,9 +467,17 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
       if (q + 1 < full) cp += kStride; /* unconditional prefetch: the last iteration re-reads its own chunk */
       next.load(cp);
       int32_t y[kChunk];
-      decode_chunk16<BITS>(L, wd, lds, y, finish);
-      next.touch();
-      out.chunk((uint32_t)kTaps + q * kChunk, y);
+      if constexpr (GAIN) {
+        typename WindowRow<ST, MIX, STATS, GAIN>::Old old = {};
+        out.fetch((uint32_t)kTaps + q * kChunk, old);
+        decode_chunk16<BITS>(L, wd, lds, y, finish);
+        next.touch();
+        out.chunk((uint32_t)kTaps + q * kChunk, y, &old);
+      } else {
+        decode_chunk16<BITS>(L, wd, lds, y, finish);
+        next.touch();
+        out.chunk((uint32_t)kTaps + q * kChunk, y);
+      }
     }
     done = full * kChunk;
   } else {
@@ -369,9 +499,17 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
       if (q + 1 < full) cp += row;
       next.load(cp, unit_stride);
       int32_t y[kChunk];
-      decode_chunk16<BITS>(L, wd, lds, y, finish);
-      next.touch();
-      out.chunk((uint32_t)kTaps + q * kChunk, y);
+      if constexpr (GAIN) {
+        typename WindowRow<ST, MIX, STATS, GAIN>::Old old = {};
+        out.fetch((uint32_t)kTaps + q * kChunk, old);
+        decode_chunk16<BITS>(L, wd, lds, y, finish);
+        next.touch();
+        out.chunk((uint32_t)kTaps + q * kChunk, y, &old);
+      } else {
+        decode_chunk16<BITS>(L, wd, lds, y, finish);
+        next.touch();
+        out.chunk((uint32_t)kTaps + q * kChunk, y);
+      }
     }
     done = full * kChunk;
   }

@@ -1177,6 +1177,13 @@ void AADHip_WindowDecodePlanDestroy(struct AADHipWindowDecodePlan *plan)
 namespace {
 /* AADHip_WindowDecodePlanRunStats: the lanes add into the table, so the run clears it in front of its first launch - the start
  * event recorded in front of the clear, and the launches carry the stop event alone (as a segmented reconstruct's statistics) */
+/* AADHip_WindowDecodePlanRunGain's part of a run: the launches are the gain units' (aad_launch.h) */
+struct WindowGainRun {
+  bool on;
+  const float *gain; /* device memory, or null: every gain is 1 */
+  uint32_t add;
+};
+
 bool clear_window_stats(AADHipContext *ctx, aad::LaunchSignal *signal, struct AADHipRowStats *stats, uint64_t bytes)
 {
   if (signal->start != nullptr && !hip_ok(ctx, hipEventRecord(signal->start, ctx->stream), "hipEventRecord")) return false;
@@ -1190,7 +1197,8 @@ bool clear_window_stats(AADHipContext *ctx, aad::LaunchSignal *signal, struct AA
  * device_out may be null. */
 AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &run_signal, const uint8_t *device_data,
                                      uint64_t num_windows, const struct AADHipWindow *device_windows, uint32_t frames_per_window,
-                                     int32_t sample_type, void *device_out, struct AADHipRowStats *stats, uint64_t stats_bytes)
+                                     int32_t sample_type, void *device_out, struct AADHipRowStats *stats, uint64_t stats_bytes,
+                                     const WindowGainRun &gain)
 {
   aad::LaunchSignal signal = run_signal;
   AADHipContext *ctx = plan->ctx;
@@ -1228,6 +1236,7 @@ AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::La
     last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
     aad::tl_launch_signal = last;
     if (stats != nullptr) aad::launch_decode_window_mixed_stats(a, stats, m.launch[i], sample_type, ctx->stream);
+    else if (gain.on) aad::launch_decode_window_mixed_gain(a, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
     else aad::launch_decode_window_mixed(a, m.launch[i], sample_type, ctx->stream);
     if (!hip_ok(ctx, hipGetLastError(), "mixed window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   }
@@ -1238,7 +1247,7 @@ AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::La
 AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &run_signal, const uint8_t *device_data,
                                            uint64_t num_windows, const struct AADHipWindow *device_windows,
                                            uint32_t frames_per_window, int32_t sample_type, void *device_out,
-                                           struct AADHipRowStats *stats, uint64_t stats_bytes)
+                                           struct AADHipRowStats *stats, uint64_t stats_bytes, const WindowGainRun &gain)
 {
   aad::LaunchSignal signal = run_signal;
   AADHipContext *ctx = plan->ctx;
@@ -1278,6 +1287,8 @@ AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const a
     aad::tl_launch_signal = last;
     if (stats != nullptr)
       aad::launch_decode_window_channel_mix_stats(a, stats, m.launch[i], sample_type, ctx->stream);
+    else if (gain.on)
+      aad::launch_decode_window_channel_mix_gain(a, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
     else aad::launch_decode_window_channel_mix(a, m.launch[i], sample_type, ctx->stream);
     if (!hip_ok(ctx, hipGetLastError(), "channel-mix window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   }
@@ -1291,14 +1302,25 @@ bool window_sample_type_ok(int32_t sample_type)
          sample_type == AAD_HIP_SAMPLE_BFLOAT16;
 }
 
-/* AADHip_WindowDecodePlanRun, and with_stats AADHip_WindowDecodePlanRunStats: the table as a further output, device_out optional */
+/* AADHip_WindowDecodePlanRun, and with_stats AADHip_WindowDecodePlanRunStats: the table as a further output, device_out optional;
+ * gain.on: AADHip_WindowDecodePlanRunGain, float rows alone, `mode` its STORE / ADD argument as the caller gave it */
 AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
                                const struct AADHipWindow *device_windows, uint32_t frames_per_window, int32_t sample_type,
-                               void *device_out, bool with_stats, struct AADHipRowStats *stats)
+                               void *device_out, bool with_stats, struct AADHipRowStats *stats,
+                               WindowGainRun gain = WindowGainRun{false, nullptr, 0}, int32_t mode = 0)
 {
   if (plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
   AADHipContext *ctx = plan->ctx;
   aad::LaunchSignal signal = take_signal(ctx);
+  if (gain.on) {
+    if (sample_type == AAD_HIP_SAMPLE_INT16 || (mode != AAD_HIP_WINDOW_GAIN_STORE && mode != AAD_HIP_WINDOW_GAIN_ADD) ||
+        (reinterpret_cast<uintptr_t>(gain.gain) & 3u) != 0) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error),
+               "window decode with gain: int16 rows, a mode that is neither STORE nor ADD, or a gain table off 4-byte alignment");
+      return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
+    }
+    gain.add = mode == AAD_HIP_WINDOW_GAIN_ADD;
+  }
   if (frames_per_window == 0 || !window_sample_type_ok(sample_type) ||
       (num_windows != 0 && (device_data == nullptr || device_windows == nullptr || (device_out == nullptr && !with_stats))))
     return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
@@ -1317,10 +1339,10 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
   }
   if (plan->mixed)
     return run_mixed_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out,
-                                   stats, stats_bytes);
+                                   stats, stats_bytes, gain);
   if (plan->channel_mix)
     return run_channel_mix_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type,
-                                         device_out, stats, stats_bytes);
+                                         device_out, stats, stats_bytes, gain);
   const aad::DecodeArgs &d = plan->args;
   const aad::WindowLaunch p =
       aad::plan_window_decode(ctx->device_info, ctx->knobs, aad::WindowBatch{num_windows, frames_per_window, d.channels, d.bits, d.samples_per_block});
@@ -1352,6 +1374,7 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
   if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
   if (stats != nullptr) aad::launch_decode_window_stats(a, stats, p, sample_type, ctx->stream);
+  else if (gain.on) aad::launch_decode_window_gain(a, gain.gain, gain.add, p, sample_type, ctx->stream);
   else aad::launch_decode_window(a, p, sample_type, ctx->stream);
   return finish_signal(ctx, signal, hip_ok(ctx, hipGetLastError(), "window decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG);
 }
@@ -1370,6 +1393,14 @@ AADApiResult AADHip_WindowDecodePlanRunStats(struct AADHipWindowDecodePlan *plan
 {
   return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out, true,
                            device_stats);
+}
+
+AADApiResult AADHip_WindowDecodePlanRunGain(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
+                                            const struct AADHipWindow *device_windows, uint32_t frames_per_window,
+                                            int32_t sample_type, void *device_out, const float *device_gain, int32_t mode)
+{
+  return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out, false, nullptr,
+                           WindowGainRun{true, device_gain, 0}, mode);
 }
 
 /* -------------------------------------------------------------------- window reconstruct -- */

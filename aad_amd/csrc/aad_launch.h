@@ -28,7 +28,7 @@ extern thread_local LaunchSignal tl_launch_signal; /* defined in aad_hip_engine.
 struct DecodeArgs;
 void launch_decode_split(const DecodeArgs &args, const DecodeLaunch &p, int32_t *residual, hipStream_t stream);
 void launch_decode_tiled(const DecodeArgs &args, const DecodeLaunch &p, hipStream_t stream);
-/* The window decoders (AADHip_WindowDecodePlanRun, AADHip_WindowDecodePlanRunStats).  Each of their six translation units is
+/* The window decoders (AADHip_WindowDecodePlanRun, ...RunStats, ...RunGain).  Each of their nine translation units is
  * compiled twice (Makefile): with AAD_WINDOW_HALF=0 its kernels write int16 and float32 rows, with AAD_WINDOW_HALF=1 (the _half
  * objects) float16 and bfloat16 rows.  A unit defines launch_..._unit<AAD_WINDOW_HALF>; the launch_... below pick the unit by the
  * run's sample_type (enum AADHipSampleType, validated by the entry point). */
@@ -76,6 +76,18 @@ AAD_WINDOW_UNIT(launch_decode_window_mixed_stats_unit,
 AAD_WINDOW_UNIT(launch_decode_window_channel_mix_stats_unit,
                 const ChannelMixWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, int32_t sample_type,
                 hipStream_t stream);
+/* aad_decode_window_gain.hip, aad_decode_window_mixed_gain.hip, aad_decode_window_channel_mix_gain.hip: the same launches of
+ * AADHip_WindowDecodePlanRunGain - float rows scaled by the window's gain (`gain`: device memory, null for 1) and stored, or with
+ * `add` added to what the rows hold.  Their AAD_WINDOW_HALF=0 objects hold float32 alone */
+AAD_WINDOW_UNIT(launch_decode_window_gain_unit,
+                const WindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
+                hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_mixed_gain_unit,
+                const MixedWindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
+                hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_channel_mix_gain_unit,
+                const ChannelMixWindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
+                hipStream_t stream);
 
 inline void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
 {
@@ -110,6 +122,24 @@ inline void launch_decode_window_channel_mix_stats(const ChannelMixWindowArgs &a
 {
   if (window_half_type(sample_type)) launch_decode_window_channel_mix_stats_unit<true>(args, stats, p, sample_type, stream);
   else launch_decode_window_channel_mix_stats_unit<false>(args, stats, p, sample_type, stream);
+}
+inline void launch_decode_window_gain(const WindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p,
+                                      int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_gain_unit<true>(args, gain, add, p, sample_type, stream);
+  else launch_decode_window_gain_unit<false>(args, gain, add, p, sample_type, stream);
+}
+inline void launch_decode_window_mixed_gain(const MixedWindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p,
+                                            int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_mixed_gain_unit<true>(args, gain, add, p, sample_type, stream);
+  else launch_decode_window_mixed_gain_unit<false>(args, gain, add, p, sample_type, stream);
+}
+inline void launch_decode_window_channel_mix_gain(const ChannelMixWindowArgs &args, const float *gain, uint32_t add,
+                                                  const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_channel_mix_gain_unit<true>(args, gain, add, p, sample_type, stream);
+  else launch_decode_window_channel_mix_gain_unit<false>(args, gain, add, p, sample_type, stream);
 }
 /* the decoded rows of a planar reconstruct run (AADHip_PlanarReconstructPlanRun; launched through aad_encode_launch.hip.h).
  * base: per stream (segmented: per chain) the element of `out` that holds channel 0's sample of the lane's first frame, device

@@ -10,7 +10,7 @@ import numpy as np
 
 from .capi import (AADApiResult, AADHeaderInfo, AADHipPlanarLayout, AADHipPlanarOutput, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
                    OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_SIMD_ROLE, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
-                   SAMPLE_BFLOAT16, SAMPLE_FLOAT16, SAMPLE_FLOAT32, SAMPLE_INT16, SIMD_ROLE_OFF, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, load_library, make_parameter)
+                   SAMPLE_BFLOAT16, SAMPLE_FLOAT16, SAMPLE_FLOAT32, SAMPLE_INT16, SIMD_ROLE_OFF, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, WINDOW_GAIN_ADD, WINDOW_GAIN_STORE, load_library, make_parameter)
 
 
 def _check(where, rc):
@@ -618,33 +618,63 @@ class Engine:
         d["num_samples"] = header.num_samples
         return self.window_decode_plan(header, d, True)
 
-    def decode_windows(self, data, image_size, windows, frames, dtype=None, return_stats=False):
+    def decode_windows(self, data, image_size, windows, frames, dtype=None, return_stats=False, out=None, gain=None,
+                       accumulate=False):
         """data: uint8 cuda tensor [streams, pitch] of same-format images (encode_uniform's output, or a view of it with
         data.stride(1) == 1: row i is read where it lies, at i * data.stride(0)); windows: int64 cuda tensor
         [N, 2] of (stream, first_frame) -> [N, channels, frames] tensor of `dtype` (torch.float32 = sample / 32768, torch.int16, or
         torch.float16 / torch.bfloat16 = the float32 row rounded to nearest even).
         The header is read once, from the first image; the windows are never read on the host.
-        return_stats: -> (rows, int64 [N, channels, 4] level statistics of the rows), see WindowDecodePlan.run."""
+        return_stats: -> (rows, int64 [N, channels, 4] level statistics of the rows), see WindowDecodePlan.run.
+        gain / accumulate / out: float rows scaled by a float32 [N] gain per window, stored or added into `out`, see there."""
         self.image_rows("data", data, image_size)
         head = bytes(data[0, :31].cpu().numpy())
         header = parse_header(head)
         plan = self.uniform_window_decode_plan(header, data.shape[0], data.stride(0), image_size)  # the view's row pitch
         try:
-            return plan.run(data, windows, frames, dtype, stats=True if return_stats else None)
+            return plan.run(data, windows, frames, dtype, out=out, stats=True if return_stats else None, gain=gain,
+                            accumulate=accumulate)
         finally:
             plan.close()  # synchronises the context's stream first
 
-    def decode_windows_mixed(self, data, image_sizes, windows, frames, dtype=None, channels=None, return_stats=False):
+    def decode_windows_mixed(self, data, image_sizes, windows, frames, dtype=None, channels=None, return_stats=False, out=None,
+                             gain=None, accumulate=False):
         """decode_windows over images that do not share a format (encode_planar_mixed's output): data is a uint8 cuda tensor
         [streams, stride], row i starting with an image of image_sizes[i] bytes (an int: the same for all).  The 31-byte headers of
         all the images come to the host in one copy and are parsed one by one (the channel counts must agree); the windows are
         never read on the host.  channels = 1 or 2: mono and stereo images may share the tensor and the result has that many rows
-        per window (channel_mix_window_decode_plan).  return_stats: -> (rows, int64 [N, channels, 4] level statistics)."""
+        per window (channel_mix_window_decode_plan).  return_stats: -> (rows, int64 [N, channels, 4] level statistics).
+        gain / accumulate / out: float rows scaled by a float32 [N] gain per window, stored or added into `out`
+        (WindowDecodePlan.run)."""
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
-            return plan.run(data, windows, frames, dtype, stats=True if return_stats else None)
+            return plan.run(data, windows, frames, dtype, out=out, stats=True if return_stats else None, gain=gain,
+                            accumulate=accumulate)
         finally:
             plan.close()  # synchronises the context's stream first
+
+    def mix_windows(self, signal, noise, frames, snr_db, dtype=None, channels=None):
+        """A noisy batch at a chosen SNR without a temporary batch or an elementwise pass.  signal, noise: each
+        (data, image_sizes, windows) as for decode_windows_mixed, the same number of windows; snr_db: a number or a tensor [N].
+        Two statistics-only runs give the levels, snr_gains the noise gains on the device, then one run STORES the signal rows
+        and one ADDS gain * noise into them -> (rows [N, channels, frames] of `dtype`, float32 [N] noise gains).  Per element
+        fl32(signal_float32 rounded to dtype, widened + fl32(gain * noise_float32)) rounded once to dtype."""
+        torch = self.torch
+        dtype = torch.float32 if dtype is None else dtype
+        s_plan = self._corpus_window_plan(signal[0], signal[1], channels)
+        try:
+            n_plan = self._corpus_window_plan(noise[0], noise[1], channels)
+            try:
+                s_stats = s_plan.run(signal[0], signal[2], frames, stats=True, rows=False)
+                n_stats = n_plan.run(noise[0], noise[2], frames, stats=True, rows=False)
+                gains = snr_gains(s_stats, n_stats, snr_db)
+                rows = s_plan.run(signal[0], signal[2], frames, dtype, gain=torch.ones_like(gains))
+                n_plan.run(noise[0], noise[2], frames, dtype, out=rows, gain=gains, accumulate=True)
+                return rows, gains
+            finally:
+                n_plan.close()  # synchronises the context's stream first
+        finally:
+            s_plan.close()
 
     def window_levels(self, data, image_sizes, windows, frames, channels=None):
         """The level statistics of decode_windows_mixed's rows without the rows: int64 [N, channels, 4] of (sum_sq, sum_abs,
@@ -818,6 +848,23 @@ def level_dbfs(stats):
     sum_sq, _, _, count = _stats_f64(stats)
     mean = torch.where(count == 0, torch.zeros_like(sum_sq), sum_sq / count.clamp(min=1.0))
     return 20.0 * (mean.sqrt() / 32768.0).log10()
+
+
+def snr_gains(signal_stats, noise_stats, snr_db):
+    """The noise gains that put each window's noise snr_db below its signal: from two int64 [N, C, 4] statistics tables (the two
+    may differ in C) float32 [N] of sqrt(P_s / P_n) * 10^(-snr_db / 20), P = the sum of sum_sq over the window's rows divided by
+    the sum of count, computed in float64; 0 where either power or either count is 0.  snr_db: a number or a tensor [N].
+    Stays on the tables' device, no synchronisation."""
+    import torch
+    s_sq, _, _, s_count = _stats_f64(signal_stats)
+    n_sq, _, _, n_count = _stats_f64(noise_stats)
+    s_sq, s_count, n_sq, n_count = s_sq.sum(-1), s_count.sum(-1), n_sq.sum(-1), n_count.sum(-1)
+    p_s, p_n = s_sq / s_count.clamp(min=1.0), n_sq / n_count.clamp(min=1.0)
+    silent = (s_sq == 0) | (n_sq == 0) | (s_count == 0) | (n_count == 0)
+    scale = torch.pow(10.0, -snr_db.to(device=s_sq.device, dtype=torch.float64) / 20.0) if torch.is_tensor(snr_db) \
+        else 10.0 ** (-float(snr_db) / 20.0)  # a number never becomes a tensor: no copy to the device
+    g = (p_s / torch.where(silent, torch.ones_like(p_n), p_n)).sqrt() * scale
+    return torch.where(silent, torch.zeros_like(g), g).to(torch.float32)
 
 
 def snr_db(stats, signal_sum_sq):
@@ -1035,7 +1082,7 @@ class WindowDecodePlan:
         self._memo = {}
         self.data_extent = run_extent("images", descs)
 
-    def run(self, data, windows, frames, dtype=None, out=None, ordered=True, stats=None, rows=True):
+    def run(self, data, windows, frames, dtype=None, out=None, ordered=True, stats=None, rows=True, gain=None, accumulate=False):
         """data: uint8 cuda tensor of the images; windows: int64 cuda tensor [N, 2] of (stream, first_frame) ->
         `out` ([N, channels, frames] of dtype torch.float32 - sample / 32768 - or torch.int16; allocated when None).
         dtype torch.float16 / torch.bfloat16: the float32 row rounded once to nearest even, bit for bit row_float32.to(dtype),
@@ -1043,9 +1090,16 @@ class WindowDecodePlan:
         Asynchronous on the engine's stream, ordered against torch's current one; the windows stay on the device.
         stats (AADHip_WindowDecodePlanRunStats): True, or a contiguous cuda int64 tensor [N, channels, 4] - the exact level
         statistics of every row (sum_sq, sum_abs, max_abs in int16 units, count = the frames the stream had), from the same
-        kernels -> (out, stats).  rows=False: statistics only, no row is written -> stats."""
+        kernels -> (out, stats).  rows=False: statistics only, no row is written -> stats.
+        gain (AADHip_WindowDecodePlanRunGain): a contiguous float32 cuda tensor [N], one gain per window for all its rows - the
+        float rows hold fl32(gain * row_float32) rounded once to `dtype`; it stays on the device and must stay alive until the run
+        is done (nothing is copied, so ordered=False needs no more than that).  accumulate=True: the run ADDS into `out`
+        (needed then) instead of storing - (out.float() + gain[:, None, None] * row_float32).to(dtype), a multiply and an add,
+        two roundings; without `gain` every gain is 1.  Not for torch.int16, and not together with stats: the levels come first,
+        from a statistics-only run (stats=True, rows=False), and the gains from them (snr_gains)."""
         torch = self.engine.torch
         dtype = torch.float32 if dtype is None else dtype
+        gained = gain is not None or bool(accumulate)
         kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
         if dtype not in kinds:
             raise ValueError("window decode writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % dtype)
@@ -1053,6 +1107,16 @@ class WindowDecodePlan:
         e.tensor("data", data, torch.uint8, self.data_extent, rows_in_place=True, memo=self._memo)
         windows = e.window_table(windows, ordered)
         n, ch, frames = int(windows.shape[0]), int(self.header.num_channels), int(frames)
+        if gained:
+            if dtype == torch.int16:
+                raise ValueError("gain / accumulate: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
+            if not (stats is None or stats is False) or not rows:
+                raise ValueError("gain / accumulate: no statistics variant - take the levels first from a statistics-only run "
+                                 "(stats=True, rows=False), then run with the gains")
+            if accumulate and out is None:
+                raise ValueError("accumulate=True adds into `out`: pass the rows to add to")
+            if gain is not None:
+                e.tensor("gain", gain, torch.float32, n, shape=(n,), contiguous=True)
         if stats is None or stats is False:
             stats = None
             if not rows:
@@ -1071,7 +1135,12 @@ class WindowDecodePlan:
                      contiguous=True)
         kind = kinds[dtype]
         cur = self.engine._enter() if ordered else None
-        if stats is None:
+        if gained:
+            _check("AADHip_WindowDecodePlanRunGain",
+                   self.engine.lib.AADHip_WindowDecodePlanRunGain(self.handle, data.data_ptr(), n, windows.data_ptr(), frames, kind,
+                                                                  out.data_ptr(), gain.data_ptr() if gain is not None else None,
+                                                                  WINDOW_GAIN_ADD if accumulate else WINDOW_GAIN_STORE))
+        elif stats is None:
             _check("AADHip_WindowDecodePlanRun",
                    self.engine.lib.AADHip_WindowDecodePlanRun(self.handle, data.data_ptr(), n, windows.data_ptr(), frames, kind,
                                                               out.data_ptr()))
@@ -1298,4 +1367,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "select_least_bits", "run_extent", "tensor_span"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]

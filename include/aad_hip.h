@@ -84,7 +84,7 @@ const char *AADHip_ContextLastError(const struct AADHipContext *context);
 
 /* Cross-stream ordering and kernel timing without packets of their own.  `hip_start_event` / `hip_stop_event` (hipEvent_t the
  * caller owns; either may be NULL, both NULL withdraws) are recorded when the work of the NEXT AADHip_EncodePlanRun /
- * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_WindowReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_WindowDecodePlanRunStats / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
+ * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_WindowReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_WindowDecodePlanRunStats / AADHip_WindowDecodePlanRunGain / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
  * the run takes them.  An encode, decode or window decode plan run is one kernel (a mixed-format or channel-mix window decode several: start on the first, stop on
  * the last; a run that first clears a statistics table - AADHip_WindowDecodePlanRunStats, a segmented AADHip_PlanarReconstructPlanRunStats - records the
  * start event with hipEventRecord in front of the clear and its last kernel carries the stop event), and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
@@ -246,7 +246,7 @@ struct AADHipWindow {
   uint64_t first_frame; /* first frame of the window */
 };
 /* AAD_HIP_SAMPLE_FLOAT16 and AAD_HIP_SAMPLE_BFLOAT16: 2-byte float rows for a model under autocast, without a cast pass over a
- * float32 batch.  They are sample types of AADHip_WindowDecodePlanRun and AADHip_WindowDecodePlanRunStats alone, for plans of all
+ * float32 batch.  They are sample types of AADHip_WindowDecodePlanRun, AADHip_WindowDecodePlanRunStats and AADHip_WindowDecodePlanRunGain alone, for plans of all
  * three constructors; the planar encode, planar reconstruct and window reconstruct entry points refuse them, and 2 and 3 are no
  * sample type anywhere.
  *
@@ -381,6 +381,53 @@ AADApiResult AADHip_WindowDecodePlanRunStats(
     uint32_t frames_per_window, int32_t sample_type,
     void *device_out,                     /* may be NULL: statistics only, no row is written */
     struct AADHipRowStats *device_stats); /* N * C records, 8-byte aligned, every one written by the run */
+
+/* Window decode with a gain per window, written or added into float rows: what a loader does with the levels above - speech plus
+ * noise at a chosen SNR, level normalisation, mixup, polarity flips - without a multiply pass over each batch and an add pass over
+ * both.  A noisy batch is two runs into one buffer: STORE of g_s * speech, then ADD of g_n * noise.  For all three kinds of window
+ * decode plan; asynchronous on the context's stream.  The gain table stays on the device and the host never reads it, exactly like
+ * the window table (a contiguous torch float32 tensor [N] on the device IS the table).
+ *
+ * Definition.  IEEE arithmetic and nothing else.  For each element let f be the float32 value an AAD_HIP_SAMPLE_FLOAT32 run of
+ * AADHip_WindowDecodePlanRun writes for the same plan, data and windows: sample * 2^-15, (L + R) * 2^-16 for the channel-mix
+ * down-mix, +0 for every frame the stream does not produce, for stray windows and for wrapped values.  Let g = device_gain[w], one
+ * gain for all rows of window w; 1.0f with a NULL table.  Let p = fl32(g * f): ONE float32 multiply, round to nearest even,
+ * subnormal results kept - f is formed first, which is exact, then multiplied; (sample * g) * 2^-15 rounds twice once the result is
+ * subnormal and is not the definition.  The element becomes
+ *                                float32 rows                     float16 / bfloat16 rows
+ *   AAD_HIP_WINDOW_GAIN_STORE    p                                p rounded once to the type, nearest even, subnormals kept
+ *   AAD_HIP_WINDOW_GAIN_ADD      fl32(old + p)                    fl32(float32(old) + p) rounded once to the type
+ * with old the element's content before the run.  The multiply and the add are two roundings, never a fused multiply-add, and a
+ * 2-byte row is never rounded from a product that skipped its float32 rounding.  That is torch's
+ * (out.float() + gain[:, None, None] * row_float32).to(dtype) for ADD and the same without `out.float() +` for STORE, evaluated on
+ * every element of the N x C x T output, padding included.  Consequences:
+ *   - a negative gain turns a zero sample, or padding, into -0 under STORE;
+ *   - under ADD padding changes nothing, except that an old -0 plus +0 becomes +0;
+ *   - every element is read at most once (ADD) and written exactly once per run, by one lane: a run is deterministic, and
+ *     device_out may hold anything before a STORE run;
+ *   - non-finite gains follow IEEE: NaN where f = 0, infinities elsewhere.  NaN payloads are unspecified;
+ *   - a NULL table under STORE writes byte for byte what AADHip_WindowDecodePlanRun writes.
+ *
+ * Errors.  AADHip_WindowDecodePlanRun's, plus AAD_APIRESULT_INVALID_ARGUMENT for AAD_HIP_SAMPLE_INT16 (a gain on integer rows
+ * needs a rounding and clipping rule that nobody has asked for), a mode outside {0, 1} and a device_gain that is not 4-byte
+ * aligned.  num_windows == 0 is OK and launches nothing.  A refused run writes nothing.
+ *
+ * There is no statistics variant: the levels are needed before the gains exist, so they come from a statistics-only
+ * AADHip_WindowDecodePlanRunStats (device_out == NULL) first.
+ *
+ * The run launches the kernels AADHip_WindowDecodePlanRun launches for the plan - same lanes, same variants, same launch plan -
+ * with the gain in the row writer.  AADHip_ContextSignalNextRun: the start event rides on the first kernel, the stop event on the
+ * last. */
+enum AADHipWindowGainMode {
+  AAD_HIP_WINDOW_GAIN_STORE = 0, /* the element becomes g * f */
+  AAD_HIP_WINDOW_GAIN_ADD = 1    /* the element becomes old + g * f */
+};
+AADApiResult AADHip_WindowDecodePlanRunGain(
+    struct AADHipWindowDecodePlan *plan, const uint8_t *device_data,
+    uint64_t num_windows, const struct AADHipWindow *device_windows,
+    uint32_t frames_per_window, int32_t sample_type, void *device_out,
+    const float *device_gain, /* num_windows floats on the device, 4-byte aligned; NULL: every gain is 1 */
+    int32_t mode);            /* enum AADHipWindowGainMode */
 
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 

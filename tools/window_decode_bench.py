@@ -46,8 +46,19 @@ corpus, same-format plan.  Kernel times from the events of AADHip_ContextSignalN
 alternating rounds over the types; a figure is the median of the rounds' medians and its spread the range of the rounds' medians.
 float16 and bfloat16 rows are compared bitwise with torch's conversion of the float32 rows.
 
+--gain (profiles/window_decode_gain.txt): the gain run (AADHip_WindowDecodePlanRunGain) on the tool's corpus - stereo 4-bit,
+float32 rows, same-format plan, two window tables (a "signal" and a "noise" draw) and two float32 [N] gain tables:
+  (a) AADHip_WindowDecodePlanRun alone;
+  (b) a STORE run: gs * x;
+  (c) an ADD run: gn * y added into rows that are there;
+  (d) what a caller has without it: two plain runs, then gs[:, None, None] * x + gn[:, None, None] * y in torch - against
+      (b) followed by (c) into one buffer, "(b)+(c)".
+  All are warmed up, then timed in alternating rounds of --reps calls (wall clock with a device synchronise); a figure is the
+  median of the rounds' medians and its spread the range of the rounds' medians.  (b)+(c)'s rows are compared bitwise with torch's
+  two-rounding expression x * gs + y * gn over the plain rows ((d)'s own expression may be contracted differently by torch).
+
 Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25]
-       [--mixed | --channel-mix | --stats | --half]"""
+       [--mixed | --channel-mix | --stats | --half | --gain]"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -465,6 +476,84 @@ def half_main(args, say):
     engine.close()
 
 
+def gain_main(args, say):
+    import torch
+    from aad_amd.engine import Engine, parse_header
+    engine = Engine(0)
+    samples, frames, streams = int(round(args.seconds * 48000)), args.frames, args.streams
+    rounds, results = 5, []
+    corpus, size, stride = build_corpus(engine, torch, streams, samples, seed=args.seed)
+    hd = parse_header(bytes(corpus[0, :31].cpu().numpy()))
+    plan = engine.uniform_window_decode_plan(hd, streams, stride, size)
+    say("window decode with gain: %d stereo 4-bit streams x %d frames (spb %d), T = %d, float32 rows; %d alternating rounds of %d "
+        "calls, median of the rounds' medians (range of the rounds' medians); device %s"
+        % (streams, samples, hd.num_samples_per_block, frames, rounds, args.reps, torch.cuda.get_device_name(0)))
+    for n in args.windows:
+        g = torch.Generator(device="cuda")
+        g.manual_seed(args.seed + n)
+        draw = lambda: torch.stack([torch.randint(0, streams, (n,), device="cuda", generator=g),
+                                    torch.randint(0, samples - frames + 1, (n,), device="cuda", generator=g)], dim=1)
+        win_s, win_n = draw(), draw()
+        gs = torch.rand((n,), device="cuda", generator=g) + 0.5
+        gn = torch.rand((n,), device="cuda", generator=g) * 0.5 - 0.25
+        x = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        y = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        mixed = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        keep = {}
+
+        def plain():
+            plan.run(corpus, win_s, frames, torch.float32, out=x)
+
+        def store():
+            plan.run(corpus, win_s, frames, torch.float32, out=mixed, gain=gs)
+
+        def add():
+            plan.run(corpus, win_n, frames, torch.float32, out=mixed, gain=gn, accumulate=True)
+
+        def store_then_add():
+            store()
+            add()
+
+        def composite():
+            plan.run(corpus, win_s, frames, torch.float32, out=x)
+            plan.run(corpus, win_n, frames, torch.float32, out=y)
+            keep["d"] = gs[:, None, None] * x + gn[:, None, None] * y
+
+        sides = [plain, store, add, store_then_add, composite]
+        for _ in range(3):
+            for f in sides:
+                f()
+        torch.cuda.synchronize()
+        times = [[] for _ in sides]
+        for _ in range(rounds):
+            for t, f in zip(times, sides):
+                t.append(call_ms(torch, f, args.reps))
+        med = [float(np.median(t)) for t in times]
+        rng = [max(t) - min(t) for t in times]
+        keep.clear()
+        store_then_add()
+        plan.run(corpus, win_s, frames, torch.float32, out=x)
+        plan.run(corpus, win_n, frames, torch.float32, out=y)
+        x.mul_(gs[:, None, None])       # two roundings, in place: the product, then the sum
+        y.mul_(gn[:, None, None])
+        x.add_(y)
+        torch.cuda.synchronize()
+        exact = bool(torch.equal(mixed.view(torch.int32), x.view(torch.int32)))
+        a, b, c, bc, d = med
+        nbytes = n * 2 * frames * 4
+        say("  N = %5d (%.1f MB of rows): (a) plain %.4f ms (range %.4f); (b) STORE %.4f ms (range %.4f), (b) / (a) = %.3f; (c) ADD "
+            "%.4f ms (range %.4f), (c) / (a) = %.3f; (b)+(c) %.4f ms (range %.4f); (d) two plain runs + torch %.4f ms (range %.4f), "
+            "(d) / ((b)+(c)) = %.2fx; rows of (b)+(c) == the two-rounding expression: %s"
+            % (n, nbytes / 1e6, a, rng[0], b, rng[1], b / a, c, rng[2], c / a, bc, rng[3], d, rng[4], d / bc, exact))
+        results.append(dict(windows=n, a_ms=a, b_ms=b, c_ms=c, bc_ms=bc, d_ms=d, ranges_ms=rng, exact=exact))
+        del x, y, mixed, keep
+        torch.cuda.empty_cache()
+    say("")
+    say("json " + json.dumps(results))
+    plan.close()
+    engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=1000)
@@ -478,6 +567,7 @@ def main():
     ap.add_argument("--channel-mix", action="store_true", help="the channel-mix plan against what a caller has without it (see above)")
     ap.add_argument("--stats", action="store_true", help="the statistics run against the row run and torch reductions (see above)")
     ap.add_argument("--half", action="store_true", help="the run's kernel per sample type, float16 and bfloat16 included (see above)")
+    ap.add_argument("--gain", action="store_true", help="the gain run: STORE, ADD and both against two plain runs + torch (see above)")
     args = ap.parse_args()
 
     import torch
@@ -488,8 +578,9 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    if args.mixed or args.channel_mix or args.stats or args.half:
-        (mixed_main if args.mixed else channel_mix_main if args.channel_mix else stats_main if args.stats else half_main)(args, say)
+    if args.mixed or args.channel_mix or args.stats or args.half or args.gain:
+        (mixed_main if args.mixed else channel_mix_main if args.channel_mix else stats_main if args.stats else
+         half_main if args.half else gain_main)(args, say)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "a" if args.half else "w") as fh:  # --half: one report per library, appended
