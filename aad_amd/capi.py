@@ -62,6 +62,10 @@ class AADHipRowStats(C.Structure):  # include/aad_hip.h: one row of a torch int6
     _fields_ = [("sum_sq", C.c_uint64), ("sum_abs", C.c_uint64), ("max_abs", C.c_uint64), ("count", C.c_uint64)]
 
 
+class AADHipWindowSpan(C.Structure):  # include/aad_hip.h: one row of a torch int64 [N, 2] tensor (WindowDecodePlan.run with spans)
+    _fields_ = [("num_frames", C.c_uint64), ("out_frame", C.c_uint64)]
+
+
 class AADHipLaneState(C.Structure):  # include/aad_hip.h
     _fields_ = [("weight", C.c_int32 * 4), ("history", C.c_int32 * 4),
                 ("stepsize_index", C.c_int32), ("quantize_error", C.c_int32)]
@@ -101,7 +105,8 @@ HIP_SYMBOLS = [
     "AADHip_ReconstructBatch", "AADHip_SegmentedEncodePlanCreate", "AADHip_SegmentedEncodeBatch",
     "AADHip_SegmentedReconstructPlanCreate", "AADHip_SegmentedReconstructBatch",
     "AADHip_WindowDecodePlanCreate", "AADHip_WindowDecodePlanDestroy", "AADHip_WindowDecodePlanRun",
-    "AADHip_WindowDecodePlanRunStats", "AADHip_WindowDecodePlanRunGain", "AADHip_MixedWindowDecodePlanCreate", "AADHip_ChannelMixWindowDecodePlanCreate",
+    "AADHip_WindowDecodePlanRunStats", "AADHip_WindowDecodePlanRunGain", "AADHip_WindowDecodePlanRunPlaced", "AADHip_WindowDecodePlanRunPlacedStats",
+    "AADHip_MixedWindowDecodePlanCreate", "AADHip_ChannelMixWindowDecodePlanCreate",
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
     "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
     "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
@@ -220,6 +225,10 @@ def _declare_hip(lib):
     lib.AADHip_WindowDecodePlanRunStats.restype = C.c_int
     lib.AADHip_WindowDecodePlanRunGain.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, vp, C.c_int32]
     lib.AADHip_WindowDecodePlanRunGain.restype = C.c_int
+    lib.AADHip_WindowDecodePlanRunPlaced.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int32, vp, vp, C.c_int32]
+    lib.AADHip_WindowDecodePlanRunPlaced.restype = C.c_int
+    lib.AADHip_WindowDecodePlanRunPlacedStats.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp]
+    lib.AADHip_WindowDecodePlanRunPlacedStats.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

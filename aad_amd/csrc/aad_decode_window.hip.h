@@ -23,6 +23,7 @@
 
 #include "aad_decode.hip.h"
 #include "aad_launch_policy.h" /* StreamFormat */
+#include "aad_window_span.h"
 
 namespace aad {
 
@@ -99,11 +100,14 @@ struct WindowGain<true> {
  * STATS: every kept sample is added to the lane's WindowLevels as the int16 value the row holds, zeros() adds nothing.
  * GAIN (the float types): with f the float32 value above, the element becomes p = fl32(g * f), under `add` fl32(old + p) - two
  * roundings, never one fma - and then the one rounding of the type; zeros() writes g * 0 / old + g * 0 likewise.  The twin rows of
- * kMixTwin hold different old values: each is loaded, added and stored on its own. */
-template <int ST, int MIX = kMixNone, bool STATS = false, bool GAIN = false>
+ * kMixTwin hold different old values: each is loaded, added and stored on its own.
+ * PLACED (a run with spans, aad_decode_window_placed.hip.h): `row` is the row at the span's first element and lo, hi, base are
+ * crop indices as ever; fill() writes the +0 of a STORE run outside the span. */
+template <int ST, int MIX = kMixNone, bool STATS = false, bool GAIN = false, bool PLACED = false>
 struct WindowRow : WindowLevels<STATS>, WindowGain<GAIN> {
   static_assert(ST == kRowI16 || ST == kRowF32 || ST == kRowF16 || ST == kRowBF16, "a sample type of window decode");
   static_assert(!GAIN || (ST != kRowI16 && !STATS), "a gain is for float rows, and has no statistics variant");
+  static_assert(!PLACED || GAIN || STATS, "spans come with a gain run's rows or with a statistics-only run");
   static constexpr bool F32 = ST == kRowF32, HALF = ST == kRowF16 || ST == kRowBF16;
   using T = std::conditional_t<F32, float, std::conditional_t<HALF, uint16_t, int16_t>>;
   T *row;
@@ -288,6 +292,29 @@ struct WindowRow : WindowLevels<STATS>, WindowGain<GAIN> {
 #pragma unroll
     for (int j = 0; j < kChunk; j++) one(i0 + (uint32_t)j, y[j]);
   }
+  /* PLACED only.  +0 into elements [from, to) of the whole row `r` (kMixTwin: and of the row `pitch` elements on): 16 elements at
+   * a time by the chunk path's 16-byte stores at the row's own alignment, the rest one by one */
+  __device__ __forceinline__ static void fill(T *r, int64_t from, int64_t to, [[maybe_unused]] int64_t pitch)
+  {
+    int64_t t = from;
+    for (; t + kChunk <= to; t += kChunk) {
+#pragma unroll
+      for (int twin = 0; twin < (MIX == kMixTwin ? 2 : 1); twin++) {
+        T *p = r + t + twin * pitch;
+        if constexpr (F32) {
+#pragma unroll
+          for (int q = 0; q < 4; q++) *reinterpret_cast<f32x4_u4 *>(p + 4 * q) = f32x4_u4{0.0f, 0.0f, 0.0f, 0.0f};
+        } else {
+          store_u32x4<false>(reinterpret_cast<int16_t *>(p), u32x4{0, 0, 0, 0});
+          store_u32x4<false>(reinterpret_cast<int16_t *>(p) + 8, u32x4{0, 0, 0, 0});
+        }
+      }
+    }
+    for (; t < to; t++) {
+      r[t] = (T)0;
+      if constexpr (MIX == kMixTwin) r[t + pitch] = (T)0;
+    }
+  }
   /* zeros over [from, hi) */
   __device__ __forceinline__ void zeros(int64_t from) const
   {
@@ -314,12 +341,18 @@ struct WindowRow : WindowLevels<STATS>, WindowGain<GAIN> {
  * STATS (aad_decode_window_stats.hip.h): the lane also sums the levels of the samples it keeps and ends by adding them into its
  * row's record of `stats`, which the run cleared; a.out may then be null - nothing is stored, the ranges stay.
  * GAIN (aad_decode_window_gain.hip.h): the lane reads its window's gain from `gain` (null: 1) and its row writer stores g * f, or
- * with `add` adds it to what the row holds (WindowRow). */
+ * with `add` adds it to what the row holds (WindowRow).
+ * PLACED (aad_decode_window_placed.hip.h; with GAIN, or with STATS and no rows): the window's record of `spans` - (L, o), null:
+ * (T, 0) - clips to Le frames (aad_window_span.h) and the lane's crop arithmetic runs over Le instead of T: the early leave, hi,
+ * n, count.  The row starts at element o, its pitch stays T.  Under STORE the lane first writes +0 into its fill tile, the part
+ * outside the span of the tile it owns in a run without spans - also the lanes that then leave; the R lane of a down-mixed pair
+ * fills nothing, a twin fills both rows.  Under ADD nothing outside the span is read or written. */
 template <int BITS, int CHF, bool MS, int ST, bool MIXED = false, int OUTC = 0, class FORMAT = StreamFormat, bool STATS = false,
-          bool GAIN = false>
+          bool GAIN = false, bool PLACED = false>
 __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds, uint64_t lane, const FORMAT *formats = nullptr,
                                             uint32_t owns_strays = 0, unsigned long long *stats = nullptr,
-                                            const float *gain = nullptr, uint32_t add = 0)
+                                            const float *gain = nullptr, uint32_t add = 0,
+                                            [[maybe_unused]] const uint64_t *spans = nullptr)
 {
   static_assert(OUTC == 0 || ((CHF == 1 || CHF == 2) && (OUTC == 1 || OUTC == 2)), "a channel mix is between one and two channels");
   constexpr int MIX = OUTC == 0 || OUTC == CHF ? kMixNone : OUTC == 2 ? kMixTwin : kMixDown;
@@ -345,12 +378,32 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
       return;
     }
   }
-  const uint64_t frames = a.frames;
+  [[maybe_unused]] const uint64_t pitch = a.frames; /* elements of a row */
+  [[maybe_unused]] uint64_t out_frame = 0;
+  uint64_t crop = a.frames;
+  if constexpr (PLACED) {
+    if (spans != nullptr) {
+      out_frame = spans[2 * w + 1];
+      crop = window_span_frames(spans[2 * w], out_frame, a.frames);
+    }
+  }
+  const uint64_t frames = crop; /* the frames of the crop: T, PLACED: Le */
   const uint64_t phase = first_frame % spb;
   const uint64_t kspb = (uint64_t)k * spb;
+  using Row = WindowRow<ST, MIX, STATS, GAIN, PLACED>;
+  if constexpr (PLACED && GAIN) {
+    if (!add && !(MIX == kMixDown && c)) {
+      typename Row::T *r = reinterpret_cast<typename Row::T *>(a.out) + (MIX == kMixNone ? w * ch + c : w * OUTC) * pitch;
+      const WindowFillTile tile = window_fill_tile(k, spb, phase, a.frames, out_frame, frames);
+      Row::fill(r, tile.lo[0], tile.hi[0], (int64_t)pitch);
+      Row::fill(r, tile.lo[1], tile.hi[1], (int64_t)pitch);
+    }
+  }
+  if constexpr (PLACED)
+    if (frames == 0) return; /* an empty span: nothing to decode, whatever the phase */
   if (kspb >= frames + phase) return; /* past the window's last block: lanes of one (window, block) leave together */
 
-  WindowRow<ST, MIX, STATS, GAIN> out;
+  Row out;
   if constexpr (STATS) {
     out.sum_sq = out.sum_abs = 0;
     out.max_abs = 0;
@@ -360,15 +413,25 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
     out.g = gain != nullptr ? gain[w] : 1.0f;
     out.add = add != 0;
   }
-  if constexpr (MIX == kMixNone) {
-    out.row = reinterpret_cast<typename WindowRow<ST>::T *>(a.out) + (w * ch + c) * frames;
+  if constexpr (PLACED) {
+    /* frames = Le > 0 here: out_frame < T.  The crop range is aad_window_span.h's */
+    out.row = reinterpret_cast<typename Row::T *>(a.out) + (MIX == kMixNone ? w * ch + c : w * OUTC) * pitch + out_frame;
+    if constexpr (MIX != kMixNone) out.twin = (int64_t)pitch;
+    const WindowCropRange range = window_crop_range(k, spb, phase, frames);
+    out.base = range.base;
+    out.lo = range.lo;
+    out.hi = range.hi;
   } else {
-    out.row = reinterpret_cast<typename WindowRow<ST>::T *>(a.out) + w * OUTC * frames;
-    out.twin = (int64_t)frames;
+    if constexpr (MIX == kMixNone) {
+      out.row = reinterpret_cast<typename WindowRow<ST>::T *>(a.out) + (w * ch + c) * frames;
+    } else {
+      out.row = reinterpret_cast<typename WindowRow<ST>::T *>(a.out) + w * OUTC * frames;
+      out.twin = (int64_t)frames;
+    }
+    out.base = (int64_t)kspb - (int64_t)phase;
+    out.lo = out.base > 0 ? out.base : 0;
+    out.hi = out.base + (int64_t)spb < (int64_t)frames ? out.base + (int64_t)spb : (int64_t)frames;
   }
-  out.base = (int64_t)kspb - (int64_t)phase;
-  out.lo = out.base > 0 ? out.base : 0;
-  out.hi = out.base + (int64_t)spb < (int64_t)frames ? out.base + (int64_t)spb : (int64_t)frames;
 
   /* samples of this block the window needs, as far as the stream has them (n = 0: none) */
   uint32_t n = 0, avail = 0;
@@ -468,7 +531,7 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
       next.load(cp);
       int32_t y[kChunk];
       if constexpr (GAIN) {
-        typename WindowRow<ST, MIX, STATS, GAIN>::Old old = {};
+        typename Row::Old old = {};
         out.fetch((uint32_t)kTaps + q * kChunk, old);
         decode_chunk16<BITS>(L, wd, lds, y, finish);
         next.touch();
@@ -500,7 +563,7 @@ __device__ __forceinline__ void window_lane(const WindowArgs &a, const char *lds
       next.load(cp, unit_stride);
       int32_t y[kChunk];
       if constexpr (GAIN) {
-        typename WindowRow<ST, MIX, STATS, GAIN>::Old old = {};
+        typename Row::Old old = {};
         out.fetch((uint32_t)kTaps + q * kChunk, old);
         decode_chunk16<BITS>(L, wd, lds, y, finish);
         next.touch();

@@ -1183,6 +1183,12 @@ struct WindowGainRun {
   const float *gain; /* device memory, or null: every gain is 1 */
   uint32_t add;
 };
+/* AADHip_WindowDecodePlanRunPlaced's / ...RunPlacedStats' part of a run: the launches are the placed units' (aad_launch.h) - the
+ * gain units' rows or the statistics alone, each window's crop clipped to and placed by its span */
+struct WindowPlacedRun {
+  bool on;
+  const struct AADHipWindowSpan *spans; /* device memory, or null: every span is (T, 0) */
+};
 
 bool clear_window_stats(AADHipContext *ctx, aad::LaunchSignal *signal, struct AADHipRowStats *stats, uint64_t bytes)
 {
@@ -1198,7 +1204,7 @@ bool clear_window_stats(AADHipContext *ctx, aad::LaunchSignal *signal, struct AA
 AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &run_signal, const uint8_t *device_data,
                                      uint64_t num_windows, const struct AADHipWindow *device_windows, uint32_t frames_per_window,
                                      int32_t sample_type, void *device_out, struct AADHipRowStats *stats, uint64_t stats_bytes,
-                                     const WindowGainRun &gain)
+                                     const WindowGainRun &gain, const WindowPlacedRun &placed)
 {
   aad::LaunchSignal signal = run_signal;
   AADHipContext *ctx = plan->ctx;
@@ -1235,7 +1241,10 @@ AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::La
     a.owns_strays = i == 0;
     last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
     aad::tl_launch_signal = last;
-    if (stats != nullptr) aad::launch_decode_window_mixed_stats(a, stats, m.launch[i], sample_type, ctx->stream);
+    if (placed.on && stats != nullptr) aad::launch_decode_window_mixed_placed_stats(a, placed.spans, stats, m.launch[i], ctx->stream);
+    else if (placed.on)
+      aad::launch_decode_window_mixed_placed(a, placed.spans, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
+    else if (stats != nullptr) aad::launch_decode_window_mixed_stats(a, stats, m.launch[i], sample_type, ctx->stream);
     else if (gain.on) aad::launch_decode_window_mixed_gain(a, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
     else aad::launch_decode_window_mixed(a, m.launch[i], sample_type, ctx->stream);
     if (!hip_ok(ctx, hipGetLastError(), "mixed window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
@@ -1247,7 +1256,8 @@ AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::La
 AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &run_signal, const uint8_t *device_data,
                                            uint64_t num_windows, const struct AADHipWindow *device_windows,
                                            uint32_t frames_per_window, int32_t sample_type, void *device_out,
-                                           struct AADHipRowStats *stats, uint64_t stats_bytes, const WindowGainRun &gain)
+                                           struct AADHipRowStats *stats, uint64_t stats_bytes, const WindowGainRun &gain,
+                                           const WindowPlacedRun &placed)
 {
   aad::LaunchSignal signal = run_signal;
   AADHipContext *ctx = plan->ctx;
@@ -1285,7 +1295,11 @@ AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const a
     a.out_channels = d.channels;
     last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
     aad::tl_launch_signal = last;
-    if (stats != nullptr)
+    if (placed.on && stats != nullptr)
+      aad::launch_decode_window_channel_mix_placed_stats(a, placed.spans, stats, m.launch[i], ctx->stream);
+    else if (placed.on)
+      aad::launch_decode_window_channel_mix_placed(a, placed.spans, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
+    else if (stats != nullptr)
       aad::launch_decode_window_channel_mix_stats(a, stats, m.launch[i], sample_type, ctx->stream);
     else if (gain.on)
       aad::launch_decode_window_channel_mix_gain(a, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
@@ -1303,11 +1317,13 @@ bool window_sample_type_ok(int32_t sample_type)
 }
 
 /* AADHip_WindowDecodePlanRun, and with_stats AADHip_WindowDecodePlanRunStats: the table as a further output, device_out optional;
- * gain.on: AADHip_WindowDecodePlanRunGain, float rows alone, `mode` its STORE / ADD argument as the caller gave it */
+ * gain.on: AADHip_WindowDecodePlanRunGain, float rows alone, `mode` its STORE / ADD argument as the caller gave it;
+ * placed.on: with gain.on AADHip_WindowDecodePlanRunPlaced, with_stats (and no rows) AADHip_WindowDecodePlanRunPlacedStats */
 AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
                                const struct AADHipWindow *device_windows, uint32_t frames_per_window, int32_t sample_type,
                                void *device_out, bool with_stats, struct AADHipRowStats *stats,
-                               WindowGainRun gain = WindowGainRun{false, nullptr, 0}, int32_t mode = 0)
+                               WindowGainRun gain = WindowGainRun{false, nullptr, 0}, int32_t mode = 0,
+                               WindowPlacedRun placed = WindowPlacedRun{false, nullptr})
 {
   if (plan == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
   AADHipContext *ctx = plan->ctx;
@@ -1320,6 +1336,10 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
       return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
     }
     gain.add = mode == AAD_HIP_WINDOW_GAIN_ADD;
+  }
+  if (placed.on && (reinterpret_cast<uintptr_t>(placed.spans) & 7u) != 0) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "window decode with spans: a span table off 8-byte alignment");
+    return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
   }
   if (frames_per_window == 0 || !window_sample_type_ok(sample_type) ||
       (num_windows != 0 && (device_data == nullptr || device_windows == nullptr || (device_out == nullptr && !with_stats))))
@@ -1339,10 +1359,10 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
   }
   if (plan->mixed)
     return run_mixed_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out,
-                                   stats, stats_bytes, gain);
+                                   stats, stats_bytes, gain, placed);
   if (plan->channel_mix)
     return run_channel_mix_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type,
-                                         device_out, stats, stats_bytes, gain);
+                                         device_out, stats, stats_bytes, gain, placed);
   const aad::DecodeArgs &d = plan->args;
   const aad::WindowLaunch p =
       aad::plan_window_decode(ctx->device_info, ctx->knobs, aad::WindowBatch{num_windows, frames_per_window, d.channels, d.bits, d.samples_per_block});
@@ -1373,7 +1393,9 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
   a.bits = d.bits;
   if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
-  if (stats != nullptr) aad::launch_decode_window_stats(a, stats, p, sample_type, ctx->stream);
+  if (placed.on && stats != nullptr) aad::launch_decode_window_placed_stats(a, placed.spans, stats, p, ctx->stream);
+  else if (placed.on) aad::launch_decode_window_placed(a, placed.spans, gain.gain, gain.add, p, sample_type, ctx->stream);
+  else if (stats != nullptr) aad::launch_decode_window_stats(a, stats, p, sample_type, ctx->stream);
   else if (gain.on) aad::launch_decode_window_gain(a, gain.gain, gain.add, p, sample_type, ctx->stream);
   else aad::launch_decode_window(a, p, sample_type, ctx->stream);
   return finish_signal(ctx, signal, hip_ok(ctx, hipGetLastError(), "window decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG);
@@ -1401,6 +1423,25 @@ AADApiResult AADHip_WindowDecodePlanRunGain(struct AADHipWindowDecodePlan *plan,
 {
   return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out, false, nullptr,
                            WindowGainRun{true, device_gain, 0}, mode);
+}
+
+AADApiResult AADHip_WindowDecodePlanRunPlaced(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
+                                              const struct AADHipWindow *device_windows, const struct AADHipWindowSpan *device_spans,
+                                              uint32_t frames_per_window, int32_t sample_type, void *device_out,
+                                              const float *device_gain, int32_t mode)
+{
+  return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out, false, nullptr,
+                           WindowGainRun{true, device_gain, 0}, mode, WindowPlacedRun{true, device_spans});
+}
+
+/* no rows: the sample type is of no account, and window_decode_run sees the statistics run of int16 rows that are not there */
+AADApiResult AADHip_WindowDecodePlanRunPlacedStats(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data,
+                                                   uint64_t num_windows, const struct AADHipWindow *device_windows,
+                                                   const struct AADHipWindowSpan *device_spans, uint32_t frames_per_window,
+                                                   struct AADHipRowStats *device_stats)
+{
+  return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, AAD_HIP_SAMPLE_INT16, nullptr, true,
+                           device_stats, WindowGainRun{false, nullptr, 0}, 0, WindowPlacedRun{true, device_spans});
 }
 
 /* -------------------------------------------------------------------- window reconstruct -- */

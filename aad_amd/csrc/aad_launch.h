@@ -28,8 +28,8 @@ extern thread_local LaunchSignal tl_launch_signal; /* defined in aad_hip_engine.
 struct DecodeArgs;
 void launch_decode_split(const DecodeArgs &args, const DecodeLaunch &p, int32_t *residual, hipStream_t stream);
 void launch_decode_tiled(const DecodeArgs &args, const DecodeLaunch &p, hipStream_t stream);
-/* The window decoders (AADHip_WindowDecodePlanRun, ...RunStats, ...RunGain).  Each of their nine translation units is
- * compiled twice (Makefile): with AAD_WINDOW_HALF=0 its kernels write int16 and float32 rows, with AAD_WINDOW_HALF=1 (the _half
+/* The window decoders (AADHip_WindowDecodePlanRun, ...RunStats, ...RunGain, ...RunPlaced).  Each of their twelve translation units
+ * that write rows is compiled twice (Makefile): with AAD_WINDOW_HALF=0 its kernels write int16 and float32 rows, with AAD_WINDOW_HALF=1 (the _half
  * objects) float16 and bfloat16 rows.  A unit defines launch_..._unit<AAD_WINDOW_HALF>; the launch_... below pick the unit by the
  * run's sample_type (enum AADHipSampleType, validated by the entry point). */
 #ifndef AAD_WINDOW_HALF
@@ -88,6 +88,48 @@ AAD_WINDOW_UNIT(launch_decode_window_mixed_gain_unit,
 AAD_WINDOW_UNIT(launch_decode_window_channel_mix_gain_unit,
                 const ChannelMixWindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
                 hipStream_t stream);
+/* aad_decode_window_placed.hip, aad_decode_window_mixed_placed.hip, aad_decode_window_channel_mix_placed.hip: the same launches of
+ * AADHip_WindowDecodePlanRunPlaced - the gain units' rows, each window's crop clipped to and placed by its record of `spans`
+ * (device memory, null: every span is (T, 0)).  Compiled twice as the gain units are */
+AAD_WINDOW_UNIT(launch_decode_window_placed_unit,
+                const WindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain, uint32_t add, const WindowLaunch &p,
+                int32_t sample_type, hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_mixed_placed_unit,
+                const MixedWindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain, uint32_t add,
+                const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
+AAD_WINDOW_UNIT(launch_decode_window_channel_mix_placed_unit,
+                const ChannelMixWindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain, uint32_t add,
+                const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
+/* aad_decode_window_placed_stats.hip, aad_decode_window_mixed_placed_stats.hip, aad_decode_window_channel_mix_placed_stats.hip: the
+ * same launches of AADHip_WindowDecodePlanRunPlacedStats - the level statistics of every window's clipped crop added into `stats`,
+ * which the run cleared; no rows (args' out is null), so no sample type and one object each */
+void launch_decode_window_placed_stats(const WindowArgs &args, const struct AADHipWindowSpan *spans, struct AADHipRowStats *stats,
+                                       const WindowLaunch &p, hipStream_t stream);
+void launch_decode_window_mixed_placed_stats(const MixedWindowArgs &args, const struct AADHipWindowSpan *spans,
+                                             struct AADHipRowStats *stats, const WindowLaunch &p, hipStream_t stream);
+void launch_decode_window_channel_mix_placed_stats(const ChannelMixWindowArgs &args, const struct AADHipWindowSpan *spans,
+                                                   struct AADHipRowStats *stats, const WindowLaunch &p, hipStream_t stream);
+
+inline void launch_decode_window_placed(const WindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain, uint32_t add,
+                                        const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_placed_unit<true>(args, spans, gain, add, p, sample_type, stream);
+  else launch_decode_window_placed_unit<false>(args, spans, gain, add, p, sample_type, stream);
+}
+inline void launch_decode_window_mixed_placed(const MixedWindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain,
+                                              uint32_t add, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
+{
+  if (window_half_type(sample_type)) launch_decode_window_mixed_placed_unit<true>(args, spans, gain, add, p, sample_type, stream);
+  else launch_decode_window_mixed_placed_unit<false>(args, spans, gain, add, p, sample_type, stream);
+}
+inline void launch_decode_window_channel_mix_placed(const ChannelMixWindowArgs &args, const struct AADHipWindowSpan *spans,
+                                                    const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
+                                                    hipStream_t stream)
+{
+  if (window_half_type(sample_type))
+    launch_decode_window_channel_mix_placed_unit<true>(args, spans, gain, add, p, sample_type, stream);
+  else launch_decode_window_channel_mix_placed_unit<false>(args, spans, gain, add, p, sample_type, stream);
+}
 
 inline void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
 {

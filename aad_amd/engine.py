@@ -160,19 +160,20 @@ class Engine:
                              "overlap; pass %s.contiguous() if a copy is intended" % (what, name, x.stride(1), int(lengths.max()), name))
         return n, ch, t, lengths
 
-    def window_table(self, windows, ordered):
+    def window_table(self, windows, ordered, name="windows", rows=None):
         """windows: int64 [N, 2] of (stream, first_frame) on the device -> the contiguous table the C call takes.
+        name="spans", rows=N: the span table of a run with spans, int64 [N, 2] of (num_frames, out_frame), by the same rules.
         A non-contiguous one is copied.  The copy is a temporary that goes back to torch's caching allocator when the run
         returns, while the kernel may not have read it yet.  With ordered=True that is safe: the allocator hands a block out again
         to work on the stream it was allocated on, torch's current stream, and _exit has made that stream wait for the engine's, so
         whatever reuses the block is queued behind the kernel.  With ordered=False nothing orders the two streams and the
         kernel could read a table that has been handed out again: refused, the caller keeps a contiguous table alive."""
-        self.tensor("windows", windows, self.torch.int64, shape=(None, 2))
+        self.tensor(name, windows, self.torch.int64, shape=(rows, 2))
         if not windows.is_contiguous():
             if not ordered:
-                raise ValueError("windows: a contiguous tensor is needed with ordered=False (a temporary copy could be freed and "
-                                 "reused while the kernel still reads it); got strides %s - keep windows.contiguous() alive until "
-                                 "the run is done" % (tuple(windows.stride()),))
+                raise ValueError("%s: a contiguous tensor is needed with ordered=False (a temporary copy could be freed and "
+                                 "reused while the kernel still reads it); got strides %s - keep %s.contiguous() alive until "
+                                 "the run is done" % (name, tuple(windows.stride()), name))
             windows = windows.contiguous()
         return windows
 
@@ -619,46 +620,53 @@ class Engine:
         return self.window_decode_plan(header, d, True)
 
     def decode_windows(self, data, image_size, windows, frames, dtype=None, return_stats=False, out=None, gain=None,
-                       accumulate=False):
+                       accumulate=False, spans=None):
         """data: uint8 cuda tensor [streams, pitch] of same-format images (encode_uniform's output, or a view of it with
         data.stride(1) == 1: row i is read where it lies, at i * data.stride(0)); windows: int64 cuda tensor
         [N, 2] of (stream, first_frame) -> [N, channels, frames] tensor of `dtype` (torch.float32 = sample / 32768, torch.int16, or
         torch.float16 / torch.bfloat16 = the float32 row rounded to nearest even).
         The header is read once, from the first image; the windows are never read on the host.
         return_stats: -> (rows, int64 [N, channels, 4] level statistics of the rows), see WindowDecodePlan.run.
-        gain / accumulate / out: float rows scaled by a float32 [N] gain per window, stored or added into `out`, see there."""
+        gain / accumulate / out: float rows scaled by a float32 [N] gain per window, stored or added into `out`, see there.
+        spans: int64 cuda tensor [N, 2] of (num_frames, out_frame) - each crop clipped to and placed inside its row, see there."""
         self.image_rows("data", data, image_size)
         head = bytes(data[0, :31].cpu().numpy())
         header = parse_header(head)
         plan = self.uniform_window_decode_plan(header, data.shape[0], data.stride(0), image_size)  # the view's row pitch
         try:
             return plan.run(data, windows, frames, dtype, out=out, stats=True if return_stats else None, gain=gain,
-                            accumulate=accumulate)
+                            accumulate=accumulate, spans=spans)
         finally:
             plan.close()  # synchronises the context's stream first
 
     def decode_windows_mixed(self, data, image_sizes, windows, frames, dtype=None, channels=None, return_stats=False, out=None,
-                             gain=None, accumulate=False):
+                             gain=None, accumulate=False, spans=None):
         """decode_windows over images that do not share a format (encode_planar_mixed's output): data is a uint8 cuda tensor
         [streams, stride], row i starting with an image of image_sizes[i] bytes (an int: the same for all).  The 31-byte headers of
         all the images come to the host in one copy and are parsed one by one (the channel counts must agree); the windows are
         never read on the host.  channels = 1 or 2: mono and stereo images may share the tensor and the result has that many rows
         per window (channel_mix_window_decode_plan).  return_stats: -> (rows, int64 [N, channels, 4] level statistics).
-        gain / accumulate / out: float rows scaled by a float32 [N] gain per window, stored or added into `out`
+        gain / accumulate / out: float rows scaled by a float32 [N] gain per window, stored or added into `out`;
+        spans: int64 cuda tensor [N, 2] of (num_frames, out_frame), each crop clipped to and placed inside its row
         (WindowDecodePlan.run)."""
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
             return plan.run(data, windows, frames, dtype, out=out, stats=True if return_stats else None, gain=gain,
-                            accumulate=accumulate)
+                            accumulate=accumulate, spans=spans)
         finally:
             plan.close()  # synchronises the context's stream first
 
-    def mix_windows(self, signal, noise, frames, snr_db, dtype=None, channels=None):
+    def mix_windows(self, signal, noise, frames, snr_db, dtype=None, channels=None, noise_spans=None):
         """A noisy batch at a chosen SNR without a temporary batch or an elementwise pass.  signal, noise: each
         (data, image_sizes, windows) as for decode_windows_mixed, the same number of windows; snr_db: a number or a tensor [N].
         Two statistics-only runs give the levels, snr_gains the noise gains on the device, then one run STORES the signal rows
         and one ADDS gain * noise into them -> (rows [N, channels, frames] of `dtype`, float32 [N] noise gains).  Per element
-        fl32(signal_float32 rounded to dtype, widened + fl32(gain * noise_float32)) rounded once to dtype."""
+        fl32(signal_float32 rounded to dtype, widened + fl32(gain * noise_float32)) rounded once to dtype.
+        noise_spans: int64 cuda tensor [N, 2] of (num_frames, out_frame) - the noise of window w is an event of num_frames frames
+        added at element out_frame of the signal's row (WindowDecodePlan.run with spans).  The noise levels then come from a
+        statistics-only run over the spans, and the SNR is the signal's power over ITS counted frames - the whole row, not the
+        part under the event - against the noise's power over the event's own counted frames: the level of the event while it
+        sounds, not averaged over the row."""
         torch = self.torch
         dtype = torch.float32 if dtype is None else dtype
         s_plan = self._corpus_window_plan(signal[0], signal[1], channels)
@@ -666,23 +674,24 @@ class Engine:
             n_plan = self._corpus_window_plan(noise[0], noise[1], channels)
             try:
                 s_stats = s_plan.run(signal[0], signal[2], frames, stats=True, rows=False)
-                n_stats = n_plan.run(noise[0], noise[2], frames, stats=True, rows=False)
+                n_stats = n_plan.run(noise[0], noise[2], frames, stats=True, rows=False, spans=noise_spans)
                 gains = snr_gains(s_stats, n_stats, snr_db)
                 rows = s_plan.run(signal[0], signal[2], frames, dtype, gain=torch.ones_like(gains))
-                n_plan.run(noise[0], noise[2], frames, dtype, out=rows, gain=gains, accumulate=True)
+                n_plan.run(noise[0], noise[2], frames, dtype, out=rows, gain=gains, accumulate=True, spans=noise_spans)
                 return rows, gains
             finally:
                 n_plan.close()  # synchronises the context's stream first
         finally:
             s_plan.close()
 
-    def window_levels(self, data, image_sizes, windows, frames, channels=None):
+    def window_levels(self, data, image_sizes, windows, frames, channels=None, spans=None):
         """The level statistics of decode_windows_mixed's rows without the rows: int64 [N, channels, 4] of (sum_sq, sum_abs,
         max_abs, count) per row, in int16 units (rmse, level_dbfs).  Nothing is stored but the table - what a rejection sampler
-        asks of its candidates before it decodes the ones it keeps.  channels=None: the images share a channel count."""
+        asks of its candidates before it decodes the ones it keeps.  channels=None: the images share a channel count.
+        spans: int64 cuda tensor [N, 2] of (num_frames, out_frame) - the levels of each window's clipped crop alone."""
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
-            return plan.run(data, windows, frames, stats=True, rows=False)
+            return plan.run(data, windows, frames, stats=True, rows=False, spans=spans)
         finally:
             plan.close()  # synchronises the context's stream first
 
@@ -1082,7 +1091,8 @@ class WindowDecodePlan:
         self._memo = {}
         self.data_extent = run_extent("images", descs)
 
-    def run(self, data, windows, frames, dtype=None, out=None, ordered=True, stats=None, rows=True, gain=None, accumulate=False):
+    def run(self, data, windows, frames, dtype=None, out=None, ordered=True, stats=None, rows=True, gain=None, accumulate=False,
+            spans=None):
         """data: uint8 cuda tensor of the images; windows: int64 cuda tensor [N, 2] of (stream, first_frame) ->
         `out` ([N, channels, frames] of dtype torch.float32 - sample / 32768 - or torch.int16; allocated when None).
         dtype torch.float16 / torch.bfloat16: the float32 row rounded once to nearest even, bit for bit row_float32.to(dtype),
@@ -1096,10 +1106,23 @@ class WindowDecodePlan:
         is done (nothing is copied, so ordered=False needs no more than that).  accumulate=True: the run ADDS into `out`
         (needed then) instead of storing - (out.float() + gain[:, None, None] * row_float32).to(dtype), a multiply and an add,
         two roundings; without `gain` every gain is 1.  Not for torch.int16, and not together with stats: the levels come first,
-        from a statistics-only run (stats=True, rows=False), and the gains from them (snr_gains)."""
+        from a statistics-only run (stats=True, rows=False), and the gains from them (snr_gains).
+        spans (AADHip_WindowDecodePlanRunPlaced / ...RunPlacedStats): an int64 cuda tensor [N, 2] of (num_frames, out_frame) by
+        the rules of `windows`, never read on the host.  Window w's crop is clipped to Le = 0 if out_frame >= frames, else
+        min(num_frames, frames - out_frame), and lands at out[w, :, out_frame:out_frame + Le].  With rows - float dtypes only,
+        `gain` and `accumulate` as above - the rest of the row becomes +0, or under accumulate=True stays untouched;
+        with stats=True, rows=False the levels and `count` are those of the Le frames.  Not for torch.int16, and not for rows and
+        statistics together."""
         torch = self.engine.torch
         dtype = torch.float32 if dtype is None else dtype
         gained = gain is not None or bool(accumulate)
+        placed = spans is not None
+        if placed:
+            if not (stats is None or stats is False) and rows:
+                raise ValueError("spans: no run with both rows and statistics - take the levels from a statistics-only run "
+                                 "(stats=True, rows=False, spans=...), then the rows")
+            if rows and dtype == torch.int16:
+                raise ValueError("spans: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
         kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
         if dtype not in kinds:
             raise ValueError("window decode writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % dtype)
@@ -1107,6 +1130,8 @@ class WindowDecodePlan:
         e.tensor("data", data, torch.uint8, self.data_extent, rows_in_place=True, memo=self._memo)
         windows = e.window_table(windows, ordered)
         n, ch, frames = int(windows.shape[0]), int(self.header.num_channels), int(frames)
+        if placed:
+            spans = e.window_table(spans, ordered, name="spans", rows=n)
         if gained:
             if dtype == torch.int16:
                 raise ValueError("gain / accumulate: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
@@ -1135,7 +1160,17 @@ class WindowDecodePlan:
                      contiguous=True)
         kind = kinds[dtype]
         cur = self.engine._enter() if ordered else None
-        if gained:
+        if placed and rows:
+            _check("AADHip_WindowDecodePlanRunPlaced",
+                   self.engine.lib.AADHip_WindowDecodePlanRunPlaced(self.handle, data.data_ptr(), n, windows.data_ptr(), spans.data_ptr(),
+                                                                    frames, kind, out.data_ptr(),
+                                                                    gain.data_ptr() if gain is not None else None,
+                                                                    WINDOW_GAIN_ADD if accumulate else WINDOW_GAIN_STORE))
+        elif placed:
+            _check("AADHip_WindowDecodePlanRunPlacedStats",
+                   self.engine.lib.AADHip_WindowDecodePlanRunPlacedStats(self.handle, data.data_ptr(), n, windows.data_ptr(),
+                                                                         spans.data_ptr(), frames, stats.data_ptr()))
+        elif gained:
             _check("AADHip_WindowDecodePlanRunGain",
                    self.engine.lib.AADHip_WindowDecodePlanRunGain(self.handle, data.data_ptr(), n, windows.data_ptr(), frames, kind,
                                                                   out.data_ptr(), gain.data_ptr() if gain is not None else None,

@@ -84,7 +84,7 @@ const char *AADHip_ContextLastError(const struct AADHipContext *context);
 
 /* Cross-stream ordering and kernel timing without packets of their own.  `hip_start_event` / `hip_stop_event` (hipEvent_t the
  * caller owns; either may be NULL, both NULL withdraws) are recorded when the work of the NEXT AADHip_EncodePlanRun /
- * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_WindowReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_WindowDecodePlanRunStats / AADHip_WindowDecodePlanRunGain / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
+ * AADHip_PlanarEncodePlanRun / AADHip_PlanarReconstructPlanRun / AADHip_PlanarReconstructPlanRunStats / AADHip_WindowReconstructPlanRun / AADHip_DecodePlanRun / AADHip_WindowDecodePlanRun / AADHip_WindowDecodePlanRunStats / AADHip_WindowDecodePlanRunGain / AADHip_WindowDecodePlanRunPlaced / AADHip_WindowDecodePlanRunPlacedStats / AADHip_ReconstructPlanRun call on this context starts / is done - one-shot:
  * the run takes them.  An encode, decode or window decode plan run is one kernel (a mixed-format or channel-mix window decode several: start on the first, stop on
  * the last; a run that first clears a statistics table - AADHip_WindowDecodePlanRunStats, a segmented AADHip_PlanarReconstructPlanRunStats - records the
  * start event with hipEventRecord in front of the clear and its last kernel carries the stop event), and the events ride on that kernel's own dispatch (hipExtLaunchKernelGGL's start and
@@ -246,7 +246,7 @@ struct AADHipWindow {
   uint64_t first_frame; /* first frame of the window */
 };
 /* AAD_HIP_SAMPLE_FLOAT16 and AAD_HIP_SAMPLE_BFLOAT16: 2-byte float rows for a model under autocast, without a cast pass over a
- * float32 batch.  They are sample types of AADHip_WindowDecodePlanRun, AADHip_WindowDecodePlanRunStats and AADHip_WindowDecodePlanRunGain alone, for plans of all
+ * float32 batch.  They are sample types of AADHip_WindowDecodePlanRun, AADHip_WindowDecodePlanRunStats, AADHip_WindowDecodePlanRunGain and AADHip_WindowDecodePlanRunPlaced alone, for plans of all
  * three constructors; the planar encode, planar reconstruct and window reconstruct entry points refuse them, and 2 and 3 are no
  * sample type anywhere.
  *
@@ -428,6 +428,61 @@ AADApiResult AADHip_WindowDecodePlanRunGain(
     uint32_t frames_per_window, int32_t sample_type, void *device_out,
     const float *device_gain, /* num_windows floats on the device, 4-byte aligned; NULL: every gain is 1 */
     int32_t mode);            /* enum AADHipWindowGainMode */
+
+/* Window decode with a span per window: a crop of L frames that starts at element o of its row instead of filling it - a noise
+ * event, a second talker or an impulse shorter than the row, added at a random offset into a batch that is already there; a
+ * variable-length utterance with zeros behind it, or in front of it for centred and right-aligned padding and random time shifts;
+ * and the level of the L frames alone, which the SNR of an event needs.  For all three kinds of window decode plan; asynchronous
+ * on the context's stream.  The span table stays on the device and the host never reads it, exactly like the window table.
+ *
+ * Definition.  T = frames_per_window, (L, o) = the span of window w; a NULL table: every span is (T, 0).
+ *   Le = 0 if o >= T, else min(L, T - o)  - the comparison first: no sum of two 64-bit values is formed, huge and wrapped int64
+ *   values are not an error.
+ * Let f[c][i] be the float32 value AADHip_WindowDecodePlanRun with AAD_HIP_SAMPLE_FLOAT32 writes to element i of row c for the same
+ * plan, data and window {stream, first_frame}: +0 past num_samples, for stray windows and for wrapped values included, and
+ * (L + R) * 2^-16 for the down-mix.  Let g = device_gain[w] (1 with NULL) and p = fl32(g * f), exactly as in
+ * AADHip_WindowDecodePlanRunGain.
+ *   Inside the span, o <= t < o + Le:   STORE  the element becomes p[c][t - o]
+ *                                       ADD    the element becomes fl32(old + p[c][t - o])
+ *     then rounded once to the row's type; the multiply and the add are two roundings, never a fused multiply-add.
+ *   Outside the span:                   STORE  the element becomes +0 - not g * 0: a negative gain gives no -0 there
+ *                                       ADD    the element is neither read nor written: an old -0 stays -0, a NaN keeps its bits
+ * In torch, per window: row = zeros (STORE) or out[w] (ADD), then
+ *   row[:, o:o+Le] = (row[:, o:o+Le].float() + g * row_float32[:, :Le]).to(dtype)        without `row.float() +` under STORE.
+ * Every element is written at most once per run, by one lane, under STORE exactly once: a run is deterministic.  With NULL spans,
+ * or (T, 0) in every record, the bytes are those of AADHip_WindowDecodePlanRunGain.
+ *
+ * Statistics (AADHip_WindowDecodePlanRunPlacedStats): records only, no rows.  With v the int16 value of
+ * AADHip_WindowDecodePlanRunStats' definition at crop index i, sum_sq, sum_abs and max_abs run over i < Le, and
+ * count = min(Le, num_samples - first_frame): 0 for a stray window, a wrapped value or first_frame >= num_samples.  Every one of
+ * the N * C records is written; the run clears the table first - AADHip_ContextSignalNextRun's start event sits in front of the
+ * clear, its stop event rides on the last kernel.  With NULL spans the table is that of AADHip_WindowDecodePlanRunStats with
+ * device_out == NULL.
+ *
+ * Errors.  Those of AADHip_WindowDecodePlanRunGain (AAD_HIP_SAMPLE_INT16 refused included) and of
+ * AADHip_WindowDecodePlanRunStats respectively, plus AAD_APIRESULT_INVALID_ARGUMENT for a device_spans that is not 8-byte
+ * aligned.  num_windows == 0 is OK and launches nothing.  A refused run writes nothing.
+ *
+ * Out of scope, deliberately: int16 rows; a run with both rows and statistics (the levels come first, as for the gain run); more
+ * than one span per row in a run - several events in one row are several ADD runs; a span that loops a short stream.
+ *
+ * The run launches the kernels, lanes and launch plans of the run without spans for the same T; under STORE the K lanes of a
+ * window share the zeros outside its span, each the tile it owns in a run without spans. */
+struct AADHipWindowSpan {   /* a contiguous torch int64 [N, 2] tensor on the device IS the table */
+  uint64_t num_frames;      /* L: frames of the crop */
+  uint64_t out_frame;       /* o: row element that receives frame first_frame */
+};
+AADApiResult AADHip_WindowDecodePlanRunPlaced(
+    struct AADHipWindowDecodePlan *plan, const uint8_t *device_data,
+    uint64_t num_windows, const struct AADHipWindow *device_windows,
+    const struct AADHipWindowSpan *device_spans,   /* NULL: every span is (T, 0) */
+    uint32_t frames_per_window, int32_t sample_type, void *device_out,
+    const float *device_gain, int32_t mode);
+AADApiResult AADHip_WindowDecodePlanRunPlacedStats(
+    struct AADHipWindowDecodePlan *plan, const uint8_t *device_data,
+    uint64_t num_windows, const struct AADHipWindow *device_windows,
+    const struct AADHipWindowSpan *device_spans,   /* NULL: every span is (T, 0) */
+    uint32_t frames_per_window, struct AADHipRowStats *device_stats);
 
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 

@@ -57,8 +57,19 @@ float32 rows, same-format plan, two window tables (a "signal" and a "noise" draw
   median of the rounds' medians and its spread the range of the rounds' medians.  (b)+(c)'s rows are compared bitwise with torch's
   two-rounding expression x * gs + y * gn over the plain rows ((d)'s own expression may be contracted differently by torch).
 
+--placed (profiles/window_decode_placed.txt): the run with a span per window (AADHip_WindowDecodePlanRunPlaced) on --gain's
+corpus, float32 rows, same-format plan, one window table, one gain table:
+  (a) AADHip_WindowDecodePlanRunGain, STORE;
+  (b) the placed run, STORE, every span (T, 0);
+  (c) the placed run, STORE, L = T / 2 at a random o in [0, T - L];
+  (d) the placed run, ADD, L = T / 4 at a random o in [0, T - L], into rows that are there;
+  (e) what (d) replaces: a plain run with T' = T / 4 into a temporary, then out[w, :, o:o+L] += g[w] * tmp[w] for all windows in
+      one torch scatter-add over an index tensor (a loop over the distinct offsets would be N small kernels).
+  Warm-up, alternating rounds and the figures as under --gain.  (b)'s rows are compared bitwise with (a)'s, (c)'s and (d)'s with
+  torch's expression of the definition over the plain rows.
+
 Usage: python tools/window_decode_bench.py [--streams 1000] [--seconds 60] [--windows 4096 64] [--frames 48000] [--reps 25]
-       [--mixed | --channel-mix | --stats | --half | --gain]"""
+       [--mixed | --channel-mix | --stats | --half | --gain | --placed]"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -554,6 +565,98 @@ def gain_main(args, say):
     engine.close()
 
 
+def placed_main(args, say):
+    import torch
+    from aad_amd.engine import Engine, parse_header
+    engine = Engine(0)
+    samples, frames, streams = int(round(args.seconds * 48000)), args.frames, args.streams
+    rounds, results = 5, []
+    corpus, size, stride = build_corpus(engine, torch, streams, samples, seed=args.seed)
+    hd = parse_header(bytes(corpus[0, :31].cpu().numpy()))
+    plan = engine.uniform_window_decode_plan(hd, streams, stride, size)
+    half, quarter = frames // 2, frames // 4
+    say("window decode with spans: %d stereo 4-bit streams x %d frames (spb %d), T = %d, float32 rows; %d alternating rounds of %d "
+        "calls, median of the rounds' medians (range of the rounds' medians); device %s"
+        % (streams, samples, hd.num_samples_per_block, frames, rounds, args.reps, torch.cuda.get_device_name(0)))
+    for n in args.windows:
+        g = torch.Generator(device="cuda")
+        g.manual_seed(args.seed + n)
+        win = torch.stack([torch.randint(0, streams, (n,), device="cuda", generator=g),
+                           torch.randint(0, samples - frames + 1, (n,), device="cuda", generator=g)], dim=1)
+        gain = torch.rand((n,), device="cuda", generator=g) + 0.5
+        span = lambda length: torch.stack([torch.full((n,), length, dtype=torch.int64, device="cuda"),
+                                           torch.randint(0, frames - length + 1, (n,), device="cuda", generator=g)], dim=1)
+        full = torch.stack([torch.full((n,), frames, dtype=torch.int64, device="cuda"), torch.zeros((n,), dtype=torch.int64, device="cuda")], dim=1)
+        span_c, span_d = span(half), span(quarter)
+        base = torch.rand((n, 2, frames), device="cuda", generator=g) - 0.5
+        out_a = torch.empty((n, 2, frames), dtype=torch.float32, device="cuda")
+        out_b, out_c = torch.empty_like(out_a), torch.empty_like(out_a)
+        out_d, out_e = base.clone(), base.clone()
+        tmp = torch.empty((n, 2, quarter), dtype=torch.float32, device="cuda")
+        index = (span_d[:, 1, None] + torch.arange(quarter, device="cuda")[None, :])[:, None, :].expand(n, 2, quarter).contiguous()
+
+        def a():
+            plan.run(corpus, win, frames, torch.float32, out=out_a, gain=gain)
+
+        def b():
+            plan.run(corpus, win, frames, torch.float32, out=out_b, gain=gain, spans=full)
+
+        def c():
+            plan.run(corpus, win, frames, torch.float32, out=out_c, gain=gain, spans=span_c)
+
+        def d():
+            plan.run(corpus, win, frames, torch.float32, out=out_d, gain=gain, accumulate=True, spans=span_d)
+
+        def e():
+            plan.run(corpus, win, quarter, torch.float32, out=tmp)
+            out_e.scatter_add_(2, index, gain[:, None, None] * tmp)
+
+        sides = [a, b, c, d, e]
+        for _ in range(3):
+            for f in sides:
+                f()
+        torch.cuda.synchronize()
+        times = [[] for _ in sides]
+        for _ in range(rounds):
+            for t, f in zip(times, sides):
+                t.append(call_ms(torch, f, args.reps))
+        med = [float(np.median(t)) for t in times]
+        rng = [max(t) - min(t) for t in times]
+        # the rows: (b) == (a); (c) and (d) == the definition over the plain rows, two roundings
+        a(), b(), c()
+        out_d.copy_(base)
+        d()
+        x = plan.run(corpus, win, frames, torch.float32)
+        x.mul_(gain[:, None, None])
+        t_idx = torch.arange(frames, device="cuda")[None, :]
+        inside = ((t_idx >= span_c[:, 1, None]) & (t_idx < span_c[:, 1, None] + half))[:, None, :]
+        src = (t_idx - span_c[:, 1, None]).clamp(0, frames - 1)[:, None, :].expand(n, 2, frames)
+        want_c = torch.where(inside, x.gather(2, src), torch.zeros((), device="cuda"))
+        inside = ((t_idx >= span_d[:, 1, None]) & (t_idx < span_d[:, 1, None] + quarter))[:, None, :]
+        src = (t_idx - span_d[:, 1, None]).clamp(0, frames - 1)[:, None, :].expand(n, 2, frames)
+        shifted = x.gather(2, src)
+        shifted.add_(base)              # the second rounding, a kernel of its own
+        want_d = torch.where(inside, shifted, base)
+        torch.cuda.synchronize()
+        bits = lambda t: t.view(torch.int32)
+        exact = [bool(torch.equal(bits(out_b), bits(out_a))), bool(torch.equal(bits(out_c), bits(want_c))),
+                 bool(torch.equal(bits(out_d), bits(want_d)))]
+        ta, tb, tc, td, te = med
+        say("  N = %5d (%.1f MB of rows): (a) RunGain STORE %.4f ms (range %.4f); (b) placed STORE (T, 0) %.4f ms (range %.4f), "
+            "(b) / (a) = %.3f; (c) placed STORE L = T/2 %.4f ms (range %.4f), (c) / (a) = %.3f; (d) placed ADD L = T/4 %.4f ms "
+            "(range %.4f); (e) plain run of T/4 + torch scatter-add %.4f ms (range %.4f), (e) / (d) = %.2fx; rows: (b) == (a): %s, "
+            "(c) == definition: %s, (d) == definition: %s"
+            % (n, n * 2 * frames * 4 / 1e6, ta, rng[0], tb, rng[1], tb / ta, tc, rng[2], tc / ta, td, rng[3], te, rng[4], te / td,
+               exact[0], exact[1], exact[2]))
+        results.append(dict(windows=n, a_ms=ta, b_ms=tb, c_ms=tc, d_ms=td, e_ms=te, ranges_ms=rng, exact=exact))
+        del out_a, out_b, out_c, out_d, out_e, tmp, index, base, x, want_c, want_d, inside, src, shifted
+        torch.cuda.empty_cache()
+    say("")
+    say("json " + json.dumps(results))
+    plan.close()
+    engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=1000)
@@ -568,6 +671,7 @@ def main():
     ap.add_argument("--stats", action="store_true", help="the statistics run against the row run and torch reductions (see above)")
     ap.add_argument("--half", action="store_true", help="the run's kernel per sample type, float16 and bfloat16 included (see above)")
     ap.add_argument("--gain", action="store_true", help="the gain run: STORE, ADD and both against two plain runs + torch (see above)")
+    ap.add_argument("--placed", action="store_true", help="the run with spans against the gain run and a plain run + torch (see above)")
     args = ap.parse_args()
 
     import torch
@@ -578,9 +682,9 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    if args.mixed or args.channel_mix or args.stats or args.half or args.gain:
+    if args.mixed or args.channel_mix or args.stats or args.half or args.gain or args.placed:
         (mixed_main if args.mixed else channel_mix_main if args.channel_mix else stats_main if args.stats else
-         half_main if args.half else gain_main)(args, say)
+         half_main if args.half else gain_main if args.gain else placed_main)(args, say)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "a" if args.half else "w") as fh:  # --half: one report per library, appended
