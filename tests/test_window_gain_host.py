@@ -1,6 +1,9 @@
 """Window decode with a per-window gain (AADHip_WindowDecodePlanRunGain), what can be checked without a device:
   * the symbol: in include/aad_hip.h and in HIP_SYMBOLS, 9 arguments, the enum's values;
   * tests/window_gain_oracle.py pinned on hand-computed cases, and each of its witnesses confirmed with fractions.Fraction;
+  * the vector-path witnesses of every case of tests/test_gpu_window_decode_matrix.py: each confirmed with fractions.Fraction, the
+    four classes of a chunk covered per stream and kind, each element on the chunk path by the formula and by a restatement of
+    the lane's arithmetic;
   * snr_gains against a float64 computation on crafted tables;
   * the engine's refusals, over the library that records its calls (tests/test_engine_tensor_contract.py)."""
 import ctypes as C
@@ -130,6 +133,118 @@ def test_witness_windows_point_at_the_header_samples():
     for i, t, old in olds:
         sample = hist[windows[i, 1] // spb][t]
         assert (np.float32(old), gains[i], sample) in [(np.float32(o), g, s) for o, g, s in w["fused"]]
+
+
+# ---- the witnesses on the vector path ----------------------------------------------------------------------------------------------
+def _matrix_cases():
+    """every case of tests/test_gpu_window_decode_matrix.py, as the GPU file itself builds it (on the CPU, cached)"""
+    import test_gpu_window_decode_matrix as gm
+    import window_matrix as wm
+    keys = [("same", g) for g in wm.GEOMETRIES] + [("mixed", p) for p in wm.MIXED_PLANS] + [("mix", oc) for oc in wm.OUT_CHANNELS]
+    return gm, [(k, gm.matrix_case(*k)) for k in keys]
+
+
+def test_chunk_elements_and_classes_by_hand():
+    assert list(go.chunk_elements(150, 225)) == list(range(4, 4 + 16 * 9))   # (150 - 4) // 16 = 9 chunks, the crop is longer
+    assert list(go.chunk_elements(150, 40)) == list(range(4, 36))            # (40 - 4) // 16 = 2: the span ends inside the third
+    assert list(go.chunk_elements(19, 225)) == [] and list(go.chunk_elements(150, 3)) == []
+    assert [int(go.chunk_class(np.int64(t))) for t in (4, 5, 11, 12, 13, 19, 20, 21, 28)] == [0, 1, 1, 2, 3, 3, 0, 1, 2]
+
+
+def test_vector_witnesses_of_the_matrix_are_witnesses():
+    """each witness the matrix cases carry, with fractions.Fraction on the oracle's own row value: never with the code under test"""
+    gm, cases = _matrix_cases()
+    fr = lambda v: Fraction(float(v))
+    total = 0
+    for key, case in cases:
+        assert len(case.witnesses) == 16 * len(case.variants) > 0
+        for i, w in enumerate(case.witnesses):
+            k = case.n_plain + i
+            stream = int(case.windows[k, 0])
+            mono_twin = key[0] == "mix" and case.channels == 2 and case.headers[stream].num_channels == 1
+            down = key[0] == "mix" and case.channels == 1 and case.headers[stream].num_channels == 2
+            scale = 65536 if down else 32768
+            f = fr(case.rows32[k, w.channel, w.t])
+            s = f * scale
+            assert s.denominator == 1 and 0 < abs(s) <= (65535 if down else 32768), (key, i, f)  # the integer the decoder holds
+            g = fr(w.gain)
+            assert case.gains[k] == w.gain and fr(np.float32(w.gain)) == g
+            exact = g * f
+            one = np.array([w.gain], dtype=np.float32)
+            row = case.rows32[k:k + 1, w.channel:w.channel + 1, w.t:w.t + 1]
+            if w.kind.startswith("double_"):
+                name = w.kind[len("double_"):]
+                by_definition = go.round_fraction(go.round_fraction(exact, "float32"), name)
+                assert by_definition != go.round_fraction(exact, name), (key, i, w)
+                assert fr(go.from_bits(go.gain_expected(row, one, name), name).float().item()) == by_definition
+                assert w.olds is None
+            elif w.kind == "fused":
+                rows = [r for r, _ in w.olds]
+                assert rows == ([0, 1] if mono_twin else [w.channel]), (key, i, w)
+                assert len({old for _, old in w.olds}) == len(w.olds)  # twin rows: two different old values
+                for r, old in w.olds:
+                    assert case.rows32[k, r, w.t] == case.rows32[k, w.channel, w.t]
+                    assert go.round_fraction(fr(old), "bfloat16") == fr(old)  # a value of every row type
+                    two = go.round_fraction(fr(old) + go.round_fraction(exact, "float32"), "float32")
+                    assert two != go.round_fraction(fr(old) + exact, "float32"), (key, i, w)
+                    old_bits = np.array([[[np.float32(old).view(np.uint32)]]], dtype=np.uint32)
+                    assert fr(go.from_bits(go.gain_expected(row, one, "float32", old_bits), "float32").item()) == two
+                    assert (k, r, w.t, old) in case.olds
+            else:
+                assert w.kind == "order" and 2.0 ** -134 <= float(w.gain) < 2.0 ** -133 and w.olds is None
+                once = go.round_fraction(exact, "float32")
+                twice = go.round_fraction(go.round_fraction(g * s, "float32") / scale, "float32")
+                assert once != twice and abs(once) < Fraction(2) ** -126, (key, i, w)
+                assert fr(go.from_bits(go.gain_expected(row, one, "float32"), "float32").item()) == once
+            total += 1
+    assert total == 16 * (12 + 3 + 6 + 3 + 9 + 9)
+
+
+def test_vector_witnesses_cover_the_four_classes_and_rotate_the_channel():
+    _, cases = _matrix_cases()
+    for key, case in cases:
+        by_stream = {}
+        for i, w in enumerate(case.witnesses):
+            stream = int(case.windows[case.n_plain + i, 0])
+            by_stream.setdefault((stream, w.kind), []).append(w)
+        assert len(by_stream) == len(go.VECTOR_KINDS) * len(case.variants)
+        for (stream, kind), ws in by_stream.items():
+            classes = sorted(((w.t - 4) % 2, (w.t - 4) % 16 >= 8) for w in ws)  # the half of the word, the put8 call
+            assert classes == [(0, False), (0, True), (1, False), (1, True)], (key, stream, kind, classes)
+            assert [int(go.chunk_class(np.int64(w.t))) for w in ws] == [0, 1, 2, 3]
+        for stream in {s for s, _ in by_stream}:
+            if case.rows32.shape[1] > 1:
+                seen = {w.channel for (s, _), ws in by_stream.items() if s == stream for w in ws}
+                assert len(seen) == case.rows32.shape[1], (key, stream, seen)
+
+
+def test_vector_witnesses_lie_on_the_chunk_path():
+    """by the formula - t in [4, 4 + 16 m), m = min((spb - 4) // 16, (Le - 4) // 16), the window on a block boundary of a complete
+    block - and by a restatement of the lane's own arithmetic: lane k = 0 of the window keeps [lo, hi) = [0, min(spb, Le)),
+    decodes n = min(num_samples - first_frame, hi) samples, of them (n - 4) // 16 whole chunks, and chunk t0 goes out by the vector
+    stores when whole(t0): t0 >= lo and t0 + 16 <= hi.  Le: T in the gain run, the clipped span in the placed run."""
+    gm, cases = _matrix_cases()
+    for key, case in cases:
+        frames = case.frames
+        for i, w in enumerate(case.witnesses):
+            k = case.n_plain + i
+            stream, first = case.windows[k].tolist()
+            spb, header = case.spbs[stream], case.headers[stream]
+            block = first // spb
+            assert first % spb == 0 and first + spb <= case.lengths[stream]                   # a block boundary, a complete block
+            assert 31 + (block + 1) * header.block_size + 18 <= len(case.images[stream])      # ... untruncated, another one behind
+            length, o = case.spans[k].tolist()
+            assert o == 1 + i % gm.WITNESS_SHIFTS and 0 < o and length == frames - o
+            for le in (frames, min(length, frames - o)):
+                m = min((spb - 4) // 16, (le - 4) // 16)
+                assert m >= 2 and 4 <= w.t < 4 + 16 * m, (key, i, w, le)
+                assert w.t in go.chunk_elements(spb, le)
+                lo, hi = 0, min(spb, le)
+                n = min(case.lengths[stream] - first, hi)
+                full = (n - 4) // 16
+                t0 = 4 + 16 * ((w.t - 4) // 16)
+                assert (t0 - 4) // 16 < full and t0 >= lo and t0 + 16 <= hi, (key, i, w, le)
+            assert o + w.t < frames
 
 
 # ---- snr_gains ---------------------------------------------------------------------------------------------------------------------
