@@ -66,6 +66,14 @@ class AADHipWindowSpan(C.Structure):  # include/aad_hip.h: one row of a torch in
     _fields_ = [("num_frames", C.c_uint64), ("out_frame", C.c_uint64)]
 
 
+class AADHipResampleRatio(C.Structure):  # include/aad_hip.h: output rate / source rate
+    _fields_ = [("up", C.c_uint32), ("down", C.c_uint32)]
+
+
+class AADHipResampleLane(C.Structure):  # include/aad_hip.h: one row of a torch int32 [N, 2] tensor (Resampler.run)
+    _fields_ = [("bank", C.c_uint32), ("shift", C.c_uint32)]
+
+
 class AADHipLaneState(C.Structure):  # include/aad_hip.h
     _fields_ = [("weight", C.c_int32 * 4), ("history", C.c_int32 * 4),
                 ("stepsize_index", C.c_int32), ("quantize_error", C.c_int32)]
@@ -77,6 +85,7 @@ ERROR_STATS_DTYPE = np.dtype([("rms_error", "<f8"), ("mean_abs_error", "<f8"), (
 WINDOW_DTYPE = np.dtype([("stream", "<i8"), ("first_frame", "<i8")])  # struct AADHipWindow: an int64 pair, a torch int64 [N, 2] row
 SAMPLE_INT16, SAMPLE_FLOAT32 = 0, 1  # enum AADHipSampleType
 SAMPLE_FLOAT16, SAMPLE_BFLOAT16 = 4, 5  # window decode rows alone (WindowDecodePlan.run)
+RESAMPLE_NO_BANK = 0xFFFF  # a select entry of AADHip_ResamplerCreate: the row is zeros
 WINDOW_GAIN_STORE, WINDOW_GAIN_ADD = 0, 1  # enum AADHipWindowGainMode (WindowDecodePlan.run with gain / accumulate)
 RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL = 0, 1  # enum AADHipReconstructOutput
 OPTION_LANE_MAPPING, OPTION_TRIAL_LANES, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_COMPARE_ORDER = 0, 1, 2, 3, 4  # enum AADHipOption
@@ -110,6 +119,8 @@ HIP_SYMBOLS = [
     "AADHip_PlanarEncodePlanCreate", "AADHip_PlanarEncodePlanRun",
     "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
     "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
+    "AADHip_ResamplerCreate", "AADHip_ResamplerDestroy", "AADHip_ResamplerBank", "AADHip_ResamplerSourceFrames",
+    "AADHip_ResamplerResolve", "AADHip_ResamplerRun",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -229,6 +240,18 @@ def _declare_hip(lib):
     lib.AADHip_WindowDecodePlanRunPlaced.restype = C.c_int
     lib.AADHip_WindowDecodePlanRunPlacedStats.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp]
     lib.AADHip_WindowDecodePlanRunPlacedStats.restype = C.c_int
+    lib.AADHip_ResamplerCreate.argtypes = [vp, C.c_uint32, C.POINTER(AADHipResampleRatio), C.c_uint32, C.c_uint32, vp, C.POINTER(vp)]
+    lib.AADHip_ResamplerCreate.restype = C.c_int
+    lib.AADHip_ResamplerDestroy.argtypes = [vp]
+    lib.AADHip_ResamplerDestroy.restype = None
+    lib.AADHip_ResamplerBank.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, C.c_uint64]
+    lib.AADHip_ResamplerBank.restype = C.c_int
+    lib.AADHip_ResamplerSourceFrames.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.AADHip_ResamplerSourceFrames.restype = C.c_int
+    lib.AADHip_ResamplerResolve.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp]
+    lib.AADHip_ResamplerResolve.restype = C.c_int
+    lib.AADHip_ResamplerRun.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_int32, vp]
+    lib.AADHip_ResamplerRun.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

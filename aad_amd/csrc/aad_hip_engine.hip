@@ -33,6 +33,7 @@
 #include "aad_encode_launch.hip.h"
 #include "aad_format.h"
 #include "aad_hip_internal.h"
+#include "aad_resample.hip.h"
 #include "aad_tiles.h"
 #include "aad_window_reconstruct.hip.h"
 
@@ -161,6 +162,18 @@ struct AADHipWindowDecodePlan {
   bool channel_mix;
   aad::ChannelStreamFormat *d_mix_formats; /* one record per stream */
   aad::ChannelMixVariants mix_variants;
+};
+
+/* AADHip_ResamplerCreate: the banks on the host (AADHip_ResamplerBank reads them) and on the device, the select table */
+struct AADHipResampler {
+  AADHipContext *ctx = nullptr;
+  uint32_t num_streams = 0, variants = 0;
+  std::vector<aad::ResampleBankDesc> banks; /* one per ratio, in the caller's order */
+  std::vector<int16_t> coefficients;
+  uint64_t bank_elements = 0, span_elements = 0; /* the FIR kernel's LDS, in int16 elements: the largest bank and span */
+  uint16_t *d_select = nullptr, *d_lead = nullptr;
+  aad::ResampleBankDesc *d_banks = nullptr;
+  int16_t *d_coefficients = nullptr;
 };
 
 struct AADHipReconstructPlan {
@@ -1442,6 +1455,192 @@ AADApiResult AADHip_WindowDecodePlanRunPlacedStats(struct AADHipWindowDecodePlan
 {
   return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, AAD_HIP_SAMPLE_INT16, nullptr, true,
                            device_stats, WindowGainRun{false, nullptr, 0}, 0, WindowPlacedRun{true, device_spans});
+}
+
+/* ------------------------------------------------------------------------------ resample -- */
+
+static_assert(sizeof(AADHipResampleLane) == sizeof(aad::ResampleLane), "lane record layout");
+
+AADApiResult AADHip_ResamplerCreate(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
+                                    uint32_t num_streams, uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler)
+{
+  if (ctx == nullptr || resampler == nullptr || ratios == nullptr || num_ratios == 0 || num_ratios >= aad::kResampleNoBank ||
+      variants == 0 || (num_streams != 0 && select == nullptr))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *resampler = nullptr;
+  const uint64_t entries = (uint64_t)num_streams * variants;
+  for (uint64_t i = 0; i < entries; i++)
+    if (select[i] != aad::kResampleNoBank && select[i] >= num_ratios) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipResampler *r = new (std::nothrow) AADHipResampler();
+  if (r == nullptr) return AAD_APIRESULT_NG;
+  r->ctx = ctx;
+  r->num_streams = num_streams;
+  r->variants = variants;
+  std::vector<uint16_t> lead(num_ratios);
+  for (uint32_t i = 0; i < num_ratios; i++) {
+    aad::ResampleRatio q;
+    if (!aad::resample_reduce(ratios[i].up, ratios[i].down, &q) || !aad::resample_shape_ok(q.L, q.M)) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error),
+               "resampler: ratio %u (%u / %u) is zero, or has more than 1024 phases, 256 taps or 65536 bytes of bank", i, ratios[i].up,
+               ratios[i].down);
+      delete r;
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    const uint32_t K = (uint32_t)aad::resample_taps(q.L, q.M);
+    const size_t at = r->coefficients.size();
+    r->coefficients.resize(at + (size_t)q.L * K);
+    if (!aad::resample_build_bank(q.L, q.M, r->coefficients.data() + at)) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "resampler: ratio %u (%u / %u) has a phase with sum |h| above 65535", i,
+               ratios[i].up, ratios[i].down);
+      delete r;
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    r->banks.push_back(aad::ResampleBankDesc{q.L, q.M, K, (uint32_t)at});
+    lead[i] = (uint16_t)(K / 2 - 1);
+    r->bank_elements = std::max<uint64_t>(r->bank_elements, (uint64_t)q.L * aad::resample_lds_stride(K));
+    r->span_elements = std::max<uint64_t>(r->span_elements, aad::resample_span_elements(q.L, q.M, K));
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &r->d_select, select, (size_t)entries) || !upload(ctx, &r->d_lead, lead.data(), lead.size()) ||
+      !upload(ctx, &r->d_banks, r->banks.data(), r->banks.size()) ||
+      !upload(ctx, &r->d_coefficients, r->coefficients.data(), r->coefficients.size())) {
+    AADHip_ResamplerDestroy(r);
+    return AAD_APIRESULT_NG;
+  }
+  *resampler = r;
+  return AAD_APIRESULT_OK;
+}
+
+void AADHip_ResamplerDestroy(struct AADHipResampler *r)
+{
+  if (r == nullptr) return;
+  DeviceGuard guard(r->ctx);
+  if (guard.ok) {
+    (void)hipStreamSynchronize(r->ctx->stream);
+    if (r->d_select) (void)hipFree(r->d_select);
+    if (r->d_lead) (void)hipFree(r->d_lead);
+    if (r->d_banks) (void)hipFree(r->d_banks);
+    if (r->d_coefficients) (void)hipFree(r->d_coefficients);
+  }
+  delete r;
+}
+
+AADApiResult AADHip_ResamplerBank(const struct AADHipResampler *r, uint32_t ratio, uint32_t *L, uint32_t *M, uint32_t *taps,
+                                  int16_t *coefficients, uint64_t capacity)
+{
+  if (r == nullptr || ratio >= r->banks.size() || L == nullptr || M == nullptr || taps == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  const aad::ResampleBankDesc &b = r->banks[ratio];
+  if (coefficients != nullptr && capacity < (uint64_t)b.L * b.K) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
+  *L = b.L;
+  *M = b.M;
+  *taps = b.K;
+  if (coefficients != nullptr) memcpy(coefficients, r->coefficients.data() + b.offset, sizeof(int16_t) * b.L * b.K);
+  return AAD_APIRESULT_OK;
+}
+
+namespace {
+/* T_src = max over the banks of ((T - 1) M) div L + K; false for T == 0 and a bank with (T - 1) M >= 2^31 */
+bool resampler_source_frames(const AADHipResampler *r, uint32_t frames, uint32_t *source_frames)
+{
+  uint64_t most = 0;
+  for (const aad::ResampleBankDesc &b : r->banks) {
+    uint64_t n = 0;
+    if (!aad::resample_source_frames(frames, b.L, b.M, b.K, &n)) return false;
+    most = std::max(most, n);
+  }
+  *source_frames = (uint32_t)most; /* < 2^31 + 256 */
+  return true;
+}
+} /* namespace */
+
+AADApiResult AADHip_ResamplerSourceFrames(const struct AADHipResampler *r, uint32_t frames, uint32_t *source_frames)
+{
+  if (r == nullptr || source_frames == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  uint32_t n = 0;
+  if (!resampler_source_frames(r, frames, &n)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  *source_frames = n;
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_ResamplerResolve(struct AADHipResampler *r, uint64_t num_windows, const struct AADHipWindow *device_windows,
+                                     const int64_t *device_variant, uint32_t frames, struct AADHipWindow *device_source_windows,
+                                     struct AADHipResampleLane *device_lanes)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = r->ctx;
+  uint32_t source_frames = 0;
+  if (!resampler_source_frames(r, frames, &source_frames) || device_windows == nullptr || device_source_windows == nullptr ||
+      device_lanes == nullptr || num_windows > (uint64_t)INT32_MAX * 256u ||
+      ((reinterpret_cast<uintptr_t>(device_windows) | reinterpret_cast<uintptr_t>(device_variant) |
+        reinterpret_cast<uintptr_t>(device_source_windows)) & 7u) != 0 ||
+      (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "resampler resolve: a null or unaligned table, %u frames (0, or (T - 1) M >= 2^31 for a bank), or %llu windows", frames,
+             (unsigned long long)num_windows);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_windows == 0) return AAD_APIRESULT_OK;
+  aad::ResampleResolveArgs a;
+  a.windows = reinterpret_cast<const uint64_t *>(device_windows);
+  a.variant = reinterpret_cast<const uint64_t *>(device_variant);
+  a.select = r->d_select;
+  a.lead = r->d_lead;
+  a.num_windows = num_windows;
+  a.num_streams = r->num_streams;
+  a.variants = r->variants;
+  a.source_windows = reinterpret_cast<uint64_t *>(device_source_windows);
+  a.lanes = reinterpret_cast<aad::ResampleLane *>(device_lanes);
+  aad::launch_resample_resolve(a, ctx->stream);
+  return hip_ok(ctx, hipGetLastError(), "resampler resolve launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
+}
+
+AADApiResult AADHip_ResamplerRun(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
+                                 uint32_t source_frames, const struct AADHipResampleLane *device_lanes, uint32_t frames,
+                                 int32_t sample_type, void *device_out)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = r->ctx;
+  const uint64_t elem = sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4 : 2;
+  uint32_t needed = 0;
+  uint64_t rows = 0, n = 0;
+  if (!window_sample_type_ok(sample_type) || channels == 0 || !resampler_source_frames(r, frames, &needed) || source_frames < needed ||
+      device_source_rows == nullptr || device_lanes == nullptr || device_out == nullptr ||
+      (reinterpret_cast<uintptr_t>(device_source_rows) & 1u) != 0 || (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0 ||
+      (reinterpret_cast<uintptr_t>(device_out) & (elem - 1)) != 0 || __builtin_mul_overflow(num_windows, (uint64_t)channels, &rows) ||
+      __builtin_mul_overflow(rows, (uint64_t)frames, &n) || __builtin_mul_overflow(n, elem, &n) ||
+      __builtin_mul_overflow(rows, (uint64_t)source_frames, &n) || __builtin_mul_overflow(n, (uint64_t)2, &n) ||
+      __builtin_mul_overflow(rows, (uint64_t)((frames - 1) / aad::kResampleTile + 1), &n)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "resampler run: an unknown sample type, a null or unaligned pointer, 0 channels, %u frames (0, or (T - 1) M >= 2^31 for a "
+             "bank), source rows of %u frames where %u are needed, or %llu windows x %u channels x frames past 64 bits",
+             frames, source_frames, needed, (unsigned long long)num_windows, channels);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_windows == 0) return AAD_APIRESULT_OK;
+  aad::ResampleRowsArgs a;
+  a.src = device_source_rows;
+  a.lanes = reinterpret_cast<const aad::ResampleLane *>(device_lanes);
+  a.banks = r->d_banks;
+  a.coefficients = r->d_coefficients;
+  a.out = device_out;
+  a.rows = rows;
+  a.channels = channels;
+  a.num_banks = (uint32_t)r->banks.size();
+  a.frames = frames;
+  a.source_frames = source_frames;
+  a.tiles = (frames - 1) / aad::kResampleTile + 1;
+  a.bank_elements = (uint32_t)r->bank_elements;
+  a.span_elements = (uint32_t)r->span_elements;
+  if (!aad::launch_resample_rows(a, sample_type, (uint32_t)(2 * (r->bank_elements + r->span_elements)), ctx->stream)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "resampler run: the device refuses %llu bytes of LDS for a workgroup",
+             (unsigned long long)(2 * (r->bank_elements + r->span_elements)));
+    return AAD_APIRESULT_NG;
+  }
+  return hip_ok(ctx, hipGetLastError(), "resampler run launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
 }
 
 /* -------------------------------------------------------------------- window reconstruct -- */

@@ -1,0 +1,72 @@
+/* aad_resample.hip.h - the device side of the resample stage (AADHip_ResamplerResolve, AADHip_ResamplerRun; include/aad_hip.h
+ * "resample"): the resolve kernel in front of a window decode and the FIR kernel behind it.  The arithmetic is aad_resample.h's. */
+#ifndef AAD_RESAMPLE_HIP_H
+#define AAD_RESAMPLE_HIP_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "aad_resample.h"
+
+namespace aad {
+
+constexpr uint32_t kResampleThreads = 256;
+constexpr uint32_t kResamplePerThread = 4;
+constexpr uint32_t kResampleTile = kResampleThreads * kResamplePerThread; /* outputs of one workgroup's tile */
+
+struct ResampleResolveArgs {
+  const uint64_t *windows; /* struct AADHipWindow[num_windows], device memory */
+  const uint64_t *variant; /* int64[num_windows], device memory; null: every variant is 0 */
+  const uint16_t *select;  /* [num_streams][variants], device memory */
+  const uint16_t *lead;    /* K/2 - 1 per bank, device memory */
+  uint64_t num_windows;
+  uint64_t num_streams;
+  uint32_t variants;
+  uint64_t *source_windows; /* struct AADHipWindow[num_windows] */
+  ResampleLane *lanes;      /* [num_windows] */
+};
+
+/* one bank as the FIR kernel sees it */
+struct ResampleBankDesc {
+  uint32_t L, M, K;
+  uint32_t offset; /* first coefficient, in elements of the coefficient array: phase p's K taps at offset + p * K */
+};
+
+/* int16 elements between two phases of a bank in LDS: adjacent outputs read different phases, each its K taps as K/2 words in
+ * step, so the phases' rows start an odd number of words apart - p -> p * stride / 2 mod 32 then maps 32 phases onto 32 banks */
+__host__ __device__ inline uint32_t resample_lds_stride(uint32_t K) { return (K / 2) % 2 == 0 ? K + 2 : K; }
+/* int16 elements of a tile's span of the source row: the frames from the first output's first tap to the last output's last,
+ * one in front for the 4-byte alignment of the row's loads, and the word a thread at an odd element reads past its last tap */
+inline uint64_t resample_span_elements(uint32_t L, uint32_t M, uint32_t K)
+{
+  return ((((uint64_t)(kResampleTile - 1) * M) / L + 1 + K + 1 + 2) + 1) / 2 * 2;
+}
+/* bytes of LDS of a workgroup whose bank is (L, M, K) */
+inline uint64_t resample_lds_bytes(uint32_t L, uint32_t M, uint32_t K)
+{
+  return 2 * ((uint64_t)L * resample_lds_stride(K) + resample_span_elements(L, M, K));
+}
+
+struct ResampleRowsArgs {
+  const int16_t *src;            /* [num_windows, channels, source_frames] */
+  const ResampleLane *lanes;     /* [num_windows] */
+  const ResampleBankDesc *banks; /* [num_banks], device memory */
+  const int16_t *coefficients;   /* device memory */
+  void *out;                     /* [num_windows, channels, frames] of the sample type */
+  uint64_t rows;                 /* num_windows * channels */
+  uint32_t channels;
+  uint32_t num_banks;
+  uint32_t frames;        /* T */
+  uint32_t source_frames; /* the source rows' length */
+  uint32_t tiles;         /* ceil(T / kResampleTile) */
+  uint32_t bank_elements; /* int16 elements of LDS in front of the span: the largest L * resample_lds_stride(K) */
+  uint32_t span_elements; /* the largest resample_span_elements */
+};
+
+void launch_resample_resolve(const ResampleResolveArgs &a, hipStream_t stream);
+/* lds_bytes: 2 * (bank_elements + span_elements); false when the device refuses that much LDS for a workgroup */
+bool launch_resample_rows(const ResampleRowsArgs &a, int32_t sample_type, uint32_t lds_bytes, hipStream_t stream);
+
+} /* namespace aad */
+
+#endif /* AAD_RESAMPLE_HIP_H */

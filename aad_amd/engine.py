@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import (AADApiResult, AADHeaderInfo, AADHipPlanarLayout, AADHipPlanarOutput, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
+from .capi import (AADApiResult, AADHeaderInfo, AADHipResampleRatio, RESAMPLE_NO_BANK, AADHipPlanarLayout, AADHipPlanarOutput, AADHipSegmentation, ApiError, ERROR_STATS_DTYPE, LANE_MAPPINGS, LANE_STATE_DTYPE,
                    OPTION_COMPARE_ORDER, OPTION_LANE_MAPPING, OPTION_SIMD_ROLE, OPTION_STAGING_THREADS, OPTION_TILE_KBYTES, OPTION_TRIAL_LANES, RECONSTRUCT_DECODED, RECONSTRUCT_RESIDUAL,
                    SAMPLE_BFLOAT16, SAMPLE_FLOAT16, SAMPLE_FLOAT32, SAMPLE_INT16, SIMD_ROLE_OFF, STREAM_DESC_DTYPE, TRIAL_LANES, WINDOW_DTYPE, WINDOW_GAIN_ADD, WINDOW_GAIN_STORE, load_library, make_parameter)
 
@@ -695,6 +695,59 @@ class Engine:
         finally:
             plan.close()  # synchronises the context's stream first
 
+    def resampler(self, ratios, select):
+        """A resample stage behind window decode plans (AADHip_ResamplerCreate): ratios is a list of (up, down), output rate over
+        source rate, each with a bank of its own; select[stream][variant] is the index of the ratio that windows of `stream` drawn
+        with `variant` take, None (or RESAMPLE_NO_BANK) for a row of zeros.  Resampler.run decodes windows at their ratios."""
+        ratios = [(int(u), int(d)) for u, d in ratios]
+        table = np.array([[RESAMPLE_NO_BANK if v is None else int(v) for v in row] for row in select], dtype=np.int64)
+        table = table.reshape(len(table), -1)
+        if table.shape[1] == 0 or (table.size and (table.min() < 0 or table.max() > RESAMPLE_NO_BANK)):
+            raise ValueError("select: [streams][variants] of ratio indices, at least one variant, got shape %s" % (table.shape,))
+        if any(not (0 <= v < 1 << 32) for r in ratios for v in r):
+            raise ValueError("ratios: (up, down) pairs of 32-bit unsigned integers, got %s" % (ratios,))
+        table = np.ascontiguousarray(table, dtype=np.uint16)
+        records = (AADHipResampleRatio * max(len(ratios), 1))(*[AADHipResampleRatio(u, d) for u, d in ratios])
+        handle = C.c_void_p()
+        _check("AADHip_ResamplerCreate",
+               self.lib.AADHip_ResamplerCreate(self._ctx, len(ratios), records, table.shape[0], table.shape[1], table.ctypes.data,
+                                               C.byref(handle)))
+        return Resampler(self, handle, ratios, table)
+
+    def decode_windows_resampled(self, data, image_sizes, windows, frames, rate, speeds=((1, 1),), variant=None, dtype=None,
+                                 channels=None, out=None):
+        """decode_windows_mixed at one output rate: every image's header names its sampling_rate, and a window of stream s drawn
+        with variant v - an index into `speeds`, pairs (a, b) for the speed a / b; `variant` is an int64 cuda tensor [N], None for
+        all 0 - is resampled by rate * b / (sampling_rate_s * a).  Speed 11/10 plays a stream 10 % faster: fewer output frames
+        per source frame.  `frames` counts output frames, windows[:, 1] source frames as everywhere.  Streams and speeds whose
+        reduced ratios agree share a bank.  dtype, channels, out: as decode_windows_mixed."""
+        from math import gcd
+        speeds = [(int(a), int(b)) for a, b in speeds]
+        if int(rate) <= 0 or not speeds or any(a <= 0 or b <= 0 for a, b in speeds):
+            raise ValueError("rate and speeds: positive integers, at least one speed; got rate %r, speeds %r" % (rate, speeds))
+        plan = self._corpus_window_plan(data, image_sizes, channels)
+        try:
+            ratios, select = [], []
+            for h in plan.headers:
+                if h.sampling_rate == 0:
+                    raise ValueError("an image's header has sampling_rate 0: no ratio to resample it by")
+                row = []
+                for a, b in speeds:
+                    up, down = int(rate) * b, int(h.sampling_rate) * a
+                    g = gcd(up, down)
+                    r = (up // g, down // g)
+                    if r not in ratios:
+                        ratios.append(r)
+                    row.append(ratios.index(r))
+                select.append(row)
+            res = self.resampler(ratios, select)
+            try:
+                return res.run(plan, data, windows, frames, variant=variant, dtype=dtype, out=out)
+            finally:
+                res.close()  # synchronises the context's stream first
+        finally:
+            plan.close()
+
     def _corpus_window_plan(self, data, image_sizes, channels):
         """the window decode plan over the images in the rows of `data`: mixed-format, or channel-mix when `channels` is given"""
         sizes = self.image_rows("data", data, image_sizes)
@@ -1201,6 +1254,76 @@ class WindowDecodePlan:
             pass
 
 
+class Resampler:
+    """AADHip_Resampler*: banks of integer polyphase filters and the table that picks one per (stream, variant)."""
+
+    def __init__(self, engine, handle, ratios, select):
+        self.engine, self.handle, self.ratios, self.select = engine, handle, ratios, select
+
+    def bank(self, r):
+        """-> (L, M, int16 array [L, K]): ratio r reduced, and its bank - phase p's K taps in Q14 (AADHip_ResamplerBank)"""
+        lib = self.engine.lib
+        L, M, K = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check("AADHip_ResamplerBank", lib.AADHip_ResamplerBank(self.handle, int(r), C.byref(L), C.byref(M), C.byref(K), None, 0))
+        h = np.zeros((L.value, K.value), dtype=np.int16)
+        _check("AADHip_ResamplerBank", lib.AADHip_ResamplerBank(self.handle, int(r), C.byref(L), C.byref(M), C.byref(K), h.ctypes.data, h.size))
+        return L.value, M.value, h
+
+    def source_frames(self, frames):
+        """T_src: the frames of a source row that `frames` output frames read, over all the banks (AADHip_ResamplerSourceFrames)"""
+        n = C.c_uint32()
+        _check("AADHip_ResamplerSourceFrames", self.engine.lib.AADHip_ResamplerSourceFrames(self.handle, int(frames), C.byref(n)))
+        return n.value
+
+    def run(self, window_plan, data, windows, frames, variant=None, dtype=None, out=None):
+        """window_plan: a WindowDecodePlan of any kind over `data`; windows: int64 cuda tensor [N, 2] of (stream, first_frame in
+        source frames); variant: contiguous int64 cuda tensor [N], None for all 0 -> `out` ([N, channels, frames] of dtype
+        torch.float32, torch.int16, torch.float16 or torch.bfloat16; allocated when None): window w resampled by the ratio
+        select[stream][variant[w]], zeros where there is none.  Three steps on the engine's stream, ordered against torch's current
+        one: AADHip_ResamplerResolve, the plan's own run into an int16 source batch of source_frames(frames) frames per row, and
+        AADHip_ResamplerRun.  Neither table is read on the host.  The source batch and the tables between the steps are
+        temporaries of this call; torch's current stream waits for the engine's before it can reuse them (Engine.window_table)."""
+        e = self.engine
+        torch = e.torch
+        dtype = torch.float32 if dtype is None else dtype
+        kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
+        if dtype not in kinds:
+            raise ValueError("resample writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % dtype)
+        windows = e.window_table(windows, True)
+        n, ch, frames = int(windows.shape[0]), int(window_plan.header.num_channels), int(frames)
+        if variant is not None:
+            e.tensor("variant", variant, torch.int64, n, shape=(n,), contiguous=True)
+        if out is None:
+            out = torch.empty((n, ch, frames), dtype=dtype, device=windows.device)
+        else:
+            e.tensor("out", out, dtype, run_extent("window_rows", rows=n, channels=ch, frames=frames), shape=(n, ch, frames),
+                     contiguous=True)
+        source_frames = self.source_frames(frames)
+        source_windows = torch.empty((n, 2), dtype=torch.int64, device=windows.device)
+        lanes = torch.empty((n, 2), dtype=torch.int32, device=windows.device)
+        cur = e._enter()
+        _check("AADHip_ResamplerResolve",
+               e.lib.AADHip_ResamplerResolve(self.handle, n, windows.data_ptr(), variant.data_ptr() if variant is not None else None,
+                                             frames, source_windows.data_ptr(), lanes.data_ptr()))
+        rows = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False)
+        _check("AADHip_ResamplerRun",
+               e.lib.AADHip_ResamplerRun(self.handle, n, ch, rows.data_ptr(), source_frames, lanes.data_ptr(), frames, kinds[dtype],
+                                         out.data_ptr()))
+        e._exit(cur)
+        return out
+
+    def close(self):
+        if self.handle:
+            self.engine.lib.AADHip_ResamplerDestroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HipEvent:
     """A hipEvent_t of our own (timing disabled): what AADHip_ContextSignalNextRun takes and hipStreamWaitEvent waits for.
     torch.cuda.Event cannot wrap a foreign handle and creates its own lazily, hence the few runtime calls made directly."""
@@ -1402,4 +1525,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "Resampler", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]

@@ -484,6 +484,86 @@ AADApiResult AADHip_WindowDecodePlanRunPlacedStats(
     const struct AADHipWindowSpan *device_spans,   /* NULL: every span is (T, 0) */
     uint32_t frames_per_window, struct AADHipRowStats *device_stats);
 
+/* ---- resample: window decode at another rate, per-window rational ratio, exact integer FIR --------------------------------- */
+
+/* A corpus holds files of several sampling rates, and speed perturbation draws a rate per window.  A resampler is a stage of its
+ * own behind AADHip_WindowDecodePlanRun, for plans of all three constructors: a resolve kernel moves every window to the front by
+ * the filter's lead, the window decode writes an int16 SOURCE BATCH of T_src frames per row, and a FIR kernel turns each source
+ * row into T output frames at the window's own ratio.  The decode kernels are the ones of a plain run; the price is one int16
+ * write and read per source sample.  Measured on MI355X, 1024 stereo windows of 48 000 frames at 147/160 into float32 rows:
+ * resolve 0.006 ms, decode 0.146 ms, FIR 0.451 ms (1.35 TB/s moved), against 0.243 ms for a plain float32 decode of the same
+ * windows - the FIR kernel, not the extra batch, is the cost (DESIGN.md "Window decode at another rate").  All arithmetic is
+ * integer, so the rows are defined bit for bit.
+ *
+ * Ratio.  {up, down} is output rate / source rate, reduced by its gcd to (L, M).
+ *
+ * Bank of (L, M): L phases of K int16 taps in Q14.  (1, 1): K = 2, taps {16384, 0}.  Otherwise s = min(1, L / M),
+ * K = 2 ceil(12 / s), and tap k of phase p sits at t = k - (K/2 - 1) - p / L with
+ *   g = 0.94 s sinc(0.94 s t) I0(9 sqrt(1 - (t / (K/2))^2)) / I0(9),   sinc(x) = sin(pi x) / (pi x),   0 where |t| > K/2:
+ * a Kaiser-windowed low-pass at 0.94 of the lower rate's Nyquist frequency, twelve zero crossings a side.  The phase is scaled to
+ * sum to 16384 and floored, and the 16384 - sum(floors) taps with the largest fractional parts get 1 more, ties to the lower k:
+ * every phase sums to exactly 16384, a constant stays a constant.  The bank is built on the host in double precision;
+ * AADHip_ResamplerBank returns it (coefficients: L * K values, phase p's taps at p * K; NULL asks for L, M and K alone;
+ * AAD_APIRESULT_INSUFFICIENT_BUFFER when capacity, in values, is below L * K).
+ *
+ * Row.  Window w = {stream, first_frame}, x the stream's decode (D_s of "window decode", any channel of the plan's rows), zero
+ * before frame 0 and from num_samples on, (L, M, K, h) the window's bank.  For n < T, with i = (n M) div L and p = (n M) mod L:
+ *   acc[n] = sum over k < K of h[p][k] * x[first_frame + i + k - (K/2 - 1)]
+ * which int32 holds exactly, every phase having sum |h| <= 65535.  The element is
+ *   INT16     clamp(floor((acc + 8192) / 16384), -32768, 32767)
+ *   FLOAT32   fl32(acc) * 2^-29: the integer rounded to nearest even, then an exact scale
+ *   FLOAT16 / BFLOAT16   that float32 value rounded once to nearest even, as for window decode rows
+ * and with the (1, 1) bank bit for bit what AADHip_WindowDecodePlanRun writes for the window and type (a channel-mix plan's
+ * stereo-to-mono rows are resampled as their int16 rows, (L + R) >> 1).
+ *
+ * Bank selection.  A resampler holds num_ratios ratios - bank r is ratio r's - and select[num_streams][variants] of bank indices,
+ * 0xFFFF for none.  A run takes device_variant, int64[N] in device memory, NULL for all 0: window w's bank is
+ * select[stream][variant[w]].  A stream index >= num_streams, a variant outside [0, variants) - negative ones included - and
+ * 0xFFFF give a row of +0.  The host reads neither table.
+ *
+ * Source batch.  T_src = max over the banks of ((T - 1) M) div L + K (AADHip_ResamplerSourceFrames).  AADHip_ResamplerResolve
+ * writes, per window, the source window {stream, src_first} with src_first = first_frame - min(first_frame, K/2 - 1), and the
+ * lane record {bank, shift} with shift = first_frame - src_first.  The caller runs AADHip_WindowDecodePlanRun over the source
+ * windows with frames_per_window = T_src and AAD_HIP_SAMPLE_INT16; element j of a source row is then frame src_first + j, and
+ * AADHip_ResamplerRun reads j = shift + i + k - (K/2 - 1), 0 for j < 0.  Huge first_frame values pass through: window decode
+ * makes their rows zeros.
+ *
+ * AADHip_ResamplerCreate: AAD_APIRESULT_INVALID_ARGUMENT for a null pointer, num_ratios == 0 or >= 0xFFFF, variants == 0, a
+ * select entry that is neither a ratio's index nor 0xFFFF, and a ratio with up == 0 or down == 0, L > 1024, K > 256,
+ * 2 L K > 65536 bytes or a phase with sum |h| > 65535.
+ * AADHip_ResamplerResolve and AADHip_ResamplerRun are asynchronous on the context's stream, one kernel each; num_windows == 0
+ * launches nothing and is OK; AADHip_ContextSignalNextRun's events are not theirs (the window decode between them takes them).
+ * AAD_APIRESULT_INVALID_ARGUMENT: a null pointer (device_variant aside), a table off its alignment (8 bytes for windows and
+ * variants, 4 for lanes, the element's for the rows), frames == 0 or (frames - 1) * M >= 2^31 for a bank, channels == 0,
+ * source_frames below T_src, a sample_type other than the four of window decode, and N * C * T or N * C * source_frames elements
+ * or bytes past 64 bits.  No refused call writes anything. */
+struct AADHipResampleRatio {
+  uint32_t up, down; /* output rate / source rate */
+};
+struct AADHipResampleLane { /* a contiguous torch int32 [N, 2] tensor on the device IS the table */
+  uint32_t bank;            /* the window's bank, 0xFFFF: a row of zeros */
+  uint32_t shift;           /* element of the source row that holds frame first_frame */
+};
+struct AADHipResampler;
+AADApiResult AADHip_ResamplerCreate(
+    struct AADHipContext *context, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
+    uint32_t num_streams, uint32_t variants, const uint16_t *select,
+    struct AADHipResampler **resampler);
+void AADHip_ResamplerDestroy(struct AADHipResampler *resampler);
+AADApiResult AADHip_ResamplerBank(
+    const struct AADHipResampler *resampler, uint32_t ratio,
+    uint32_t *L, uint32_t *M, uint32_t *taps, int16_t *coefficients, uint64_t capacity);
+AADApiResult AADHip_ResamplerSourceFrames(
+    const struct AADHipResampler *resampler, uint32_t frames, uint32_t *source_frames);
+AADApiResult AADHip_ResamplerResolve(
+    struct AADHipResampler *resampler, uint64_t num_windows, const struct AADHipWindow *device_windows,
+    const int64_t *device_variant,   /* NULL: every variant is 0 */
+    uint32_t frames, struct AADHipWindow *device_source_windows, struct AADHipResampleLane *device_lanes);
+AADApiResult AADHip_ResamplerRun(
+    struct AADHipResampler *resampler, uint64_t num_windows, uint32_t channels,
+    const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipResampleLane *device_lanes,
+    uint32_t frames, int32_t sample_type, void *device_out);
+
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 
 /* The write side of the planar layout window decode reads out: one row per channel, int16 or float32 - torch's [N, C, T] - encoded

@@ -1,0 +1,107 @@
+"""What the resample stage costs next to the window decode it follows (DESIGN.md "Window decode at another rate").
+
+Shape: --windows stereo windows (default 1024) of --frames output frames (default 48000) drawn from a 4-bit corpus on the device,
+once at 147/160 (48 kHz to 44.1 kHz) and once at 160/147.  Per ratio, each step's time from HIP events recorded on the engine's
+stream around it, the median of --steps runs after --warmup:
+  resolve   AADHip_ResamplerResolve
+  decode    AADHip_WindowDecodePlanRun of the source windows, T_src frames, int16 - the source batch
+  fir       AADHip_ResamplerRun into float32 rows, with the bytes it moves (the source batch read once, the rows written once)
+  plain     AADHip_WindowDecodePlanRun of the same windows, T frames, float32: the path without resampling
+The first window's row is checked against tests/resample_oracle.py.  Prints one line per ratio; --out appends them to a file."""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from aad_amd.capi import SAMPLE_FLOAT32, make_parameter  # noqa: E402
+from aad_amd.engine import Engine, _check  # noqa: E402
+from aad_amd.synth import synth_pcm  # noqa: E402
+
+
+def timed(stream, steps, warmup, fn):
+    """median milliseconds of fn's work on `stream`, between two events recorded around it"""
+    ms = []
+    for k in range(warmup + steps):
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record(stream)
+        fn()
+        stop.record(stream)
+        stop.synchronize()
+        if k >= warmup:
+            ms.append(start.elapsed_time(stop))
+    return statistics.median(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=1024)
+    ap.add_argument("--frames", type=int, default=48000)
+    ap.add_argument("--streams", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    engine = Engine(0, stream=None)
+    lib = engine.lib
+    n, frames, ch = args.windows, args.frames, 2
+    samples = frames * 160 // 147 * 2 + 4096  # every window lies inside its stream at either ratio
+    pcm = synth_pcm(args.streams, samples, ch, seed=5)
+    lines = []
+    with torch.cuda.stream(engine.stream):
+        data, size = engine.encode_uniform(torch.from_numpy(pcm).cuda(), make_parameter(ch, 4, 1024, 48000, False, 0))
+        plan = engine._corpus_window_plan(data, size, None)
+        gen = torch.Generator(device="cuda").manual_seed(11)
+        windows = torch.stack([torch.randint(0, args.streams, (n,), generator=gen, device="cuda"),
+                               torch.randint(0, samples // 2 - 4096, (n,), generator=gen, device="cuda")], dim=1).contiguous()
+        for ratio in ((147, 160), (160, 147)):
+            res = engine.resampler([ratio], [[0]] * args.streams)
+            t_src = res.source_frames(frames)
+            src_windows = torch.empty((n, 2), dtype=torch.int64, device="cuda")
+            lanes = torch.empty((n, 2), dtype=torch.int32, device="cuda")
+            rows = torch.empty((n, ch, t_src), dtype=torch.int16, device="cuda")
+            out = torch.empty((n, ch, frames), dtype=torch.float32, device="cuda")
+            plain = torch.empty((n, ch, frames), dtype=torch.float32, device="cuda")
+            resolve = lambda: _check("AADHip_ResamplerResolve", lib.AADHip_ResamplerResolve(
+                res.handle, n, windows.data_ptr(), None, frames, src_windows.data_ptr(), lanes.data_ptr()))
+            decode = lambda: plan.run(data, src_windows, t_src, torch.int16, out=rows, ordered=False)
+            fir = lambda: _check("AADHip_ResamplerRun", lib.AADHip_ResamplerRun(
+                res.handle, n, ch, rows.data_ptr(), t_src, lanes.data_ptr(), frames, SAMPLE_FLOAT32, out.data_ptr()))
+            decode_plain = lambda: plan.run(data, windows, frames, torch.float32, out=plain, ordered=False)
+            t = {name: timed(engine.stream, args.steps, args.warmup, fn)
+                 for name, fn in (("resolve", resolve), ("decode", decode), ("fir", fir), ("plain", decode_plain))}
+            t["plain again"] = timed(engine.stream, args.steps, args.warmup, decode_plain)  # drift between the first and the last
+            moved = n * ch * (t_src * 2 + frames * 4)
+            import resample_oracle as ro
+            L, M, h = res.bank(0)
+            s, f = (int(v) for v in windows[0].cpu())
+            want = ro.convert(ro.fir(pcm_decoded(engine, data, size, s)[:, 0], f, frames, L, M, h), "float32")
+            exact = bool((out[0, 0].cpu().numpy().view(np.uint32) == want).all())
+            lines.append("ratio %d/%d  N=%d C=%d T=%d T_src=%d  resolve %.4f ms  decode (int16 source batch) %.3f ms  fir %.3f ms "
+                         "(%.1f MB moved, %.0f GB/s)  three steps %.3f ms  plain float32 decode %.3f ms (again %.3f)  fir / decode %.2f  "
+                         "exact=%s" % (ratio[0], ratio[1], n, ch, frames, t_src, t["resolve"], t["decode"], t["fir"], moved / 1e6,
+                                       moved / t["fir"] / 1e6, t["resolve"] + t["decode"] + t["fir"], t["plain"], t["plain again"],
+                                       t["fir"] / t["decode"], exact))
+            print(lines[-1], flush=True)
+            res.close()
+        plan.close()
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    engine.close()
+
+
+def pcm_decoded(engine, data, size, stream):
+    """one stream's whole decode, int16 [samples, channels], from the device decoder"""
+    dec, _ = engine.decode_uniform(data[stream:stream + 1], size)
+    return dec[0].cpu().numpy()
+
+
+if __name__ == "__main__":
+    main()
