@@ -120,7 +120,7 @@ HIP_SYMBOLS = [
     "AADHip_PlanarReconstructPlanCreate", "AADHip_PlanarReconstructPlanRun", "AADHip_PlanarReconstructPlanRunStats",
     "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
     "AADHip_ResamplerCreate", "AADHip_ResamplerDestroy", "AADHip_ResamplerBank", "AADHip_ResamplerSourceFrames",
-    "AADHip_ResamplerResolve", "AADHip_ResamplerRun",
+    "AADHip_ResamplerResolve", "AADHip_ResamplerRun", "AADHip_ResamplerRunGain", "AADHip_ResamplerRunStats",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -252,6 +252,10 @@ def _declare_hip(lib):
     lib.AADHip_ResamplerResolve.restype = C.c_int
     lib.AADHip_ResamplerRun.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_int32, vp]
     lib.AADHip_ResamplerRun.restype = C.c_int
+    lib.AADHip_ResamplerRunGain.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_int32, vp, vp, C.c_int32]
+    lib.AADHip_ResamplerRunGain.restype = C.c_int
+    lib.AADHip_ResamplerRunStats.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_int32, vp, vp]
+    lib.AADHip_ResamplerRunStats.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

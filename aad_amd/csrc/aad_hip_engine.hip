@@ -1596,51 +1596,139 @@ AADApiResult AADHip_ResamplerResolve(struct AADHipResampler *r, uint64_t num_win
   return hip_ok(ctx, hipGetLastError(), "resampler resolve launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
 }
 
-AADApiResult AADHip_ResamplerRun(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
-                                 uint32_t source_frames, const struct AADHipResampleLane *device_lanes, uint32_t frames,
-                                 int32_t sample_type, void *device_out)
+namespace {
+/* What AADHip_ResamplerRun refuses, for the three FIR runs (out_optional: AADHip_ResamplerRunStats), and the kernel's arguments.
+ * `what` names the run in last_error. */
+AADApiResult resampler_rows_args(AADHipResampler *r, const char *what, uint64_t num_windows, uint32_t channels,
+                                 const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipResampleLane *device_lanes,
+                                 uint32_t frames, int32_t sample_type, void *device_out, bool out_optional, aad::ResampleRowsArgs *a)
 {
-  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
   AADHipContext *ctx = r->ctx;
   const uint64_t elem = sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4 : 2;
   uint32_t needed = 0;
   uint64_t rows = 0, n = 0;
   if (!window_sample_type_ok(sample_type) || channels == 0 || !resampler_source_frames(r, frames, &needed) || source_frames < needed ||
-      device_source_rows == nullptr || device_lanes == nullptr || device_out == nullptr ||
+      device_source_rows == nullptr || device_lanes == nullptr || (device_out == nullptr && !out_optional) ||
       (reinterpret_cast<uintptr_t>(device_source_rows) & 1u) != 0 || (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0 ||
       (reinterpret_cast<uintptr_t>(device_out) & (elem - 1)) != 0 || __builtin_mul_overflow(num_windows, (uint64_t)channels, &rows) ||
       __builtin_mul_overflow(rows, (uint64_t)frames, &n) || __builtin_mul_overflow(n, elem, &n) ||
       __builtin_mul_overflow(rows, (uint64_t)source_frames, &n) || __builtin_mul_overflow(n, (uint64_t)2, &n) ||
       __builtin_mul_overflow(rows, (uint64_t)((frames - 1) / aad::kResampleTile + 1), &n)) {
     snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "resampler run: an unknown sample type, a null or unaligned pointer, 0 channels, %u frames (0, or (T - 1) M >= 2^31 for a "
+             "%s: an unknown sample type, a null or unaligned pointer, 0 channels, %u frames (0, or (T - 1) M >= 2^31 for a "
              "bank), source rows of %u frames where %u are needed, or %llu windows x %u channels x frames past 64 bits",
-             frames, source_frames, needed, (unsigned long long)num_windows, channels);
+             what, frames, source_frames, needed, (unsigned long long)num_windows, channels);
     return AAD_APIRESULT_INVALID_ARGUMENT;
   }
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (num_windows == 0) return AAD_APIRESULT_OK;
-  aad::ResampleRowsArgs a;
-  a.src = device_source_rows;
-  a.lanes = reinterpret_cast<const aad::ResampleLane *>(device_lanes);
-  a.banks = r->d_banks;
-  a.coefficients = r->d_coefficients;
-  a.out = device_out;
-  a.rows = rows;
-  a.channels = channels;
-  a.num_banks = (uint32_t)r->banks.size();
-  a.frames = frames;
-  a.source_frames = source_frames;
-  a.tiles = (frames - 1) / aad::kResampleTile + 1;
-  a.bank_elements = (uint32_t)r->bank_elements;
-  a.span_elements = (uint32_t)r->span_elements;
-  if (!aad::launch_resample_rows(a, sample_type, (uint32_t)(2 * (r->bank_elements + r->span_elements)), ctx->stream)) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error), "resampler run: the device refuses %llu bytes of LDS for a workgroup",
+  a->src = device_source_rows;
+  a->lanes = reinterpret_cast<const aad::ResampleLane *>(device_lanes);
+  a->banks = r->d_banks;
+  a->coefficients = r->d_coefficients;
+  a->out = device_out;
+  a->rows = rows;
+  a->channels = channels;
+  a->num_banks = (uint32_t)r->banks.size();
+  a->frames = frames;
+  a->source_frames = source_frames;
+  a->tiles = (frames - 1) / aad::kResampleTile + 1;
+  a->bank_elements = (uint32_t)r->bank_elements;
+  a->span_elements = (uint32_t)r->span_elements;
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult resampler_launched(AADHipResampler *r, const char *what, bool launched)
+{
+  AADHipContext *ctx = r->ctx;
+  if (!launched) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error), "%s: the device refuses %llu bytes of LDS for a workgroup", what,
              (unsigned long long)(2 * (r->bank_elements + r->span_elements)));
     return AAD_APIRESULT_NG;
   }
-  return hip_ok(ctx, hipGetLastError(), "resampler run launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
+  char label[64];
+  snprintf(label, sizeof(label), "%s launch", what);
+  return hip_ok(ctx, hipGetLastError(), label) ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
+}
+} /* namespace */
+
+AADApiResult AADHip_ResamplerRun(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
+                                 uint32_t source_frames, const struct AADHipResampleLane *device_lanes, uint32_t frames,
+                                 int32_t sample_type, void *device_out)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = r->ctx;
+  aad::ResampleRowsArgs a;
+  const AADApiResult rc = resampler_rows_args(r, "resampler run", num_windows, channels, device_source_rows, source_frames,
+                                              device_lanes, frames, sample_type, device_out, false, &a);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_windows == 0) return AAD_APIRESULT_OK;
+  return resampler_launched(r, "resampler run",
+                            aad::launch_resample_rows(a, sample_type, (uint32_t)(2 * (r->bank_elements + r->span_elements)), ctx->stream));
+}
+
+AADApiResult AADHip_ResamplerRunGain(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels,
+                                     const int16_t *device_source_rows, uint32_t source_frames,
+                                     const struct AADHipResampleLane *device_lanes, const struct AADHipWindowSpan *device_spans,
+                                     uint32_t frames, int32_t sample_type, void *device_out, const float *device_gain, int32_t mode)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = r->ctx;
+  if (sample_type == AAD_HIP_SAMPLE_INT16 || (mode != AAD_HIP_WINDOW_GAIN_STORE && mode != AAD_HIP_WINDOW_GAIN_ADD) ||
+      (reinterpret_cast<uintptr_t>(device_gain) & 3u) != 0 || (reinterpret_cast<uintptr_t>(device_spans) & 7u) != 0) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "resampler run with gain: int16 rows, a mode that is neither STORE nor ADD, a gain table off 4-byte or a span table off "
+             "8-byte alignment");
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  aad::ResampleMixArgs m;
+  memset(&m, 0, sizeof(m));
+  const AADApiResult rc = resampler_rows_args(r, "resampler run with gain", num_windows, channels, device_source_rows, source_frames,
+                                              device_lanes, frames, sample_type, device_out, false, &m.r);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_windows == 0) return AAD_APIRESULT_OK;
+  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
+  m.gain = device_gain;
+  return resampler_launched(r, "resampler run with gain",
+                            aad::launch_resample_rows_gain(m, sample_type, mode == AAD_HIP_WINDOW_GAIN_ADD,
+                                                           (uint32_t)(2 * (r->bank_elements + r->span_elements)), ctx->stream));
+}
+
+AADApiResult AADHip_ResamplerRunStats(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels,
+                                      const int16_t *device_source_rows, uint32_t source_frames,
+                                      const struct AADHipResampleLane *device_lanes, const struct AADHipRowStats *device_source_stats,
+                                      const struct AADHipWindowSpan *device_spans, uint32_t frames, int32_t sample_type,
+                                      void *device_out, struct AADHipRowStats *device_stats)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = r->ctx;
+  const aad::WindowStatsTable t = aad::window_stats_table(num_windows, channels, (uint64_t)reinterpret_cast<uintptr_t>(device_stats));
+  const aad::WindowStatsTable ts =
+      aad::window_stats_table(num_windows, channels, (uint64_t)reinterpret_cast<uintptr_t>(device_source_stats));
+  if (!t.ok || !ts.ok || (reinterpret_cast<uintptr_t>(device_spans) & 7u) != 0 || (device_out != nullptr && device_spans != nullptr)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "resampler run with statistics: a null or unaligned statistics table, a span table off 8-byte alignment, rows together "
+             "with spans, or %llu windows x %u channels x 32 bytes overflow 64 bits",
+             (unsigned long long)num_windows, channels);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  aad::ResampleMixArgs m;
+  memset(&m, 0, sizeof(m));
+  const AADApiResult rc = resampler_rows_args(r, "resampler run with statistics", num_windows, channels, device_source_rows,
+                                              source_frames, device_lanes, frames, sample_type, device_out, true, &m.r);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_windows == 0) return AAD_APIRESULT_OK;
+  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
+  m.source_stats = reinterpret_cast<const unsigned long long *>(device_source_stats);
+  m.stats = reinterpret_cast<unsigned long long *>(device_stats);
+  if (!hip_ok(ctx, hipMemsetAsync(device_stats, 0, t.bytes, ctx->stream), "hipMemsetAsync")) return AAD_APIRESULT_NG;
+  return resampler_launched(r, "resampler run with statistics",
+                            aad::launch_resample_rows_stats(m, sample_type, (uint32_t)(2 * (r->bank_elements + r->span_elements)),
+                                                            ctx->stream));
 }
 
 /* -------------------------------------------------------------------- window reconstruct -- */

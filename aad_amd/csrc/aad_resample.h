@@ -1,13 +1,16 @@
 /* aad_resample.h - the arithmetic of the resample stage behind a window decode (AADHip_Resampler*, include/aad_hip.h "resample"),
  * compiled for the host and for the device: the reduction of a ratio and what a resampler refuses, the integer polyphase bank
  * (built on the host in double precision), the source batch's row length and the per-window resolve, which the resolve kernel
- * (aad_resample.hip) runs once per window.  A CPU test runs the same functions against a numpy restatement of the definition
- * (tests/resample_policy_driver.cpp, tests/resample_oracle.py).  Plain C++ with no container, as aad_windows.h. */
+ * (aad_resample.hip) runs once per window, and a row's span and `count` for the runs with spans and statistics.  A CPU test runs
+ * the same functions against a numpy restatement of the definition (tests/resample_policy_driver.cpp, tests/resample_oracle.py;
+ * tests/resample_mix_driver.cpp against a brute force).  Plain C++ with no container, as aad_windows.h. */
 #ifndef AAD_RESAMPLE_H
 #define AAD_RESAMPLE_H
 
 #include <math.h>
 #include <stdint.h>
+
+#include "aad_window_span.h"
 
 #if defined(__HIPCC__)
 #define AAD_RESAMPLE_FN __host__ __device__ inline
@@ -187,6 +190,27 @@ AAD_RESAMPLE_FN ResampleResolved resample_resolve(uint64_t stream, uint64_t firs
   r.lane.bank = bank;
   r.lane.shift = (uint32_t)before;
   return r;
+}
+
+/* ---- rows with spans and statistics (AADHip_ResamplerRunGain, AADHip_ResamplerRunStats) ---------------------------------------- */
+
+/* Le: the OUTPUT frames of span (L_span, o) that a row of T elements takes - the rule of window decode with spans, not a second one */
+AAD_RESAMPLE_FN uint64_t resample_span_frames(uint64_t num_frames, uint64_t out_frame, uint32_t frames)
+{
+  return window_span_frames(num_frames, out_frame, frames);
+}
+
+/* `count` of a resampled row: the number of n < Le whose centre source frame, element shift + (n M) div L of the source row, the
+ * stream had - c_src being the source row's own count (AADHip_WindowDecodePlanRunStats over the source windows), never more than
+ * the row's length.  shift + (n M) div L < c  <=>  n M < (c - shift) L  <=>  n < ceil((c - shift) L / M); c < 2^32 and L <= 1024,
+ * so 64 bits hold the product. */
+AAD_RESAMPLE_FN uint64_t resample_output_count(uint64_t c_src, uint32_t source_frames, uint32_t shift, uint32_t L, uint32_t M,
+                                               uint64_t Le)
+{
+  const uint64_t c = c_src < source_frames ? c_src : source_frames;
+  if (c <= shift) return 0;
+  const uint64_t n = ((c - shift) * L + M - 1) / M;
+  return n < Le ? n : Le;
 }
 
 } /* namespace aad */

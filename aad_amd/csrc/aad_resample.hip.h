@@ -1,5 +1,6 @@
-/* aad_resample.hip.h - the device side of the resample stage (AADHip_ResamplerResolve, AADHip_ResamplerRun; include/aad_hip.h
- * "resample"): the resolve kernel in front of a window decode and the FIR kernel behind it.  The arithmetic is aad_resample.h's. */
+/* aad_resample.hip.h - the device side of the resample stage (AADHip_ResamplerResolve, AADHip_ResamplerRun, ...RunGain,
+ * ...RunStats; include/aad_hip.h "resample"): the resolve kernel in front of a window decode and the FIR kernels behind it.  The
+ * arithmetic is aad_resample.h's. */
 #ifndef AAD_RESAMPLE_HIP_H
 #define AAD_RESAMPLE_HIP_H
 
@@ -63,9 +64,28 @@ struct ResampleRowsArgs {
   uint32_t span_elements; /* the largest resample_span_elements */
 };
 
+/* AADHip_ResamplerRunGain / AADHip_ResamplerRunStats: the plain run's arguments and the tables of the loader toolbox */
+struct ResampleMixArgs {
+  ResampleRowsArgs r;                      /* Stats: r.out may be null */
+  const uint64_t *spans;                   /* struct AADHipWindowSpan[num_windows] in OUTPUT frames, or null: every span is (T, 0) */
+  const float *gain;                       /* Gain: [num_windows], or null: every gain is 1 */
+  const unsigned long long *source_stats;  /* Stats: struct AADHipRowStats[rows] of the source batch */
+  unsigned long long *stats;               /* Stats: struct AADHipRowStats[rows], cleared in front of the launch */
+  uint32_t scratch_words;                  /* Stats: 32-bit words of LDS in front of the reduction scratch */
+  uint32_t reserved;
+};
+
+/* bytes of the statistics kernel's reduction scratch, behind bank and span on a 16-byte boundary: three 64-bit values a wave */
+constexpr uint32_t kResampleStatsScratchBytes = (kResampleThreads / 64) * 3 * 8;
+inline uint32_t resample_stats_scratch_offset(uint32_t lds_bytes) { return (lds_bytes + 15u) & ~15u; }
+
 void launch_resample_resolve(const ResampleResolveArgs &a, hipStream_t stream);
 /* lds_bytes: 2 * (bank_elements + span_elements); false when the device refuses that much LDS for a workgroup */
 bool launch_resample_rows(const ResampleRowsArgs &a, int32_t sample_type, uint32_t lds_bytes, hipStream_t stream);
+/* sample_type: one of the three float types; add: AAD_HIP_WINDOW_GAIN_ADD */
+bool launch_resample_rows_gain(const ResampleMixArgs &a, int32_t sample_type, bool add, uint32_t lds_bytes, hipStream_t stream);
+/* a.r.out == null: statistics only; lds_bytes as above - the launch adds the scratch and sets a.scratch_words */
+bool launch_resample_rows_stats(const ResampleMixArgs &a, int32_t sample_type, uint32_t lds_bytes, hipStream_t stream);
 
 } /* namespace aad */
 

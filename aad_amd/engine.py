@@ -5,6 +5,7 @@ library as raw pointers.  All codec work happens in libaad_hip.so's HIP kernels;
 or a GPU is missing every call here raises - there is no fallback path.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -715,38 +716,111 @@ class Engine:
         return Resampler(self, handle, ratios, table)
 
     def decode_windows_resampled(self, data, image_sizes, windows, frames, rate, speeds=((1, 1),), variant=None, dtype=None,
-                                 channels=None, out=None):
+                                 channels=None, out=None, gain=None, accumulate=False, spans=None, return_stats=False):
         """decode_windows_mixed at one output rate: every image's header names its sampling_rate, and a window of stream s drawn
         with variant v - an index into `speeds`, pairs (a, b) for the speed a / b; `variant` is an int64 cuda tensor [N], None for
         all 0 - is resampled by rate * b / (sampling_rate_s * a).  Speed 11/10 plays a stream 10 % faster: fewer output frames
         per source frame.  `frames` counts output frames, windows[:, 1] source frames as everywhere.  Streams and speeds whose
-        reduced ratios agree share a bank.  dtype, channels, out: as decode_windows_mixed."""
-        from math import gcd
-        speeds = [(int(a), int(b)) for a, b in speeds]
-        if int(rate) <= 0 or not speeds or any(a <= 0 or b <= 0 for a, b in speeds):
-            raise ValueError("rate and speeds: positive integers, at least one speed; got rate %r, speeds %r" % (rate, speeds))
+        reduced ratios agree share a bank.  dtype, channels, out: as decode_windows_mixed.
+        gain / accumulate / out, spans (in output frames) and return_stats: as decode_windows_mixed, on the resampled rows
+        (Resampler.run)."""
+        self._speeds(rate, speeds)
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
-            ratios, select = [], []
-            for h in plan.headers:
-                if h.sampling_rate == 0:
-                    raise ValueError("an image's header has sampling_rate 0: no ratio to resample it by")
-                row = []
-                for a, b in speeds:
-                    up, down = int(rate) * b, int(h.sampling_rate) * a
-                    g = gcd(up, down)
-                    r = (up // g, down // g)
-                    if r not in ratios:
-                        ratios.append(r)
-                    row.append(ratios.index(r))
-                select.append(row)
-            res = self.resampler(ratios, select)
+            res = self._corpus_resampler(plan, rate, speeds)
             try:
-                return res.run(plan, data, windows, frames, variant=variant, dtype=dtype, out=out)
+                return res.run(plan, data, windows, frames, variant=variant, dtype=dtype, out=out, gain=gain, accumulate=accumulate,
+                               spans=spans, stats=True if return_stats else None)
             finally:
                 res.close()  # synchronises the context's stream first
         finally:
             plan.close()
+
+    def window_levels_resampled(self, data, image_sizes, windows, frames, rate, speeds=((1, 1),), variant=None, channels=None,
+                                spans=None):
+        """The level statistics of decode_windows_resampled's rows without the rows: int64 [N, channels, 4] of (sum_sq, sum_abs,
+        max_abs, count) per row in int16 units, count = the output frames whose centre source frame the stream had.  Nothing is
+        stored but the source batch and the table.  spans: int64 cuda tensor [N, 2] of (num_frames, out_frame) in output frames -
+        the levels of each window's clipped crop alone."""
+        self._speeds(rate, speeds)
+        plan = self._corpus_window_plan(data, image_sizes, channels)
+        try:
+            res = self._corpus_resampler(plan, rate, speeds)
+            try:
+                return res.run(plan, data, windows, frames, variant=variant, stats=True, rows=False, spans=spans)
+            finally:
+                res.close()  # synchronises the context's stream first
+        finally:
+            plan.close()
+
+    def mix_windows_resampled(self, signal, noise, frames, snr_db, rate, speeds=((1, 1),), signal_variant=None, noise_variant=None,
+                              dtype=None, channels=None, noise_spans=None):
+        """mix_windows at one output rate: signal, noise: each (data, image_sizes, windows) as for decode_windows_resampled, the
+        same number of windows, each corpus with its own sampling rates; rate, speeds and the two variant tables as there.
+        Each corpus is decoded ONCE into its int16 source batch, with statistics (Resampler.decode_source); the FIR then runs
+        twice over each batch: statistics only for the levels - the noise's over noise_spans - and, with snr_gains' gains on the
+        device, a STORE run of the signal and an ADD run of gain * noise into the same rows -> (rows [N, channels, frames] of
+        `dtype`, float32 [N] noise gains).  No float32 batch, no elementwise pass; the roundings and the meaning of noise_spans
+        (in output frames) and of the SNR are mix_windows'."""
+        torch = self.torch
+        dtype = torch.float32 if dtype is None else dtype
+        self._speeds(rate, speeds)
+        s_plan = self._corpus_window_plan(signal[0], signal[1], channels)
+        try:
+            n_plan = self._corpus_window_plan(noise[0], noise[1], channels)
+            try:
+                ch, n_ch = int(s_plan.header.num_channels), int(n_plan.header.num_channels)
+                if ch != n_ch:
+                    raise ValueError("signal and noise: rows of %d and %d channels do not mix - pass channels=1 or channels=2 to bring "
+                                     "both corpora to one channel count" % (ch, n_ch))
+                s_res = self._corpus_resampler(s_plan, rate, speeds)
+                try:
+                    n_res = self._corpus_resampler(n_plan, rate, speeds)
+                    try:
+                        s_src = s_res.decode_source(s_plan, signal[0], signal[2], frames, variant=signal_variant, stats=True)
+                        n_src = n_res.decode_source(n_plan, noise[0], noise[2], frames, variant=noise_variant, stats=True)
+                        s_stats = s_res.run_source(s_src, frames, ch, stats=True, rows=False)
+                        n_stats = n_res.run_source(n_src, frames, n_ch, stats=True, rows=False, spans=noise_spans)
+                        gains = snr_gains(s_stats, n_stats, snr_db)
+                        rows = s_res.run_source(s_src, frames, ch, dtype, gain=torch.ones_like(gains))
+                        n_res.run_source(n_src, frames, n_ch, dtype, out=rows, gain=gains, accumulate=True, spans=noise_spans)
+                        return rows, gains
+                    finally:
+                        n_res.close()  # synchronises the context's stream first
+                finally:
+                    s_res.close()
+            finally:
+                n_plan.close()
+        finally:
+            s_plan.close()
+
+    @staticmethod
+    def _speeds(rate, speeds):
+        """what the resampled calls refuse of rate and speeds, before anything is built -> the speeds as pairs of ints"""
+        speeds = [(int(a), int(b)) for a, b in speeds]
+        if int(rate) <= 0 or not speeds or any(a <= 0 or b <= 0 for a, b in speeds):
+            raise ValueError("rate and speeds: positive integers, at least one speed; got rate %r, speeds %r" % (rate, speeds))
+        return speeds
+
+    def _corpus_resampler(self, plan, rate, speeds):
+        """the resampler of a corpus plan at one output rate: per stream and speed (a, b) the ratio rate * b / (sampling_rate * a),
+        equal reduced ratios sharing a bank"""
+        from math import gcd
+        speeds = self._speeds(rate, speeds)
+        ratios, select = [], []
+        for h in plan.headers:
+            if h.sampling_rate == 0:
+                raise ValueError("an image's header has sampling_rate 0: no ratio to resample it by")
+            row = []
+            for a, b in speeds:
+                up, down = int(rate) * b, int(h.sampling_rate) * a
+                g = gcd(up, down)
+                r = (up // g, down // g)
+                if r not in ratios:
+                    ratios.append(r)
+                row.append(ratios.index(r))
+            select.append(row)
+        return self.resampler(ratios, select)
 
     def _corpus_window_plan(self, data, image_sizes, channels):
         """the window decode plan over the images in the rows of `data`: mixed-format, or channel-mix when `channels` is given"""
@@ -1254,6 +1328,9 @@ class WindowDecodePlan:
             pass
 
 
+ResampleSource = namedtuple("ResampleSource", "rows lanes source_frames stats")  # Resampler.decode_source -> run_source
+
+
 class Resampler:
     """AADHip_Resampler*: banks of integer polyphase filters and the table that picks one per (stream, variant)."""
 
@@ -1275,29 +1352,40 @@ class Resampler:
         _check("AADHip_ResamplerSourceFrames", self.engine.lib.AADHip_ResamplerSourceFrames(self.handle, int(frames), C.byref(n)))
         return n.value
 
-    def run(self, window_plan, data, windows, frames, variant=None, dtype=None, out=None):
+    def run(self, window_plan, data, windows, frames, variant=None, dtype=None, out=None, gain=None, accumulate=False, spans=None,
+            stats=None, rows=True):
         """window_plan: a WindowDecodePlan of any kind over `data`; windows: int64 cuda tensor [N, 2] of (stream, first_frame in
         source frames); variant: contiguous int64 cuda tensor [N], None for all 0 -> `out` ([N, channels, frames] of dtype
         torch.float32, torch.int16, torch.float16 or torch.bfloat16; allocated when None): window w resampled by the ratio
         select[stream][variant[w]], zeros where there is none.  Three steps on the engine's stream, ordered against torch's current
         one: AADHip_ResamplerResolve, the plan's own run into an int16 source batch of source_frames(frames) frames per row, and
         AADHip_ResamplerRun.  Neither table is read on the host.  The source batch and the tables between the steps are
-        temporaries of this call; torch's current stream waits for the engine's before it can reuse them (Engine.window_table)."""
+        temporaries of this call; torch's current stream waits for the engine's before it can reuse them (Engine.window_table).
+        gain, accumulate, spans, stats, rows: the meanings and refusals of WindowDecodePlan.run, on the resampled rows - `spans`
+        in OUTPUT frames; the FIR step is then AADHip_ResamplerRunGain or AADHip_ResamplerRunStats, and with stats the source
+        batch is decoded with its own statistics, whose `count` the FIR turns into the row's -> out, (out, stats) or stats.
+        The call is decode_source and run_source composed."""
+        e = self.engine
+        self._sample_type(dtype)  # the order of the checks is the one the call had before it took gain, spans and stats
+        windows = e.window_table(windows, True)
+        if variant is not None:
+            e.tensor("variant", variant, e.torch.int64, int(windows.shape[0]), shape=(int(windows.shape[0]),), contiguous=True)
+        checked = self._check_run(int(windows.shape[0]), windows.device, window_plan.header.num_channels, frames, dtype, out, gain,
+                                  accumulate, spans, stats, rows)
+        source = self.decode_source(window_plan, data, windows, frames, variant=variant, stats=checked[-1] is not None)
+        return self._run_source(source, frames, *checked)
+
+    def decode_source(self, window_plan, data, windows, frames, variant=None, stats=False):
+        """The first two steps of run: AADHip_ResamplerResolve and the plan's own run into the int16 source batch, with
+        stats=True by AADHip_WindowDecodePlanRunStats -> ResampleSource(rows int16 [N, channels, source_frames], lanes int32
+        [N, 2], source_frames, stats int64 [N, channels, 4] or None), what run_source reads - several times for one decode, as
+        Engine.mix_windows_resampled does."""
         e = self.engine
         torch = e.torch
-        dtype = torch.float32 if dtype is None else dtype
-        kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
-        if dtype not in kinds:
-            raise ValueError("resample writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % dtype)
         windows = e.window_table(windows, True)
-        n, ch, frames = int(windows.shape[0]), int(window_plan.header.num_channels), int(frames)
+        n, frames = int(windows.shape[0]), int(frames)
         if variant is not None:
             e.tensor("variant", variant, torch.int64, n, shape=(n,), contiguous=True)
-        if out is None:
-            out = torch.empty((n, ch, frames), dtype=dtype, device=windows.device)
-        else:
-            e.tensor("out", out, dtype, run_extent("window_rows", rows=n, channels=ch, frames=frames), shape=(n, ch, frames),
-                     contiguous=True)
         source_frames = self.source_frames(frames)
         source_windows = torch.empty((n, 2), dtype=torch.int64, device=windows.device)
         lanes = torch.empty((n, 2), dtype=torch.int32, device=windows.device)
@@ -1305,12 +1393,113 @@ class Resampler:
         _check("AADHip_ResamplerResolve",
                e.lib.AADHip_ResamplerResolve(self.handle, n, windows.data_ptr(), variant.data_ptr() if variant is not None else None,
                                              frames, source_windows.data_ptr(), lanes.data_ptr()))
-        rows = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False)
-        _check("AADHip_ResamplerRun",
-               e.lib.AADHip_ResamplerRun(self.handle, n, ch, rows.data_ptr(), source_frames, lanes.data_ptr(), frames, kinds[dtype],
-                                         out.data_ptr()))
+        if stats:
+            rows, table = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False, stats=True)
+        else:
+            rows, table = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False), None
         e._exit(cur)
-        return out
+        return ResampleSource(rows, lanes, source_frames, table)
+
+    def run_source(self, source, frames, channels, dtype=None, out=None, gain=None, accumulate=False, spans=None, stats=None,
+                   rows=True):
+        """The FIR step alone over decode_source's record: AADHip_ResamplerRun, with gain / accumulate / spans
+        AADHip_ResamplerRunGain, with stats AADHip_ResamplerRunStats (the source must have been decoded with stats=True).
+        channels: the rows per window of the plan that decoded the source - the record is held to it: rows [N, channels,
+        source_frames], statistics [N, channels, 4], lanes [N, 2], contiguous, refused otherwise before any library call.
+        Arguments and return values as run."""
+        e = self.engine
+        torch = e.torch
+        self._sample_type(dtype)
+        # the C calls take the record's pointers and `channels` rows per window: the record must be of that many
+        e.tensor("source.lanes", source.lanes, torch.int32, shape=(None, 2), contiguous=True)
+        n, ch, t_src = int(source.lanes.shape[0]), int(channels), int(source.source_frames)
+        e.tensor("source.rows", source.rows, torch.int16, run_extent("window_rows", rows=n, channels=ch, frames=t_src),
+                 shape=(n, ch, t_src), contiguous=True)
+        if source.stats is not None:
+            e.tensor("source.stats", source.stats, torch.int64, run_extent("stats", rows=n, channels=ch), shape=(n, ch, 4), contiguous=True)
+        checked = self._check_run(n, source.lanes.device, ch, frames, dtype, out, gain, accumulate, spans, stats, rows)
+        if checked[-1] is not None and source.stats is None:
+            raise ValueError("stats: the source batch carries no statistics - decode it with decode_source(..., stats=True)")
+        return self._run_source(source, frames, *checked)
+
+    def _sample_type(self, dtype):
+        """-> (dtype, None: torch.float32; its AAD_HIP_SAMPLE_* value)"""
+        torch = self.engine.torch
+        dtype = torch.float32 if dtype is None else dtype
+        kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
+        if dtype not in kinds:
+            raise ValueError("resample writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % dtype)
+        return dtype, kinds[dtype]
+
+    def _check_run(self, n, device, channels, frames, dtype, out, gain, accumulate, spans, stats, rows):
+        """every rule of run's arguments for n windows on `device`, before any library call -> (channels, sample type, out, gain,
+        accumulate, spans, stats or None)"""
+        e = self.engine
+        torch = e.torch
+        dtype, kind = self._sample_type(dtype)
+        gained = gain is not None or bool(accumulate)
+        placed = spans is not None
+        with_stats = not (stats is None or stats is False)
+        if placed:
+            if with_stats and rows:
+                raise ValueError("spans: no run with both rows and statistics - take the levels from a statistics-only run "
+                                 "(stats=True, rows=False, spans=...), then the rows")
+            if rows and dtype == torch.int16:
+                raise ValueError("spans: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
+        n, ch, frames = int(n), int(channels), int(frames)
+        if placed:
+            spans = e.window_table(spans, True, name="spans", rows=n)
+        if gained:
+            if dtype == torch.int16:
+                raise ValueError("gain / accumulate: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
+            if with_stats or not rows:
+                raise ValueError("gain / accumulate: no statistics variant - take the levels first from a statistics-only run "
+                                 "(stats=True, rows=False), then run with the gains")
+            if accumulate and out is None:
+                raise ValueError("accumulate=True adds into `out`: pass the rows to add to")
+            if gain is not None:
+                e.tensor("gain", gain, torch.float32, n, shape=(n,), contiguous=True)
+        if not with_stats:
+            stats = None
+            if not rows:
+                raise ValueError("rows=False is a statistics-only run: pass stats=True or a table")
+        elif stats is True:
+            stats = torch.empty((n, ch, 4), dtype=torch.int64, device=device)
+        else:
+            e.tensor("stats", stats, torch.int64, run_extent("stats", rows=n, channels=ch), shape=(n, ch, 4), contiguous=True)
+        if not rows:
+            if out is not None:
+                raise ValueError("rows=False writes no rows: pass no `out`")
+        elif out is None:
+            out = torch.empty((n, ch, frames), dtype=dtype, device=device)
+        else:
+            e.tensor("out", out, dtype, run_extent("window_rows", rows=n, channels=ch, frames=frames), shape=(n, ch, frames),
+                     contiguous=True)
+        return ch, kind, out, gain, bool(accumulate), spans, stats
+
+    def _run_source(self, source, frames, ch, kind, out, gain, accumulate, spans, stats):
+        e = self.engine
+        n, frames = int(source.lanes.shape[0]), int(frames)
+        cur = e._enter()
+        if stats is not None:
+            _check("AADHip_ResamplerRunStats",
+                   e.lib.AADHip_ResamplerRunStats(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
+                                                  source.stats.data_ptr(), spans.data_ptr() if spans is not None else None, frames,
+                                                  kind, out.data_ptr() if out is not None else None, stats.data_ptr()))
+        elif gain is not None or accumulate or spans is not None:
+            _check("AADHip_ResamplerRunGain",
+                   e.lib.AADHip_ResamplerRunGain(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
+                                                 spans.data_ptr() if spans is not None else None, frames, kind, out.data_ptr(),
+                                                 gain.data_ptr() if gain is not None else None,
+                                                 WINDOW_GAIN_ADD if accumulate else WINDOW_GAIN_STORE))
+        else:
+            _check("AADHip_ResamplerRun",
+                   e.lib.AADHip_ResamplerRun(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
+                                             frames, kind, out.data_ptr()))
+        e._exit(cur)
+        if stats is None:
+            return out
+        return (out, stats) if out is not None else stats
 
     def close(self):
         if self.handle:

@@ -564,6 +564,68 @@ AADApiResult AADHip_ResamplerRun(
     const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipResampleLane *device_lanes,
     uint32_t frames, int32_t sample_type, void *device_out);
 
+/* Resampled rows with a gain, spans and level statistics: the loader toolbox of window decode - AADHip_WindowDecodePlanRunStats,
+ * ...RunGain, ...RunPlaced, ...RunPlacedStats - in the FIR kernel, for the corpus whose speech and noise come at different rates.
+ * A noisy batch at one output rate decodes each source batch once (AADHip_ResamplerResolve, then
+ * AADHip_WindowDecodePlanRunStats with AAD_HIP_SAMPLE_INT16 over the source windows) and runs the FIR over it twice: statistics
+ * only for the levels, then STORE of the speech and ADD of gain * noise.  Both calls take AADHip_ResamplerRun's source rows and
+ * lanes, are asynchronous on the context's stream and leave AADHip_ContextSignalNextRun's events alone.
+ *
+ * Spans are in OUTPUT frames: T = frames, (L, o) = device_spans[w], a NULL table: every span is (T, 0), and
+ *   Le = 0 if o >= T, else min(L, T - o)  - the rule of "window decode with spans", the comparison first.
+ *
+ * Rows of AADHip_ResamplerRunGain.  Let f[c][n] be the float32 element AADHip_ResamplerRun writes with AAD_HIP_SAMPLE_FLOAT32 for
+ * the same source rows and lanes: fl32(acc[n]) * 2^-29, +0 for a window without a bank.  Everything else is the text of "window
+ * decode with spans" with this f in place of the window decode's value: g = device_gain[w] (1 with NULL), p = fl32(g * f) - ONE
+ * float32 multiply of the finished f - and
+ *   inside the span, o <= t < o + Le:   STORE  the element becomes p[c][t - o]
+ *                                       ADD    the element becomes fl32(old + p[c][t - o]), a second rounding, never an fma
+ *     then rounded once to a 2-byte type;
+ *   outside the span:                   STORE  the element becomes +0 - not g * 0
+ *                                       ADD    the element is neither read nor written.
+ * A window without a bank has f = +0: STORE gives g * 0 inside the span (-0 under a negative gain, as the gain definition says
+ * for padding) and +0 outside, ADD gives old + g * 0 inside.  Every element is written at most once per run, by one thread, under
+ * STORE exactly once: device_out may hold anything before a STORE run, rows with Le = 0 included.  With NULL spans, a NULL gain
+ * and STORE the bytes are those of AADHip_ResamplerRun.
+ *
+ * Records of AADHip_ResamplerRunStats.  Let v[c][n] be the int16 element AADHip_ResamplerRun writes with AAD_HIP_SAMPLE_INT16 -
+ * whatever sample_type the run has.  Record w * C + c holds
+ *   sum_sq = sum of v^2, sum_abs = sum of |v|, max_abs = max of |v|, each over n < Le - filter tails past the stream's end are
+ *            part of the row and count into the sums;
+ *   count  = 0 when c' <= shift, else min(Le, ceil((c' - shift) L / M)), with c' = min(device_source_stats[w * C + c].count,
+ *            source_frames) and {bank, shift} the window's lane: the number of n < Le whose centre source frame, element
+ *            shift + (n M) div L of the source row, the stream had.  It is the row's padding mask.
+ * A window without a bank gets an all-zero record.  Consequence: when the source batch was decoded over AADHip_ResamplerResolve's
+ * source windows with statistics, count equals the number of n < Le with first_frame + (n M) div L < num_samples[stream].  The
+ * sums are integers: two runs give the same bits.  Rows, when device_out is not NULL, are byte for byte AADHip_ResamplerRun's.
+ * The run clears the N * C records on the context's stream, then launches one kernel; every record is written, whatever the
+ * table held before.
+ *
+ * Errors.  AADHip_ResamplerRun's - with device_out == NULL too: sample_type is validated all the same, and N * C * T elements or
+ * bytes of that type past 64 bits are refused although no row is written - plus AAD_APIRESULT_INVALID_ARGUMENT
+ * for AAD_HIP_SAMPLE_INT16 in the gain run (as for window decode), a mode outside {0, 1}, a device_gain that is not 4-byte
+ * aligned, a device_spans, device_stats or device_source_stats that is not 8-byte aligned, a null device_stats or
+ * device_source_stats while num_windows > 0, device_out != NULL together with device_spans != NULL in the statistics run (no
+ * run with both placed rows and statistics, as for window decode) and N * C * 32 bytes overflowing 64 bits.  num_windows == 0 is
+ * OK and launches nothing.  A refused run writes nothing.
+ *
+ * Out of scope, deliberately: int16 rows with a gain, placed rows together with statistics, several spans per row in one run. */
+AADApiResult AADHip_ResamplerRunGain(
+    struct AADHipResampler *resampler, uint64_t num_windows, uint32_t channels,
+    const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipResampleLane *device_lanes,
+    const struct AADHipWindowSpan *device_spans,   /* NULL: every span is (T, 0); in OUTPUT frames */
+    uint32_t frames, int32_t sample_type, void *device_out,
+    const float *device_gain,                      /* NULL: every gain is 1 */
+    int32_t mode);                                 /* enum AADHipWindowGainMode */
+AADApiResult AADHip_ResamplerRunStats(
+    struct AADHipResampler *resampler, uint64_t num_windows, uint32_t channels,
+    const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipResampleLane *device_lanes,
+    const struct AADHipRowStats *device_source_stats, /* N * C records: what AADHip_WindowDecodePlanRunStats wrote for the source batch */
+    const struct AADHipWindowSpan *device_spans,   /* NULL: every span is (T, 0); in OUTPUT frames */
+    uint32_t frames, int32_t sample_type,
+    void *device_out,                              /* may be NULL: statistics only */
+    struct AADHipRowStats *device_stats);          /* N * C records, every one written */
+
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 
 /* The write side of the planar layout window decode reads out: one row per channel, int16 or float32 - torch's [N, C, T] - encoded

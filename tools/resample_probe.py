@@ -7,7 +7,15 @@ stream around it, the median of --steps runs after --warmup:
   decode    AADHip_WindowDecodePlanRun of the source windows, T_src frames, int16 - the source batch
   fir       AADHip_ResamplerRun into float32 rows, with the bytes it moves (the source batch read once, the rows written once)
   plain     AADHip_WindowDecodePlanRun of the same windows, T frames, float32: the path without resampling
-The first window's row is checked against tests/resample_oracle.py.  Prints one line per ratio; --out appends them to a file."""
+The first window's row is checked against tests/resample_oracle.py.  Prints one line per ratio; --out appends them to a file.
+
+--mix adds, at 147/160 (DESIGN.md "Resampled rows with gain, spans and statistics"):
+  fir variants   AADHip_ResamplerRun, AADHip_ResamplerRunGain (float32, NULL spans: STORE with a gain table, STORE without one,
+                 ADD) and a statistics-only AADHip_ResamplerRunStats over the same source batch, timed in turn within every step - median and min - max of each
+                 (each behind an untimed plain run, so that all three find the caches as that run leaves them)
+  mix            Engine.mix_windows_resampled end to end (host clock around the call and a synchronise) against the composition
+                 without it: two Engine.decode_windows_resampled float32 batches, torch reductions for the levels and one
+                 torch.addcmul - with the peak of torch's allocator above what was allocated before the call, less the result."""
 import argparse
 import os
 import statistics
@@ -39,6 +47,90 @@ def timed(stream, steps, warmup, fn):
     return statistics.median(ms)
 
 
+def timed_in_turn(stream, steps, warmup, fns):
+    """{name: [ms per step]}: every step times each fn once, so that drift falls on all of them alike, and each behind an
+    untimed run of the first fn: what the kernel before left in the caches counts (a run that stores nothing leaves the source
+    batch there), so all of them follow the same one"""
+    ms = {name: [] for name, _ in fns}
+    for k in range(warmup + steps):
+        for name, fn in fns:
+            fns[0][1]()
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record(stream)
+            fn()
+            stop.record(stream)
+            stop.synchronize()
+            if k >= warmup:
+                ms[name].append(start.elapsed_time(stop))
+    return ms
+
+
+def host_timed(steps, warmup, fn):
+    """-> (median ms of fn() + synchronise by the host clock, peak bytes of torch's allocator above the start less the result's)"""
+    import time
+    ms, peak = [], 0
+    for k in range(warmup + steps):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        t0 = time.perf_counter()
+        result = fn()
+        torch.cuda.synchronize()
+        if k >= warmup:
+            ms.append((time.perf_counter() - t0) * 1e3)
+        kept = sum(t.numel() * t.element_size() for t in (result if isinstance(result, tuple) else (result,)))
+        peak = max(peak, torch.cuda.max_memory_allocated() - before - kept)
+        del result
+    return statistics.median(ms), peak
+
+
+def mix_rows(engine, args, plan, data, size, windows, lines):
+    """the three rows of --mix, at 147/160"""
+    lib = engine.lib
+    n, frames, ch = args.windows, args.frames, 2
+    res = engine.resampler([(147, 160)], [[0]] * args.streams)
+    source = res.decode_source(plan, data, windows, frames, stats=True)
+    t_src = source.source_frames
+    out = torch.empty((n, ch, frames), dtype=torch.float32, device="cuda")
+    stats = torch.empty((n, ch, 4), dtype=torch.int64, device="cuda")
+    gain = torch.rand(n, device="cuda") + 0.5
+    head = (res.handle, n, ch, source.rows.data_ptr(), t_src, source.lanes.data_ptr())
+    fns = (("plain", lambda: _check("AADHip_ResamplerRun", lib.AADHip_ResamplerRun(*head, frames, SAMPLE_FLOAT32, out.data_ptr()))),
+           ("gain", lambda: _check("AADHip_ResamplerRunGain", lib.AADHip_ResamplerRunGain(
+               *head, None, frames, SAMPLE_FLOAT32, out.data_ptr(), gain.data_ptr(), 0))),
+           ("gain no table", lambda: _check("AADHip_ResamplerRunGain", lib.AADHip_ResamplerRunGain(
+               *head, None, frames, SAMPLE_FLOAT32, out.data_ptr(), None, 0))),
+           ("gain ADD", lambda: _check("AADHip_ResamplerRunGain", lib.AADHip_ResamplerRunGain(
+               *head, None, frames, SAMPLE_FLOAT32, out.data_ptr(), gain.data_ptr(), 1))),
+           ("stats", lambda: _check("AADHip_ResamplerRunStats", lib.AADHip_ResamplerRunStats(
+               *head, source.stats.data_ptr(), None, frames, SAMPLE_FLOAT32, None, stats.data_ptr()))))
+    ms = timed_in_turn(engine.stream, args.steps, args.warmup, fns)
+    lines.append("fir variants 147/160  N=%d C=%d T=%d  " % (n, ch, frames) + "  ".join(
+        "%s %.3f ms (%.3f - %.3f)" % (name, statistics.median(v), min(v), max(v)) for name, v in ms.items()))
+    print(lines[-1], flush=True)
+    res.close()
+    del source, out, stats
+    noise_windows = windows.flip(0).contiguous()
+    sizes = size
+
+    def mix():
+        return engine.mix_windows_resampled((data, sizes, windows), (data, sizes, noise_windows), frames, 6.0, 44100)
+
+    def composed():
+        s = engine.decode_windows_resampled(data, sizes, windows, frames, 44100)
+        z = engine.decode_windows_resampled(data, sizes, noise_windows, frames, 44100)
+        p_s = torch.linalg.vector_norm(s, dim=(1, 2)).double().square()  # reductions without a temporary batch
+        p_n = torch.linalg.vector_norm(z, dim=(1, 2)).double().square()
+        g = torch.where(p_n > 0, (p_s / p_n.clamp(min=1e-300)).sqrt() * 10.0 ** (-6.0 / 20.0), torch.zeros_like(p_n)).float()
+        return torch.addcmul(s, z, g[:, None, None]), g
+
+    t_mix, peak_mix = host_timed(args.steps, args.warmup, mix)
+    t_comp, peak_comp = host_timed(args.steps, args.warmup, composed)
+    lines.append("mix 147/160  N=%d C=%d T=%d  mix_windows_resampled %.3f ms, %.1f MB of temporaries  composed %.3f ms, %.1f MB of "
+                 "temporaries" % (n, ch, frames, t_mix, peak_mix / 1e6, t_comp, peak_comp / 1e6))
+    print(lines[-1], flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=1024)
@@ -47,6 +139,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out")
+    ap.add_argument("--mix", action="store_true", help="add the rows of the FIR variants and of mix_windows_resampled")
     args = ap.parse_args()
     engine = Engine(0, stream=None)
     lib = engine.lib
@@ -90,6 +183,8 @@ def main():
                                        t["fir"] / t["decode"], exact))
             print(lines[-1], flush=True)
             res.close()
+        if args.mix:
+            mix_rows(engine, args, plan, data, size, windows, lines)
         plan.close()
     if args.out:
         with open(args.out, "a") as f:
