@@ -121,6 +121,7 @@ HIP_SYMBOLS = [
     "AADHip_WindowReconstructPlanCreate", "AADHip_WindowReconstructPlanDestroy", "AADHip_WindowReconstructPlanRun",
     "AADHip_ResamplerCreate", "AADHip_ResamplerDestroy", "AADHip_ResamplerBank", "AADHip_ResamplerSourceFrames",
     "AADHip_ResamplerResolve", "AADHip_ResamplerRun", "AADHip_ResamplerRunGain", "AADHip_ResamplerRunStats",
+    "AADHip_ResamplerCreateWide",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -242,6 +243,8 @@ def _declare_hip(lib):
     lib.AADHip_WindowDecodePlanRunPlacedStats.restype = C.c_int
     lib.AADHip_ResamplerCreate.argtypes = [vp, C.c_uint32, C.POINTER(AADHipResampleRatio), C.c_uint32, C.c_uint32, vp, C.POINTER(vp)]
     lib.AADHip_ResamplerCreate.restype = C.c_int
+    lib.AADHip_ResamplerCreateWide.argtypes = list(lib.AADHip_ResamplerCreate.argtypes)
+    lib.AADHip_ResamplerCreateWide.restype = C.c_int
     lib.AADHip_ResamplerDestroy.argtypes = [vp]
     lib.AADHip_ResamplerDestroy.restype = None
     lib.AADHip_ResamplerBank.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, C.c_uint64]

@@ -169,8 +169,12 @@ struct AADHipResampler {
   AADHipContext *ctx = nullptr;
   uint32_t num_streams = 0, variants = 0;
   std::vector<aad::ResampleBankDesc> banks; /* one per ratio, in the caller's order */
-  std::vector<int16_t> coefficients;
+  std::vector<int16_t> coefficients; /* bank r's L * K taps at banks[r].offset: what AADHip_ResamplerBank returns */
   uint64_t bank_elements = 0, span_elements = 0; /* the FIR kernel's LDS, in int16 elements: the largest bank and span */
+  /* AADHip_ResamplerCreateWide: the runs launch aad_resample_wide.hip's kernels; round: R of their gather path
+   * (resample_gather_round of the gathered bank with the most taps), 0 when every bank is resident */
+  bool wide = false;
+  uint32_t round = 0;
   uint16_t *d_select = nullptr, *d_lead = nullptr;
   aad::ResampleBankDesc *d_banks = nullptr;
   int16_t *d_coefficients = nullptr;
@@ -1461,8 +1465,12 @@ AADApiResult AADHip_WindowDecodePlanRunPlacedStats(struct AADHipWindowDecodePlan
 
 static_assert(sizeof(AADHipResampleLane) == sizeof(aad::ResampleLane), "lane record layout");
 
-AADApiResult AADHip_ResamplerCreate(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
-                                    uint32_t num_streams, uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler)
+namespace {
+/* AADHip_ResamplerCreate, and with `wide` AADHip_ResamplerCreateWide: the same resampler but for the limits of a ratio and the
+ * kernels its runs launch */
+AADApiResult resampler_create(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
+                              uint32_t num_streams, uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler,
+                              bool wide)
 {
   if (ctx == nullptr || resampler == nullptr || ratios == nullptr || num_ratios == 0 || num_ratios >= aad::kResampleNoBank ||
       variants == 0 || (num_streams != 0 && select == nullptr))
@@ -1476,18 +1484,38 @@ AADApiResult AADHip_ResamplerCreate(struct AADHipContext *ctx, uint32_t num_rati
   r->ctx = ctx;
   r->num_streams = num_streams;
   r->variants = variants;
+  r->wide = wide;
   std::vector<uint16_t> lead(num_ratios);
+  uint64_t gathered_stride = 0; /* the longest row of a gathered bank, in int16 elements */
+  /* the device's copy: a resident bank as on the host, a gathered one with its rows resample_gather_pitch(K) apart on 16-byte
+   * boundaries; device_banks[r].offset is into it */
+  std::vector<int16_t> image;
+  std::vector<aad::ResampleBankDesc> device_banks;
   for (uint32_t i = 0; i < num_ratios; i++) {
     aad::ResampleRatio q;
-    if (!aad::resample_reduce(ratios[i].up, ratios[i].down, &q) || !aad::resample_shape_ok(q.L, q.M)) {
-      snprintf(ctx->last_error, sizeof(ctx->last_error),
-               "resampler: ratio %u (%u / %u) is zero, or has more than 1024 phases, 256 taps or 65536 bytes of bank", i, ratios[i].up,
-               ratios[i].down);
+    if (!aad::resample_reduce(ratios[i].up, ratios[i].down, &q) ||
+        !(wide ? aad::resample_wide_shape_ok(q.L, q.M) : aad::resample_shape_ok(q.L, q.M))) {
+      if (wide)
+        snprintf(ctx->last_error, sizeof(ctx->last_error),
+                 "wide resampler: ratio %u (%u / %u) is zero, or has more than 32768 phases, 256 taps or 2 MiB of bank", i, ratios[i].up,
+                 ratios[i].down);
+      else
+        snprintf(ctx->last_error, sizeof(ctx->last_error),
+                 "resampler: ratio %u (%u / %u) is zero, or has more than 1024 phases, 256 taps or 65536 bytes of bank", i, ratios[i].up,
+                 ratios[i].down);
       delete r;
       return AAD_APIRESULT_INVALID_ARGUMENT;
     }
     const uint32_t K = (uint32_t)aad::resample_taps(q.L, q.M);
     const size_t at = r->coefficients.size();
+    const bool resident = aad::resample_bank_resident(q.L, K);
+    const uint32_t pitch = resident ? K : aad::resample_gather_pitch(K);
+    const size_t image_at = resident ? image.size() : (image.size() + 7) & ~(size_t)7;
+    if (image_at + (uint64_t)q.L * pitch >= aad::kResampleMaxCoefficients) { /* a wide resampler alone can get here */
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "wide resampler: the banks up to ratio %u hold 2^31 coefficients or more", i);
+      delete r;
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
     r->coefficients.resize(at + (size_t)q.L * K);
     if (!aad::resample_build_bank(q.L, q.M, r->coefficients.data() + at)) {
       snprintf(ctx->last_error, sizeof(ctx->last_error), "resampler: ratio %u (%u / %u) has a phase with sum |h| above 65535", i,
@@ -1496,19 +1524,47 @@ AADApiResult AADHip_ResamplerCreate(struct AADHipContext *ctx, uint32_t num_rati
       return AAD_APIRESULT_INVALID_ARGUMENT;
     }
     r->banks.push_back(aad::ResampleBankDesc{q.L, q.M, K, (uint32_t)at});
+    device_banks.push_back(aad::ResampleBankDesc{q.L, q.M, K, (uint32_t)image_at});
+    image.resize(image_at + (size_t)q.L * pitch, 0);
+    for (uint32_t p = 0; p < q.L; p++)
+      memcpy(image.data() + image_at + (size_t)p * pitch, r->coefficients.data() + at + (size_t)p * K, sizeof(int16_t) * K);
     lead[i] = (uint16_t)(K / 2 - 1);
-    r->bank_elements = std::max<uint64_t>(r->bank_elements, (uint64_t)q.L * aad::resample_lds_stride(K));
+    if (resident) {
+      r->bank_elements = std::max<uint64_t>(r->bank_elements, (uint64_t)q.L * aad::resample_lds_stride(K));
+    } else { /* gathered: the round of the bank with the most taps is the smallest */
+      const uint32_t round = aad::resample_gather_round(K);
+      r->round = r->round == 0 ? round : std::min(r->round, round);
+      gathered_stride = std::max<uint64_t>(gathered_stride, aad::resample_lds_stride(K));
+    }
     r->span_elements = std::max<uint64_t>(r->span_elements, aad::resample_span_elements(q.L, q.M, K));
   }
+  r->bank_elements = std::max<uint64_t>(r->bank_elements, r->round * gathered_stride);
   DeviceGuard guard(ctx);
   if (!guard.ok || !upload(ctx, &r->d_select, select, (size_t)entries) || !upload(ctx, &r->d_lead, lead.data(), lead.size()) ||
-      !upload(ctx, &r->d_banks, r->banks.data(), r->banks.size()) ||
-      !upload(ctx, &r->d_coefficients, r->coefficients.data(), r->coefficients.size())) {
+      !upload(ctx, &r->d_banks, device_banks.data(), device_banks.size()) ||
+      !upload(ctx, &r->d_coefficients, image.data(), image.size())) {
     AADHip_ResamplerDestroy(r);
     return AAD_APIRESULT_NG;
   }
   *resampler = r;
   return AAD_APIRESULT_OK;
+}
+
+/* bytes of LDS a FIR launch of the resampler asks for, the statistics scratch aside: bank (or a round's rows), span, phase index */
+uint32_t resampler_lds_bytes(const AADHipResampler *r) { return (uint32_t)(2 * (r->bank_elements + r->span_elements) + 4 * r->round); }
+} /* namespace */
+
+AADApiResult AADHip_ResamplerCreate(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
+                                    uint32_t num_streams, uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler)
+{
+  return resampler_create(ctx, num_ratios, ratios, num_streams, variants, select, resampler, false);
+}
+
+AADApiResult AADHip_ResamplerCreateWide(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
+                                        uint32_t num_streams, uint32_t variants, const uint16_t *select,
+                                        struct AADHipResampler **resampler)
+{
+  return resampler_create(ctx, num_ratios, ratios, num_streams, variants, select, resampler, true);
 }
 
 void AADHip_ResamplerDestroy(struct AADHipResampler *r)
@@ -1641,7 +1697,7 @@ AADApiResult resampler_launched(AADHipResampler *r, const char *what, bool launc
   AADHipContext *ctx = r->ctx;
   if (!launched) {
     snprintf(ctx->last_error, sizeof(ctx->last_error), "%s: the device refuses %llu bytes of LDS for a workgroup", what,
-             (unsigned long long)(2 * (r->bank_elements + r->span_elements)));
+             (unsigned long long)resampler_lds_bytes(r));
     return AAD_APIRESULT_NG;
   }
   char label[64];
@@ -1663,8 +1719,14 @@ AADApiResult AADHip_ResamplerRun(struct AADHipResampler *r, uint64_t num_windows
   DeviceGuard guard(ctx);
   if (!guard.ok) return AAD_APIRESULT_NG;
   if (num_windows == 0) return AAD_APIRESULT_OK;
-  return resampler_launched(r, "resampler run",
-                            aad::launch_resample_rows(a, sample_type, (uint32_t)(2 * (r->bank_elements + r->span_elements)), ctx->stream));
+  if (r->wide) {
+    aad::ResampleMixArgs m;
+    memset(&m, 0, sizeof(m));
+    m.r = a;
+    m.round = r->round;
+    return resampler_launched(r, "resampler run", aad::launch_resample_rows_wide(m, sample_type, resampler_lds_bytes(r), ctx->stream));
+  }
+  return resampler_launched(r, "resampler run", aad::launch_resample_rows(a, sample_type, resampler_lds_bytes(r), ctx->stream));
 }
 
 AADApiResult AADHip_ResamplerRunGain(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels,
@@ -1691,9 +1753,11 @@ AADApiResult AADHip_ResamplerRunGain(struct AADHipResampler *r, uint64_t num_win
   if (num_windows == 0) return AAD_APIRESULT_OK;
   m.spans = reinterpret_cast<const uint64_t *>(device_spans);
   m.gain = device_gain;
+  m.round = r->round;
+  const bool add = mode == AAD_HIP_WINDOW_GAIN_ADD;
   return resampler_launched(r, "resampler run with gain",
-                            aad::launch_resample_rows_gain(m, sample_type, mode == AAD_HIP_WINDOW_GAIN_ADD,
-                                                           (uint32_t)(2 * (r->bank_elements + r->span_elements)), ctx->stream));
+                            r->wide ? aad::launch_resample_rows_gain_wide(m, sample_type, add, resampler_lds_bytes(r), ctx->stream)
+                                    : aad::launch_resample_rows_gain(m, sample_type, add, resampler_lds_bytes(r), ctx->stream));
 }
 
 AADApiResult AADHip_ResamplerRunStats(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels,
@@ -1726,9 +1790,10 @@ AADApiResult AADHip_ResamplerRunStats(struct AADHipResampler *r, uint64_t num_wi
   m.source_stats = reinterpret_cast<const unsigned long long *>(device_source_stats);
   m.stats = reinterpret_cast<unsigned long long *>(device_stats);
   if (!hip_ok(ctx, hipMemsetAsync(device_stats, 0, t.bytes, ctx->stream), "hipMemsetAsync")) return AAD_APIRESULT_NG;
+  m.round = r->round;
   return resampler_launched(r, "resampler run with statistics",
-                            aad::launch_resample_rows_stats(m, sample_type, (uint32_t)(2 * (r->bank_elements + r->span_elements)),
-                                                            ctx->stream));
+                            r->wide ? aad::launch_resample_rows_stats_wide(m, sample_type, resampler_lds_bytes(r), ctx->stream)
+                                    : aad::launch_resample_rows_stats(m, sample_type, resampler_lds_bytes(r), ctx->stream));
 }
 
 /* -------------------------------------------------------------------- window reconstruct -- */

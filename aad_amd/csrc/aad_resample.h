@@ -3,7 +3,8 @@
  * (built on the host in double precision), the source batch's row length and the per-window resolve, which the resolve kernel
  * (aad_resample.hip) runs once per window, and a row's span and `count` for the runs with spans and statistics.  A CPU test runs
  * the same functions against a numpy restatement of the definition (tests/resample_policy_driver.cpp, tests/resample_oracle.py;
- * tests/resample_mix_driver.cpp against a brute force).  Plain C++ with no container, as aad_windows.h. */
+ * tests/resample_mix_driver.cpp against a brute force; tests/resample_wide_driver.cpp for the limits of a wide resampler and the
+ * gather plan of its kernels, at the end of this file).  Plain C++ with no container, as aad_windows.h. */
 #ifndef AAD_RESAMPLE_H
 #define AAD_RESAMPLE_H
 
@@ -26,6 +27,10 @@ constexpr uint32_t kResampleMaxTaps = 256;        /* K */
 constexpr uint32_t kResampleMaxBankBytes = 65536; /* 2 L K */
 constexpr uint32_t kResampleMaxAbsSum = 65535;    /* sum |h| of a phase: 32768 * 65535 < 2^31, int32 accumulators are exact */
 constexpr uint32_t kResampleNoBank = 0xFFFF;      /* a select entry, a lane's bank: the row is zeros */
+/* AADHip_ResamplerCreateWide: K, sum |h| and the definitions as above; L and the bank are bounded by the 32-bit indices alone */
+constexpr uint32_t kResampleWideMaxPhases = 32768;       /* L */
+constexpr uint32_t kResampleWideMaxBankBytes = 2u << 20; /* 2 L K */
+constexpr uint64_t kResampleMaxCoefficients = 1ull << 31; /* all banks of a resampler: ResampleBankDesc::offset is 32-bit */
 
 /* ---- ratio -------------------------------------------------------------------------------------------------------------------- */
 
@@ -62,6 +67,21 @@ inline bool resample_shape_ok(uint32_t L, uint32_t M)
   if (L > kResampleMaxPhases) return false;
   const uint64_t K = resample_taps(L, M);
   return K <= kResampleMaxTaps && 2ull * L * K <= kResampleMaxBankBytes;
+}
+
+/* what AADHip_ResamplerCreateWide refuses before it builds the bank; everything resample_shape_ok accepts passes */
+inline bool resample_wide_shape_ok(uint32_t L, uint32_t M)
+{
+  if (L > kResampleWideMaxPhases) return false;
+  const uint64_t K = resample_taps(L, M);
+  return K <= kResampleMaxTaps && 2ull * L * K <= kResampleWideMaxBankBytes;
+}
+
+/* resample_shape_ok from a bank's own (L, K): the FIR kernels of a wide resampler keep such a bank whole in LDS ("resident") and
+ * gather the rows of any other per round of outputs */
+AAD_RESAMPLE_FN bool resample_bank_resident(uint32_t L, uint32_t K)
+{
+  return L <= kResampleMaxPhases && K <= kResampleMaxTaps && 2ull * L * K <= kResampleMaxBankBytes;
 }
 
 /* ---- bank --------------------------------------------------------------------------------------------------------------------- */
@@ -202,8 +222,8 @@ AAD_RESAMPLE_FN uint64_t resample_span_frames(uint64_t num_frames, uint64_t out_
 
 /* `count` of a resampled row: the number of n < Le whose centre source frame, element shift + (n M) div L of the source row, the
  * stream had - c_src being the source row's own count (AADHip_WindowDecodePlanRunStats over the source windows), never more than
- * the row's length.  shift + (n M) div L < c  <=>  n M < (c - shift) L  <=>  n < ceil((c - shift) L / M); c < 2^32 and L <= 1024,
- * so 64 bits hold the product. */
+ * the row's length.  shift + (n M) div L < c  <=>  n M < (c - shift) L  <=>  n < ceil((c - shift) L / M); c < 2^32 and L <= 32768
+ * (a wide resampler's largest), so the product is below 2^47 and 64 bits hold it with M added. */
 AAD_RESAMPLE_FN uint64_t resample_output_count(uint64_t c_src, uint32_t source_frames, uint32_t shift, uint32_t L, uint32_t M,
                                                uint64_t Le)
 {
@@ -211,6 +231,62 @@ AAD_RESAMPLE_FN uint64_t resample_output_count(uint64_t c_src, uint32_t source_f
   if (c <= shift) return 0;
   const uint64_t n = ((c - shift) * L + M - 1) / M;
   return n < Le ? n : Le;
+}
+
+/* ---- LDS of the FIR kernels (aad_resample_tile.hip.h, aad_resample_wide.hip) ---------------------------------------------------- */
+
+constexpr uint32_t kResampleThreads = 256;
+constexpr uint32_t kResamplePerThread = 4;
+constexpr uint32_t kResampleTile = kResampleThreads * kResamplePerThread; /* outputs of one workgroup's tile */
+
+/* int16 elements between two phases of a bank in LDS: adjacent outputs read different phases, each its K taps as K/2 words in
+ * step, so the phases' rows start an odd number of words apart - p -> p * stride / 2 mod 32 then maps 32 phases onto 32 banks */
+AAD_RESAMPLE_FN uint32_t resample_lds_stride(uint32_t K) { return (K / 2) % 2 == 0 ? K + 2 : K; }
+/* int16 elements of a tile's span of the source row: the frames from the first output's first tap to the last output's last,
+ * one in front for the 4-byte alignment of the row's loads, and the word a thread at an odd element reads past its last tap */
+inline uint64_t resample_span_elements(uint32_t L, uint32_t M, uint32_t K)
+{
+  return ((((uint64_t)(kResampleTile - 1) * M) / L + 1 + K + 1 + 2) + 1) / 2 * 2;
+}
+/* bytes of LDS of a workgroup whose bank is (L, M, K), the bank whole */
+inline uint64_t resample_lds_bytes(uint32_t L, uint32_t M, uint32_t K)
+{
+  return 2 * ((uint64_t)L * resample_lds_stride(K) + resample_span_elements(L, M, K));
+}
+
+/* The gather path of a wide resampler's kernels.  A tile is walked in rounds of R consecutive outputs, and a round has in LDS one
+ * bank row per output - resample_lds_stride(K) int16 - and the output's phase, a 32-bit word: 2 * stride + 4 bytes an output.  R is
+ * the largest of 256, 128 and 64 whose rows and phases stay within kResampleGatherBytes: small enough that, with a span of a few
+ * KB, three or four workgroups share a CU's 160 KB and run through each other's barriers; 64 always fits (K = 256: 64 * 520 bytes).
+ * 256 is the tile's 256 threads with one output each; a smaller R leaves the other waves only the copy. */
+constexpr uint32_t kResampleGatherBytes = 40960;
+constexpr uint32_t kResampleMaxRound = kResampleThreads;
+inline uint32_t resample_gather_round(uint32_t K)
+{
+  uint32_t R = kResampleMaxRound;
+  while (R > 64 && (uint64_t)R * (2 * resample_lds_stride(K) + 4) > kResampleGatherBytes) R /= 2;
+  return R;
+}
+/* int16 elements between two rows of a gathered bank in DEVICE memory: rows on 16-byte boundaries, so that the copy reads them
+ * with 16-byte loads - a quarter of the load instructions, which are what the copy costs.  The bank on the host, which
+ * AADHip_ResamplerBank returns, and a resident bank on the device keep their rows K apart. */
+AAD_RESAMPLE_FN uint32_t resample_gather_pitch(uint32_t K) { return (K + 7u) & ~7u; }
+/* Output u of a tile - thread tid's j-th output is u = tid + 256 j - belongs to round u / R of the tile and is row u mod R of it: R
+ * is a power of two.  The kernel publishes the output's phase at index[row] and reads its taps from row `row` of the round. */
+struct ResampleGatherSlot {
+  uint32_t round, row;
+};
+AAD_RESAMPLE_FN ResampleGatherSlot resample_gather_slot(uint32_t u, uint32_t R)
+{
+  return ResampleGatherSlot{u >> __builtin_ctz(R), u & (R - 1)};
+}
+/* what a gathered bank (L, M, K) needs of LDS at round R: { rows, phase index, span } in bytes */
+struct ResampleGatherLds {
+  uint64_t rows, index, span;
+};
+inline ResampleGatherLds resample_gather_lds(uint32_t L, uint32_t M, uint32_t K, uint32_t R)
+{
+  return ResampleGatherLds{2ull * R * resample_lds_stride(K), 4ull * R, 2 * resample_span_elements(L, M, K)};
 }
 
 } /* namespace aad */

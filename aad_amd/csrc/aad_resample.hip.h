@@ -11,10 +11,6 @@
 
 namespace aad {
 
-constexpr uint32_t kResampleThreads = 256;
-constexpr uint32_t kResamplePerThread = 4;
-constexpr uint32_t kResampleTile = kResampleThreads * kResamplePerThread; /* outputs of one workgroup's tile */
-
 struct ResampleResolveArgs {
   const uint64_t *windows; /* struct AADHipWindow[num_windows], device memory */
   const uint64_t *variant; /* int64[num_windows], device memory; null: every variant is 0 */
@@ -30,23 +26,10 @@ struct ResampleResolveArgs {
 /* one bank as the FIR kernel sees it */
 struct ResampleBankDesc {
   uint32_t L, M, K;
-  uint32_t offset; /* first coefficient, in elements of the coefficient array: phase p's K taps at offset + p * K */
+  uint32_t offset; /* first coefficient, in elements of the coefficient array: phase p's K taps at offset + p * K - of a gathered
+                      bank (a wide resampler's, not resample_bank_resident) at offset + p * resample_gather_pitch(K), offset a
+                      multiple of 8 */
 };
-
-/* int16 elements between two phases of a bank in LDS: adjacent outputs read different phases, each its K taps as K/2 words in
- * step, so the phases' rows start an odd number of words apart - p -> p * stride / 2 mod 32 then maps 32 phases onto 32 banks */
-__host__ __device__ inline uint32_t resample_lds_stride(uint32_t K) { return (K / 2) % 2 == 0 ? K + 2 : K; }
-/* int16 elements of a tile's span of the source row: the frames from the first output's first tap to the last output's last,
- * one in front for the 4-byte alignment of the row's loads, and the word a thread at an odd element reads past its last tap */
-inline uint64_t resample_span_elements(uint32_t L, uint32_t M, uint32_t K)
-{
-  return ((((uint64_t)(kResampleTile - 1) * M) / L + 1 + K + 1 + 2) + 1) / 2 * 2;
-}
-/* bytes of LDS of a workgroup whose bank is (L, M, K) */
-inline uint64_t resample_lds_bytes(uint32_t L, uint32_t M, uint32_t K)
-{
-  return 2 * ((uint64_t)L * resample_lds_stride(K) + resample_span_elements(L, M, K));
-}
 
 struct ResampleRowsArgs {
   const int16_t *src;            /* [num_windows, channels, source_frames] */
@@ -60,7 +43,8 @@ struct ResampleRowsArgs {
   uint32_t frames;        /* T */
   uint32_t source_frames; /* the source rows' length */
   uint32_t tiles;         /* ceil(T / kResampleTile) */
-  uint32_t bank_elements; /* int16 elements of LDS in front of the span: the largest L * resample_lds_stride(K) */
+  uint32_t bank_elements; /* int16 elements of LDS in front of the span: the largest L * resample_lds_stride(K) - of a wide
+                             resampler: over its resident banks, and R * resample_lds_stride(K) over the gathered ones */
   uint32_t span_elements; /* the largest resample_span_elements */
 };
 
@@ -72,7 +56,8 @@ struct ResampleMixArgs {
   const unsigned long long *source_stats;  /* Stats: struct AADHipRowStats[rows] of the source batch */
   unsigned long long *stats;               /* Stats: struct AADHipRowStats[rows], cleared in front of the launch */
   uint32_t scratch_words;                  /* Stats: 32-bit words of LDS in front of the reduction scratch */
-  uint32_t reserved;
+  uint32_t round;                          /* the kernels of a wide resampler: R of the gather path, its phase index R words
+                                              behind bank and span */
 };
 
 /* bytes of the statistics kernel's reduction scratch, behind bank and span on a 16-byte boundary: three 64-bit values a wave */
@@ -86,6 +71,12 @@ bool launch_resample_rows(const ResampleRowsArgs &a, int32_t sample_type, uint32
 bool launch_resample_rows_gain(const ResampleMixArgs &a, int32_t sample_type, bool add, uint32_t lds_bytes, hipStream_t stream);
 /* a.r.out == null: statistics only; lds_bytes as above - the launch adds the scratch and sets a.scratch_words */
 bool launch_resample_rows_stats(const ResampleMixArgs &a, int32_t sample_type, uint32_t lds_bytes, hipStream_t stream);
+
+/* The kernels of a wide resampler (aad_resample_wide.hip), all three over ResampleMixArgs with `round` set; lds_bytes:
+ * 2 * (bank_elements + span_elements) + 4 * round */
+bool launch_resample_rows_wide(const ResampleMixArgs &a, int32_t sample_type, uint32_t lds_bytes, hipStream_t stream);
+bool launch_resample_rows_gain_wide(const ResampleMixArgs &a, int32_t sample_type, bool add, uint32_t lds_bytes, hipStream_t stream);
+bool launch_resample_rows_stats_wide(const ResampleMixArgs &a, int32_t sample_type, uint32_t lds_bytes, hipStream_t stream);
 
 } /* namespace aad */
 

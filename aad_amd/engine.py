@@ -689,17 +689,19 @@ class Engine:
         """The level statistics of decode_windows_mixed's rows without the rows: int64 [N, channels, 4] of (sum_sq, sum_abs,
         max_abs, count) per row, in int16 units (rmse, level_dbfs).  Nothing is stored but the table - what a rejection sampler
         asks of its candidates before it decodes the ones it keeps.  channels=None: the images share a channel count.
-        spans: int64 cuda tensor [N, 2] of (num_frames, out_frame) - the levels of each window's clipped crop alone."""
+        spans: int64 cuda tensor [N, 2] of (num_frames, out_frame) - the levels of each window's clipped crop alone.  wide: as decode_windows_resampled."""
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
             return plan.run(data, windows, frames, stats=True, rows=False, spans=spans)
         finally:
             plan.close()  # synchronises the context's stream first
 
-    def resampler(self, ratios, select):
+    def resampler(self, ratios, select, wide=False):
         """A resample stage behind window decode plans (AADHip_ResamplerCreate): ratios is a list of (up, down), output rate over
         source rate, each with a bank of its own; select[stream][variant] is the index of the ratio that windows of `stream` drawn
-        with `variant` take, None (or RESAMPLE_NO_BANK) for a row of zeros.  Resampler.run decodes windows at their ratios."""
+        with `variant` take, None (or RESAMPLE_NO_BANK) for a row of zeros.  Resampler.run decodes windows at their ratios.
+        wide=True: AADHip_ResamplerCreateWide - ratios of up to 32768 phases and 2 MiB of bank, such as 1600/3969 (44.1 kHz to
+        16 kHz at speed 9/10); the same Resampler, the same rows."""
         ratios = [(int(u), int(d)) for u, d in ratios]
         table = np.array([[RESAMPLE_NO_BANK if v is None else int(v) for v in row] for row in select], dtype=np.int64)
         table = table.reshape(len(table), -1)
@@ -710,24 +712,25 @@ class Engine:
         table = np.ascontiguousarray(table, dtype=np.uint16)
         records = (AADHipResampleRatio * max(len(ratios), 1))(*[AADHipResampleRatio(u, d) for u, d in ratios])
         handle = C.c_void_p()
-        _check("AADHip_ResamplerCreate",
-               self.lib.AADHip_ResamplerCreate(self._ctx, len(ratios), records, table.shape[0], table.shape[1], table.ctypes.data,
-                                               C.byref(handle)))
+        name = "AADHip_ResamplerCreateWide" if wide else "AADHip_ResamplerCreate"
+        _check(name, getattr(self.lib, name)(self._ctx, len(ratios), records, table.shape[0], table.shape[1], table.ctypes.data,
+                                             C.byref(handle)))
         return Resampler(self, handle, ratios, table)
 
     def decode_windows_resampled(self, data, image_sizes, windows, frames, rate, speeds=((1, 1),), variant=None, dtype=None,
-                                 channels=None, out=None, gain=None, accumulate=False, spans=None, return_stats=False):
+                                 channels=None, out=None, gain=None, accumulate=False, spans=None, return_stats=False, wide=False):
         """decode_windows_mixed at one output rate: every image's header names its sampling_rate, and a window of stream s drawn
         with variant v - an index into `speeds`, pairs (a, b) for the speed a / b; `variant` is an int64 cuda tensor [N], None for
         all 0 - is resampled by rate * b / (sampling_rate_s * a).  Speed 11/10 plays a stream 10 % faster: fewer output frames
         per source frame.  `frames` counts output frames, windows[:, 1] source frames as everywhere.  Streams and speeds whose
         reduced ratios agree share a bank.  dtype, channels, out: as decode_windows_mixed.
         gain / accumulate / out, spans (in output frames) and return_stats: as decode_windows_mixed, on the resampled rows
-        (Resampler.run)."""
+        (Resampler.run).  wide=True builds the resampler with AADHip_ResamplerCreateWide: a 44.1 kHz stream at speeds 9/10 and
+        11/10 needs it (1600 phases); the default refuses such a corpus as before."""
         self._speeds(rate, speeds)
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
-            res = self._corpus_resampler(plan, rate, speeds)
+            res = self._corpus_resampler(plan, rate, speeds, wide)
             try:
                 return res.run(plan, data, windows, frames, variant=variant, dtype=dtype, out=out, gain=gain, accumulate=accumulate,
                                spans=spans, stats=True if return_stats else None)
@@ -737,15 +740,15 @@ class Engine:
             plan.close()
 
     def window_levels_resampled(self, data, image_sizes, windows, frames, rate, speeds=((1, 1),), variant=None, channels=None,
-                                spans=None):
+                                spans=None, wide=False):
         """The level statistics of decode_windows_resampled's rows without the rows: int64 [N, channels, 4] of (sum_sq, sum_abs,
         max_abs, count) per row in int16 units, count = the output frames whose centre source frame the stream had.  Nothing is
         stored but the source batch and the table.  spans: int64 cuda tensor [N, 2] of (num_frames, out_frame) in output frames -
-        the levels of each window's clipped crop alone."""
+        the levels of each window's clipped crop alone.  wide: as decode_windows_resampled."""
         self._speeds(rate, speeds)
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
-            res = self._corpus_resampler(plan, rate, speeds)
+            res = self._corpus_resampler(plan, rate, speeds, wide)
             try:
                 return res.run(plan, data, windows, frames, variant=variant, stats=True, rows=False, spans=spans)
             finally:
@@ -754,14 +757,14 @@ class Engine:
             plan.close()
 
     def mix_windows_resampled(self, signal, noise, frames, snr_db, rate, speeds=((1, 1),), signal_variant=None, noise_variant=None,
-                              dtype=None, channels=None, noise_spans=None):
+                              dtype=None, channels=None, noise_spans=None, wide=False):
         """mix_windows at one output rate: signal, noise: each (data, image_sizes, windows) as for decode_windows_resampled, the
         same number of windows, each corpus with its own sampling rates; rate, speeds and the two variant tables as there.
         Each corpus is decoded ONCE into its int16 source batch, with statistics (Resampler.decode_source); the FIR then runs
         twice over each batch: statistics only for the levels - the noise's over noise_spans - and, with snr_gains' gains on the
         device, a STORE run of the signal and an ADD run of gain * noise into the same rows -> (rows [N, channels, frames] of
         `dtype`, float32 [N] noise gains).  No float32 batch, no elementwise pass; the roundings and the meaning of noise_spans
-        (in output frames) and of the SNR are mix_windows'."""
+        (in output frames) and of the SNR are mix_windows'.  wide: as decode_windows_resampled, for both corpora."""
         torch = self.torch
         dtype = torch.float32 if dtype is None else dtype
         self._speeds(rate, speeds)
@@ -773,9 +776,9 @@ class Engine:
                 if ch != n_ch:
                     raise ValueError("signal and noise: rows of %d and %d channels do not mix - pass channels=1 or channels=2 to bring "
                                      "both corpora to one channel count" % (ch, n_ch))
-                s_res = self._corpus_resampler(s_plan, rate, speeds)
+                s_res = self._corpus_resampler(s_plan, rate, speeds, wide)
                 try:
-                    n_res = self._corpus_resampler(n_plan, rate, speeds)
+                    n_res = self._corpus_resampler(n_plan, rate, speeds, wide)
                     try:
                         s_src = s_res.decode_source(s_plan, signal[0], signal[2], frames, variant=signal_variant, stats=True)
                         n_src = n_res.decode_source(n_plan, noise[0], noise[2], frames, variant=noise_variant, stats=True)
@@ -802,7 +805,7 @@ class Engine:
             raise ValueError("rate and speeds: positive integers, at least one speed; got rate %r, speeds %r" % (rate, speeds))
         return speeds
 
-    def _corpus_resampler(self, plan, rate, speeds):
+    def _corpus_resampler(self, plan, rate, speeds, wide=False):
         """the resampler of a corpus plan at one output rate: per stream and speed (a, b) the ratio rate * b / (sampling_rate * a),
         equal reduced ratios sharing a bank"""
         from math import gcd
@@ -820,7 +823,7 @@ class Engine:
                     ratios.append(r)
                 row.append(ratios.index(r))
             select.append(row)
-        return self.resampler(ratios, select)
+        return self.resampler(ratios, select, wide) if wide else self.resampler(ratios, select)
 
     def _corpus_window_plan(self, data, image_sizes, channels):
         """the window decode plan over the images in the rows of `data`: mixed-format, or channel-mix when `channels` is given"""

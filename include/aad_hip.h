@@ -564,6 +564,24 @@ AADApiResult AADHip_ResamplerRun(
     const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipResampleLane *device_lanes,
     uint32_t frames, int32_t sample_type, void *device_out);
 
+/* A wide resampler: ratios whose bank does not fit a workgroup's LDS.  16 kHz rows from a 44.1 kHz stream at speeds 9/10 and 11/10
+ * are the ratios 1600/3969 and 1600/4851, 48 kHz rows from it at 11/10 are 1600/1617: L = 1600, which AADHip_ResamplerCreate
+ * refuses.  AADHip_ResamplerCreateWide takes AADHip_ResamplerCreate's arguments and returns an ordinary resampler:
+ * AADHip_ResamplerBank, ...SourceFrames, ...Resolve, ...Run, ...RunGain, ...RunStats and ...Destroy take it as they take any other,
+ * with their own errors, and every definition above and below - the bank, the row, the resolve, T_src, the spans, the records -
+ * holds for it word for word.  Only the limits of a ratio differ, after reduction:
+ *   L <= 32768, K <= 256 (as before), 2 L K <= 2 MiB per bank, sum |h| <= 65535 per phase (as before), and fewer than 2^31
+ *   coefficients in all banks together, a bank that AADHip_ResamplerCreate would refuse counted with K rounded up to 8;
+ * every other refusal - null pointers, num_ratios, variants, select entries, up == 0 or down == 0 - is AADHip_ResamplerCreate's.
+ * Opt-in: AADHip_ResamplerCreate keeps its limits, its refusals and its kernels.  The runs of a wide resampler launch kernels of
+ * their own, which keep a bank that AADHip_ResamplerCreate would accept whole in LDS - its rows are then computed by the same
+ * code, the same bits follow from the definition either way - and read only the bank rows a round of 64 to 256 consecutive
+ * outputs uses from global memory for any other (DESIGN.md "Wide resampler").  Banks are built on the host as before. */
+AADApiResult AADHip_ResamplerCreateWide(
+    struct AADHipContext *context, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
+    uint32_t num_streams, uint32_t variants, const uint16_t *select,
+    struct AADHipResampler **resampler);
+
 /* Resampled rows with a gain, spans and level statistics: the loader toolbox of window decode - AADHip_WindowDecodePlanRunStats,
  * ...RunGain, ...RunPlaced, ...RunPlacedStats - in the FIR kernel, for the corpus whose speech and noise come at different rates.
  * A noisy batch at one output rate decodes each source batch once (AADHip_ResamplerResolve, then

@@ -1,7 +1,8 @@
 """What the resample stage costs next to the window decode it follows (DESIGN.md "Window decode at another rate").
 
 Shape: --windows stereo windows (default 1024) of --frames output frames (default 48000) drawn from a 4-bit corpus on the device,
-once at 147/160 (48 kHz to 44.1 kHz) and once at 160/147.  Per ratio, each step's time from HIP events recorded on the engine's
+once at 147/160 (48 kHz to 44.1 kHz) and once at 160/147 - or at every --ratio UP/DOWN given, any ratio the constructor takes;
+--wide builds the resamplers with AADHip_ResamplerCreateWide (DESIGN.md "Wide resampler"), which 1600/3969 needs.  Per ratio, each step's time from HIP events recorded on the engine's
 stream around it, the median of --steps runs after --warmup:
   resolve   AADHip_ResamplerResolve
   decode    AADHip_WindowDecodePlanRun of the source windows, T_src frames, int16 - the source batch
@@ -35,6 +36,11 @@ from aad_amd.synth import synth_pcm  # noqa: E402
 
 def timed(stream, steps, warmup, fn):
     """median milliseconds of fn's work on `stream`, between two events recorded around it"""
+    return statistics.median(timed_all(stream, steps, warmup, fn))
+
+
+def timed_all(stream, steps, warmup, fn):
+    """the milliseconds of each of `steps` runs of fn on `stream`"""
     ms = []
     for k in range(warmup + steps):
         start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -44,7 +50,7 @@ def timed(stream, steps, warmup, fn):
         stop.synchronize()
         if k >= warmup:
             ms.append(start.elapsed_time(stop))
-    return statistics.median(ms)
+    return ms
 
 
 def timed_in_turn(stream, steps, warmup, fns):
@@ -88,7 +94,7 @@ def mix_rows(engine, args, plan, data, size, windows, lines):
     """the three rows of --mix, at 147/160"""
     lib = engine.lib
     n, frames, ch = args.windows, args.frames, 2
-    res = engine.resampler([(147, 160)], [[0]] * args.streams)
+    res = make_resampler(engine, args, (147, 160))
     source = res.decode_source(plan, data, windows, frames, stats=True)
     t_src = source.source_frames
     out = torch.empty((n, ch, frames), dtype=torch.float32, device="cuda")
@@ -105,7 +111,7 @@ def mix_rows(engine, args, plan, data, size, windows, lines):
            ("stats", lambda: _check("AADHip_ResamplerRunStats", lib.AADHip_ResamplerRunStats(
                *head, source.stats.data_ptr(), None, frames, SAMPLE_FLOAT32, None, stats.data_ptr()))))
     ms = timed_in_turn(engine.stream, args.steps, args.warmup, fns)
-    lines.append("fir variants 147/160  N=%d C=%d T=%d  " % (n, ch, frames) + "  ".join(
+    lines.append("fir variants 147/160%s  N=%d C=%d T=%d  " % (" wide" if args.wide else "", n, ch, frames) + "  ".join(
         "%s %.3f ms (%.3f - %.3f)" % (name, statistics.median(v), min(v), max(v)) for name, v in ms.items()))
     print(lines[-1], flush=True)
     res.close()
@@ -131,6 +137,12 @@ def mix_rows(engine, args, plan, data, size, windows, lines):
     print(lines[-1], flush=True)
 
 
+def make_resampler(engine, args, ratio):
+    """one bank for every stream; the plain call is made as it always was"""
+    select = [[0]] * args.streams
+    return engine.resampler([ratio], select, wide=True) if args.wide else engine.resampler([ratio], select)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=1024)
@@ -140,11 +152,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out")
     ap.add_argument("--mix", action="store_true", help="add the rows of the FIR variants and of mix_windows_resampled")
+    ap.add_argument("--wide", action="store_true", help="build the resamplers with AADHip_ResamplerCreateWide")
+    ap.add_argument("--ratio", action="append", metavar="UP/DOWN", help="a ratio to time instead of 147/160 and 160/147; repeatable")
     args = ap.parse_args()
+    ratios = [tuple(int(v) for v in r.split("/")) for r in args.ratio] if args.ratio else [(147, 160), (160, 147)]
     engine = Engine(0, stream=None)
     lib = engine.lib
     n, frames, ch = args.windows, args.frames, 2
-    samples = frames * 160 // 147 * 2 + 4096  # every window lies inside its stream at either ratio
+    steepest = max([160 / 147] + [down / up for up, down in ratios])
+    samples = int(frames * steepest) * 2 + 4096  # every window lies inside its stream at every ratio
     pcm = synth_pcm(args.streams, samples, ch, seed=5)
     lines = []
     with torch.cuda.stream(engine.stream):
@@ -153,8 +169,8 @@ def main():
         gen = torch.Generator(device="cuda").manual_seed(11)
         windows = torch.stack([torch.randint(0, args.streams, (n,), generator=gen, device="cuda"),
                                torch.randint(0, samples // 2 - 4096, (n,), generator=gen, device="cuda")], dim=1).contiguous()
-        for ratio in ((147, 160), (160, 147)):
-            res = engine.resampler([ratio], [[0]] * args.streams)
+        for ratio in ratios:
+            res = make_resampler(engine, args, ratio)
             t_src = res.source_frames(frames)
             src_windows = torch.empty((n, 2), dtype=torch.int64, device="cuda")
             lanes = torch.empty((n, 2), dtype=torch.int32, device="cuda")
@@ -167,8 +183,10 @@ def main():
             fir = lambda: _check("AADHip_ResamplerRun", lib.AADHip_ResamplerRun(
                 res.handle, n, ch, rows.data_ptr(), t_src, lanes.data_ptr(), frames, SAMPLE_FLOAT32, out.data_ptr()))
             decode_plain = lambda: plan.run(data, windows, frames, torch.float32, out=plain, ordered=False)
-            t = {name: timed(engine.stream, args.steps, args.warmup, fn)
-                 for name, fn in (("resolve", resolve), ("decode", decode), ("fir", fir), ("plain", decode_plain))}
+            t = {name: timed(engine.stream, args.steps, args.warmup, fn) for name, fn in (("resolve", resolve), ("decode", decode))}
+            fir_ms = timed_all(engine.stream, args.steps, args.warmup, fir)
+            t["fir"] = statistics.median(fir_ms)
+            t["plain"] = timed(engine.stream, args.steps, args.warmup, decode_plain)
             t["plain again"] = timed(engine.stream, args.steps, args.warmup, decode_plain)  # drift between the first and the last
             moved = n * ch * (t_src * 2 + frames * 4)
             import resample_oracle as ro
@@ -176,9 +194,9 @@ def main():
             s, f = (int(v) for v in windows[0].cpu())
             want = ro.convert(ro.fir(pcm_decoded(engine, data, size, s)[:, 0], f, frames, L, M, h), "float32")
             exact = bool((out[0, 0].cpu().numpy().view(np.uint32) == want).all())
-            lines.append("ratio %d/%d  N=%d C=%d T=%d T_src=%d  resolve %.4f ms  decode (int16 source batch) %.3f ms  fir %.3f ms "
+            lines.append("ratio %d/%d%s K=%d  N=%d C=%d T=%d T_src=%d  resolve %.4f ms  decode (int16 source batch) %.3f ms  fir %.3f ms (%.3f - %.3f) "
                          "(%.1f MB moved, %.0f GB/s)  three steps %.3f ms  plain float32 decode %.3f ms (again %.3f)  fir / decode %.2f  "
-                         "exact=%s" % (ratio[0], ratio[1], n, ch, frames, t_src, t["resolve"], t["decode"], t["fir"], moved / 1e6,
+                         "exact=%s" % (ratio[0], ratio[1], " wide" if args.wide else "", h.shape[1], n, ch, frames, t_src, t["resolve"], t["decode"], t["fir"], min(fir_ms), max(fir_ms), moved / 1e6,
                                        moved / t["fir"] / 1e6, t["resolve"] + t["decode"] + t["fir"], t["plain"], t["plain again"],
                                        t["fir"] / t["decode"], exact))
             print(lines[-1], flush=True)
