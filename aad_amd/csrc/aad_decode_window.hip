@@ -1,38 +1,17 @@
 /* aad_decode_window.hip - translation unit of the window decoder (aad_decode_window.hip.h). */
 #include "aad_decode_window.hip.h"
-#include "aad_launch.h"
+#include "aad_window_unit.hip.h"
 
 namespace aad {
 
-template <int BITS, int ST>
-static void launch_bits(const WindowArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
-{
-  if (a.channels == 1)
-    AAD_LAUNCH((decode_window_kernel<BITS, 1, false, ST>), grid, block, lds, stream, a);
-  else if (a.channels == 2 && a.mid_side)
-    AAD_LAUNCH((decode_window_kernel<BITS, 2, true, ST>), grid, block, lds, stream, a);
-  else if (a.channels == 2)
-    AAD_LAUNCH((decode_window_kernel<BITS, 2, false, ST>), grid, block, lds, stream, a);
-  else
-    AAD_LAUNCH((decode_window_kernel<BITS, 0, false, ST>), grid, block, lds, stream, a);
-}
-
-template <int ST>
-static void launch_type(const WindowArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
-{
-  if (a.bits == 4) launch_bits<4, ST>(a, grid, block, lds, stream);
-  else if (a.bits == 3) launch_bits<3, ST>(a, grid, block, lds, stream);
-  else launch_bits<2, ST>(a, grid, block, lds, stream);
-}
-
 template <>
-void launch_decode_window_unit<AAD_WINDOW_HALF != 0>(
-    const WindowArgs &a, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  using T = WindowUnitTypes<AAD_WINDOW_HALF != 0>;
-  const dim3 grid(p.grid), block(p.workgroup);
-  if (sample_type == T::second) launch_type<T::second>(a, grid, block, p.lds, stream);
-  else launch_type<T::first>(a, grid, block, p.lds, stream);
-}
+struct WindowUnit<WindowKind::Same, WindowMode::Rows> {
+  using Args = WindowArgs;
+  static Args pack(const WindowUnitRun &r) { return r.w; }
+  static const WindowArgs &window(const Args &a) { return a; }
+  template <int BITS, int CHF, bool MS, int ST, int OUTC>
+  static constexpr auto kernel = &decode_window_kernel<BITS, CHF, MS, ST>;
+};
+AAD_WINDOW_UNIT(Same, Rows);
 
 } /* namespace aad */

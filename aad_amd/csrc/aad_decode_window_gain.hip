@@ -1,44 +1,18 @@
 /* aad_decode_window_gain.hip - translation unit of the same-format window decoder with a per-window gain
  * (aad_decode_window_gain.hip.h).  AAD_WINDOW_HALF=0: float32 rows alone (a gain has no int16 rows). */
 #include "aad_decode_window_gain.hip.h"
-#include "aad_launch.h"
+#include "aad_window_unit.hip.h"
 
 namespace aad {
 
-template <int BITS, int ST>
-static void launch_bits(const WindowGainArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
-{
-  if (a.w.channels == 1)
-    AAD_LAUNCH((decode_window_gain_kernel<BITS, 1, false, ST>), grid, block, lds, stream, a);
-  else if (a.w.channels == 2 && a.w.mid_side)
-    AAD_LAUNCH((decode_window_gain_kernel<BITS, 2, true, ST>), grid, block, lds, stream, a);
-  else if (a.w.channels == 2)
-    AAD_LAUNCH((decode_window_gain_kernel<BITS, 2, false, ST>), grid, block, lds, stream, a);
-  else
-    AAD_LAUNCH((decode_window_gain_kernel<BITS, 0, false, ST>), grid, block, lds, stream, a);
-}
-
-template <int ST>
-static void launch_type(const WindowGainArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
-{
-  if (a.w.bits == 4) launch_bits<4, ST>(a, grid, block, lds, stream);
-  else if (a.w.bits == 3) launch_bits<3, ST>(a, grid, block, lds, stream);
-  else launch_bits<2, ST>(a, grid, block, lds, stream);
-}
-
 template <>
-void launch_decode_window_gain_unit<AAD_WINDOW_HALF != 0>(
-    const WindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  const WindowGainArgs a = {args, gain, add, 0};
-  const dim3 grid(p.grid), block(p.workgroup);
-#if AAD_WINDOW_HALF
-  if (sample_type == AAD_HIP_SAMPLE_BFLOAT16) launch_type<AAD_HIP_SAMPLE_BFLOAT16>(a, grid, block, p.lds, stream);
-  else launch_type<AAD_HIP_SAMPLE_FLOAT16>(a, grid, block, p.lds, stream);
-#else
-  (void)sample_type;
-  launch_type<AAD_HIP_SAMPLE_FLOAT32>(a, grid, block, p.lds, stream);
-#endif
-}
+struct WindowUnit<WindowKind::Same, WindowMode::Gain> {
+  using Args = WindowGainArgs;
+  static Args pack(const WindowUnitRun &r) { return Args{r.w, r.gain, r.add, 0}; }
+  static const WindowArgs &window(const Args &a) { return a.w; }
+  template <int BITS, int CHF, bool MS, int ST, int OUTC>
+  static constexpr auto kernel = &decode_window_gain_kernel<BITS, CHF, MS, ST>;
+};
+AAD_WINDOW_UNIT(Same, Gain);
 
 } /* namespace aad */

@@ -1,41 +1,18 @@
 /* aad_decode_window_mixed_stats.hip - translation unit of the mixed-format window decoder with statistics
  * (aad_decode_window_stats.hip.h). */
 #include "aad_decode_window_stats.hip.h"
-#include "aad_launch.h"
+#include "aad_window_unit.hip.h"
 
 namespace aad {
 
-template <int BITS, int ST>
-static void launch_bits(const MixedWindowStatsArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
-{
-  if (a.m.w.channels == 1)
-    AAD_LAUNCH((decode_window_mixed_stats_kernel<BITS, 1, false, ST>), grid, block, lds, stream, a);
-  else if (a.m.w.channels == 2 && a.m.w.mid_side)
-    AAD_LAUNCH((decode_window_mixed_stats_kernel<BITS, 2, true, ST>), grid, block, lds, stream, a);
-  else if (a.m.w.channels == 2)
-    AAD_LAUNCH((decode_window_mixed_stats_kernel<BITS, 2, false, ST>), grid, block, lds, stream, a);
-  else
-    AAD_LAUNCH((decode_window_mixed_stats_kernel<BITS, 0, false, ST>), grid, block, lds, stream, a);
-}
-
-template <int ST>
-static void launch_type(const MixedWindowStatsArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
-{
-  if (a.m.w.bits == 4) launch_bits<4, ST>(a, grid, block, lds, stream);
-  else if (a.m.w.bits == 3) launch_bits<3, ST>(a, grid, block, lds, stream);
-  else launch_bits<2, ST>(a, grid, block, lds, stream);
-}
-
-/* one launch of a run: args.w.bits / args.w.mid_side name the variant */
 template <>
-void launch_decode_window_mixed_stats_unit<AAD_WINDOW_HALF != 0>(
-    const MixedWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  const MixedWindowStatsArgs a = {args, reinterpret_cast<unsigned long long *>(stats)};
-  using T = WindowUnitTypes<AAD_WINDOW_HALF != 0>;
-  const dim3 grid(p.grid), block(p.workgroup);
-  if (sample_type == T::second) launch_type<T::second>(a, grid, block, p.lds, stream);
-  else launch_type<T::first>(a, grid, block, p.lds, stream);
-}
+struct WindowUnit<WindowKind::Mixed, WindowMode::Stats> {
+  using Args = MixedWindowStatsArgs;
+  static Args pack(const WindowUnitRun &r) { return Args{mixed_window_args(r), stats_words(r)}; }
+  static const WindowArgs &window(const Args &a) { return a.m.w; }
+  template <int BITS, int CHF, bool MS, int ST, int OUTC>
+  static constexpr auto kernel = &decode_window_mixed_stats_kernel<BITS, CHF, MS, ST>;
+};
+AAD_WINDOW_UNIT(Mixed, Stats);
 
 } /* namespace aad */

@@ -1,31 +1,18 @@
 /* aad_decode_window_placed_stats.hip - translation unit of the same-format window decoder's statistics over a span per window
  * (aad_decode_window_placed.hip.h).  No rows, so one object: AAD_WINDOW_HALF does not apply. */
 #include "aad_decode_window_placed.hip.h"
-#include "aad_launch.h"
+#include "aad_window_unit.hip.h"
 
 namespace aad {
 
-template <int BITS>
-static void launch_bits(const WindowPlacedStatsArgs &a, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream)
-{
-  if (a.s.w.channels == 1)
-    AAD_LAUNCH((decode_window_placed_stats_kernel<BITS, 1, false>), grid, block, lds, stream, a);
-  else if (a.s.w.channels == 2 && a.s.w.mid_side)
-    AAD_LAUNCH((decode_window_placed_stats_kernel<BITS, 2, true>), grid, block, lds, stream, a);
-  else if (a.s.w.channels == 2)
-    AAD_LAUNCH((decode_window_placed_stats_kernel<BITS, 2, false>), grid, block, lds, stream, a);
-  else
-    AAD_LAUNCH((decode_window_placed_stats_kernel<BITS, 0, false>), grid, block, lds, stream, a);
-}
-
-void launch_decode_window_placed_stats(const WindowArgs &args, const struct AADHipWindowSpan *spans, struct AADHipRowStats *stats,
-                                       const WindowLaunch &p, hipStream_t stream)
-{
-  const WindowPlacedStatsArgs a = {{args, reinterpret_cast<unsigned long long *>(stats)}, reinterpret_cast<const uint64_t *>(spans)};
-  const dim3 grid(p.grid), block(p.workgroup);
-  if (a.s.w.bits == 4) launch_bits<4>(a, grid, block, p.lds, stream);
-  else if (a.s.w.bits == 3) launch_bits<3>(a, grid, block, p.lds, stream);
-  else launch_bits<2>(a, grid, block, p.lds, stream);
-}
+template <>
+struct WindowUnit<WindowKind::Same, WindowMode::PlacedStats> {
+  using Args = WindowPlacedStatsArgs;
+  static Args pack(const WindowUnitRun &r) { return Args{{r.w, stats_words(r)}, span_words(r)}; }
+  static const WindowArgs &window(const Args &a) { return a.s.w; }
+  template <int BITS, int CHF, bool MS, int ST, int OUTC>
+  static constexpr auto kernel = &decode_window_placed_stats_kernel<BITS, CHF, MS>;
+};
+AAD_WINDOW_UNIT(Same, PlacedStats);
 
 } /* namespace aad */

@@ -27,8 +27,6 @@
 #include "aad_launch.h" /* and aad_launch_policy.h */
 #include "aad_decode.hip.h"
 #include "aad_decode_window.hip.h"
-#include "aad_decode_window_mixed.hip.h"
-#include "aad_decode_window_channel_mix.hip.h"
 #include "aad_encode.hip.h"
 #include "aad_encode_launch.hip.h"
 #include "aad_format.h"
@@ -150,18 +148,16 @@ struct AADHipDecodePlan {
   uint64_t *d_prefix;
 };
 
+/* AADHip_WindowDecodePlanCreate (Same): `args` is the format and the table (decode_plan_init); AADHip_MixedWindowDecodePlanCreate,
+ * AADHip_ChannelMixWindowDecodePlanCreate: it holds the table, the channel count (ChannelMix: the OUTPUT's) and header_bytes alone,
+ * and the formats are d_formats'.  The windows come with each run */
 struct AADHipWindowDecodePlan {
-  AADHipContext *ctx;
-  aad::DecodeArgs args; /* format and table (decode_plan_init); the windows come with each run */
-  aad::StreamDesc *d_streams;
-  /* AADHip_MixedWindowDecodePlanCreate: `args` holds the table, the channel count and header_bytes alone, the formats are these */
-  bool mixed;
-  aad::StreamFormat *d_formats; /* one record per stream */
-  aad::WindowVariants variants;
-  /* AADHip_ChannelMixWindowDecodePlanCreate: `args` as for a mixed plan with the OUTPUT's channel count, the formats are these */
-  bool channel_mix;
-  aad::ChannelStreamFormat *d_mix_formats; /* one record per stream */
-  aad::ChannelMixVariants mix_variants;
+  AADHipContext *ctx = nullptr;
+  aad::WindowKind kind = aad::WindowKind::Same;
+  aad::DecodeArgs args = {};
+  aad::StreamDesc *d_streams = nullptr;
+  void *d_formats = nullptr; /* Mixed: aad::StreamFormat, ChannelMix: aad::ChannelStreamFormat, one record per stream; Same: null */
+  aad::WindowVariants variants = {}; /* the launches of a run (plan_window_run); Same: the one variant of the header */
 };
 
 /* AADHip_ResamplerCreate: the banks on the host (AADHip_ResamplerBank reads them) and on the device, the select table */
@@ -309,6 +305,37 @@ void launch_decode(const aad::DecodeArgs &a, const aad::DecodeLaunch &p, int32_t
   }
 }
 } /* namespace */
+
+/* the window decoders: launch_window_unit (aad_launch.h), from (kind, mode, sample type) to the object that holds the kernels */
+namespace aad {
+template <WindowKind KIND, WindowMode MODE>
+void launch_window_rows(const WindowUnitRun &r, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
+{
+  if constexpr (MODE != WindowMode::PlacedStats)
+    if (window_half_type(sample_type)) return launch_window_object<KIND, MODE, true>(r, p, sample_type, stream);
+  launch_window_object<KIND, MODE, false>(r, p, sample_type, stream);
+}
+template <WindowKind KIND>
+void launch_window_mode(WindowMode mode, const WindowUnitRun &r, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
+{
+  switch (mode) {
+  case WindowMode::Rows: return launch_window_rows<KIND, WindowMode::Rows>(r, p, sample_type, stream);
+  case WindowMode::Stats: return launch_window_rows<KIND, WindowMode::Stats>(r, p, sample_type, stream);
+  case WindowMode::Gain: return launch_window_rows<KIND, WindowMode::Gain>(r, p, sample_type, stream);
+  case WindowMode::Placed: return launch_window_rows<KIND, WindowMode::Placed>(r, p, sample_type, stream);
+  case WindowMode::PlacedStats: return launch_window_rows<KIND, WindowMode::PlacedStats>(r, p, sample_type, stream);
+  }
+}
+void launch_window_unit(WindowKind kind, WindowMode mode, const WindowUnitRun &r, const WindowLaunch &p, int32_t sample_type,
+                        hipStream_t stream)
+{
+  switch (kind) {
+  case WindowKind::Same: return launch_window_mode<WindowKind::Same>(mode, r, p, sample_type, stream);
+  case WindowKind::Mixed: return launch_window_mode<WindowKind::Mixed>(mode, r, p, sample_type, stream);
+  case WindowKind::ChannelMix: return launch_window_mode<WindowKind::ChannelMix>(mode, r, p, sample_type, stream);
+  }
+}
+} /* namespace aad */
 
 /* ---- plan construction without any device work ------------------------------------------------
  * Validation + launch arguments.  AADHip_*PlanCreate adds the table upload; the host-memory
@@ -1062,6 +1089,55 @@ AADApiResult AADHip_DecodePlanRun(struct AADHipDecodePlan *plan, const uint8_t *
 
 static_assert(sizeof(AADHipWindow) == 2 * sizeof(uint64_t), "window table layout");
 
+namespace {
+/* What the three creates share, behind their validation: the plan with its descriptor table and, where the kind has them, its
+ * format records (records: num_streams of them, record_bytes each, or null) in device memory */
+AADApiResult window_plan_create(AADHipContext *ctx, aad::WindowKind kind, const aad::DecodeArgs &args, const aad::WindowVariants &variants,
+                                const struct AADHipStreamDesc *streams, const void *records, size_t record_bytes,
+                                struct AADHipWindowDecodePlan **plan)
+{
+  AADHipWindowDecodePlan *p = new (std::nothrow) AADHipWindowDecodePlan();
+  if (p == nullptr) return AAD_APIRESULT_NG;
+  p->ctx = ctx;
+  p->kind = kind;
+  p->variants = variants;
+  uint8_t *d_records = nullptr;
+  DeviceGuard guard(ctx);
+  const bool ok = guard.ok && upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), args.num_streams) &&
+                  (records == nullptr || upload(ctx, &d_records, static_cast<const uint8_t *>(records), record_bytes * args.num_streams));
+  if (!ok) {
+    if (p->d_streams) (void)hipFree(p->d_streams);
+    if (d_records) (void)hipFree(d_records);
+    delete p;
+    return AAD_APIRESULT_NG;
+  }
+  p->d_formats = d_records;
+  p->args = args;
+  p->args.streams = p->d_streams;
+  *plan = p;
+  return AAD_APIRESULT_OK;
+}
+
+/* `args` of a plan whose formats come per stream */
+aad::DecodeArgs window_plan_args(uint32_t num_streams, uint32_t channels, int32_t has_file_header)
+{
+  aad::DecodeArgs args;
+  memset(&args, 0, sizeof(args));
+  args.num_streams = num_streams;
+  args.channels = channels;
+  args.header_bytes = has_file_header ? AAD_HEADER_SIZE : 0;
+  return args;
+}
+
+/* stream i of such a plan: what AADHip_DecodePlanCreate checks of its one format and table */
+AADApiResult window_plan_stream_check(const struct AADHeaderInfo *format, int32_t has_file_header, const struct AADHipStreamDesc *stream)
+{
+  uint64_t prefix[2];
+  aad::DecodeArgs one;
+  return decode_plan_init(format, has_file_header, 1, stream, prefix, &one);
+}
+} /* namespace */
+
 AADApiResult AADHip_WindowDecodePlanCreate(struct AADHipContext *ctx, const struct AADHeaderInfo *format, int32_t has_file_header,
                                            uint32_t num_streams, const struct AADHipStreamDesc *streams,
                                            struct AADHipWindowDecodePlan **plan)
@@ -1073,25 +1149,8 @@ AADApiResult AADHip_WindowDecodePlanCreate(struct AADHipContext *ctx, const stru
   aad::DecodeArgs args;
   const AADApiResult rc = decode_plan_init(format, has_file_header, num_streams, streams, prefix.data(), &args);
   if (rc != AAD_APIRESULT_OK) return rc;
-  AADHipWindowDecodePlan *p = new (std::nothrow) AADHipWindowDecodePlan();
-  if (p == nullptr) return AAD_APIRESULT_NG;
-  p->ctx = ctx;
-  p->d_streams = nullptr;
-  p->mixed = false;
-  p->d_formats = nullptr;
-  p->variants = aad::WindowVariants{};
-  p->channel_mix = false;
-  p->d_mix_formats = nullptr;
-  DeviceGuard guard(ctx);
-  if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams)) {
-    if (p->d_streams) (void)hipFree(p->d_streams);
-    delete p;
-    return AAD_APIRESULT_NG;
-  }
-  p->args = args;
-  p->args.streams = p->d_streams;
-  *plan = p;
-  return AAD_APIRESULT_OK;
+  const aad::WindowVariants one = {1, {{args.channels, args.bits, args.mid_side, args.samples_per_block, num_streams}}};
+  return window_plan_create(ctx, aad::WindowKind::Same, args, one, streams, nullptr, 0, plan);
 }
 
 AADApiResult AADHip_MixedWindowDecodePlanCreate(struct AADHipContext *ctx, uint32_t num_channels, int32_t has_file_header,
@@ -1102,40 +1161,16 @@ AADApiResult AADHip_MixedWindowDecodePlanCreate(struct AADHipContext *ctx, uint3
     return AAD_APIRESULT_INVALID_ARGUMENT;
   *plan = nullptr;
   if (num_channels < 1 || num_channels > AAD_HIP_MAX_NUM_CHANNELS) return AAD_APIRESULT_INVALID_ARGUMENT;
-  /* stream by stream what AADHip_DecodePlanCreate checks of its one format and table; the first failing stream's error */
+  /* stream by stream; the first failing stream's error */
   std::vector<aad::StreamFormat> records(num_streams);
   for (uint32_t i = 0; i < num_streams; i++) {
     if (formats[i].num_channels != num_channels) return AAD_APIRESULT_INVALID_ARGUMENT;
-    uint64_t prefix[2];
-    aad::DecodeArgs one;
-    const AADApiResult rc = decode_plan_init(&formats[i], has_file_header, 1, &streams[i], prefix, &one);
+    const AADApiResult rc = window_plan_stream_check(&formats[i], has_file_header, &streams[i]);
     if (rc != AAD_APIRESULT_OK) return rc;
     records[i] = aad::stream_format_of(formats[i], num_channels);
   }
-  AADHipWindowDecodePlan *p = new (std::nothrow) AADHipWindowDecodePlan();
-  if (p == nullptr) return AAD_APIRESULT_NG;
-  p->ctx = ctx;
-  p->d_streams = nullptr;
-  p->mixed = true;
-  p->d_formats = nullptr;
-  p->variants = aad::window_variants(records.data(), num_streams);
-  p->channel_mix = false;
-  p->d_mix_formats = nullptr;
-  DeviceGuard guard(ctx);
-  if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams) ||
-      !upload(ctx, &p->d_formats, records.data(), num_streams)) {
-    if (p->d_streams) (void)hipFree(p->d_streams);
-    if (p->d_formats) (void)hipFree(p->d_formats);
-    delete p;
-    return AAD_APIRESULT_NG;
-  }
-  memset(&p->args, 0, sizeof(p->args));
-  p->args.streams = p->d_streams;
-  p->args.num_streams = num_streams;
-  p->args.channels = num_channels;
-  p->args.header_bytes = has_file_header ? AAD_HEADER_SIZE : 0;
-  *plan = p;
-  return AAD_APIRESULT_OK;
+  return window_plan_create(ctx, aad::WindowKind::Mixed, window_plan_args(num_streams, num_channels, has_file_header),
+                            aad::window_variants(records.data(), num_streams), streams, records.data(), sizeof(records[0]), plan);
 }
 
 AADApiResult AADHip_ChannelMixWindowDecodePlanCreate(struct AADHipContext *ctx, uint32_t out_channels, int32_t has_file_header,
@@ -1146,36 +1181,15 @@ AADApiResult AADHip_ChannelMixWindowDecodePlanCreate(struct AADHipContext *ctx, 
     return AAD_APIRESULT_INVALID_ARGUMENT;
   *plan = nullptr;
   if (out_channels < 1 || out_channels > 2) return AAD_APIRESULT_INVALID_ARGUMENT;
-  /* stream by stream what AADHip_DecodePlanCreate checks of its one format and table; the first failing stream's error */
   std::vector<aad::ChannelStreamFormat> records(num_streams);
   for (uint32_t i = 0; i < num_streams; i++) {
     if (formats[i].num_channels < 1 || formats[i].num_channels > 2) return AAD_APIRESULT_INVALID_ARGUMENT;
-    uint64_t prefix[2];
-    aad::DecodeArgs one;
-    const AADApiResult rc = decode_plan_init(&formats[i], has_file_header, 1, &streams[i], prefix, &one);
+    const AADApiResult rc = window_plan_stream_check(&formats[i], has_file_header, &streams[i]);
     if (rc != AAD_APIRESULT_OK) return rc;
     records[i] = aad::channel_stream_format_of(formats[i]);
   }
-  AADHipWindowDecodePlan *p = new (std::nothrow) AADHipWindowDecodePlan(); /* every pointer null, no other kind */
-  if (p == nullptr) return AAD_APIRESULT_NG;
-  p->ctx = ctx;
-  p->channel_mix = true;
-  p->mix_variants = aad::channel_mix_variants(records.data(), num_streams);
-  DeviceGuard guard(ctx);
-  if (!guard.ok || !upload(ctx, &p->d_streams, reinterpret_cast<const aad::StreamDesc *>(streams), num_streams) ||
-      !upload(ctx, &p->d_mix_formats, records.data(), num_streams)) {
-    if (p->d_streams) (void)hipFree(p->d_streams);
-    if (p->d_mix_formats) (void)hipFree(p->d_mix_formats);
-    delete p;
-    return AAD_APIRESULT_NG;
-  }
-  memset(&p->args, 0, sizeof(p->args));
-  p->args.streams = p->d_streams;
-  p->args.num_streams = num_streams;
-  p->args.channels = out_channels;
-  p->args.header_bytes = has_file_header ? AAD_HEADER_SIZE : 0;
-  *plan = p;
-  return AAD_APIRESULT_OK;
+  return window_plan_create(ctx, aad::WindowKind::ChannelMix, window_plan_args(num_streams, out_channels, has_file_header),
+                            aad::channel_mix_variants(records.data(), num_streams), streams, records.data(), sizeof(records[0]), plan);
 }
 
 void AADHip_WindowDecodePlanDestroy(struct AADHipWindowDecodePlan *plan)
@@ -1186,144 +1200,31 @@ void AADHip_WindowDecodePlanDestroy(struct AADHipWindowDecodePlan *plan)
     (void)hipStreamSynchronize(plan->ctx->stream);
     (void)hipFree(plan->d_streams);
     if (plan->d_formats) (void)hipFree(plan->d_formats);
-    if (plan->d_mix_formats) (void)hipFree(plan->d_mix_formats);
   }
   delete plan;
 }
 
 namespace {
-/* AADHip_WindowDecodePlanRunStats: the lanes add into the table, so the run clears it in front of its first launch - the start
- * event recorded in front of the clear, and the launches carry the stop event alone (as a segmented reconstruct's statistics) */
-/* AADHip_WindowDecodePlanRunGain's part of a run: the launches are the gain units' (aad_launch.h) */
+/* AADHip_WindowDecodePlanRunGain's part of a run: the launches are the gain units' (aad_launch.h WindowMode) */
 struct WindowGainRun {
   bool on;
   const float *gain; /* device memory, or null: every gain is 1 */
   uint32_t add;
 };
-/* AADHip_WindowDecodePlanRunPlaced's / ...RunPlacedStats' part of a run: the launches are the placed units' (aad_launch.h) - the
+/* AADHip_WindowDecodePlanRunPlaced's / ...RunPlacedStats' part of a run: the launches are the placed units' (WindowMode) - the
  * gain units' rows or the statistics alone, each window's crop clipped to and placed by its span */
 struct WindowPlacedRun {
   bool on;
   const struct AADHipWindowSpan *spans; /* device memory, or null: every span is (T, 0) */
 };
 
+/* AADHip_WindowDecodePlanRunStats: the lanes add into the table, so the run clears it in front of its first launch - the start
+ * event recorded in front of the clear, and the launches carry the stop event alone (as a segmented reconstruct's statistics) */
 bool clear_window_stats(AADHipContext *ctx, aad::LaunchSignal *signal, struct AADHipRowStats *stats, uint64_t bytes)
 {
   if (signal->start != nullptr && !hip_ok(ctx, hipEventRecord(signal->start, ctx->stream), "hipEventRecord")) return false;
   signal->start = nullptr;
   return hip_ok(ctx, hipMemsetAsync(stats, 0, bytes, ctx->stream), "hipMemsetAsync");
-}
-
-/* The launches of a mixed-format run, in the stream's order: one per kernel variant of the plan, each over all the windows.  The
- * start event rides on the first and the stop event on the last (aad_launch.h); a plan with one variant is one kernel.
- * stats (AADHip_WindowDecodePlanRunStats; stats_bytes: the table's size), else null: the launches also fill the table, and
- * device_out may be null. */
-AADApiResult run_mixed_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &run_signal, const uint8_t *device_data,
-                                     uint64_t num_windows, const struct AADHipWindow *device_windows, uint32_t frames_per_window,
-                                     int32_t sample_type, void *device_out, struct AADHipRowStats *stats, uint64_t stats_bytes,
-                                     const WindowGainRun &gain, const WindowPlacedRun &placed)
-{
-  aad::LaunchSignal signal = run_signal;
-  AADHipContext *ctx = plan->ctx;
-  const aad::DecodeArgs &d = plan->args;
-  const aad::MixedWindowLaunch m =
-      aad::plan_mixed_window_decode(ctx->device_info, ctx->knobs, plan->variants, num_windows, frames_per_window, d.channels);
-  if (!m.ok) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error), "window decode: %llu windows x %u channels x %u frames overflow 64 bits",
-             (unsigned long long)num_windows, d.channels, frames_per_window);
-    return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
-  }
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
-  if (num_windows == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
-  if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
-  aad::LaunchSignal last = signal;
-  for (uint32_t i = 0; i < m.count; i++) {
-    aad::MixedWindowArgs a;
-    memset(&a, 0, sizeof(a));
-    a.w.streams = d.streams;
-    a.w.data = device_data;
-    a.w.windows = reinterpret_cast<const uint64_t *>(device_windows);
-    a.w.out = device_out;
-    a.w.lanes = m.launch[i].lanes;
-    a.w.blocks_per_window = m.launch[i].blocks_per_window;
-    a.w.frames = frames_per_window;
-    a.w.num_streams = d.num_streams;
-    a.w.channels = d.channels;
-    a.w.samples_per_block = m.variant[i].min_samples_per_block;
-    a.w.header_bytes = d.header_bytes;
-    a.w.mid_side = m.variant[i].mid_side;
-    a.w.bits = m.variant[i].bits;
-    a.formats = plan->d_formats;
-    a.owns_strays = i == 0;
-    last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
-    aad::tl_launch_signal = last;
-    if (placed.on && stats != nullptr) aad::launch_decode_window_mixed_placed_stats(a, placed.spans, stats, m.launch[i], ctx->stream);
-    else if (placed.on)
-      aad::launch_decode_window_mixed_placed(a, placed.spans, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
-    else if (stats != nullptr) aad::launch_decode_window_mixed_stats(a, stats, m.launch[i], sample_type, ctx->stream);
-    else if (gain.on) aad::launch_decode_window_mixed_gain(a, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
-    else aad::launch_decode_window_mixed(a, m.launch[i], sample_type, ctx->stream);
-    if (!hip_ok(ctx, hipGetLastError(), "mixed window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
-  }
-  return finish_signal(ctx, last, AAD_APIRESULT_OK);
-}
-
-/* ... and of a channel-mix run: one per (source channels, bits, mid/side) of the plan, d.channels rows per window */
-AADApiResult run_channel_mix_window_decode(AADHipWindowDecodePlan *plan, const aad::LaunchSignal &run_signal, const uint8_t *device_data,
-                                           uint64_t num_windows, const struct AADHipWindow *device_windows,
-                                           uint32_t frames_per_window, int32_t sample_type, void *device_out,
-                                           struct AADHipRowStats *stats, uint64_t stats_bytes, const WindowGainRun &gain,
-                                           const WindowPlacedRun &placed)
-{
-  aad::LaunchSignal signal = run_signal;
-  AADHipContext *ctx = plan->ctx;
-  const aad::DecodeArgs &d = plan->args;
-  const aad::ChannelMixWindowLaunch m =
-      aad::plan_channel_mix_window_decode(ctx->device_info, ctx->knobs, plan->mix_variants, num_windows, frames_per_window, d.channels);
-  if (!m.ok) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error), "window decode: %llu windows x %u channels x %u frames overflow 64 bits",
-             (unsigned long long)num_windows, d.channels, frames_per_window);
-    return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
-  }
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
-  if (num_windows == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
-  if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
-  aad::LaunchSignal last = signal;
-  for (uint32_t i = 0; i < m.count; i++) {
-    aad::ChannelMixWindowArgs a;
-    memset(&a, 0, sizeof(a));
-    a.w.streams = d.streams;
-    a.w.data = device_data;
-    a.w.windows = reinterpret_cast<const uint64_t *>(device_windows);
-    a.w.out = device_out;
-    a.w.lanes = m.launch[i].lanes;
-    a.w.blocks_per_window = m.launch[i].blocks_per_window;
-    a.w.frames = frames_per_window;
-    a.w.num_streams = d.num_streams;
-    a.w.channels = m.variant[i].channels;
-    a.w.samples_per_block = m.variant[i].min_samples_per_block;
-    a.w.header_bytes = d.header_bytes;
-    a.w.mid_side = m.variant[i].mid_side;
-    a.w.bits = m.variant[i].bits;
-    a.formats = plan->d_mix_formats;
-    a.owns_strays = i == 0;
-    a.out_channels = d.channels;
-    last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
-    aad::tl_launch_signal = last;
-    if (placed.on && stats != nullptr)
-      aad::launch_decode_window_channel_mix_placed_stats(a, placed.spans, stats, m.launch[i], ctx->stream);
-    else if (placed.on)
-      aad::launch_decode_window_channel_mix_placed(a, placed.spans, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
-    else if (stats != nullptr)
-      aad::launch_decode_window_channel_mix_stats(a, stats, m.launch[i], sample_type, ctx->stream);
-    else if (gain.on)
-      aad::launch_decode_window_channel_mix_gain(a, gain.gain, gain.add, m.launch[i], sample_type, ctx->stream);
-    else aad::launch_decode_window_channel_mix(a, m.launch[i], sample_type, ctx->stream);
-    if (!hip_ok(ctx, hipGetLastError(), "channel-mix window decode launch")) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
-  }
-  return finish_signal(ctx, last, AAD_APIRESULT_OK);
 }
 
 /* the sample types of window decode rows: 2 and 3 are no type, and float16 / bfloat16 exist for window decode alone */
@@ -1333,7 +1234,8 @@ bool window_sample_type_ok(int32_t sample_type)
          sample_type == AAD_HIP_SAMPLE_BFLOAT16;
 }
 
-/* AADHip_WindowDecodePlanRun, and with_stats AADHip_WindowDecodePlanRunStats: the table as a further output, device_out optional;
+/* Every run of every kind of plan.  AADHip_WindowDecodePlanRun, and with_stats AADHip_WindowDecodePlanRunStats (stats_bytes
+ * below: the table's size): the table as a further output, device_out optional;
  * gain.on: AADHip_WindowDecodePlanRunGain, float rows alone, `mode` its STORE / ADD argument as the caller gave it;
  * placed.on: with gain.on AADHip_WindowDecodePlanRunPlaced, with_stats (and no rows) AADHip_WindowDecodePlanRunPlacedStats */
 AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_t *device_data, uint64_t num_windows,
@@ -1374,16 +1276,10 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
   } else {
     stats = nullptr;
   }
-  if (plan->mixed)
-    return run_mixed_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type, device_out,
-                                   stats, stats_bytes, gain, placed);
-  if (plan->channel_mix)
-    return run_channel_mix_window_decode(plan, signal, device_data, num_windows, device_windows, frames_per_window, sample_type,
-                                         device_out, stats, stats_bytes, gain, placed);
   const aad::DecodeArgs &d = plan->args;
-  const aad::WindowLaunch p =
-      aad::plan_window_decode(ctx->device_info, ctx->knobs, aad::WindowBatch{num_windows, frames_per_window, d.channels, d.bits, d.samples_per_block});
-  if (!p.ok) {
+  const aad::WindowRunPlan m =
+      aad::plan_window_run(ctx->device_info, ctx->knobs, plan->kind, plan->variants, num_windows, frames_per_window, d.channels);
+  if (!m.ok) {
     snprintf(ctx->last_error, sizeof(ctx->last_error), "window decode: %llu windows x %u channels x %u frames overflow 64 bits",
              (unsigned long long)num_windows, d.channels, frames_per_window);
     return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_ARGUMENT);
@@ -1391,31 +1287,42 @@ AADApiResult window_decode_run(struct AADHipWindowDecodePlan *plan, const uint8_
   DeviceGuard guard(ctx);
   if (!guard.ok) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
   if (num_windows == 0) return finish_signal(ctx, signal, AAD_APIRESULT_OK);
-  if (d.bits < 2 || d.bits > 4) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_FORMAT);
-  aad::WindowArgs a;
-  memset(&a, 0, sizeof(a));
-  a.streams = d.streams;
-  a.data = device_data;
-  a.windows = reinterpret_cast<const uint64_t *>(device_windows);
-  a.out = device_out;
-  a.lanes = p.lanes;
-  a.blocks_per_window = p.blocks_per_window;
-  a.frames = frames_per_window;
-  a.num_streams = d.num_streams;
-  a.channels = d.channels;
-  a.block_size = d.block_size;
-  a.samples_per_block = d.samples_per_block;
-  a.header_bytes = d.header_bytes;
-  a.mid_side = d.mid_side;
-  a.bits = d.bits;
+  /* a same-format plan's header may name bits no kernel decodes; the formats of the other kinds were checked stream by stream */
+  if (m.variant[0].bits < 2 || m.variant[0].bits > 4) return finish_signal(ctx, signal, AAD_APIRESULT_INVALID_FORMAT);
   if (stats != nullptr && !clear_window_stats(ctx, &signal, stats, stats_bytes)) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
-  aad::tl_launch_signal = signal; /* the run's one kernel takes it (aad_launch.h) */
-  if (placed.on && stats != nullptr) aad::launch_decode_window_placed_stats(a, placed.spans, stats, p, ctx->stream);
-  else if (placed.on) aad::launch_decode_window_placed(a, placed.spans, gain.gain, gain.add, p, sample_type, ctx->stream);
-  else if (stats != nullptr) aad::launch_decode_window_stats(a, stats, p, sample_type, ctx->stream);
-  else if (gain.on) aad::launch_decode_window_gain(a, gain.gain, gain.add, p, sample_type, ctx->stream);
-  else aad::launch_decode_window(a, p, sample_type, ctx->stream);
-  return finish_signal(ctx, signal, hip_ok(ctx, hipGetLastError(), "window decode launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG);
+  const aad::WindowMode unit_mode = placed.on && stats != nullptr ? aad::WindowMode::PlacedStats
+                                    : placed.on                   ? aad::WindowMode::Placed
+                                    : stats != nullptr            ? aad::WindowMode::Stats
+                                    : gain.on                     ? aad::WindowMode::Gain
+                                                                  : aad::WindowMode::Rows;
+  static const char *const launch_name[] = {"window decode launch", "mixed window decode launch", "channel-mix window decode launch"};
+  /* The launches of the run, in the stream's order: one per kernel variant of the plan, each over all the windows.  The start
+   * event rides on the first and the stop event on the last (aad_launch.h); a plan with one variant is one kernel */
+  aad::LaunchSignal last = signal;
+  for (uint32_t i = 0; i < m.count; i++) {
+    aad::WindowArgs a;
+    memset(&a, 0, sizeof(a));
+    a.streams = d.streams;
+    a.data = device_data;
+    a.windows = reinterpret_cast<const uint64_t *>(device_windows);
+    a.out = device_out;
+    a.lanes = m.launch[i].lanes;
+    a.blocks_per_window = m.launch[i].blocks_per_window;
+    a.frames = frames_per_window;
+    a.num_streams = d.num_streams;
+    a.channels = m.variant[i].channels;
+    a.block_size = d.block_size; /* 0 but in a same-format plan: the other kernels read their stream's record */
+    a.samples_per_block = m.variant[i].min_samples_per_block;
+    a.header_bytes = d.header_bytes;
+    a.mid_side = m.variant[i].mid_side;
+    a.bits = m.variant[i].bits;
+    const aad::WindowUnitRun run = {a, plan->d_formats, i == 0, d.channels, gain.gain, gain.add, placed.spans, stats};
+    last = aad::LaunchSignal{i == 0 ? signal.start : nullptr, i + 1 == m.count ? signal.stop : nullptr};
+    aad::tl_launch_signal = last;
+    aad::launch_window_unit(plan->kind, unit_mode, run, m.launch[i], sample_type, ctx->stream);
+    if (!hip_ok(ctx, hipGetLastError(), launch_name[(uint32_t)plan->kind])) return finish_signal(ctx, signal, AAD_APIRESULT_NG);
+  }
+  return finish_signal(ctx, last, AAD_APIRESULT_OK);
 }
 } /* namespace */
 

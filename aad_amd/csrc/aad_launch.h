@@ -28,161 +28,42 @@ extern thread_local LaunchSignal tl_launch_signal; /* defined in aad_hip_engine.
 struct DecodeArgs;
 void launch_decode_split(const DecodeArgs &args, const DecodeLaunch &p, int32_t *residual, hipStream_t stream);
 void launch_decode_tiled(const DecodeArgs &args, const DecodeLaunch &p, hipStream_t stream);
-/* The window decoders (AADHip_WindowDecodePlanRun, ...RunStats, ...RunGain, ...RunPlaced).  Each of their twelve translation units
- * that write rows is compiled twice (Makefile): with AAD_WINDOW_HALF=0 its kernels write int16 and float32 rows, with AAD_WINDOW_HALF=1 (the _half
- * objects) float16 and bfloat16 rows.  A unit defines launch_..._unit<AAD_WINDOW_HALF>; the launch_... below pick the unit by the
- * run's sample_type (enum AADHipSampleType, validated by the entry point). */
+/* The window decoders (AADHip_WindowDecodePlanRun, ...RunStats, ...RunGain, ...RunPlaced, ...RunPlacedStats): one translation unit
+ * per plan kind (aad_launch_policy.h WindowKind) and mode, aad_decode_window[_mixed|_channel_mix][_stats|_gain|_placed|_placed_stats].hip.
+ * Each of the twelve that write rows is compiled twice (Makefile): with AAD_WINDOW_HALF=0 its kernels write int16 and float32 rows -
+ * the gain and placed units float32 alone - and with AAD_WINDOW_HALF=1 (the _half objects) float16 and bfloat16 rows.  The
+ * placed-stats units write no rows: one object each, and no sample type. */
 #ifndef AAD_WINDOW_HALF
 #define AAD_WINDOW_HALF 0
 #endif
-template <bool HALF>
-struct WindowUnitTypes { /* a unit's two sample types: sample_type == second runs the second, anything else the first */
-  static constexpr int32_t first = HALF ? AAD_HIP_SAMPLE_FLOAT16 : AAD_HIP_SAMPLE_INT16;
-  static constexpr int32_t second = HALF ? AAD_HIP_SAMPLE_BFLOAT16 : AAD_HIP_SAMPLE_FLOAT32;
-};
-/* the unit's launch function: declared with both explicit specialisations, one defined by each object of the unit */
-#define AAD_WINDOW_UNIT(name, ...)     \
-  template <bool HALF>                 \
-  void name(__VA_ARGS__);              \
-  template <>                          \
-  void name<false>(__VA_ARGS__);       \
-  template <>                          \
-  void name<true>(__VA_ARGS__)
+enum class WindowMode { Rows, Stats, Gain, Placed, PlacedStats };
 inline bool window_half_type(int32_t sample_type)
 {
   return sample_type == AAD_HIP_SAMPLE_FLOAT16 || sample_type == AAD_HIP_SAMPLE_BFLOAT16;
 }
-/* aad_decode_window.hip: the same-format window decoder */
+/* One launch of a run, as every unit takes it: the unit packs what its kernel's argument struct holds of this.
+ * w.channels / w.bits / w.mid_side name the launch's kernel variant, out_channels (1 or 2, a channel-mix run's) the rows */
 struct WindowArgs;
-AAD_WINDOW_UNIT(launch_decode_window_unit,
-                const WindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
-/* aad_decode_window_mixed.hip: one launch (one kernel variant: args.w.bits, args.w.mid_side) of a mixed-format window decode run */
-struct MixedWindowArgs;
-AAD_WINDOW_UNIT(launch_decode_window_mixed_unit,
-                const MixedWindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
-/* aad_decode_window_channel_mix.hip: one launch (args.w.channels, args.w.bits, args.w.mid_side: the variant) of a channel-mix run */
-struct ChannelMixWindowArgs;
-AAD_WINDOW_UNIT(launch_decode_window_channel_mix_unit,
-                const ChannelMixWindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
-/* aad_decode_window_stats.hip, aad_decode_window_mixed_stats.hip, aad_decode_window_channel_mix_stats.hip: the same launches of
- * AADHip_WindowDecodePlanRunStats - the rows (args' out, which may be null) and the level statistics of every row added into
- * `stats`, which the run cleared */
-AAD_WINDOW_UNIT(launch_decode_window_stats_unit,
-                const WindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, int32_t sample_type,
-                hipStream_t stream);
-AAD_WINDOW_UNIT(launch_decode_window_mixed_stats_unit,
-                const MixedWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, int32_t sample_type,
-                hipStream_t stream);
-AAD_WINDOW_UNIT(launch_decode_window_channel_mix_stats_unit,
-                const ChannelMixWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p, int32_t sample_type,
-                hipStream_t stream);
-/* aad_decode_window_gain.hip, aad_decode_window_mixed_gain.hip, aad_decode_window_channel_mix_gain.hip: the same launches of
- * AADHip_WindowDecodePlanRunGain - float rows scaled by the window's gain (`gain`: device memory, null for 1) and stored, or with
- * `add` added to what the rows hold.  Their AAD_WINDOW_HALF=0 objects hold float32 alone */
-AAD_WINDOW_UNIT(launch_decode_window_gain_unit,
-                const WindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
-                hipStream_t stream);
-AAD_WINDOW_UNIT(launch_decode_window_mixed_gain_unit,
-                const MixedWindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
-                hipStream_t stream);
-AAD_WINDOW_UNIT(launch_decode_window_channel_mix_gain_unit,
-                const ChannelMixWindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
-                hipStream_t stream);
-/* aad_decode_window_placed.hip, aad_decode_window_mixed_placed.hip, aad_decode_window_channel_mix_placed.hip: the same launches of
- * AADHip_WindowDecodePlanRunPlaced - the gain units' rows, each window's crop clipped to and placed by its record of `spans`
- * (device memory, null: every span is (T, 0)).  Compiled twice as the gain units are */
-AAD_WINDOW_UNIT(launch_decode_window_placed_unit,
-                const WindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain, uint32_t add, const WindowLaunch &p,
-                int32_t sample_type, hipStream_t stream);
-AAD_WINDOW_UNIT(launch_decode_window_mixed_placed_unit,
-                const MixedWindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain, uint32_t add,
-                const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
-AAD_WINDOW_UNIT(launch_decode_window_channel_mix_placed_unit,
-                const ChannelMixWindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain, uint32_t add,
-                const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
-/* aad_decode_window_placed_stats.hip, aad_decode_window_mixed_placed_stats.hip, aad_decode_window_channel_mix_placed_stats.hip: the
- * same launches of AADHip_WindowDecodePlanRunPlacedStats - the level statistics of every window's clipped crop added into `stats`,
- * which the run cleared; no rows (args' out is null), so no sample type and one object each */
-void launch_decode_window_placed_stats(const WindowArgs &args, const struct AADHipWindowSpan *spans, struct AADHipRowStats *stats,
-                                       const WindowLaunch &p, hipStream_t stream);
-void launch_decode_window_mixed_placed_stats(const MixedWindowArgs &args, const struct AADHipWindowSpan *spans,
-                                             struct AADHipRowStats *stats, const WindowLaunch &p, hipStream_t stream);
-void launch_decode_window_channel_mix_placed_stats(const ChannelMixWindowArgs &args, const struct AADHipWindowSpan *spans,
-                                                   struct AADHipRowStats *stats, const WindowLaunch &p, hipStream_t stream);
+struct WindowUnitRun {
+  const WindowArgs &w;
+  const void *formats;  /* Mixed: StreamFormat, ChannelMix: ChannelStreamFormat, [w.num_streams] in device memory; Same: unused */
+  uint32_t owns_strays; /* Mixed, ChannelMix: this launch writes the windows whose stream is out of range */
+  uint32_t out_channels; /* ChannelMix */
+  const float *gain;    /* Gain, Placed: float rows scaled by the window's gain (device memory, null for 1) and stored, or with */
+  uint32_t add;         /* `add` added to what the rows hold */
+  const struct AADHipWindowSpan *spans; /* Placed, PlacedStats: each window's crop clipped to and placed by its record (device
+                                         * memory, null: every span is (T, 0)) */
+  struct AADHipRowStats *stats; /* Stats (w.out may be null), PlacedStats (w.out is null): the level statistics of every row added
+                                 * into the table, which the run cleared */
+};
+/* an object's launch function: defined once, in aad_window_unit.hip.h, and instantiated by the object of <KIND, MODE, HALF> */
+template <WindowKind KIND, WindowMode MODE, bool HALF>
+void launch_window_object(const WindowUnitRun &r, const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
 
-inline void launch_decode_window_placed(const WindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain, uint32_t add,
-                                        const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_placed_unit<true>(args, spans, gain, add, p, sample_type, stream);
-  else launch_decode_window_placed_unit<false>(args, spans, gain, add, p, sample_type, stream);
-}
-inline void launch_decode_window_mixed_placed(const MixedWindowArgs &args, const struct AADHipWindowSpan *spans, const float *gain,
-                                              uint32_t add, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_mixed_placed_unit<true>(args, spans, gain, add, p, sample_type, stream);
-  else launch_decode_window_mixed_placed_unit<false>(args, spans, gain, add, p, sample_type, stream);
-}
-inline void launch_decode_window_channel_mix_placed(const ChannelMixWindowArgs &args, const struct AADHipWindowSpan *spans,
-                                                    const float *gain, uint32_t add, const WindowLaunch &p, int32_t sample_type,
-                                                    hipStream_t stream)
-{
-  if (window_half_type(sample_type))
-    launch_decode_window_channel_mix_placed_unit<true>(args, spans, gain, add, p, sample_type, stream);
-  else launch_decode_window_channel_mix_placed_unit<false>(args, spans, gain, add, p, sample_type, stream);
-}
-
-inline void launch_decode_window(const WindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_unit<true>(args, p, sample_type, stream);
-  else launch_decode_window_unit<false>(args, p, sample_type, stream);
-}
-inline void launch_decode_window_mixed(const MixedWindowArgs &args, const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_mixed_unit<true>(args, p, sample_type, stream);
-  else launch_decode_window_mixed_unit<false>(args, p, sample_type, stream);
-}
-inline void launch_decode_window_channel_mix(const ChannelMixWindowArgs &args, const WindowLaunch &p, int32_t sample_type,
-                                             hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_channel_mix_unit<true>(args, p, sample_type, stream);
-  else launch_decode_window_channel_mix_unit<false>(args, p, sample_type, stream);
-}
-inline void launch_decode_window_stats(const WindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p,
-                                       int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_stats_unit<true>(args, stats, p, sample_type, stream);
-  else launch_decode_window_stats_unit<false>(args, stats, p, sample_type, stream);
-}
-inline void launch_decode_window_mixed_stats(const MixedWindowArgs &args, struct AADHipRowStats *stats, const WindowLaunch &p,
-                                             int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_mixed_stats_unit<true>(args, stats, p, sample_type, stream);
-  else launch_decode_window_mixed_stats_unit<false>(args, stats, p, sample_type, stream);
-}
-inline void launch_decode_window_channel_mix_stats(const ChannelMixWindowArgs &args, struct AADHipRowStats *stats,
-                                                   const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_channel_mix_stats_unit<true>(args, stats, p, sample_type, stream);
-  else launch_decode_window_channel_mix_stats_unit<false>(args, stats, p, sample_type, stream);
-}
-inline void launch_decode_window_gain(const WindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p,
-                                      int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_gain_unit<true>(args, gain, add, p, sample_type, stream);
-  else launch_decode_window_gain_unit<false>(args, gain, add, p, sample_type, stream);
-}
-inline void launch_decode_window_mixed_gain(const MixedWindowArgs &args, const float *gain, uint32_t add, const WindowLaunch &p,
-                                            int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_mixed_gain_unit<true>(args, gain, add, p, sample_type, stream);
-  else launch_decode_window_mixed_gain_unit<false>(args, gain, add, p, sample_type, stream);
-}
-inline void launch_decode_window_channel_mix_gain(const ChannelMixWindowArgs &args, const float *gain, uint32_t add,
-                                                  const WindowLaunch &p, int32_t sample_type, hipStream_t stream)
-{
-  if (window_half_type(sample_type)) launch_decode_window_channel_mix_gain_unit<true>(args, gain, add, p, sample_type, stream);
-  else launch_decode_window_channel_mix_gain_unit<false>(args, gain, add, p, sample_type, stream);
-}
+/* ... and the one way to them: the object of (kind, mode, window_half_type(sample_type)) launches.  sample_type: enum
+ * AADHipSampleType, validated by the entry point.  Defined in aad_hip_engine.hip */
+void launch_window_unit(WindowKind kind, WindowMode mode, const WindowUnitRun &r, const WindowLaunch &p, int32_t sample_type,
+                        hipStream_t stream);
 /* the decoded rows of a planar reconstruct run (AADHip_PlanarReconstructPlanRun; launched through aad_encode_launch.hip.h).
  * base: per stream (segmented: per chain) the element of `out` that holds channel 0's sample of the lane's first frame, device
  * memory */

@@ -396,7 +396,7 @@ constexpr uint64_t kWindowMaxGrid = 1ull << 20;
 /* The window kernel is the per-lane dense decoder with predicated stores: the dense decoder's workgroup rule (one-wave workgroups
  * while the batch has at most one wave per SIMD) and its occupancy cap (dense_decode_lds_pad) */
 /* out_channels: the rows a window has in the output (`elements`), b.channels: the channels a window's lanes decode.  They differ
- * in a channel-mix run alone (plan_channel_mix_window_decode). */
+ * in a channel-mix run alone (plan_window_run). */
 inline WindowLaunch plan_window_decode_into(const Device &d, const Knobs &k, const WindowBatch &b, uint32_t out_channels)
 {
   WindowLaunch p = {};
@@ -451,68 +451,57 @@ struct StreamFormat {
 static_assert(sizeof(StreamFormat) == 8, "per-stream format record");
 
 /* mid/side is a kernel variant for two channels only: every other channel count runs the L/R instantiation whatever the method
- * says, as launch_decode_window does (the plan's validation refuses M/S there anyway) */
+ * says, as the launch nest does (the plan's validation refuses M/S there anyway) */
 inline StreamFormat stream_format_of(const struct AADHeaderInfo &h, uint32_t channels)
 {
   return StreamFormat{h.num_samples_per_block, h.block_size, (uint8_t)h.bits_per_sample,
                       (uint8_t)(channels == 2 && h.ch_process_method == AAD_CH_PROCESS_METHOD_MS)};
 }
 
-/* a kernel variant of a plan: the template parameters its streams need, and the smallest block among them (the launch's K) */
+/* a kernel variant of a plan: the template parameters its streams need, and the smallest block among them (the launch's K).
+ * channels: what a stream of the variant holds; 0 in a list stands for the plan's own count (a mixed plan's records do not hold
+ * it), which plan_window_run puts in its place */
 struct WindowVariant {
-  uint32_t bits, mid_side, min_samples_per_block, streams;
+  uint32_t channels, bits, mid_side, min_samples_per_block, streams;
 };
-constexpr uint32_t kMaxWindowVariants = 6;
+constexpr uint32_t kMaxWindowVariants = 9;
 struct WindowVariants {
   uint32_t count;
   WindowVariant v[kMaxWindowVariants];
 };
 
-/* The variants present in formats[0 .. n), each once, in the fixed order 4-bit L/R, 4-bit M/S, 3-bit L/R, 3-bit M/S, 2-bit L/R,
- * 2-bit M/S.  Records with bits outside 2 .. 4 belong to no variant (plan create has refused them). */
-inline WindowVariants window_variants(const StreamFormat *formats, uint64_t n)
+/* The builders below count every stream into its variant's slot - 4-bit L/R, 4-bit M/S, 3-bit L/R, 3-bit M/S, 2-bit L/R, 2-bit M/S,
+ * then mono 4-, 3- and 2-bit (a channel-mix plan alone tells mono apart) - and list the slots that hold streams, in that order */
+inline void count_window_stream(WindowVariant (&slot)[kMaxWindowVariants], bool mono_slot, uint32_t channels, uint32_t bits, bool mid_side,
+                                uint32_t samples_per_block)
 {
-  WindowVariant slot[kMaxWindowVariants] = {};
-  for (uint64_t i = 0; i < n; i++) {
-    const StreamFormat &f = formats[i];
-    if (f.bits < 2 || f.bits > 4) continue;
-    WindowVariant &s = slot[(4u - f.bits) * 2u + (f.mid_side ? 1u : 0u)];
-    if (s.streams == 0 || f.samples_per_block < s.min_samples_per_block) s.min_samples_per_block = f.samples_per_block;
-    s.bits = f.bits;
-    s.mid_side = f.mid_side ? 1u : 0u;
-    s.streams++;
-  }
+  WindowVariant &s = slot[mono_slot ? 6u + (4u - bits) : (4u - bits) * 2u + (mid_side ? 1u : 0u)];
+  if (s.streams == 0 || samples_per_block < s.min_samples_per_block) s.min_samples_per_block = samples_per_block;
+  s.channels = channels;
+  s.bits = bits;
+  s.mid_side = mid_side ? 1u : 0u;
+  s.streams++;
+}
+inline WindowVariants window_variants_present(const WindowVariant (&slot)[kMaxWindowVariants])
+{
   WindowVariants out = {};
   for (const WindowVariant &s : slot)
     if (s.streams != 0) out.v[out.count++] = s;
   return out;
 }
 
-struct MixedWindowLaunch {
-  bool ok;        /* false: some launch's lane count, or the output's elements or bytes, overflow 64 bits - nothing is launched */
-  uint32_t count; /* launches of the run: one per variant, and ONE for a plan without variants (num_streams == 0) */
-  WindowVariant variant[kMaxWindowVariants];
-  WindowLaunch launch[kMaxWindowVariants]; /* launch[0] also writes the zeros of the windows whose stream is out of range */
-};
-
-/* Every launch walks all the windows and is planned by plan_window_decode's rules with its variant's bits and smallest block: K
- * covers that variant's every stream, the lanes past a stream's own last covering block leave.  A plan without variants has no
- * stream a window could name: its one launch (the 4-bit L/R kernel over blocks of `frames` frames) only writes zeros. */
-inline MixedWindowLaunch plan_mixed_window_decode(const Device &d, const Knobs &k, const WindowVariants &variants, uint64_t windows,
-                                                  uint32_t frames, uint32_t channels)
+/* The variants present in formats[0 .. n) of a mixed-format plan, each once, in the fixed order 4-bit L/R, 4-bit M/S, 3-bit L/R,
+ * 3-bit M/S, 2-bit L/R, 2-bit M/S, every one of the plan's channel count.  Records with bits outside 2 .. 4 belong to no variant
+ * (plan create has refused them). */
+inline WindowVariants window_variants(const StreamFormat *formats, uint64_t n)
 {
-  MixedWindowLaunch m = {};
-  WindowVariants vs = variants;
-  if (vs.count == 0) vs.v[vs.count++] = WindowVariant{4, 0, frames, 0};
-  if (vs.count > kMaxWindowVariants) return m;
-  for (uint32_t i = 0; i < vs.count; i++) {
-    m.variant[i] = vs.v[i];
-    m.launch[i] = plan_window_decode(d, k, WindowBatch{windows, frames, channels, vs.v[i].bits, vs.v[i].min_samples_per_block});
-    if (!m.launch[i].ok) return m;
+  WindowVariant slot[kMaxWindowVariants] = {};
+  for (uint64_t i = 0; i < n; i++) {
+    const StreamFormat &f = formats[i];
+    if (f.bits < 2 || f.bits > 4) continue;
+    count_window_stream(slot, false, 0, f.bits, f.mid_side != 0, f.samples_per_block);
   }
-  m.count = vs.count;
-  m.ok = true;
-  return m;
+  return window_variants_present(slot);
 }
 
 /* ---- channel-mix window decode (AADHip_ChannelMixWindowDecodePlanCreate): mono and stereo streams into one channel count ---- */
@@ -537,65 +526,71 @@ inline ChannelStreamFormat channel_stream_format_of(const struct AADHeaderInfo &
   return ChannelStreamFormat{h.num_samples_per_block, h.block_size, (uint8_t)h.bits_per_sample, source};
 }
 
-/* a kernel variant of a channel-mix plan: WindowVariant with the source channel count in front */
-struct ChannelMixVariant {
-  uint32_t channels, bits, mid_side, min_samples_per_block, streams;
-};
-constexpr uint32_t kMaxChannelMixVariants = 9;
-struct ChannelMixVariants {
-  uint32_t count;
-  ChannelMixVariant v[kMaxChannelMixVariants];
-};
-
-/* The variants present in formats[0 .. n), each once: window_variants' six stereo ones in its order, then mono 4-, 3- and 2-bit.
- * Records with bits outside 2 .. 4 or without a source belong to no variant. */
-inline ChannelMixVariants channel_mix_variants(const ChannelStreamFormat *formats, uint64_t n)
+/* The variants present in formats[0 .. n) of a channel-mix plan, each once: window_variants' six stereo ones in its order, then
+ * mono 4-, 3- and 2-bit.  Records with bits outside 2 .. 4 or without a source belong to no variant. */
+inline WindowVariants channel_mix_variants(const ChannelStreamFormat *formats, uint64_t n)
 {
-  ChannelMixVariant slot[kMaxChannelMixVariants] = {};
+  WindowVariant slot[kMaxWindowVariants] = {};
   for (uint64_t i = 0; i < n; i++) {
     const ChannelStreamFormat &f = formats[i];
     if (f.bits < 2 || f.bits > 4 || f.source >= kSourceNone) continue;
-    const bool mono = f.source == kSourceMono, ms = f.source == kSourceMidSide;
-    ChannelMixVariant &s = slot[mono ? 6u + (4u - f.bits) : (4u - f.bits) * 2u + (ms ? 1u : 0u)];
-    if (s.streams == 0 || f.samples_per_block < s.min_samples_per_block) s.min_samples_per_block = f.samples_per_block;
-    s.channels = mono ? 1u : 2u;
-    s.bits = f.bits;
-    s.mid_side = ms ? 1u : 0u;
-    s.streams++;
+    const bool mono = f.source == kSourceMono;
+    count_window_stream(slot, mono, mono ? 1u : 2u, f.bits, f.source == kSourceMidSide, f.samples_per_block);
   }
-  ChannelMixVariants out = {};
-  for (const ChannelMixVariant &s : slot)
-    if (s.streams != 0) out.v[out.count++] = s;
-  return out;
+  return window_variants_present(slot);
 }
 
-struct ChannelMixWindowLaunch {
+/* ---- the launches of a window decode run, whatever the plan's kind ---------------------------------------------------------- */
+/* Same: AADHip_WindowDecodePlanCreate, one format - its list is the one variant of that header; Mixed, ChannelMix: above */
+enum class WindowKind : uint32_t { Same = 0, Mixed = 1, ChannelMix = 2 };
+
+struct WindowRunPlan {
   bool ok;        /* false: some launch's lane count, or the output's elements or bytes, overflow 64 bits - nothing is launched */
   uint32_t count; /* launches of the run: one per variant, and ONE for a plan without variants (num_streams == 0) */
-  ChannelMixVariant variant[kMaxChannelMixVariants];
-  WindowLaunch launch[kMaxChannelMixVariants]; /* launch[0] also writes the zeros of the windows whose stream is out of range */
+  WindowVariant variant[kMaxWindowVariants];
+  WindowLaunch launch[kMaxWindowVariants]; /* launch[0] also writes the zeros of the windows whose stream is out of range */
 };
 
-/* plan_mixed_window_decode with two channel counts: a launch's lanes are (window, block, SOURCE channel) of its variant - planned
- * by plan_window_decode's rules for that channel count, bits and smallest block - and `elements` is the output's,
- * windows * out_channels * frames, whose overflow refuses the run whatever the sources.  A plan without variants: the mono 4-bit
- * kernel over blocks of `frames` frames writes the zeros (one lane per window and block covers out_channels rows). */
-inline ChannelMixWindowLaunch plan_channel_mix_window_decode(const Device &d, const Knobs &k, const ChannelMixVariants &variants,
-                                                             uint64_t windows, uint32_t frames, uint32_t out_channels)
+/* Every launch walks all the windows and is planned by plan_window_decode_into's rules with its variant's bits and smallest block:
+ * K covers that variant's every stream, the lanes past a stream's own last covering block leave.  A launch's lanes are (window,
+ * block, SOURCE channel) of its variant, and `elements` is the output's, windows * out_channels * frames, whose overflow refuses
+ * the run whatever the sources; the two channel counts differ in a channel-mix run alone, which has one or two rows per window.
+ * A plan without variants has no stream a window could name: its one launch over blocks of `frames` frames only writes zeros - the
+ * 4-bit L/R kernel of out_channels channels, and in a channel-mix run the mono 4-bit kernel (one lane per window and block covers
+ * out_channels rows). */
+inline WindowRunPlan plan_window_run(const Device &d, const Knobs &k, WindowKind kind, const WindowVariants &variants, uint64_t windows,
+                                     uint32_t frames, uint32_t out_channels)
 {
-  ChannelMixWindowLaunch m = {};
-  ChannelMixVariants vs = variants;
-  if (vs.count == 0) vs.v[vs.count++] = ChannelMixVariant{1, 4, 0, frames, 0};
-  if (vs.count > kMaxChannelMixVariants || out_channels < 1 || out_channels > 2) return m;
+  WindowRunPlan m = {};
+  const bool mix = kind == WindowKind::ChannelMix;
+  WindowVariants vs = variants;
+  if (vs.count == 0) vs.v[vs.count++] = WindowVariant{mix ? 1u : out_channels, 4, 0, frames, 0};
+  if (vs.count > kMaxWindowVariants || (mix && (out_channels < 1 || out_channels > 2))) return m;
   for (uint32_t i = 0; i < vs.count; i++) {
-    m.variant[i] = vs.v[i];
-    m.launch[i] = plan_window_decode_into(d, k, WindowBatch{windows, frames, vs.v[i].channels, vs.v[i].bits, vs.v[i].min_samples_per_block},
-                                          out_channels);
+    WindowVariant &v = m.variant[i] = vs.v[i];
+    if (v.channels == 0) v.channels = out_channels;
+    m.launch[i] = plan_window_decode_into(d, k, WindowBatch{windows, frames, v.channels, v.bits, v.min_samples_per_block}, out_channels);
     if (!m.launch[i].ok) return m;
   }
   m.count = vs.count;
   m.ok = true;
   return m;
+}
+
+/* plan_window_run under the names of the two kinds that plan more than one launch, as tests/mixed_window_policy_driver.cpp and
+ * tests/channel_mix_policy_driver.cpp call it */
+using MixedWindowLaunch = WindowRunPlan;
+using ChannelMixVariants = WindowVariants;
+using ChannelMixWindowLaunch = WindowRunPlan;
+inline WindowRunPlan plan_mixed_window_decode(const Device &d, const Knobs &k, const WindowVariants &variants, uint64_t windows,
+                                              uint32_t frames, uint32_t channels)
+{
+  return plan_window_run(d, k, WindowKind::Mixed, variants, windows, frames, channels);
+}
+inline WindowRunPlan plan_channel_mix_window_decode(const Device &d, const Knobs &k, const WindowVariants &variants, uint64_t windows,
+                                                    uint32_t frames, uint32_t out_channels)
+{
+  return plan_window_run(d, k, WindowKind::ChannelMix, variants, windows, frames, out_channels);
 }
 
 } /* namespace aad */

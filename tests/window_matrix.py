@@ -1,8 +1,8 @@
 """The case table of window decode: every kernel instantiation that the entry points of include/aad_hip.h can reach
 (AADHip_WindowDecodePlanRun, ...RunStats, ...RunGain, ...RunPlaced, ...RunPlacedStats over same-format, mixed-format and
 channel-mix plans), written down from the dispatch code of the fifteen translation units aad_amd/csrc/aad_decode_window*.hip -
-launch_bits / launch_type / launch_rows and the unit's choice of sample types - and the half / not-half switch of
-aad_amd/csrc/aad_launch.h.  Nothing here is read from the built library: tests/test_window_kernel_census.py compares this table
+the launch nest and the objects' sample types of aad_amd/csrc/aad_window_unit.hip.h - and the half / not-half switch of
+launch_window_unit (aad_amd/csrc/aad_launch.h).  Nothing here is read from the built library: tests/test_window_kernel_census.py compares this table
 with the kernels the library holds, and tests/test_gpu_window_decode_matrix.py runs the case each record names.
 
 A record is (kernel, args, case): the kernel's name in namespace aad, its template arguments in the order of the C++ parameter
@@ -18,14 +18,14 @@ Cell = namedtuple("Cell", "kernel args case")
 
 GPU_FILE = "test_gpu_window_decode_matrix.py"
 
-BITS = (4, 3, 2)                                      # launch_type's rungs: 4, 3, anything else
-# launch_bits' rungs as (CHF, MS): channels == 1; channels == 2 && mid_side; channels == 2; anything else
+BITS = (4, 3, 2)                                      # launch_window_bits' rungs: 4, 3, anything else
+# launch_window_channels' rungs as (CHF, MS): channels == 1; channels == 2 && mid_side; channels == 2; anything else
 FOUR_RUNGS = ((1, 0), (2, 1), (2, 0), (0, 0))
 # a channel mix knows one and two channels: channels == 1; mid_side; anything else
 THREE_RUNGS = ((1, 0), (2, 1), (2, 0))
-OUT_CHANNELS = (1, 2)                                 # launch_rows: out_channels == 1, anything else
+OUT_CHANNELS = (1, 2)                                 # launch_window_out: out_channels == 1, anything else
 
-# the sample types of a unit's two objects: WindowUnitTypes<false> and <true> of aad_launch.h; the gain and placed units hold
+# the sample types of a unit's two objects: WindowUnitTypes<MODE, false> and <MODE, true>; the gain and placed units hold
 # float32 alone in their first object (AAD_WINDOW_HALF=0) and float16 / bfloat16 in their second
 ROW_TYPES = (SAMPLE_INT16, SAMPLE_FLOAT32, SAMPLE_FLOAT16, SAMPLE_BFLOAT16)
 GAIN_TYPES = (SAMPLE_FLOAT32, SAMPLE_FLOAT16, SAMPLE_BFLOAT16)
