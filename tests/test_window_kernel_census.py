@@ -3,16 +3,12 @@ tests/window_matrix.py.  The host object keeps every kernel's mangled name as a 
 it), so the names are read from the library's bytes - names only, no code - and the template arguments from their Li<n>E /
 Lb<0|1>E groups.  The two sets must be EQUAL: a kernel without a record has no matrix case that runs it, a record without a kernel
 is a case that runs something else.  No GPU."""
-import re
-
 import pytest
 
 import aad_amd
+import kernel_names
 import window_matrix as wm
 from aad_amd import capi
-
-NAME = re.compile(rb"_ZN3aad(\d+)(decode_window[a-z_]*_kernel)I((?:L[ib]\d+E)+)E")
-ARG = re.compile(rb"L([ib])(\d+)E")
 
 
 @pytest.fixture(scope="module")
@@ -21,14 +17,9 @@ def lib():
 
 
 def kernels_in(data):
-    """bytes -> the set of (kernel, template arguments) among the mangled names in them"""
-    found = set()
-    for m in NAME.finditer(data):
-        name = m.group(2)
-        if int(m.group(1)) != len(name):  # a __device_stub__ twin never gets here: its length prefix stands before "__device_stub__"
-            continue
-        found.add((name.decode(), tuple(int(v) for _, v in ARG.findall(m.group(3)))))
-    return found
+    """bytes -> the set of (kernel, template arguments) among the mangled names of window decode kernels in them (the parser:
+    tests/kernel_names.py, shared with test_encode_kernel_census.py; a __device_stub__ twin and a wrong length prefix never match)"""
+    return kernel_names.kernels_in(data, kernel_names.is_window_kernel)
 
 
 def test_the_parser_on_names_written_by_hand():
