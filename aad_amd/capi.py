@@ -74,6 +74,10 @@ class AADHipResampleLane(C.Structure):  # include/aad_hip.h: one row of a torch 
     _fields_ = [("bank", C.c_uint32), ("shift", C.c_uint32)]
 
 
+class AADHipConvolveLane(C.Structure):  # include/aad_hip.h: one row of a torch int32 [N, 2] tensor (Convolver.run)
+    _fields_ = [("response", C.c_uint32), ("shift", C.c_uint32)]
+
+
 class AADHipLaneState(C.Structure):  # include/aad_hip.h
     _fields_ = [("weight", C.c_int32 * 4), ("history", C.c_int32 * 4),
                 ("stepsize_index", C.c_int32), ("quantize_error", C.c_int32)]
@@ -122,6 +126,8 @@ HIP_SYMBOLS = [
     "AADHip_ResamplerCreate", "AADHip_ResamplerDestroy", "AADHip_ResamplerBank", "AADHip_ResamplerSourceFrames",
     "AADHip_ResamplerResolve", "AADHip_ResamplerRun", "AADHip_ResamplerRunGain", "AADHip_ResamplerRunStats",
     "AADHip_ResamplerCreateWide",
+    "AADHip_ConvolverCreate", "AADHip_ConvolverDestroy", "AADHip_ConvolverResponse", "AADHip_ConvolverSourceFrames",
+    "AADHip_ConvolverResolve", "AADHip_ConvolverRun", "AADHip_ConvolverRunGain",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -259,6 +265,20 @@ def _declare_hip(lib):
     lib.AADHip_ResamplerRunGain.restype = C.c_int
     lib.AADHip_ResamplerRunStats.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_int32, vp, vp]
     lib.AADHip_ResamplerRunStats.restype = C.c_int
+    lib.AADHip_ConvolverCreate.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(vp)]
+    lib.AADHip_ConvolverCreate.restype = C.c_int
+    lib.AADHip_ConvolverDestroy.argtypes = [vp]
+    lib.AADHip_ConvolverDestroy.restype = None
+    lib.AADHip_ConvolverResponse.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, C.c_uint64]
+    lib.AADHip_ConvolverResponse.restype = C.c_int
+    lib.AADHip_ConvolverSourceFrames.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.AADHip_ConvolverSourceFrames.restype = C.c_int
+    lib.AADHip_ConvolverResolve.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp]
+    lib.AADHip_ConvolverResolve.restype = C.c_int
+    lib.AADHip_ConvolverRun.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_int32, vp]
+    lib.AADHip_ConvolverRun.restype = C.c_int
+    lib.AADHip_ConvolverRunGain.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_int32, vp, vp, C.c_int32]
+    lib.AADHip_ConvolverRunGain.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

@@ -32,6 +32,7 @@
 #include "aad_format.h"
 #include "aad_hip_internal.h"
 #include "aad_resample.hip.h"
+#include "aad_convolve.hip.h"
 #include "aad_tiles.h"
 #include "aad_window_reconstruct.hip.h"
 
@@ -174,6 +175,17 @@ struct AADHipResampler {
   uint16_t *d_select = nullptr, *d_lead = nullptr;
   aad::ResampleBankDesc *d_banks = nullptr;
   int16_t *d_coefficients = nullptr;
+};
+
+/* AADHip_ConvolverCreate: the responses on the host (AADHip_ConvolverResponse reads them) and, as byte planes, on the device */
+struct AADHipConvolver {
+  AADHipContext *ctx = nullptr;
+  std::vector<aad::convolve::ResponseDesc> responses; /* offset: the first tap in `taps` */
+  std::vector<int16_t> taps;
+  uint32_t max_taps = 0; /* the longest response: T_src = T + max_taps - 1 */
+  uint32_t *d_lead = nullptr;
+  aad::convolve::ResponseDesc *d_responses = nullptr; /* offset: the first byte in d_planes */
+  int8_t *d_planes = nullptr;
 };
 
 struct AADHipReconstructPlan {
@@ -1701,6 +1713,206 @@ AADApiResult AADHip_ResamplerRunStats(struct AADHipResampler *r, uint64_t num_wi
   return resampler_launched(r, "resampler run with statistics",
                             r->wide ? aad::launch_resample_rows_stats_wide(m, sample_type, resampler_lds_bytes(r), ctx->stream)
                                     : aad::launch_resample_rows_stats(m, sample_type, resampler_lds_bytes(r), ctx->stream));
+}
+
+/* ------------------------------------------------------------------------------ convolve -- */
+
+static_assert(sizeof(AADHipConvolveLane) == sizeof(aad::ConvolveLane), "lane record layout");
+
+AADApiResult AADHip_ConvolverCreate(struct AADHipContext *ctx, uint32_t num_responses, const float *const *taps, const uint32_t *lengths,
+                                    const int32_t *delays, struct AADHipConvolver **convolver)
+{
+  if (ctx == nullptr || convolver == nullptr || taps == nullptr || lengths == nullptr || num_responses == 0)
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *convolver = nullptr;
+  AADHipConvolver *c = new (std::nothrow) AADHipConvolver();
+  if (c == nullptr) return AAD_APIRESULT_NG;
+  c->ctx = ctx;
+  std::vector<uint32_t> lead(num_responses);
+  std::vector<int8_t> planes;
+  std::vector<aad::convolve::ResponseDesc> device_responses;
+  for (uint32_t i = 0; i < num_responses; i++) {
+    const uint32_t K = lengths[i];
+    const size_t at = c->taps.size();
+    c->taps.resize(at + (K <= aad::kConvolveMaxTaps ? K : 0));
+    uint32_t q = 0, delay = 0;
+    if (taps[i] == nullptr || !aad::convolve_quantise(taps[i], K, delays != nullptr ? delays[i] : -1, c->taps.data() + at, &q, &delay)) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error),
+               "convolver: response %u has %u taps (1 ... 32768), a tap that is not finite or past 32639 in magnitude, or a delay "
+               "outside its taps", i, K);
+      delete c;
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    const uint32_t steps = aad::convolve_steps(K);
+    const size_t image_at = planes.size();
+    planes.resize(image_at + (size_t)steps * aad::kConvolveStepBytes);
+    aad::convolve_build_planes(c->taps.data() + at, K, planes.data() + image_at);
+    const int64_t bias = aad::convolve_bias(c->taps.data() + at, K);
+    c->responses.push_back(aad::convolve::ResponseDesc{K, q, delay, steps, (uint64_t)at, bias});
+    device_responses.push_back(aad::convolve::ResponseDesc{K, q, delay, steps, (uint64_t)image_at, bias});
+    lead[i] = K - 1 - delay;
+    c->max_taps = std::max(c->max_taps, K);
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &c->d_lead, lead.data(), lead.size()) ||
+      !upload(ctx, &c->d_responses, device_responses.data(), device_responses.size()) ||
+      !upload(ctx, &c->d_planes, planes.data(), planes.size())) {
+    AADHip_ConvolverDestroy(c);
+    return AAD_APIRESULT_NG;
+  }
+  *convolver = c;
+  return AAD_APIRESULT_OK;
+}
+
+void AADHip_ConvolverDestroy(struct AADHipConvolver *c)
+{
+  if (c == nullptr) return;
+  DeviceGuard guard(c->ctx);
+  if (guard.ok) {
+    (void)hipStreamSynchronize(c->ctx->stream);
+    if (c->d_lead) (void)hipFree(c->d_lead);
+    if (c->d_responses) (void)hipFree(c->d_responses);
+    if (c->d_planes) (void)hipFree(c->d_planes);
+  }
+  delete c;
+}
+
+AADApiResult AADHip_ConvolverResponse(const struct AADHipConvolver *c, uint32_t response, uint32_t *num_taps, uint32_t *scale,
+                                      uint32_t *delay, int16_t *taps, uint64_t capacity)
+{
+  if (c == nullptr || response >= c->responses.size() || num_taps == nullptr || scale == nullptr || delay == nullptr)
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  const aad::convolve::ResponseDesc &d = c->responses[response];
+  if (taps != nullptr && capacity < d.K) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
+  *num_taps = d.K;
+  *scale = d.q;
+  *delay = d.delay;
+  if (taps != nullptr) memcpy(taps, c->taps.data() + d.offset, sizeof(int16_t) * d.K);
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_ConvolverSourceFrames(const struct AADHipConvolver *c, uint32_t frames, uint32_t *source_frames)
+{
+  uint64_t n = 0;
+  if (c == nullptr || source_frames == nullptr || !aad::convolve_source_frames(frames, c->max_taps, &n) || n > UINT32_MAX)
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *source_frames = (uint32_t)n;
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_ConvolverResolve(struct AADHipConvolver *c, uint64_t num_windows, const struct AADHipWindow *device_windows,
+                                     const int64_t *device_response, uint32_t frames, struct AADHipWindow *device_source_windows,
+                                     struct AADHipConvolveLane *device_lanes)
+{
+  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = c->ctx;
+  uint32_t source_frames = 0;
+  if (AADHip_ConvolverSourceFrames(c, frames, &source_frames) != AAD_APIRESULT_OK || device_windows == nullptr ||
+      device_source_windows == nullptr || device_lanes == nullptr || num_windows > (uint64_t)INT32_MAX * 256u ||
+      ((reinterpret_cast<uintptr_t>(device_windows) | reinterpret_cast<uintptr_t>(device_response) |
+        reinterpret_cast<uintptr_t>(device_source_windows)) & 7u) != 0 ||
+      (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "convolver resolve: a null or unaligned table, %u frames (0, or T + K - 1 past 32 bits), or %llu windows", frames,
+             (unsigned long long)num_windows);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_windows == 0) return AAD_APIRESULT_OK;
+  aad::convolve::ResolveArgs a;
+  a.windows = reinterpret_cast<const uint64_t *>(device_windows);
+  a.response = reinterpret_cast<const uint64_t *>(device_response);
+  a.lead = c->d_lead;
+  a.num_windows = num_windows;
+  a.num_responses = (uint32_t)c->responses.size();
+  a.source_windows = reinterpret_cast<uint64_t *>(device_source_windows);
+  a.lanes = reinterpret_cast<aad::ConvolveLane *>(device_lanes);
+  aad::convolve::launch_resolve(a, ctx->stream);
+  return hip_ok(ctx, hipGetLastError(), "convolver resolve launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
+}
+
+namespace {
+/* What AADHip_ConvolverRun refuses, for both FIR runs, and the kernel's arguments.  `what` names the run in last_error. */
+AADApiResult convolver_rows_args(AADHipConvolver *c, const char *what, uint64_t num_windows, uint32_t channels,
+                                 const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipConvolveLane *device_lanes,
+                                 uint32_t frames, int32_t sample_type, void *device_out, aad::convolve::RowsArgs *a)
+{
+  AADHipContext *ctx = c->ctx;
+  const uint64_t elem = sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4 : 2;
+  uint32_t needed = 0;
+  uint64_t rows = 0, n = 0;
+  if (!window_sample_type_ok(sample_type) || channels == 0 || AADHip_ConvolverSourceFrames(c, frames, &needed) != AAD_APIRESULT_OK ||
+      source_frames < needed || device_source_rows == nullptr || device_lanes == nullptr || device_out == nullptr ||
+      (reinterpret_cast<uintptr_t>(device_source_rows) & 1u) != 0 || (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0 ||
+      (reinterpret_cast<uintptr_t>(device_out) & (elem - 1)) != 0 || __builtin_mul_overflow(num_windows, (uint64_t)channels, &rows) ||
+      __builtin_mul_overflow(rows, (uint64_t)frames, &n) || __builtin_mul_overflow(n, elem, &n) ||
+      __builtin_mul_overflow(rows, (uint64_t)source_frames, &n) || __builtin_mul_overflow(n, (uint64_t)2, &n) ||
+      __builtin_mul_overflow(rows, (uint64_t)((frames - 1) / aad::kConvolveTile + 1), &n)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "%s: an unknown sample type, a null or unaligned pointer, 0 channels, %u frames (0, or T + K - 1 past 32 bits), source "
+             "rows of %u frames where %u are needed, or %llu windows x %u channels x frames past 64 bits",
+             what, frames, source_frames, needed, (unsigned long long)num_windows, channels);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  a->src = device_source_rows;
+  a->lanes = reinterpret_cast<const aad::ConvolveLane *>(device_lanes);
+  a->responses = c->d_responses;
+  a->planes = c->d_planes;
+  a->out = device_out;
+  a->rows = rows;
+  a->channels = channels;
+  a->num_responses = (uint32_t)c->responses.size();
+  a->frames = frames;
+  a->source_frames = source_frames;
+  a->tiles = (frames - 1) / aad::kConvolveTile + 1;
+  return AAD_APIRESULT_OK;
+}
+} /* namespace */
+
+AADApiResult AADHip_ConvolverRun(struct AADHipConvolver *c, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
+                                 uint32_t source_frames, const struct AADHipConvolveLane *device_lanes, uint32_t frames,
+                                 int32_t sample_type, void *device_out)
+{
+  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = c->ctx;
+  aad::convolve::RowsArgs a;
+  const AADApiResult rc = convolver_rows_args(c, "convolver run", num_windows, channels, device_source_rows, source_frames,
+                                              device_lanes, frames, sample_type, device_out, &a);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_windows == 0) return AAD_APIRESULT_OK;
+  aad::convolve::launch_rows(a, sample_type, ctx->stream);
+  return hip_ok(ctx, hipGetLastError(), "convolver run launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
+}
+
+AADApiResult AADHip_ConvolverRunGain(struct AADHipConvolver *c, uint64_t num_windows, uint32_t channels,
+                                     const int16_t *device_source_rows, uint32_t source_frames,
+                                     const struct AADHipConvolveLane *device_lanes, const struct AADHipWindowSpan *device_spans,
+                                     uint32_t frames, int32_t sample_type, void *device_out, const float *device_gain, int32_t mode)
+{
+  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipContext *ctx = c->ctx;
+  if (sample_type == AAD_HIP_SAMPLE_INT16 || (mode != AAD_HIP_WINDOW_GAIN_STORE && mode != AAD_HIP_WINDOW_GAIN_ADD) ||
+      (reinterpret_cast<uintptr_t>(device_gain) & 3u) != 0 || (reinterpret_cast<uintptr_t>(device_spans) & 7u) != 0) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "convolver run with gain: int16 rows, a mode that is neither STORE nor ADD, a gain table off 4-byte or a span table off "
+             "8-byte alignment");
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  aad::convolve::GainArgs m;
+  memset(&m, 0, sizeof(m));
+  const AADApiResult rc = convolver_rows_args(c, "convolver run with gain", num_windows, channels, device_source_rows, source_frames,
+                                              device_lanes, frames, sample_type, device_out, &m.r);
+  if (rc != AAD_APIRESULT_OK) return rc;
+  DeviceGuard guard(ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_windows == 0) return AAD_APIRESULT_OK;
+  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
+  m.gain = device_gain;
+  aad::convolve::launch_rows_gain(m, sample_type, mode == AAD_HIP_WINDOW_GAIN_ADD, ctx->stream);
+  return hip_ok(ctx, hipGetLastError(), "convolver run with gain launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
 }
 
 /* -------------------------------------------------------------------- window reconstruct -- */

@@ -797,6 +797,59 @@ class Engine:
         finally:
             s_plan.close()
 
+    def convolver(self, responses, delays=None):
+        """A convolve stage behind window decode plans (AADHip_ConvolverCreate): responses is a list of 1-d float arrays, impulse
+        responses of 1 to 32768 taps, each quantised on the host to int16 taps with a scale exponent; delays: per response the tap
+        that is the direct path, None (or -1 for one response) for the largest tap.  Convolver.run reverberates windows."""
+        return self._convolver(*self._responses(responses, delays))
+
+    @staticmethod
+    def _responses(responses, delays):
+        """what `convolver` refuses of responses and delays, before anything is built -> (float32 arrays, ints or None)"""
+        taps = [np.ascontiguousarray(np.asarray(h, dtype=np.float32).reshape(-1)) for h in responses]
+        if not taps or any(not (1 <= h.size <= 32768) for h in taps):
+            raise ValueError("responses: at least one, each of 1 to 32768 taps, got lengths %s" % ([int(h.size) for h in taps],))
+        if delays is not None:
+            delays = [-1 if d is None else int(d) for d in delays]
+            if len(delays) != len(taps) or any(not (-1 <= d < h.size) for d, h in zip(delays, taps)):
+                raise ValueError("delays: one per response, each a tap's index or -1 for the peak, got %s" % (delays,))
+        return taps, delays
+
+    def _convolver(self, taps, delays):
+        n = len(taps)
+        pointers = (C.c_void_p * n)(*[h.ctypes.data for h in taps])
+        lengths = (C.c_uint32 * n)(*[h.size for h in taps])
+        handle = C.c_void_p()
+        _check("AADHip_ConvolverCreate",
+               self.lib.AADHip_ConvolverCreate(self._ctx, n, pointers, lengths, (C.c_int32 * n)(*delays) if delays is not None else None,
+                                               C.byref(handle)))
+        return Convolver(self, handle, n)
+
+    def decode_windows_reverberated(self, data, image_sizes, windows, frames, responses, response=None, delays=None, dtype=None,
+                                    channels=None, out=None, gain=None, accumulate=False, spans=None):
+        """decode_windows_mixed with every window convolved with an impulse response: responses as for `convolver`, `response` an
+        int64 cuda tensor [N] of indices into them, None for all 0.  The same response goes over every channel row; the direct path
+        (delays) stays at the window's first frame, so the row is time-aligned with the dry one.  dtype, channels, out, gain /
+        accumulate, spans: as decode_windows_mixed, on the reverberated rows (Convolver.run).  Every argument is checked before
+        the convolver is built: a refused call has allocated nothing on the device but the plan's tables."""
+        taps, delays = self._responses(responses, delays)
+        plan = self._corpus_window_plan(data, image_sizes, channels)
+        try:
+            windows = self.window_table(windows, True)
+            n = int(windows.shape[0])
+            if response is not None:
+                self.tensor("response", response, self.torch.int64, n, shape=(n,), contiguous=True)
+            out = _check_fir_run(self, "convolve", n, windows.device, plan.header.num_channels, frames, dtype, out, gain, accumulate,
+                                 spans, None, True)[2]
+            conv = self._convolver(taps, delays)
+            try:
+                return conv.run(plan, data, windows, frames, response=response, dtype=dtype, out=out, gain=gain,
+                                accumulate=accumulate, spans=spans)
+            finally:
+                conv.close()  # synchronises the context's stream first
+        finally:
+            plan.close()
+
     @staticmethod
     def _speeds(rate, speeds):
         """what the resampled calls refuse of rate and speeds, before anything is built -> the speeds as pairs of ints"""
@@ -1331,6 +1384,61 @@ class WindowDecodePlan:
             pass
 
 
+def _fir_sample_type(torch, what, dtype):
+    """the row type of a FIR stage (`what`: "resample", "convolve") -> (dtype, None: torch.float32; its AAD_HIP_SAMPLE_* value)"""
+    dtype = torch.float32 if dtype is None else dtype
+    kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
+    if dtype not in kinds:
+        raise ValueError("%s writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % (what, dtype))
+    return dtype, kinds[dtype]
+
+
+def _check_fir_run(e, what, n, device, channels, frames, dtype, out, gain, accumulate, spans, stats, rows):
+    """every rule of the arguments of a FIR stage's run (Resampler.run, Convolver.run) for n windows on `device`, before any
+    library call -> (channels, sample type, out, gain, accumulate, spans, stats or None)"""
+    torch = e.torch
+    dtype, kind = _fir_sample_type(torch, what, dtype)
+    gained = gain is not None or bool(accumulate)
+    placed = spans is not None
+    with_stats = not (stats is None or stats is False)
+    if placed:
+        if with_stats and rows:
+            raise ValueError("spans: no run with both rows and statistics - take the levels from a statistics-only run "
+                             "(stats=True, rows=False, spans=...), then the rows")
+        if rows and dtype == torch.int16:
+            raise ValueError("spans: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
+    n, ch, frames = int(n), int(channels), int(frames)
+    if placed:
+        spans = e.window_table(spans, True, name="spans", rows=n)
+    if gained:
+        if dtype == torch.int16:
+            raise ValueError("gain / accumulate: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
+        if with_stats or not rows:
+            raise ValueError("gain / accumulate: no statistics variant - take the levels first from a statistics-only run "
+                             "(stats=True, rows=False), then run with the gains")
+        if accumulate and out is None:
+            raise ValueError("accumulate=True adds into `out`: pass the rows to add to")
+        if gain is not None:
+            e.tensor("gain", gain, torch.float32, n, shape=(n,), contiguous=True)
+    if not with_stats:
+        stats = None
+        if not rows:
+            raise ValueError("rows=False is a statistics-only run: pass stats=True or a table")
+    elif stats is True:
+        stats = torch.empty((n, ch, 4), dtype=torch.int64, device=device)
+    else:
+        e.tensor("stats", stats, torch.int64, run_extent("stats", rows=n, channels=ch), shape=(n, ch, 4), contiguous=True)
+    if not rows:
+        if out is not None:
+            raise ValueError("rows=False writes no rows: pass no `out`")
+    elif out is None:
+        out = torch.empty((n, ch, frames), dtype=dtype, device=device)
+    else:
+        e.tensor("out", out, dtype, run_extent("window_rows", rows=n, channels=ch, frames=frames), shape=(n, ch, frames),
+                 contiguous=True)
+    return ch, kind, out, gain, bool(accumulate), spans, stats
+
+
 ResampleSource = namedtuple("ResampleSource", "rows lanes source_frames stats")  # Resampler.decode_source -> run_source
 
 
@@ -1427,58 +1535,12 @@ class Resampler:
 
     def _sample_type(self, dtype):
         """-> (dtype, None: torch.float32; its AAD_HIP_SAMPLE_* value)"""
-        torch = self.engine.torch
-        dtype = torch.float32 if dtype is None else dtype
-        kinds = {torch.float32: SAMPLE_FLOAT32, torch.int16: SAMPLE_INT16, torch.float16: SAMPLE_FLOAT16, torch.bfloat16: SAMPLE_BFLOAT16}
-        if dtype not in kinds:
-            raise ValueError("resample writes torch.float32, torch.int16, torch.float16 or torch.bfloat16, not %s" % dtype)
-        return dtype, kinds[dtype]
+        return _fir_sample_type(self.engine.torch, "resample", dtype)
 
     def _check_run(self, n, device, channels, frames, dtype, out, gain, accumulate, spans, stats, rows):
         """every rule of run's arguments for n windows on `device`, before any library call -> (channels, sample type, out, gain,
         accumulate, spans, stats or None)"""
-        e = self.engine
-        torch = e.torch
-        dtype, kind = self._sample_type(dtype)
-        gained = gain is not None or bool(accumulate)
-        placed = spans is not None
-        with_stats = not (stats is None or stats is False)
-        if placed:
-            if with_stats and rows:
-                raise ValueError("spans: no run with both rows and statistics - take the levels from a statistics-only run "
-                                 "(stats=True, rows=False, spans=...), then the rows")
-            if rows and dtype == torch.int16:
-                raise ValueError("spans: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
-        n, ch, frames = int(n), int(channels), int(frames)
-        if placed:
-            spans = e.window_table(spans, True, name="spans", rows=n)
-        if gained:
-            if dtype == torch.int16:
-                raise ValueError("gain / accumulate: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
-            if with_stats or not rows:
-                raise ValueError("gain / accumulate: no statistics variant - take the levels first from a statistics-only run "
-                                 "(stats=True, rows=False), then run with the gains")
-            if accumulate and out is None:
-                raise ValueError("accumulate=True adds into `out`: pass the rows to add to")
-            if gain is not None:
-                e.tensor("gain", gain, torch.float32, n, shape=(n,), contiguous=True)
-        if not with_stats:
-            stats = None
-            if not rows:
-                raise ValueError("rows=False is a statistics-only run: pass stats=True or a table")
-        elif stats is True:
-            stats = torch.empty((n, ch, 4), dtype=torch.int64, device=device)
-        else:
-            e.tensor("stats", stats, torch.int64, run_extent("stats", rows=n, channels=ch), shape=(n, ch, 4), contiguous=True)
-        if not rows:
-            if out is not None:
-                raise ValueError("rows=False writes no rows: pass no `out`")
-        elif out is None:
-            out = torch.empty((n, ch, frames), dtype=dtype, device=device)
-        else:
-            e.tensor("out", out, dtype, run_extent("window_rows", rows=n, channels=ch, frames=frames), shape=(n, ch, frames),
-                     contiguous=True)
-        return ch, kind, out, gain, bool(accumulate), spans, stats
+        return _check_fir_run(self.engine, "resample", n, device, channels, frames, dtype, out, gain, accumulate, spans, stats, rows)
 
     def _run_source(self, source, frames, ch, kind, out, gain, accumulate, spans, stats):
         e = self.engine
@@ -1507,6 +1569,124 @@ class Resampler:
     def close(self):
         if self.handle:
             self.engine.lib.AADHip_ResamplerDestroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ConvolveSource = namedtuple("ConvolveSource", "rows lanes source_frames")  # Convolver.decode_source -> run_source
+
+
+class Convolver:
+    """AADHip_Convolver*: impulse responses as int16 taps with a scale exponent and a delay, one picked per window."""
+
+    def __init__(self, engine, handle, num_responses):
+        self.engine, self.handle, self.num_responses = engine, handle, num_responses
+
+    def response(self, r):
+        """-> (q, delay, int16 array [K]): response r as the library quantised it - h_q = rint(h * 2^q) (AADHip_ConvolverResponse)"""
+        lib = self.engine.lib
+        K, q, d = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check("AADHip_ConvolverResponse", lib.AADHip_ConvolverResponse(self.handle, int(r), C.byref(K), C.byref(q), C.byref(d), None, 0))
+        h = np.zeros(K.value, dtype=np.int16)
+        _check("AADHip_ConvolverResponse",
+               lib.AADHip_ConvolverResponse(self.handle, int(r), C.byref(K), C.byref(q), C.byref(d), h.ctypes.data, h.size))
+        return q.value, d.value, h
+
+    def source_frames(self, frames):
+        """T_src = frames + the longest response's taps - 1 (AADHip_ConvolverSourceFrames)"""
+        n = C.c_uint32()
+        _check("AADHip_ConvolverSourceFrames", self.engine.lib.AADHip_ConvolverSourceFrames(self.handle, int(frames), C.byref(n)))
+        return n.value
+
+    def run(self, window_plan, data, windows, frames, response=None, dtype=None, out=None, gain=None, accumulate=False, spans=None):
+        """window_plan: a WindowDecodePlan of any kind over `data`; windows: int64 cuda tensor [N, 2] of (stream, first_frame);
+        response: contiguous int64 cuda tensor [N], None for all 0 -> `out` ([N, channels, frames] of dtype torch.float32,
+        torch.int16, torch.float16 or torch.bfloat16; allocated when None): window w convolved with response[w], zeros where the
+        index names none.  Three steps on the engine's stream, ordered against torch's current one: AADHip_ConvolverResolve, the
+        plan's own run into an int16 source batch of source_frames(frames) frames per row, and AADHip_ConvolverRun - with gain,
+        accumulate or spans AADHip_ConvolverRunGain, their meanings and refusals those of Resampler.run.  Neither table is read on
+        the host; the source batch and the tables between the steps are temporaries of this call (Engine.window_table).
+        The call is decode_source and run_source composed."""
+        e = self.engine
+        self._sample_type(dtype)
+        windows = e.window_table(windows, True)
+        n = int(windows.shape[0])
+        if response is not None:
+            e.tensor("response", response, e.torch.int64, n, shape=(n,), contiguous=True)
+        checked = self._check_run(n, windows.device, window_plan.header.num_channels, frames, dtype, out, gain, accumulate, spans)
+        source = self.decode_source(window_plan, data, windows, frames, response=response)
+        return self._run_source(source, frames, *checked)
+
+    def decode_source(self, window_plan, data, windows, frames, response=None):
+        """The first two steps of run: AADHip_ConvolverResolve and the plan's own run into the int16 source batch ->
+        ConvolveSource(rows int16 [N, channels, source_frames], lanes int32 [N, 2], source_frames), what run_source reads."""
+        e = self.engine
+        torch = e.torch
+        windows = e.window_table(windows, True)
+        n, frames = int(windows.shape[0]), int(frames)
+        if response is not None:
+            e.tensor("response", response, torch.int64, n, shape=(n,), contiguous=True)
+        source_frames = self.source_frames(frames)
+        source_windows = torch.empty((n, 2), dtype=torch.int64, device=windows.device)
+        lanes = torch.empty((n, 2), dtype=torch.int32, device=windows.device)
+        cur = e._enter()
+        _check("AADHip_ConvolverResolve",
+               e.lib.AADHip_ConvolverResolve(self.handle, n, windows.data_ptr(), response.data_ptr() if response is not None else None,
+                                             frames, source_windows.data_ptr(), lanes.data_ptr()))
+        rows = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False)
+        e._exit(cur)
+        return ConvolveSource(rows, lanes, source_frames)
+
+    def run_source(self, source, frames, channels, dtype=None, out=None, gain=None, accumulate=False, spans=None):
+        """The FIR step alone: AADHip_ConvolverRun, with gain / accumulate / spans AADHip_ConvolverRunGain, over decode_source's
+        record or any int16 rows [N, channels, source_frames] with a lane table int32 [N, 2] of (response, shift) - the rows of
+        Resampler.run(dtype=torch.int16) with a table of the caller's, for one.  The record is held to `channels`, contiguous,
+        refused otherwise before any library call.  Arguments and return value as run."""
+        e = self.engine
+        torch = e.torch
+        self._sample_type(dtype)
+        e.tensor("source.lanes", source.lanes, torch.int32, shape=(None, 2), contiguous=True)
+        n, ch, t_src = int(source.lanes.shape[0]), int(channels), int(source.source_frames)
+        e.tensor("source.rows", source.rows, torch.int16, run_extent("window_rows", rows=n, channels=ch, frames=t_src),
+                 shape=(n, ch, t_src), contiguous=True)
+        checked = self._check_run(n, source.lanes.device, ch, frames, dtype, out, gain, accumulate, spans)
+        if int(frames) > 0 and t_src < self.source_frames(frames):
+            raise ValueError("source.rows: %d frames per row where %d output frames read %d" % (t_src, int(frames), self.source_frames(frames)))
+        return self._run_source(source, frames, *checked)
+
+    def _sample_type(self, dtype):
+        """-> (dtype, None: torch.float32; its AAD_HIP_SAMPLE_* value)"""
+        return _fir_sample_type(self.engine.torch, "convolve", dtype)
+
+    def _check_run(self, n, device, channels, frames, dtype, out, gain, accumulate, spans):
+        """the rules of Resampler.run's arguments, without statistics -> (channels, sample type, out, gain, accumulate, spans)"""
+        return _check_fir_run(self.engine, "convolve", n, device, channels, frames, dtype, out, gain, accumulate, spans, None, True)[:-1]
+
+    def _run_source(self, source, frames, ch, kind, out, gain, accumulate, spans):
+        e = self.engine
+        n, frames = int(source.lanes.shape[0]), int(frames)
+        cur = e._enter()
+        if gain is not None or accumulate or spans is not None:
+            _check("AADHip_ConvolverRunGain",
+                   e.lib.AADHip_ConvolverRunGain(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
+                                                 spans.data_ptr() if spans is not None else None, frames, kind, out.data_ptr(),
+                                                 gain.data_ptr() if gain is not None else None,
+                                                 WINDOW_GAIN_ADD if accumulate else WINDOW_GAIN_STORE))
+        else:
+            _check("AADHip_ConvolverRun",
+                   e.lib.AADHip_ConvolverRun(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
+                                             frames, kind, out.data_ptr()))
+        e._exit(cur)
+        return out
+
+    def close(self):
+        if self.handle:
+            self.engine.lib.AADHip_ConvolverDestroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1717,4 +1897,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "Resampler", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "Resampler", "Convolver", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]

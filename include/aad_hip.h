@@ -644,6 +644,87 @@ AADApiResult AADHip_ResamplerRunStats(
     void *device_out,                              /* may be NULL: statistics only */
     struct AADHipRowStats *device_stats);          /* N * C records, every one written */
 
+/* ---- reverberation: decoded windows convolved with impulse responses, exact integer FIR on the matrix cores ------------------ */
+
+/* The third waveform augmentation of a loader, beside speed perturbation (the resample stage) and additive noise (the gain runs):
+ * each crop convolved with a room impulse response drawn per window.  A convolver is a stage of the resample stage's shape: a
+ * resolve kernel moves every window to the front by the response's lead, the plan's own window decode writes an int16 SOURCE
+ * BATCH of T_src frames per row, and a FIR kernel turns each source row into T output frames through the row writers of the
+ * resample stage.  A response has thousands of taps, so the sums run as int8 matrix products (DESIGN.md "Reverberation"); all
+ * arithmetic is integer and the rows are defined bit for bit.
+ *
+ * Response r of a convolver: K_r int16 taps h_r[k], 1 <= K_r <= 32768, a scale exponent q_r in 0..15 and a delay d_r in
+ * 0..K_r - 1, built on the host from float32 taps h (aad_convolve.h):
+ *   h_q[k] = rint(h[k] * 2^q), ties to even, the product formed in double (exact); q is the largest value in 0..15 with
+ *   max |h_q| <= 32639 - the bound under which every tap splits into two signed bytes - and 15 for an all-zero response;
+ *   d_r is delays[r] when delays is not NULL and delays[r] >= 0, else the index of the largest |h_q|, the lowest on ties: the
+ *   direct path, so that the reverberant row stays time-aligned with the dry one.  lead_r = K_r - 1 - d_r.
+ * AADHip_ConvolverResponse returns K, q, the delay and the taps (taps: K values; NULL asks for the three numbers alone;
+ * AAD_APIRESULT_INSUFFICIENT_BUFFER when capacity, in values, is below K).
+ *
+ * Row.  Window w = {stream, first_frame} with response r = response[w], x the stream's decode (one channel row of the plan), zero
+ * before frame 0 and from num_samples on.  For n < T:
+ *   acc[n] = sum over k < K_r of h_r[k] * x[first_frame + n + d_r - k]
+ * an exact integer, |acc| < 2^45, held in 64 bits; the same response is applied to every channel row.  With Q = q_r the element is
+ *   INT16     clamp(floor((acc + (Q ? 2^(Q-1) : 0)) / 2^Q), -32768, 32767)
+ *   FLOAT32   fl32(acc) * 2^-(15 + Q): the 64-bit integer rounded once to nearest even, then an exact scale
+ *   FLOAT16 / BFLOAT16   that float32 value rounded once to nearest even, as for window decode rows
+ * With the response {1.0} the taps are {16384}, Q = 14, and the rows are bit for bit AADHip_WindowDecodePlanRun's.
+ *
+ * Selection.  device_response is int64[N] in device memory, never read on the host; NULL: every window uses response 0.  An index
+ * outside [0, R), negative ones included, gives a row of +0; a stream index the plan does not have gives a row of +0 as well (its
+ * source row is zeros).
+ *
+ * Source batch.  T_src = T + max_r K_r - 1 (AADHip_ConvolverSourceFrames).  AADHip_ConvolverResolve writes, per window, the source
+ * window {stream, src_first} with src_first = first_frame - min(first_frame, lead_r) and the lane record {response, shift} with
+ * shift = first_frame - src_first; a window without a response keeps its start and gets response 0xFFFFFFFF.  The caller runs
+ * AADHip_WindowDecodePlanRun over the source windows with frames_per_window = T_src and AAD_HIP_SAMPLE_INT16, and
+ * AADHip_ConvolverRun reads source element j = shift + n + d_r - k, 0 for j < 0.  Huge and wrapped first_frame values pass
+ * through, as for AADHip_ResamplerResolve.
+ *
+ * AADHip_ConvolverRunGain: the definitions of "Resampled rows with a gain, spans and level statistics", word for word, with f the
+ * FLOAT32 element above: p = fl32(g * f), one float32 multiply; ADD is a second rounding, never an fma; Le by the rule of window
+ * decode with spans, in output frames; STORE writes +0 outside the span, ADD touches nothing there; float rows only.
+ *
+ * AADHip_ConvolverCreate: AAD_APIRESULT_INVALID_ARGUMENT for a null pointer, num_responses == 0, a length outside 1..32768, a tap
+ * that is not finite or misses the bound even at q = 0, and a delay >= K.  Resolve and the runs are asynchronous on the context's
+ * stream, one kernel each; num_windows == 0 launches nothing and is OK.  They refuse what AADHip_ResamplerResolve and
+ * AADHip_ResamplerRun / ...RunGain refuse: a null pointer (device_response, device_spans and device_gain aside), a table off its
+ * alignment, frames == 0, channels == 0, source_frames below T_src, an unknown sample type, int16 rows or a mode outside {0, 1}
+ * in the gain run, and extents past 64 bits.  No refused call writes anything.
+ *
+ * Out of scope, deliberately: level statistics of reverberated rows, a response per channel, responses past 32768 taps. */
+struct AADHipConvolveLane { /* a contiguous torch int32 [N, 2] tensor on the device IS the table */
+  uint32_t response;        /* the window's response, 0xFFFFFFFF: a row of zeros */
+  uint32_t shift;           /* element of the source row that holds frame first_frame */
+};
+struct AADHipConvolver;
+AADApiResult AADHip_ConvolverCreate(
+    struct AADHipContext *context, uint32_t num_responses, const float *const *taps, const uint32_t *lengths,
+    const int32_t *delays,           /* NULL, or -1 for a response: the peak */
+    struct AADHipConvolver **convolver);
+void AADHip_ConvolverDestroy(struct AADHipConvolver *convolver);
+AADApiResult AADHip_ConvolverResponse(
+    const struct AADHipConvolver *convolver, uint32_t response,
+    uint32_t *num_taps, uint32_t *scale, uint32_t *delay, int16_t *taps, uint64_t capacity);
+AADApiResult AADHip_ConvolverSourceFrames(
+    const struct AADHipConvolver *convolver, uint32_t frames, uint32_t *source_frames);
+AADApiResult AADHip_ConvolverResolve(
+    struct AADHipConvolver *convolver, uint64_t num_windows, const struct AADHipWindow *device_windows,
+    const int64_t *device_response,  /* NULL: every window uses response 0 */
+    uint32_t frames, struct AADHipWindow *device_source_windows, struct AADHipConvolveLane *device_lanes);
+AADApiResult AADHip_ConvolverRun(
+    struct AADHipConvolver *convolver, uint64_t num_windows, uint32_t channels,
+    const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipConvolveLane *device_lanes,
+    uint32_t frames, int32_t sample_type, void *device_out);
+AADApiResult AADHip_ConvolverRunGain(
+    struct AADHipConvolver *convolver, uint64_t num_windows, uint32_t channels,
+    const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipConvolveLane *device_lanes,
+    const struct AADHipWindowSpan *device_spans,   /* NULL: every span is (T, 0); in output frames */
+    uint32_t frames, int32_t sample_type, void *device_out,
+    const float *device_gain,                      /* NULL: every gain is 1 */
+    int32_t mode);                                 /* enum AADHipWindowGainMode */
+
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 
 /* The write side of the planar layout window decode reads out: one row per channel, int16 or float32 - torch's [N, C, T] - encoded
