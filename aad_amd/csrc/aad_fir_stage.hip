@@ -1,0 +1,499 @@
+/* aad_fir_stage.hip - host side of the FIR stages behind a window decode (include/aad_hip.h "resample", "reverberation"): every
+ * AADHip_Resampler* and AADHip_Convolver* entry point.  No kernel is instantiated here: the launches are aad_resample.hip's,
+ * aad_resample_wide.hip's and aad_convolve.hip's.  A stage is made by its own Create; what a Resolve or a Run refuses is one rule
+ * for both (aad_fir_stage.h), asked through the few members a stage states about itself, and every launch ends in `launched`. */
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "aad_convolve.hip.h"
+#include "aad_fir_stage.h"
+#include "aad_hip_context.hip.h"
+#include "aad_resample.hip.h"
+
+static_assert(sizeof(AADHipResampleLane) == sizeof(aad::ResampleLane), "lane record layout");
+static_assert(sizeof(AADHipConvolveLane) == sizeof(aad::ConvolveLane), "lane record layout");
+
+/* What the shared checks ask of a stage: ctx; kName and kFrames, the stage and why it refuses a frame count, for last_error;
+ * kTile, the output frames of a workgroup; source_frames, false where `frames` is refused; lds_bytes, what a launch that can
+ * be refused asked for; fill, the stage's own fields of its kernels' arguments.
+ * AADHip_ResamplerCreate: the banks on the host (AADHip_ResamplerBank reads them) and on the device, the select table */
+struct AADHipResampler {
+  static constexpr const char *kName = "resampler", *kFrames = "0, or (T - 1) M >= 2^31 for a bank";
+  static constexpr uint32_t kTile = aad::kResampleTile;
+  AADHipContext *ctx = nullptr;
+  uint32_t num_streams = 0, variants = 0;
+  std::vector<aad::ResampleBankDesc> banks; /* one per ratio, in the caller's order */
+  std::vector<int16_t> coefficients; /* bank r's L * K taps at banks[r].offset: what AADHip_ResamplerBank returns */
+  uint64_t bank_elements = 0, span_elements = 0; /* the FIR kernel's LDS, in int16 elements: the largest bank and span */
+  /* AADHip_ResamplerCreateWide: the runs launch aad_resample_wide.hip's kernels; round: R of their gather path
+   * (resample_gather_round of the gathered bank with the most taps), 0 when every bank is resident */
+  bool wide = false;
+  uint32_t round = 0;
+  uint16_t *d_select = nullptr, *d_lead = nullptr;
+  aad::ResampleBankDesc *d_banks = nullptr;
+  int16_t *d_coefficients = nullptr;
+
+  /* T_src = max over the banks of ((T - 1) M) div L + K; false for T == 0 and a bank with (T - 1) M >= 2^31 */
+  bool source_frames(uint32_t frames, uint32_t *source_frames) const
+  {
+    uint64_t most = 0, n = 0;
+    for (const aad::ResampleBankDesc &b : banks) {
+      if (!aad::resample_source_frames(frames, b.L, b.M, b.K, &n)) return false;
+      most = std::max(most, n);
+    }
+    *source_frames = (uint32_t)most; /* < 2^31 + 256 */
+    return true;
+  }
+  /* bytes of LDS a FIR launch asks for, the statistics scratch aside: bank (or a round's rows), span, phase index */
+  uint32_t lds_bytes() const { return (uint32_t)(2 * (bank_elements + span_elements) + 4 * round); }
+  void fill(aad::ResampleMixArgs *m) const
+  {
+    m->r.banks = d_banks;
+    m->r.coefficients = d_coefficients;
+    m->r.num_banks = (uint32_t)banks.size();
+    m->r.bank_elements = (uint32_t)bank_elements;
+    m->r.span_elements = (uint32_t)span_elements;
+    m->round = round;
+  }
+};
+
+/* AADHip_ConvolverCreate: the responses on the host (AADHip_ConvolverResponse reads them) and, as byte planes, on the device */
+struct AADHipConvolver {
+  static constexpr const char *kName = "convolver", *kFrames = "0, or T + K - 1 past 32 bits";
+  static constexpr uint32_t kTile = aad::kConvolveTile;
+  AADHipContext *ctx = nullptr;
+  std::vector<aad::convolve::ResponseDesc> responses; /* offset: the first tap in `taps` */
+  std::vector<int16_t> taps;
+  uint32_t max_taps = 0; /* the longest response: T_src = T + max_taps - 1 */
+  uint32_t *d_lead = nullptr;
+  aad::convolve::ResponseDesc *d_responses = nullptr; /* offset: the first byte in d_planes */
+  int8_t *d_planes = nullptr;
+
+  bool source_frames(uint32_t frames, uint32_t *source_frames) const
+  {
+    uint64_t n = 0;
+    if (!aad::convolve_source_frames(frames, max_taps, &n) || n > UINT32_MAX) return false;
+    *source_frames = (uint32_t)n;
+    return true;
+  }
+  uint32_t lds_bytes() const { return 0; } /* static LDS alone: no launch of the stage is refused */
+  void fill(aad::convolve::GainArgs *m) const
+  {
+    m->r.responses = d_responses;
+    m->r.planes = d_planes;
+    m->r.num_responses = (uint32_t)responses.size();
+  }
+};
+
+namespace {
+
+uint64_t address(const void *p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); }
+
+/* The tail of every launch: ok false - the launch function refused the stage's LDS - or what the launch left behind.  `run`
+ * names the call in last_error, here and below: "resolve", "run", "run with gain", "run with statistics". */
+template <class Stage>
+AADApiResult launched(Stage *s, const char *run, bool ok)
+{
+  const hipError_t e = ok ? hipGetLastError() : hipSuccess;
+  if (ok && e == hipSuccess) return AAD_APIRESULT_OK; /* nothing is formatted on the way of a good call */
+  char *error = s->ctx->last_error;
+  if (ok) snprintf(error, sizeof(s->ctx->last_error), "%s %s launch: %s", Stage::kName, run, hipGetErrorString(e));
+  else snprintf(error, sizeof(s->ctx->last_error), "%s %s: the device refuses %llu bytes of LDS for a workgroup", Stage::kName, run,
+                (unsigned long long)s->lds_bytes());
+  return AAD_APIRESULT_NG;
+}
+
+/* A Resolve of either stage: what it refuses, then - with the context's device selected, and unless the run is empty - `launch`,
+ * which ends in `launched` */
+template <class Stage, class Launch>
+AADApiResult resolve(Stage *s, uint64_t num_windows, const void *windows, const void *selector, uint32_t frames,
+                     const void *source_windows, const void *lanes, Launch launch)
+{
+  uint32_t source_frames = 0;
+  if (!s->source_frames(frames, &source_frames) ||
+      !aad::fir_resolve_ok(num_windows, address(windows), address(selector), address(source_windows), address(lanes))) {
+    snprintf(s->ctx->last_error, sizeof(s->ctx->last_error), "%s resolve: a null or unaligned table, %u frames (%s), or %llu windows",
+             Stage::kName, frames, Stage::kFrames, (unsigned long long)num_windows);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(s->ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  return num_windows == 0 ? AAD_APIRESULT_OK : launch();
+}
+
+/* Every FIR run of either stage: what AADHip_ResamplerRun refuses (out_optional: AADHip_ResamplerRunStats), the kernel's
+ * arguments - the rows' into m->r and the stage's own, which `launch` reads - then `launch` */
+template <class Stage, class Lane, class Args, class Launch>
+AADApiResult run_rows(Stage *s, const char *run, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
+                      uint32_t source_frames, const Lane *device_lanes, uint32_t frames, int32_t sample_type, void *device_out,
+                      bool out_optional, Args *m, Launch launch)
+{
+  uint32_t needed = 0;
+  aad::FirRows f = {false, 0, 0};
+  if (window_sample_type_ok(sample_type) && channels != 0 && s->source_frames(frames, &needed))
+    f = aad::fir_rows(num_windows, channels, frames, source_frames, needed, sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4 : 2,
+                      address(device_source_rows), address(device_lanes), address(device_out), out_optional, Stage::kTile);
+  if (!f.ok) {
+    snprintf(s->ctx->last_error, sizeof(s->ctx->last_error),
+             "%s %s: an unknown sample type, a null or unaligned pointer, 0 channels, %u frames (%s), source rows of %u frames where "
+             "%u are needed, or %llu windows x %u channels x frames past 64 bits",
+             Stage::kName, run, frames, Stage::kFrames, source_frames, needed, (unsigned long long)num_windows, channels);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  m->r.src = device_source_rows;
+  m->r.lanes = reinterpret_cast<decltype(m->r.lanes)>(device_lanes);
+  m->r.out = device_out;
+  m->r.rows = f.rows;
+  m->r.channels = channels;
+  m->r.frames = frames;
+  m->r.source_frames = source_frames;
+  m->r.tiles = f.tiles;
+  s->fill(m);
+  DeviceGuard guard(s->ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  return num_windows == 0 ? AAD_APIRESULT_OK : launch();
+}
+
+/* A run with gain of either stage: what it refuses in front of run_rows, the tables into `m`, and launch(add) */
+template <class Stage, class Lane, class Args, class Launch>
+AADApiResult run_gain(Stage *s, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows, uint32_t source_frames,
+                      const Lane *device_lanes, const struct AADHipWindowSpan *device_spans, uint32_t frames, int32_t sample_type,
+                      void *device_out, const float *device_gain, int32_t mode, Args *m, Launch launch)
+{
+  if (!aad::fir_gain_ok(sample_type, mode, address(device_gain), address(device_spans))) {
+    snprintf(s->ctx->last_error, sizeof(s->ctx->last_error),
+             "%s run with gain: int16 rows, a mode that is neither STORE nor ADD, a gain table off 4-byte or a span table off 8-byte "
+             "alignment", Stage::kName);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  m->spans = reinterpret_cast<const uint64_t *>(device_spans);
+  m->gain = device_gain;
+  const bool add = mode == AAD_HIP_WINDOW_GAIN_ADD;
+  return run_rows(s, "run with gain", num_windows, channels, device_source_rows, source_frames, device_lanes, frames, sample_type,
+                  device_out, false, m, [&] { return launch(add); });
+}
+
+/* a Destroy: the stage's device memory, once the context's stream has drained, and the stage */
+template <class Stage>
+void destroy(Stage *s, std::initializer_list<void *> device)
+{
+  DeviceGuard guard(s->ctx);
+  if (guard.ok) {
+    (void)hipStreamSynchronize(s->ctx->stream);
+    for (void *p : device) (void)hipFree(p); /* a null pointer: no operation */
+  }
+  delete s;
+}
+
+/* AADHip_ResamplerCreate, and with `wide` AADHip_ResamplerCreateWide: the same resampler but for the limits of a ratio and the
+ * kernels its runs launch */
+AADApiResult resampler_create(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios, uint32_t num_streams,
+                              uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler, bool wide)
+{
+  if (ctx == nullptr || resampler == nullptr || ratios == nullptr || num_ratios == 0 || num_ratios >= aad::kResampleNoBank ||
+      variants == 0 || (num_streams != 0 && select == nullptr))
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *resampler = nullptr;
+  const uint64_t entries = (uint64_t)num_streams * variants;
+  for (uint64_t i = 0; i < entries; i++)
+    if (select[i] != aad::kResampleNoBank && select[i] >= num_ratios) return AAD_APIRESULT_INVALID_ARGUMENT;
+  AADHipResampler *r = new (std::nothrow) AADHipResampler();
+  if (r == nullptr) return AAD_APIRESULT_NG;
+  r->ctx = ctx;
+  r->num_streams = num_streams;
+  r->variants = variants;
+  r->wide = wide;
+  std::vector<uint16_t> lead(num_ratios);
+  uint64_t gathered_stride = 0; /* the longest row of a gathered bank, in int16 elements */
+  /* the device's copy: a resident bank as on the host, a gathered one with its rows resample_gather_pitch(K) apart on 16-byte
+   * boundaries; device_banks[r].offset is into it */
+  std::vector<int16_t> image;
+  std::vector<aad::ResampleBankDesc> device_banks;
+  for (uint32_t i = 0; i < num_ratios; i++) {
+    aad::ResampleRatio q;
+    if (!aad::resample_reduce(ratios[i].up, ratios[i].down, &q) ||
+        !(wide ? aad::resample_wide_shape_ok(q.L, q.M) : aad::resample_shape_ok(q.L, q.M))) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error),
+               wide ? "wide resampler: ratio %u (%u / %u) is zero, or has more than 32768 phases, 256 taps or 2 MiB of bank"
+                    : "resampler: ratio %u (%u / %u) is zero, or has more than 1024 phases, 256 taps or 65536 bytes of bank",
+               i, ratios[i].up, ratios[i].down);
+      delete r;
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    const uint32_t K = (uint32_t)aad::resample_taps(q.L, q.M);
+    const size_t at = r->coefficients.size();
+    const bool resident = aad::resample_bank_resident(q.L, K);
+    const uint32_t pitch = resident ? K : aad::resample_gather_pitch(K);
+    const size_t image_at = resident ? image.size() : (image.size() + 7) & ~(size_t)7;
+    if (image_at + (uint64_t)q.L * pitch >= aad::kResampleMaxCoefficients) { /* a wide resampler alone can get here */
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "wide resampler: the banks up to ratio %u hold 2^31 coefficients or more", i);
+      delete r;
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    r->coefficients.resize(at + (size_t)q.L * K);
+    if (!aad::resample_build_bank(q.L, q.M, r->coefficients.data() + at)) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error), "resampler: ratio %u (%u / %u) has a phase with sum |h| above 65535", i,
+               ratios[i].up, ratios[i].down);
+      delete r;
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    r->banks.push_back(aad::ResampleBankDesc{q.L, q.M, K, (uint32_t)at});
+    device_banks.push_back(aad::ResampleBankDesc{q.L, q.M, K, (uint32_t)image_at});
+    image.resize(image_at + (size_t)q.L * pitch, 0);
+    for (uint32_t p = 0; p < q.L; p++)
+      memcpy(image.data() + image_at + (size_t)p * pitch, r->coefficients.data() + at + (size_t)p * K, sizeof(int16_t) * K);
+    lead[i] = (uint16_t)(K / 2 - 1);
+    if (resident) {
+      r->bank_elements = std::max<uint64_t>(r->bank_elements, (uint64_t)q.L * aad::resample_lds_stride(K));
+    } else { /* gathered: the round of the bank with the most taps is the smallest */
+      const uint32_t round = aad::resample_gather_round(K);
+      r->round = r->round == 0 ? round : std::min(r->round, round);
+      gathered_stride = std::max<uint64_t>(gathered_stride, aad::resample_lds_stride(K));
+    }
+    r->span_elements = std::max<uint64_t>(r->span_elements, aad::resample_span_elements(q.L, q.M, K));
+  }
+  r->bank_elements = std::max<uint64_t>(r->bank_elements, r->round * gathered_stride);
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &r->d_select, select, (size_t)entries) || !upload(ctx, &r->d_lead, lead.data(), lead.size()) ||
+      !upload(ctx, &r->d_banks, device_banks.data(), device_banks.size()) ||
+      !upload(ctx, &r->d_coefficients, image.data(), image.size())) {
+    AADHip_ResamplerDestroy(r);
+    return AAD_APIRESULT_NG;
+  }
+  *resampler = r;
+  return AAD_APIRESULT_OK;
+}
+} /* namespace */
+
+AADApiResult AADHip_ResamplerCreate(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
+                                    uint32_t num_streams, uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler)
+{
+  return resampler_create(ctx, num_ratios, ratios, num_streams, variants, select, resampler, false);
+}
+
+AADApiResult AADHip_ResamplerCreateWide(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
+                                        uint32_t num_streams, uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler)
+{
+  return resampler_create(ctx, num_ratios, ratios, num_streams, variants, select, resampler, true);
+}
+
+void AADHip_ResamplerDestroy(struct AADHipResampler *r)
+{
+  if (r != nullptr) destroy(r, {r->d_select, r->d_lead, r->d_banks, r->d_coefficients});
+}
+
+AADApiResult AADHip_ResamplerBank(const struct AADHipResampler *r, uint32_t ratio, uint32_t *L, uint32_t *M, uint32_t *taps,
+                                  int16_t *coefficients, uint64_t capacity)
+{
+  if (r == nullptr || ratio >= r->banks.size() || L == nullptr || M == nullptr || taps == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  const aad::ResampleBankDesc &b = r->banks[ratio];
+  if (coefficients != nullptr && capacity < (uint64_t)b.L * b.K) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
+  *L = b.L;
+  *M = b.M;
+  *taps = b.K;
+  if (coefficients != nullptr) memcpy(coefficients, r->coefficients.data() + b.offset, sizeof(int16_t) * b.L * b.K);
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_ResamplerSourceFrames(const struct AADHipResampler *r, uint32_t frames, uint32_t *source_frames)
+{
+  if (r == nullptr || source_frames == nullptr || !r->source_frames(frames, source_frames)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_ResamplerResolve(struct AADHipResampler *r, uint64_t num_windows, const struct AADHipWindow *device_windows,
+                                     const int64_t *device_variant, uint32_t frames, struct AADHipWindow *device_source_windows,
+                                     struct AADHipResampleLane *device_lanes)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return resolve(r, num_windows, device_windows, device_variant, frames, device_source_windows, device_lanes, [&] {
+    aad::ResampleResolveArgs a;
+    a.windows = reinterpret_cast<const uint64_t *>(device_windows);
+    a.variant = reinterpret_cast<const uint64_t *>(device_variant);
+    a.select = r->d_select;
+    a.lead = r->d_lead;
+    a.num_windows = num_windows;
+    a.num_streams = r->num_streams;
+    a.variants = r->variants;
+    a.source_windows = reinterpret_cast<uint64_t *>(device_source_windows);
+    a.lanes = reinterpret_cast<aad::ResampleLane *>(device_lanes);
+    aad::launch_resample_resolve(a, r->ctx->stream);
+    return launched(r, "resolve", true);
+  });
+}
+
+AADApiResult AADHip_ResamplerRun(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
+                                 uint32_t source_frames, const struct AADHipResampleLane *device_lanes, uint32_t frames,
+                                 int32_t sample_type, void *device_out)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  aad::ResampleMixArgs m = {}; /* a wide resampler's kernels take the plain run's arguments in it */
+  const auto launch = [&] {
+    return launched(r, "run", r->wide ? aad::launch_resample_rows_wide(m, sample_type, r->lds_bytes(), r->ctx->stream)
+                                      : aad::launch_resample_rows(m.r, sample_type, r->lds_bytes(), r->ctx->stream));
+  };
+  return run_rows(r, "run", num_windows, channels, device_source_rows, source_frames, device_lanes, frames, sample_type, device_out,
+                  false, &m, launch);
+}
+
+AADApiResult AADHip_ResamplerRunGain(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels,
+                                     const int16_t *device_source_rows, uint32_t source_frames,
+                                     const struct AADHipResampleLane *device_lanes, const struct AADHipWindowSpan *device_spans,
+                                     uint32_t frames, int32_t sample_type, void *device_out, const float *device_gain, int32_t mode)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  aad::ResampleMixArgs m = {};
+  const auto rows = r->wide ? aad::launch_resample_rows_gain_wide : aad::launch_resample_rows_gain;
+  const auto launch = [&](bool add) { return launched(r, "run with gain", rows(m, sample_type, add, r->lds_bytes(), r->ctx->stream)); };
+  return run_gain(r, num_windows, channels, device_source_rows, source_frames, device_lanes, device_spans, frames, sample_type,
+                  device_out, device_gain, mode, &m, launch);
+}
+
+AADApiResult AADHip_ResamplerRunStats(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels,
+                                      const int16_t *device_source_rows, uint32_t source_frames,
+                                      const struct AADHipResampleLane *device_lanes, const struct AADHipRowStats *device_source_stats,
+                                      const struct AADHipWindowSpan *device_spans, uint32_t frames, int32_t sample_type,
+                                      void *device_out, struct AADHipRowStats *device_stats)
+{
+  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  const aad::WindowStatsTable t = aad::window_stats_table(num_windows, channels, address(device_stats));
+  const aad::WindowStatsTable ts = aad::window_stats_table(num_windows, channels, address(device_source_stats));
+  if (!t.ok || !ts.ok || (address(device_spans) & 7u) != 0 || (device_out != nullptr && device_spans != nullptr)) {
+    snprintf(r->ctx->last_error, sizeof(r->ctx->last_error),
+             "resampler run with statistics: a null or unaligned statistics table, a span table off 8-byte alignment, rows together "
+             "with spans, or %llu windows x %u channels x 32 bytes overflow 64 bits",
+             (unsigned long long)num_windows, channels);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  aad::ResampleMixArgs m = {};
+  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
+  m.source_stats = reinterpret_cast<const unsigned long long *>(device_source_stats);
+  m.stats = reinterpret_cast<unsigned long long *>(device_stats);
+  const auto rows = r->wide ? aad::launch_resample_rows_stats_wide : aad::launch_resample_rows_stats;
+  const auto launch = [&] {
+    if (!hip_ok(r->ctx, hipMemsetAsync(device_stats, 0, t.bytes, r->ctx->stream), "hipMemsetAsync")) return AAD_APIRESULT_NG;
+    return launched(r, "run with statistics", rows(m, sample_type, r->lds_bytes(), r->ctx->stream));
+  };
+  return run_rows(r, "run with statistics", num_windows, channels, device_source_rows, source_frames, device_lanes, frames, sample_type,
+                  device_out, true, &m, launch);
+}
+
+AADApiResult AADHip_ConvolverCreate(struct AADHipContext *ctx, uint32_t num_responses, const float *const *taps, const uint32_t *lengths,
+                                    const int32_t *delays, struct AADHipConvolver **convolver)
+{
+  if (ctx == nullptr || convolver == nullptr || taps == nullptr || lengths == nullptr || num_responses == 0)
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  *convolver = nullptr;
+  AADHipConvolver *c = new (std::nothrow) AADHipConvolver();
+  if (c == nullptr) return AAD_APIRESULT_NG;
+  c->ctx = ctx;
+  std::vector<uint32_t> lead(num_responses);
+  std::vector<int8_t> planes;
+  std::vector<aad::convolve::ResponseDesc> device_responses;
+  for (uint32_t i = 0; i < num_responses; i++) {
+    const uint32_t K = lengths[i];
+    const size_t at = c->taps.size();
+    c->taps.resize(at + (K <= aad::kConvolveMaxTaps ? K : 0));
+    uint32_t q = 0, delay = 0;
+    if (taps[i] == nullptr || !aad::convolve_quantise(taps[i], K, delays != nullptr ? delays[i] : -1, c->taps.data() + at, &q, &delay)) {
+      snprintf(ctx->last_error, sizeof(ctx->last_error),
+               "convolver: response %u has %u taps (1 ... 32768), a tap that is not finite or past 32639 in magnitude, or a delay "
+               "outside its taps", i, K);
+      delete c;
+      return AAD_APIRESULT_INVALID_ARGUMENT;
+    }
+    const uint32_t steps = aad::convolve_steps(K);
+    const size_t image_at = planes.size();
+    planes.resize(image_at + (size_t)steps * aad::kConvolveStepBytes);
+    aad::convolve_build_planes(c->taps.data() + at, K, planes.data() + image_at);
+    const int64_t bias = aad::convolve_bias(c->taps.data() + at, K);
+    c->responses.push_back(aad::convolve::ResponseDesc{K, q, delay, steps, (uint64_t)at, bias});
+    device_responses.push_back(aad::convolve::ResponseDesc{K, q, delay, steps, (uint64_t)image_at, bias});
+    lead[i] = K - 1 - delay;
+    c->max_taps = std::max(c->max_taps, K);
+  }
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &c->d_lead, lead.data(), lead.size()) ||
+      !upload(ctx, &c->d_responses, device_responses.data(), device_responses.size()) ||
+      !upload(ctx, &c->d_planes, planes.data(), planes.size())) {
+    AADHip_ConvolverDestroy(c);
+    return AAD_APIRESULT_NG;
+  }
+  *convolver = c;
+  return AAD_APIRESULT_OK;
+}
+
+void AADHip_ConvolverDestroy(struct AADHipConvolver *c)
+{
+  if (c != nullptr) destroy(c, {c->d_lead, c->d_responses, c->d_planes});
+}
+
+AADApiResult AADHip_ConvolverResponse(const struct AADHipConvolver *c, uint32_t response, uint32_t *num_taps, uint32_t *scale,
+                                      uint32_t *delay, int16_t *taps, uint64_t capacity)
+{
+  if (c == nullptr || response >= c->responses.size() || num_taps == nullptr || scale == nullptr || delay == nullptr)
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  const aad::convolve::ResponseDesc &d = c->responses[response];
+  if (taps != nullptr && capacity < d.K) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
+  *num_taps = d.K;
+  *scale = d.q;
+  *delay = d.delay;
+  if (taps != nullptr) memcpy(taps, c->taps.data() + d.offset, sizeof(int16_t) * d.K);
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_ConvolverSourceFrames(const struct AADHipConvolver *c, uint32_t frames, uint32_t *source_frames)
+{
+  if (c == nullptr || source_frames == nullptr || !c->source_frames(frames, source_frames)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_ConvolverResolve(struct AADHipConvolver *c, uint64_t num_windows, const struct AADHipWindow *device_windows,
+                                     const int64_t *device_response, uint32_t frames, struct AADHipWindow *device_source_windows,
+                                     struct AADHipConvolveLane *device_lanes)
+{
+  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return resolve(c, num_windows, device_windows, device_response, frames, device_source_windows, device_lanes, [&] {
+    aad::convolve::ResolveArgs a;
+    a.windows = reinterpret_cast<const uint64_t *>(device_windows);
+    a.response = reinterpret_cast<const uint64_t *>(device_response);
+    a.lead = c->d_lead;
+    a.num_windows = num_windows;
+    a.num_responses = (uint32_t)c->responses.size();
+    a.source_windows = reinterpret_cast<uint64_t *>(device_source_windows);
+    a.lanes = reinterpret_cast<aad::ConvolveLane *>(device_lanes);
+    aad::convolve::launch_resolve(a, c->ctx->stream);
+    return launched(c, "resolve", true);
+  });
+}
+
+AADApiResult AADHip_ConvolverRun(struct AADHipConvolver *c, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
+                                 uint32_t source_frames, const struct AADHipConvolveLane *device_lanes, uint32_t frames,
+                                 int32_t sample_type, void *device_out)
+{
+  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  aad::convolve::GainArgs m = {}; /* m.r: the run's arguments */
+  const auto launch = [&] { aad::convolve::launch_rows(m.r, sample_type, c->ctx->stream); return launched(c, "run", true); };
+  return run_rows(c, "run", num_windows, channels, device_source_rows, source_frames, device_lanes, frames, sample_type, device_out,
+                  false, &m, launch);
+}
+
+AADApiResult AADHip_ConvolverRunGain(struct AADHipConvolver *c, uint64_t num_windows, uint32_t channels,
+                                     const int16_t *device_source_rows, uint32_t source_frames,
+                                     const struct AADHipConvolveLane *device_lanes, const struct AADHipWindowSpan *device_spans,
+                                     uint32_t frames, int32_t sample_type, void *device_out, const float *device_gain, int32_t mode)
+{
+  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  aad::convolve::GainArgs m = {};
+  const auto launch = [&](bool add) {
+    aad::convolve::launch_rows_gain(m, sample_type, add, c->ctx->stream);
+    return launched(c, "run with gain", true);
+  };
+  return run_gain(c, num_windows, channels, device_source_rows, source_frames, device_lanes, device_spans, frames, sample_type,
+                  device_out, device_gain, mode, &m, launch);
+}

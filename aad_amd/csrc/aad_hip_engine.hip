@@ -1,13 +1,13 @@
 /*
- * aad_hip_engine.hip - host side of the batched C-ABI declared in include/aad_hip.h:
- * contexts, plans (uploaded stream tables), kernel launches and the host-memory convenience
- * calls.  Device code lives in aad_encode.hip.h / aad_decode.hip.h (shared parts: aad_device.hip.h)
- * and, for the split, sector-tiled and window decoders and the planar-input and planar reconstruct encoders, in units of their own
- * (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_units.hip - one object per input type and REC; the
- * window reconstruct run's resolve kernel: aad_window_reconstruct.hip).  Every
- * kind of encode plan is made by encode_plan_create and run by encode_plan_run over one description of a run (aad::EncodeRun,
- * aad_encode_launch.hip.h), which the host-memory paths build directly.  gfx950 only; no CPU code path - every entry point that
- * needs the GPU fails with AAD_APIRESULT_NG when HIP does.
+ * aad_hip_engine.hip - host side of the batched C-ABI declared in include/aad_hip.h: contexts, plans (uploaded stream tables), kernel
+ * launches and the host-memory convenience calls.  Device code lives in aad_encode.hip.h / aad_decode.hip.h (shared parts:
+ * aad_device.hip.h) and, for the split, sector-tiled and window decoders and the planar-input and planar reconstruct encoders, in
+ * units of their own (aad_decode_split.hip, aad_decode_tiled.hip, aad_decode_window.hip, aad_encode_units.hip - one object per input
+ * type and REC; the window reconstruct run's resolve kernel: aad_window_reconstruct.hip).  Every kind of encode plan is made by
+ * encode_plan_create and run by encode_plan_run over one description of a run (aad::EncodeRun, aad_encode_launch.hip.h), which the
+ * host-memory paths build directly.  The FIR stages behind a window decode (AADHip_Resampler*, AADHip_Convolver*) have a host unit
+ * of their own, aad_fir_stage.hip; the context and the helpers that both units use are aad_hip_context.hip.h's.  gfx950 only; no
+ * CPU code path - every entry point that needs the GPU fails with AAD_APIRESULT_NG when HIP does.
  */
 #include <hip/hip_runtime.h>
 
@@ -24,15 +24,13 @@
 
 #include "../../include/aad_hip.h"
 #include "aad_compare.hip.h"
-#include "aad_launch.h" /* and aad_launch_policy.h */
 #include "aad_decode.hip.h"
 #include "aad_decode_window.hip.h"
 #include "aad_encode.hip.h"
 #include "aad_encode_launch.hip.h"
 #include "aad_format.h"
+#include "aad_hip_context.hip.h" /* and aad_launch.h, aad_launch_policy.h */
 #include "aad_hip_internal.h"
-#include "aad_resample.hip.h"
-#include "aad_convolve.hip.h"
 #include "aad_tiles.h"
 #include "aad_window_reconstruct.hip.h"
 
@@ -43,16 +41,6 @@ thread_local LaunchSignal tl_launch_signal = {nullptr, nullptr}; /* aad_launch.h
 static_assert(sizeof(AADHipStreamDesc) == sizeof(aad::StreamDesc), "stream table layout");
 static_assert(sizeof(AADHipLaneState) == sizeof(aad::LaneStateRecord), "lane state layout");
 static_assert(sizeof(AADHipErrorStats) == sizeof(aad::ErrorStatsRecord), "error stats layout");
-
-/* grow-only pinned-host + device buffer pair used by the host-memory calls.  Everything a run
- * needs (stream table, block prefix, carried state, payload) is laid out in ONE pinned block and
- * crosses PCIe in ONE copy each way: a copy per stream from pageable memory cost ~10 us apiece
- * (20 ms for a 1000-stream batch), and per-call hipMalloc / table upload / extra synchronisations
- * cost more than the kernels themselves (round 1: 2.9 ms per call for a 0.075 ms kernel). */
-struct Staging {
-  void *host = nullptr, *dev = nullptr;
-  size_t cap = 0;
-};
 
 /* A few helper threads that only ever memcpy: the staging copies between the caller's pageable buffers
  * and the pinned blocks are the slowest stage of the host-memory path (one core moves ~10 GB/s, PCIe
@@ -66,51 +54,6 @@ struct StagingPool {
   std::function<void(unsigned)> job;
   unsigned generation = 0, pending = 0;
   bool stop = false;
-};
-
-struct AADHipContext {
-  int device;
-  hipStream_t stream;
-  bool owns_stream;
-  char last_error[256];
-  /* double-buffered so that a big batch can be cut into chunks: while chunk k is on the device the
-   * host fills chunk k+1's input block and drains chunk k-1's output block */
-  Staging in[2], out[2];
-  hipEvent_t chunk_done[2];
-  hipEvent_t piece_done[3]; /* the earlier pieces of a one-tile decode's output copy */
-  /* a cut batch runs its copies on streams of their own, so that tile k+1 goes up and tile k-1
-   * comes down while tile k computes */
-  hipStream_t up_stream, down_stream;
-  hipEvent_t uploaded[2], computed[2];
-  bool have_events, have_pipeline;
-  /* device blocks of the host-memory reconstruction (grow-only): the wave's PCM, its output + statistics */
-  void *d_rc_in, *d_rc_out;
-  size_t rc_in_capacity, rc_out_capacity;
-  /* device-only scratch of the reconstruction modes (the .aad images never leave HBM) */
-  void *d_scratch;
-  size_t scratch_capacity;
-  /* scratch of the split decoder (dequantised differences), grow-only and shared by every decode
-   * plan of the context: their runs are ordered by the context's one stream */
-  int32_t *d_residual;
-  uint64_t residual_capacity;
-  /* scratch of the dual trial search (three block-sized slots per stream, aad_encode.hip.h
-   * encode_block_dual), grow-only, shared by the context's encode launches like d_residual */
-  uint8_t *d_trial;
-  uint64_t trial_capacity;
-  /* the images of a window reconstruct run that did not ask for them (the encoders always write images), grow-only likewise */
-  uint8_t *d_window_images;
-  uint64_t window_images_capacity;
-  /* AADHip_ContextSetOption; the defaults come from the environment ONCE, at creation */
-  aad::LaunchSignal signal_next; /* AADHip_ContextSignalNextRun: the events the next plan run records around its work (one-shot) */
-  bool signal_refused;           /* ROC_SYSTEM_SCOPE_SIGNAL=0 at creation: an event on a dispatch packet is never seen by another queue */
-  aad::Device device_info; /* filled once at creation: the launch policy's residency terms */
-  aad::Knobs knobs;        /* lane mapping, trial lanes (enum AADHipLaneMapping / AADHipTrialLanes) and the measurement aids */
-  int32_t compare_sequential; /* AAD_HIP_OPTION_COMPARE_ORDER: the -c sums always in the reference's order */
-  int64_t tile_bytes;      /* 0 = the built-in tile budget of the host-memory path, else that many bytes */
-  void *d_state;           /* predictor states of a group of streams between its tiles (host-memory encode) */
-  size_t state_capacity;   /* in records */
-  int32_t staging_threads; /* 0 = by core count, else the number of threads that copy (1 = the caller alone) */
-  StagingPool *pool;    /* staging helper threads, created on demand */
 };
 
 /* which of the three ...PlanRun entry points runs a plan: they take different pointers */
@@ -161,33 +104,6 @@ struct AADHipWindowDecodePlan {
   aad::WindowVariants variants = {}; /* the launches of a run (plan_window_run); Same: the one variant of the header */
 };
 
-/* AADHip_ResamplerCreate: the banks on the host (AADHip_ResamplerBank reads them) and on the device, the select table */
-struct AADHipResampler {
-  AADHipContext *ctx = nullptr;
-  uint32_t num_streams = 0, variants = 0;
-  std::vector<aad::ResampleBankDesc> banks; /* one per ratio, in the caller's order */
-  std::vector<int16_t> coefficients; /* bank r's L * K taps at banks[r].offset: what AADHip_ResamplerBank returns */
-  uint64_t bank_elements = 0, span_elements = 0; /* the FIR kernel's LDS, in int16 elements: the largest bank and span */
-  /* AADHip_ResamplerCreateWide: the runs launch aad_resample_wide.hip's kernels; round: R of their gather path
-   * (resample_gather_round of the gathered bank with the most taps), 0 when every bank is resident */
-  bool wide = false;
-  uint32_t round = 0;
-  uint16_t *d_select = nullptr, *d_lead = nullptr;
-  aad::ResampleBankDesc *d_banks = nullptr;
-  int16_t *d_coefficients = nullptr;
-};
-
-/* AADHip_ConvolverCreate: the responses on the host (AADHip_ConvolverResponse reads them) and, as byte planes, on the device */
-struct AADHipConvolver {
-  AADHipContext *ctx = nullptr;
-  std::vector<aad::convolve::ResponseDesc> responses; /* offset: the first tap in `taps` */
-  std::vector<int16_t> taps;
-  uint32_t max_taps = 0; /* the longest response: T_src = T + max_taps - 1 */
-  uint32_t *d_lead = nullptr;
-  aad::convolve::ResponseDesc *d_responses = nullptr; /* offset: the first byte in d_planes */
-  int8_t *d_planes = nullptr;
-};
-
 struct AADHipReconstructPlan {
   AADHipContext *ctx;
   AADHipEncodePlan *encode;
@@ -198,27 +114,6 @@ struct AADHipReconstructPlan {
 };
 
 namespace {
-
-bool hip_ok(AADHipContext *ctx, hipError_t e, const char *what)
-{
-  if (e == hipSuccess) return true;
-  if (ctx) snprintf(ctx->last_error, sizeof(ctx->last_error), "%s: %s", what, hipGetErrorString(e));
-  return false;
-}
-
-struct DeviceGuard { /* select the context's device for the calling thread, restore on exit */
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(AADHipContext *ctx)
-  {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = hip_ok(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  }
-  ~DeviceGuard()
-  {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 /* arithmetic-progression stream tables get the table-free kernel path (aad::UniformLayout) */
 aad::UniformLayout detect_uniform(uint32_t n, const AADHipStreamDesc *t)
@@ -241,8 +136,6 @@ aad::UniformLayout detect_uniform(uint32_t n, const AADHipStreamDesc *t)
   return u;
 }
 
-bool hip_ok(AADHipContext *ctx, hipError_t e, const char *what);
-
 bool staging_reserve(AADHipContext *ctx, Staging &st, size_t bytes)
 {
   if (bytes <= st.cap) return true;
@@ -262,16 +155,6 @@ void staging_release(Staging &st)
   if (st.host) (void)hipHostFree(st.host);
   if (st.dev) (void)hipFree(st.dev);
   st = Staging();
-}
-
-template <typename T>
-bool upload(AADHipContext *ctx, T **dst, const T *src, size_t count)
-{
-  if (!hip_ok(ctx, hipMalloc((void **)dst, sizeof(T) * (count ? count : 1)), "hipMalloc")) return false;
-  if (count == 0) return true;
-  /* pageable source: the copy is complete (staged) when this returns */
-  return hip_ok(ctx, hipMemcpyAsync(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync") &&
-         hip_ok(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
 }
 
 /* ---- dispatch: from a plan (aad_launch_policy.h) to a template instantiation ---------------------------------------------- */
@@ -1239,13 +1122,6 @@ bool clear_window_stats(AADHipContext *ctx, aad::LaunchSignal *signal, struct AA
   return hip_ok(ctx, hipMemsetAsync(stats, 0, bytes, ctx->stream), "hipMemsetAsync");
 }
 
-/* the sample types of window decode rows: 2 and 3 are no type, and float16 / bfloat16 exist for window decode alone */
-bool window_sample_type_ok(int32_t sample_type)
-{
-  return sample_type == AAD_HIP_SAMPLE_INT16 || sample_type == AAD_HIP_SAMPLE_FLOAT32 || sample_type == AAD_HIP_SAMPLE_FLOAT16 ||
-         sample_type == AAD_HIP_SAMPLE_BFLOAT16;
-}
-
 /* Every run of every kind of plan.  AADHip_WindowDecodePlanRun, and with_stats AADHip_WindowDecodePlanRunStats (stats_bytes
  * below: the table's size): the table as a further output, device_out optional;
  * gain.on: AADHip_WindowDecodePlanRunGain, float rows alone, `mode` its STORE / ADD argument as the caller gave it;
@@ -1378,541 +1254,6 @@ AADApiResult AADHip_WindowDecodePlanRunPlacedStats(struct AADHipWindowDecodePlan
 {
   return window_decode_run(plan, device_data, num_windows, device_windows, frames_per_window, AAD_HIP_SAMPLE_INT16, nullptr, true,
                            device_stats, WindowGainRun{false, nullptr, 0}, 0, WindowPlacedRun{true, device_spans});
-}
-
-/* ------------------------------------------------------------------------------ resample -- */
-
-static_assert(sizeof(AADHipResampleLane) == sizeof(aad::ResampleLane), "lane record layout");
-
-namespace {
-/* AADHip_ResamplerCreate, and with `wide` AADHip_ResamplerCreateWide: the same resampler but for the limits of a ratio and the
- * kernels its runs launch */
-AADApiResult resampler_create(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
-                              uint32_t num_streams, uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler,
-                              bool wide)
-{
-  if (ctx == nullptr || resampler == nullptr || ratios == nullptr || num_ratios == 0 || num_ratios >= aad::kResampleNoBank ||
-      variants == 0 || (num_streams != 0 && select == nullptr))
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  *resampler = nullptr;
-  const uint64_t entries = (uint64_t)num_streams * variants;
-  for (uint64_t i = 0; i < entries; i++)
-    if (select[i] != aad::kResampleNoBank && select[i] >= num_ratios) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipResampler *r = new (std::nothrow) AADHipResampler();
-  if (r == nullptr) return AAD_APIRESULT_NG;
-  r->ctx = ctx;
-  r->num_streams = num_streams;
-  r->variants = variants;
-  r->wide = wide;
-  std::vector<uint16_t> lead(num_ratios);
-  uint64_t gathered_stride = 0; /* the longest row of a gathered bank, in int16 elements */
-  /* the device's copy: a resident bank as on the host, a gathered one with its rows resample_gather_pitch(K) apart on 16-byte
-   * boundaries; device_banks[r].offset is into it */
-  std::vector<int16_t> image;
-  std::vector<aad::ResampleBankDesc> device_banks;
-  for (uint32_t i = 0; i < num_ratios; i++) {
-    aad::ResampleRatio q;
-    if (!aad::resample_reduce(ratios[i].up, ratios[i].down, &q) ||
-        !(wide ? aad::resample_wide_shape_ok(q.L, q.M) : aad::resample_shape_ok(q.L, q.M))) {
-      if (wide)
-        snprintf(ctx->last_error, sizeof(ctx->last_error),
-                 "wide resampler: ratio %u (%u / %u) is zero, or has more than 32768 phases, 256 taps or 2 MiB of bank", i, ratios[i].up,
-                 ratios[i].down);
-      else
-        snprintf(ctx->last_error, sizeof(ctx->last_error),
-                 "resampler: ratio %u (%u / %u) is zero, or has more than 1024 phases, 256 taps or 65536 bytes of bank", i, ratios[i].up,
-                 ratios[i].down);
-      delete r;
-      return AAD_APIRESULT_INVALID_ARGUMENT;
-    }
-    const uint32_t K = (uint32_t)aad::resample_taps(q.L, q.M);
-    const size_t at = r->coefficients.size();
-    const bool resident = aad::resample_bank_resident(q.L, K);
-    const uint32_t pitch = resident ? K : aad::resample_gather_pitch(K);
-    const size_t image_at = resident ? image.size() : (image.size() + 7) & ~(size_t)7;
-    if (image_at + (uint64_t)q.L * pitch >= aad::kResampleMaxCoefficients) { /* a wide resampler alone can get here */
-      snprintf(ctx->last_error, sizeof(ctx->last_error), "wide resampler: the banks up to ratio %u hold 2^31 coefficients or more", i);
-      delete r;
-      return AAD_APIRESULT_INVALID_ARGUMENT;
-    }
-    r->coefficients.resize(at + (size_t)q.L * K);
-    if (!aad::resample_build_bank(q.L, q.M, r->coefficients.data() + at)) {
-      snprintf(ctx->last_error, sizeof(ctx->last_error), "resampler: ratio %u (%u / %u) has a phase with sum |h| above 65535", i,
-               ratios[i].up, ratios[i].down);
-      delete r;
-      return AAD_APIRESULT_INVALID_ARGUMENT;
-    }
-    r->banks.push_back(aad::ResampleBankDesc{q.L, q.M, K, (uint32_t)at});
-    device_banks.push_back(aad::ResampleBankDesc{q.L, q.M, K, (uint32_t)image_at});
-    image.resize(image_at + (size_t)q.L * pitch, 0);
-    for (uint32_t p = 0; p < q.L; p++)
-      memcpy(image.data() + image_at + (size_t)p * pitch, r->coefficients.data() + at + (size_t)p * K, sizeof(int16_t) * K);
-    lead[i] = (uint16_t)(K / 2 - 1);
-    if (resident) {
-      r->bank_elements = std::max<uint64_t>(r->bank_elements, (uint64_t)q.L * aad::resample_lds_stride(K));
-    } else { /* gathered: the round of the bank with the most taps is the smallest */
-      const uint32_t round = aad::resample_gather_round(K);
-      r->round = r->round == 0 ? round : std::min(r->round, round);
-      gathered_stride = std::max<uint64_t>(gathered_stride, aad::resample_lds_stride(K));
-    }
-    r->span_elements = std::max<uint64_t>(r->span_elements, aad::resample_span_elements(q.L, q.M, K));
-  }
-  r->bank_elements = std::max<uint64_t>(r->bank_elements, r->round * gathered_stride);
-  DeviceGuard guard(ctx);
-  if (!guard.ok || !upload(ctx, &r->d_select, select, (size_t)entries) || !upload(ctx, &r->d_lead, lead.data(), lead.size()) ||
-      !upload(ctx, &r->d_banks, device_banks.data(), device_banks.size()) ||
-      !upload(ctx, &r->d_coefficients, image.data(), image.size())) {
-    AADHip_ResamplerDestroy(r);
-    return AAD_APIRESULT_NG;
-  }
-  *resampler = r;
-  return AAD_APIRESULT_OK;
-}
-
-/* bytes of LDS a FIR launch of the resampler asks for, the statistics scratch aside: bank (or a round's rows), span, phase index */
-uint32_t resampler_lds_bytes(const AADHipResampler *r) { return (uint32_t)(2 * (r->bank_elements + r->span_elements) + 4 * r->round); }
-} /* namespace */
-
-AADApiResult AADHip_ResamplerCreate(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
-                                    uint32_t num_streams, uint32_t variants, const uint16_t *select, struct AADHipResampler **resampler)
-{
-  return resampler_create(ctx, num_ratios, ratios, num_streams, variants, select, resampler, false);
-}
-
-AADApiResult AADHip_ResamplerCreateWide(struct AADHipContext *ctx, uint32_t num_ratios, const struct AADHipResampleRatio *ratios,
-                                        uint32_t num_streams, uint32_t variants, const uint16_t *select,
-                                        struct AADHipResampler **resampler)
-{
-  return resampler_create(ctx, num_ratios, ratios, num_streams, variants, select, resampler, true);
-}
-
-void AADHip_ResamplerDestroy(struct AADHipResampler *r)
-{
-  if (r == nullptr) return;
-  DeviceGuard guard(r->ctx);
-  if (guard.ok) {
-    (void)hipStreamSynchronize(r->ctx->stream);
-    if (r->d_select) (void)hipFree(r->d_select);
-    if (r->d_lead) (void)hipFree(r->d_lead);
-    if (r->d_banks) (void)hipFree(r->d_banks);
-    if (r->d_coefficients) (void)hipFree(r->d_coefficients);
-  }
-  delete r;
-}
-
-AADApiResult AADHip_ResamplerBank(const struct AADHipResampler *r, uint32_t ratio, uint32_t *L, uint32_t *M, uint32_t *taps,
-                                  int16_t *coefficients, uint64_t capacity)
-{
-  if (r == nullptr || ratio >= r->banks.size() || L == nullptr || M == nullptr || taps == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  const aad::ResampleBankDesc &b = r->banks[ratio];
-  if (coefficients != nullptr && capacity < (uint64_t)b.L * b.K) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
-  *L = b.L;
-  *M = b.M;
-  *taps = b.K;
-  if (coefficients != nullptr) memcpy(coefficients, r->coefficients.data() + b.offset, sizeof(int16_t) * b.L * b.K);
-  return AAD_APIRESULT_OK;
-}
-
-namespace {
-/* T_src = max over the banks of ((T - 1) M) div L + K; false for T == 0 and a bank with (T - 1) M >= 2^31 */
-bool resampler_source_frames(const AADHipResampler *r, uint32_t frames, uint32_t *source_frames)
-{
-  uint64_t most = 0;
-  for (const aad::ResampleBankDesc &b : r->banks) {
-    uint64_t n = 0;
-    if (!aad::resample_source_frames(frames, b.L, b.M, b.K, &n)) return false;
-    most = std::max(most, n);
-  }
-  *source_frames = (uint32_t)most; /* < 2^31 + 256 */
-  return true;
-}
-} /* namespace */
-
-AADApiResult AADHip_ResamplerSourceFrames(const struct AADHipResampler *r, uint32_t frames, uint32_t *source_frames)
-{
-  if (r == nullptr || source_frames == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  uint32_t n = 0;
-  if (!resampler_source_frames(r, frames, &n)) return AAD_APIRESULT_INVALID_ARGUMENT;
-  *source_frames = n;
-  return AAD_APIRESULT_OK;
-}
-
-AADApiResult AADHip_ResamplerResolve(struct AADHipResampler *r, uint64_t num_windows, const struct AADHipWindow *device_windows,
-                                     const int64_t *device_variant, uint32_t frames, struct AADHipWindow *device_source_windows,
-                                     struct AADHipResampleLane *device_lanes)
-{
-  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = r->ctx;
-  uint32_t source_frames = 0;
-  if (!resampler_source_frames(r, frames, &source_frames) || device_windows == nullptr || device_source_windows == nullptr ||
-      device_lanes == nullptr || num_windows > (uint64_t)INT32_MAX * 256u ||
-      ((reinterpret_cast<uintptr_t>(device_windows) | reinterpret_cast<uintptr_t>(device_variant) |
-        reinterpret_cast<uintptr_t>(device_source_windows)) & 7u) != 0 ||
-      (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "resampler resolve: a null or unaligned table, %u frames (0, or (T - 1) M >= 2^31 for a bank), or %llu windows", frames,
-             (unsigned long long)num_windows);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (num_windows == 0) return AAD_APIRESULT_OK;
-  aad::ResampleResolveArgs a;
-  a.windows = reinterpret_cast<const uint64_t *>(device_windows);
-  a.variant = reinterpret_cast<const uint64_t *>(device_variant);
-  a.select = r->d_select;
-  a.lead = r->d_lead;
-  a.num_windows = num_windows;
-  a.num_streams = r->num_streams;
-  a.variants = r->variants;
-  a.source_windows = reinterpret_cast<uint64_t *>(device_source_windows);
-  a.lanes = reinterpret_cast<aad::ResampleLane *>(device_lanes);
-  aad::launch_resample_resolve(a, ctx->stream);
-  return hip_ok(ctx, hipGetLastError(), "resampler resolve launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
-}
-
-namespace {
-/* What AADHip_ResamplerRun refuses, for the three FIR runs (out_optional: AADHip_ResamplerRunStats), and the kernel's arguments.
- * `what` names the run in last_error. */
-AADApiResult resampler_rows_args(AADHipResampler *r, const char *what, uint64_t num_windows, uint32_t channels,
-                                 const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipResampleLane *device_lanes,
-                                 uint32_t frames, int32_t sample_type, void *device_out, bool out_optional, aad::ResampleRowsArgs *a)
-{
-  AADHipContext *ctx = r->ctx;
-  const uint64_t elem = sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4 : 2;
-  uint32_t needed = 0;
-  uint64_t rows = 0, n = 0;
-  if (!window_sample_type_ok(sample_type) || channels == 0 || !resampler_source_frames(r, frames, &needed) || source_frames < needed ||
-      device_source_rows == nullptr || device_lanes == nullptr || (device_out == nullptr && !out_optional) ||
-      (reinterpret_cast<uintptr_t>(device_source_rows) & 1u) != 0 || (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0 ||
-      (reinterpret_cast<uintptr_t>(device_out) & (elem - 1)) != 0 || __builtin_mul_overflow(num_windows, (uint64_t)channels, &rows) ||
-      __builtin_mul_overflow(rows, (uint64_t)frames, &n) || __builtin_mul_overflow(n, elem, &n) ||
-      __builtin_mul_overflow(rows, (uint64_t)source_frames, &n) || __builtin_mul_overflow(n, (uint64_t)2, &n) ||
-      __builtin_mul_overflow(rows, (uint64_t)((frames - 1) / aad::kResampleTile + 1), &n)) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "%s: an unknown sample type, a null or unaligned pointer, 0 channels, %u frames (0, or (T - 1) M >= 2^31 for a "
-             "bank), source rows of %u frames where %u are needed, or %llu windows x %u channels x frames past 64 bits",
-             what, frames, source_frames, needed, (unsigned long long)num_windows, channels);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  a->src = device_source_rows;
-  a->lanes = reinterpret_cast<const aad::ResampleLane *>(device_lanes);
-  a->banks = r->d_banks;
-  a->coefficients = r->d_coefficients;
-  a->out = device_out;
-  a->rows = rows;
-  a->channels = channels;
-  a->num_banks = (uint32_t)r->banks.size();
-  a->frames = frames;
-  a->source_frames = source_frames;
-  a->tiles = (frames - 1) / aad::kResampleTile + 1;
-  a->bank_elements = (uint32_t)r->bank_elements;
-  a->span_elements = (uint32_t)r->span_elements;
-  return AAD_APIRESULT_OK;
-}
-
-AADApiResult resampler_launched(AADHipResampler *r, const char *what, bool launched)
-{
-  AADHipContext *ctx = r->ctx;
-  if (!launched) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error), "%s: the device refuses %llu bytes of LDS for a workgroup", what,
-             (unsigned long long)resampler_lds_bytes(r));
-    return AAD_APIRESULT_NG;
-  }
-  char label[64];
-  snprintf(label, sizeof(label), "%s launch", what);
-  return hip_ok(ctx, hipGetLastError(), label) ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
-}
-} /* namespace */
-
-AADApiResult AADHip_ResamplerRun(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
-                                 uint32_t source_frames, const struct AADHipResampleLane *device_lanes, uint32_t frames,
-                                 int32_t sample_type, void *device_out)
-{
-  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = r->ctx;
-  aad::ResampleRowsArgs a;
-  const AADApiResult rc = resampler_rows_args(r, "resampler run", num_windows, channels, device_source_rows, source_frames,
-                                              device_lanes, frames, sample_type, device_out, false, &a);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (num_windows == 0) return AAD_APIRESULT_OK;
-  if (r->wide) {
-    aad::ResampleMixArgs m;
-    memset(&m, 0, sizeof(m));
-    m.r = a;
-    m.round = r->round;
-    return resampler_launched(r, "resampler run", aad::launch_resample_rows_wide(m, sample_type, resampler_lds_bytes(r), ctx->stream));
-  }
-  return resampler_launched(r, "resampler run", aad::launch_resample_rows(a, sample_type, resampler_lds_bytes(r), ctx->stream));
-}
-
-AADApiResult AADHip_ResamplerRunGain(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels,
-                                     const int16_t *device_source_rows, uint32_t source_frames,
-                                     const struct AADHipResampleLane *device_lanes, const struct AADHipWindowSpan *device_spans,
-                                     uint32_t frames, int32_t sample_type, void *device_out, const float *device_gain, int32_t mode)
-{
-  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = r->ctx;
-  if (sample_type == AAD_HIP_SAMPLE_INT16 || (mode != AAD_HIP_WINDOW_GAIN_STORE && mode != AAD_HIP_WINDOW_GAIN_ADD) ||
-      (reinterpret_cast<uintptr_t>(device_gain) & 3u) != 0 || (reinterpret_cast<uintptr_t>(device_spans) & 7u) != 0) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "resampler run with gain: int16 rows, a mode that is neither STORE nor ADD, a gain table off 4-byte or a span table off "
-             "8-byte alignment");
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  aad::ResampleMixArgs m;
-  memset(&m, 0, sizeof(m));
-  const AADApiResult rc = resampler_rows_args(r, "resampler run with gain", num_windows, channels, device_source_rows, source_frames,
-                                              device_lanes, frames, sample_type, device_out, false, &m.r);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (num_windows == 0) return AAD_APIRESULT_OK;
-  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
-  m.gain = device_gain;
-  m.round = r->round;
-  const bool add = mode == AAD_HIP_WINDOW_GAIN_ADD;
-  return resampler_launched(r, "resampler run with gain",
-                            r->wide ? aad::launch_resample_rows_gain_wide(m, sample_type, add, resampler_lds_bytes(r), ctx->stream)
-                                    : aad::launch_resample_rows_gain(m, sample_type, add, resampler_lds_bytes(r), ctx->stream));
-}
-
-AADApiResult AADHip_ResamplerRunStats(struct AADHipResampler *r, uint64_t num_windows, uint32_t channels,
-                                      const int16_t *device_source_rows, uint32_t source_frames,
-                                      const struct AADHipResampleLane *device_lanes, const struct AADHipRowStats *device_source_stats,
-                                      const struct AADHipWindowSpan *device_spans, uint32_t frames, int32_t sample_type,
-                                      void *device_out, struct AADHipRowStats *device_stats)
-{
-  if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = r->ctx;
-  const aad::WindowStatsTable t = aad::window_stats_table(num_windows, channels, (uint64_t)reinterpret_cast<uintptr_t>(device_stats));
-  const aad::WindowStatsTable ts =
-      aad::window_stats_table(num_windows, channels, (uint64_t)reinterpret_cast<uintptr_t>(device_source_stats));
-  if (!t.ok || !ts.ok || (reinterpret_cast<uintptr_t>(device_spans) & 7u) != 0 || (device_out != nullptr && device_spans != nullptr)) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "resampler run with statistics: a null or unaligned statistics table, a span table off 8-byte alignment, rows together "
-             "with spans, or %llu windows x %u channels x 32 bytes overflow 64 bits",
-             (unsigned long long)num_windows, channels);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  aad::ResampleMixArgs m;
-  memset(&m, 0, sizeof(m));
-  const AADApiResult rc = resampler_rows_args(r, "resampler run with statistics", num_windows, channels, device_source_rows,
-                                              source_frames, device_lanes, frames, sample_type, device_out, true, &m.r);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (num_windows == 0) return AAD_APIRESULT_OK;
-  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
-  m.source_stats = reinterpret_cast<const unsigned long long *>(device_source_stats);
-  m.stats = reinterpret_cast<unsigned long long *>(device_stats);
-  if (!hip_ok(ctx, hipMemsetAsync(device_stats, 0, t.bytes, ctx->stream), "hipMemsetAsync")) return AAD_APIRESULT_NG;
-  m.round = r->round;
-  return resampler_launched(r, "resampler run with statistics",
-                            r->wide ? aad::launch_resample_rows_stats_wide(m, sample_type, resampler_lds_bytes(r), ctx->stream)
-                                    : aad::launch_resample_rows_stats(m, sample_type, resampler_lds_bytes(r), ctx->stream));
-}
-
-/* ------------------------------------------------------------------------------ convolve -- */
-
-static_assert(sizeof(AADHipConvolveLane) == sizeof(aad::ConvolveLane), "lane record layout");
-
-AADApiResult AADHip_ConvolverCreate(struct AADHipContext *ctx, uint32_t num_responses, const float *const *taps, const uint32_t *lengths,
-                                    const int32_t *delays, struct AADHipConvolver **convolver)
-{
-  if (ctx == nullptr || convolver == nullptr || taps == nullptr || lengths == nullptr || num_responses == 0)
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  *convolver = nullptr;
-  AADHipConvolver *c = new (std::nothrow) AADHipConvolver();
-  if (c == nullptr) return AAD_APIRESULT_NG;
-  c->ctx = ctx;
-  std::vector<uint32_t> lead(num_responses);
-  std::vector<int8_t> planes;
-  std::vector<aad::convolve::ResponseDesc> device_responses;
-  for (uint32_t i = 0; i < num_responses; i++) {
-    const uint32_t K = lengths[i];
-    const size_t at = c->taps.size();
-    c->taps.resize(at + (K <= aad::kConvolveMaxTaps ? K : 0));
-    uint32_t q = 0, delay = 0;
-    if (taps[i] == nullptr || !aad::convolve_quantise(taps[i], K, delays != nullptr ? delays[i] : -1, c->taps.data() + at, &q, &delay)) {
-      snprintf(ctx->last_error, sizeof(ctx->last_error),
-               "convolver: response %u has %u taps (1 ... 32768), a tap that is not finite or past 32639 in magnitude, or a delay "
-               "outside its taps", i, K);
-      delete c;
-      return AAD_APIRESULT_INVALID_ARGUMENT;
-    }
-    const uint32_t steps = aad::convolve_steps(K);
-    const size_t image_at = planes.size();
-    planes.resize(image_at + (size_t)steps * aad::kConvolveStepBytes);
-    aad::convolve_build_planes(c->taps.data() + at, K, planes.data() + image_at);
-    const int64_t bias = aad::convolve_bias(c->taps.data() + at, K);
-    c->responses.push_back(aad::convolve::ResponseDesc{K, q, delay, steps, (uint64_t)at, bias});
-    device_responses.push_back(aad::convolve::ResponseDesc{K, q, delay, steps, (uint64_t)image_at, bias});
-    lead[i] = K - 1 - delay;
-    c->max_taps = std::max(c->max_taps, K);
-  }
-  DeviceGuard guard(ctx);
-  if (!guard.ok || !upload(ctx, &c->d_lead, lead.data(), lead.size()) ||
-      !upload(ctx, &c->d_responses, device_responses.data(), device_responses.size()) ||
-      !upload(ctx, &c->d_planes, planes.data(), planes.size())) {
-    AADHip_ConvolverDestroy(c);
-    return AAD_APIRESULT_NG;
-  }
-  *convolver = c;
-  return AAD_APIRESULT_OK;
-}
-
-void AADHip_ConvolverDestroy(struct AADHipConvolver *c)
-{
-  if (c == nullptr) return;
-  DeviceGuard guard(c->ctx);
-  if (guard.ok) {
-    (void)hipStreamSynchronize(c->ctx->stream);
-    if (c->d_lead) (void)hipFree(c->d_lead);
-    if (c->d_responses) (void)hipFree(c->d_responses);
-    if (c->d_planes) (void)hipFree(c->d_planes);
-  }
-  delete c;
-}
-
-AADApiResult AADHip_ConvolverResponse(const struct AADHipConvolver *c, uint32_t response, uint32_t *num_taps, uint32_t *scale,
-                                      uint32_t *delay, int16_t *taps, uint64_t capacity)
-{
-  if (c == nullptr || response >= c->responses.size() || num_taps == nullptr || scale == nullptr || delay == nullptr)
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  const aad::convolve::ResponseDesc &d = c->responses[response];
-  if (taps != nullptr && capacity < d.K) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
-  *num_taps = d.K;
-  *scale = d.q;
-  *delay = d.delay;
-  if (taps != nullptr) memcpy(taps, c->taps.data() + d.offset, sizeof(int16_t) * d.K);
-  return AAD_APIRESULT_OK;
-}
-
-AADApiResult AADHip_ConvolverSourceFrames(const struct AADHipConvolver *c, uint32_t frames, uint32_t *source_frames)
-{
-  uint64_t n = 0;
-  if (c == nullptr || source_frames == nullptr || !aad::convolve_source_frames(frames, c->max_taps, &n) || n > UINT32_MAX)
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  *source_frames = (uint32_t)n;
-  return AAD_APIRESULT_OK;
-}
-
-AADApiResult AADHip_ConvolverResolve(struct AADHipConvolver *c, uint64_t num_windows, const struct AADHipWindow *device_windows,
-                                     const int64_t *device_response, uint32_t frames, struct AADHipWindow *device_source_windows,
-                                     struct AADHipConvolveLane *device_lanes)
-{
-  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = c->ctx;
-  uint32_t source_frames = 0;
-  if (AADHip_ConvolverSourceFrames(c, frames, &source_frames) != AAD_APIRESULT_OK || device_windows == nullptr ||
-      device_source_windows == nullptr || device_lanes == nullptr || num_windows > (uint64_t)INT32_MAX * 256u ||
-      ((reinterpret_cast<uintptr_t>(device_windows) | reinterpret_cast<uintptr_t>(device_response) |
-        reinterpret_cast<uintptr_t>(device_source_windows)) & 7u) != 0 ||
-      (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "convolver resolve: a null or unaligned table, %u frames (0, or T + K - 1 past 32 bits), or %llu windows", frames,
-             (unsigned long long)num_windows);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (num_windows == 0) return AAD_APIRESULT_OK;
-  aad::convolve::ResolveArgs a;
-  a.windows = reinterpret_cast<const uint64_t *>(device_windows);
-  a.response = reinterpret_cast<const uint64_t *>(device_response);
-  a.lead = c->d_lead;
-  a.num_windows = num_windows;
-  a.num_responses = (uint32_t)c->responses.size();
-  a.source_windows = reinterpret_cast<uint64_t *>(device_source_windows);
-  a.lanes = reinterpret_cast<aad::ConvolveLane *>(device_lanes);
-  aad::convolve::launch_resolve(a, ctx->stream);
-  return hip_ok(ctx, hipGetLastError(), "convolver resolve launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
-}
-
-namespace {
-/* What AADHip_ConvolverRun refuses, for both FIR runs, and the kernel's arguments.  `what` names the run in last_error. */
-AADApiResult convolver_rows_args(AADHipConvolver *c, const char *what, uint64_t num_windows, uint32_t channels,
-                                 const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipConvolveLane *device_lanes,
-                                 uint32_t frames, int32_t sample_type, void *device_out, aad::convolve::RowsArgs *a)
-{
-  AADHipContext *ctx = c->ctx;
-  const uint64_t elem = sample_type == AAD_HIP_SAMPLE_FLOAT32 ? 4 : 2;
-  uint32_t needed = 0;
-  uint64_t rows = 0, n = 0;
-  if (!window_sample_type_ok(sample_type) || channels == 0 || AADHip_ConvolverSourceFrames(c, frames, &needed) != AAD_APIRESULT_OK ||
-      source_frames < needed || device_source_rows == nullptr || device_lanes == nullptr || device_out == nullptr ||
-      (reinterpret_cast<uintptr_t>(device_source_rows) & 1u) != 0 || (reinterpret_cast<uintptr_t>(device_lanes) & 3u) != 0 ||
-      (reinterpret_cast<uintptr_t>(device_out) & (elem - 1)) != 0 || __builtin_mul_overflow(num_windows, (uint64_t)channels, &rows) ||
-      __builtin_mul_overflow(rows, (uint64_t)frames, &n) || __builtin_mul_overflow(n, elem, &n) ||
-      __builtin_mul_overflow(rows, (uint64_t)source_frames, &n) || __builtin_mul_overflow(n, (uint64_t)2, &n) ||
-      __builtin_mul_overflow(rows, (uint64_t)((frames - 1) / aad::kConvolveTile + 1), &n)) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "%s: an unknown sample type, a null or unaligned pointer, 0 channels, %u frames (0, or T + K - 1 past 32 bits), source "
-             "rows of %u frames where %u are needed, or %llu windows x %u channels x frames past 64 bits",
-             what, frames, source_frames, needed, (unsigned long long)num_windows, channels);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  a->src = device_source_rows;
-  a->lanes = reinterpret_cast<const aad::ConvolveLane *>(device_lanes);
-  a->responses = c->d_responses;
-  a->planes = c->d_planes;
-  a->out = device_out;
-  a->rows = rows;
-  a->channels = channels;
-  a->num_responses = (uint32_t)c->responses.size();
-  a->frames = frames;
-  a->source_frames = source_frames;
-  a->tiles = (frames - 1) / aad::kConvolveTile + 1;
-  return AAD_APIRESULT_OK;
-}
-} /* namespace */
-
-AADApiResult AADHip_ConvolverRun(struct AADHipConvolver *c, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows,
-                                 uint32_t source_frames, const struct AADHipConvolveLane *device_lanes, uint32_t frames,
-                                 int32_t sample_type, void *device_out)
-{
-  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = c->ctx;
-  aad::convolve::RowsArgs a;
-  const AADApiResult rc = convolver_rows_args(c, "convolver run", num_windows, channels, device_source_rows, source_frames,
-                                              device_lanes, frames, sample_type, device_out, &a);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (num_windows == 0) return AAD_APIRESULT_OK;
-  aad::convolve::launch_rows(a, sample_type, ctx->stream);
-  return hip_ok(ctx, hipGetLastError(), "convolver run launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
-}
-
-AADApiResult AADHip_ConvolverRunGain(struct AADHipConvolver *c, uint64_t num_windows, uint32_t channels,
-                                     const int16_t *device_source_rows, uint32_t source_frames,
-                                     const struct AADHipConvolveLane *device_lanes, const struct AADHipWindowSpan *device_spans,
-                                     uint32_t frames, int32_t sample_type, void *device_out, const float *device_gain, int32_t mode)
-{
-  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  AADHipContext *ctx = c->ctx;
-  if (sample_type == AAD_HIP_SAMPLE_INT16 || (mode != AAD_HIP_WINDOW_GAIN_STORE && mode != AAD_HIP_WINDOW_GAIN_ADD) ||
-      (reinterpret_cast<uintptr_t>(device_gain) & 3u) != 0 || (reinterpret_cast<uintptr_t>(device_spans) & 7u) != 0) {
-    snprintf(ctx->last_error, sizeof(ctx->last_error),
-             "convolver run with gain: int16 rows, a mode that is neither STORE nor ADD, a gain table off 4-byte or a span table off "
-             "8-byte alignment");
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
-  aad::convolve::GainArgs m;
-  memset(&m, 0, sizeof(m));
-  const AADApiResult rc = convolver_rows_args(c, "convolver run with gain", num_windows, channels, device_source_rows, source_frames,
-                                              device_lanes, frames, sample_type, device_out, &m.r);
-  if (rc != AAD_APIRESULT_OK) return rc;
-  DeviceGuard guard(ctx);
-  if (!guard.ok) return AAD_APIRESULT_NG;
-  if (num_windows == 0) return AAD_APIRESULT_OK;
-  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
-  m.gain = device_gain;
-  aad::convolve::launch_rows_gain(m, sample_type, mode == AAD_HIP_WINDOW_GAIN_ADD, ctx->stream);
-  return hip_ok(ctx, hipGetLastError(), "convolver run with gain launch") ? AAD_APIRESULT_OK : AAD_APIRESULT_NG;
 }
 
 /* -------------------------------------------------------------------- window reconstruct -- */

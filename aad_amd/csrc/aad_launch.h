@@ -20,7 +20,8 @@ namespace aad {
 struct LaunchSignal {
   hipEvent_t start, stop; /* either may be null */
 };
-extern thread_local LaunchSignal tl_launch_signal; /* defined in aad_hip_engine.hip; both null when no run asked for events */
+extern thread_local LaunchSignal tl_launch_signal; /* defined in aad_hip_engine.hip, whose plan runs set it (the FIR stages of
+                                                    * aad_fir_stage.hip never do); both null when no run asked for events */
 
 /* The decoders with translation units of their own, launched as planned (aad_launch_policy.h).  aad_decode_split.hip is compiled
  * with its own instruction-scheduling strategy (see the Makefile); the residual rows of DecodeKernel::SplitScratch go through
@@ -61,7 +62,7 @@ template <WindowKind KIND, WindowMode MODE, bool HALF>
 void launch_window_object(const WindowUnitRun &r, const WindowLaunch &p, int32_t sample_type, hipStream_t stream);
 
 /* ... and the one way to them: the object of (kind, mode, window_half_type(sample_type)) launches.  sample_type: enum
- * AADHipSampleType, validated by the entry point.  Defined in aad_hip_engine.hip */
+ * AADHipSampleType, validated by the entry point (window_sample_type_ok, aad_hip_context.hip.h).  Defined in aad_hip_engine.hip */
 void launch_window_unit(WindowKind kind, WindowMode mode, const WindowUnitRun &r, const WindowLaunch &p, int32_t sample_type,
                         hipStream_t stream);
 /* the decoded rows of a planar reconstruct run (AADHip_PlanarReconstructPlanRun; launched through aad_encode_launch.hip.h).

@@ -835,12 +835,8 @@ class Engine:
         taps, delays = self._responses(responses, delays)
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
-            windows = self.window_table(windows, True)
-            n = int(windows.shape[0])
-            if response is not None:
-                self.tensor("response", response, self.torch.int64, n, shape=(n,), contiguous=True)
-            out = _check_fir_run(self, "convolve", n, windows.device, plan.header.num_channels, frames, dtype, out, gain, accumulate,
-                                 spans, None, True)[2]
+            windows, checked = Convolver.check_run(self, plan, windows, frames, response, dtype, out, gain, accumulate, spans, None, True)
+            out = checked[2]
             conv = self._convolver(taps, delays)
             try:
                 return conv.run(plan, data, windows, frames, response=response, dtype=dtype, out=out, gain=gain,
@@ -1439,11 +1435,158 @@ def _check_fir_run(e, what, n, device, channels, frames, dtype, out, gain, accum
     return ch, kind, out, gain, bool(accumulate), spans, stats
 
 
-ResampleSource = namedtuple("ResampleSource", "rows lanes source_frames stats")  # Resampler.decode_source -> run_source
+FirSource = namedtuple("FirSource", "rows lanes source_frames stats", defaults=(None,))  # FirStage.decode_source -> run_source
+ResampleSource = ConvolveSource = FirSource  # the convolver's record carries no statistics
+
+_UNSET = object()  # a keyword that the caller did not pass
 
 
-class Resampler:
+class FirStage:
+    """What Resampler and Convolver share: a FIR stage behind window decode plans, run in three steps - AADHip_<PREFIX>Resolve, the
+    plan's own run into an int16 source batch, AADHip_<PREFIX>Run[Gain|Stats].  A stage states PREFIX; SELECTOR, the keyword of its
+    per-window table (run's fifth argument); WHAT, its name in refusals; STATS, whether it has a statistics run - where not,
+    stats= and rows= are unknown keywords; CHECKS_SOURCE, whether run_source itself refuses a short source row."""
+    PREFIX = SELECTOR = WHAT = None
+    STATS = CHECKS_SOURCE = False
+
+    def source_frames(self, frames):
+        """T_src: the frames of a source row that `frames` output frames read (AADHip_<PREFIX>SourceFrames)"""
+        n = C.c_uint32()
+        name = self.PREFIX + "SourceFrames"
+        _check(name, getattr(self.engine.lib, name)(self.handle, int(frames), C.byref(n)))
+        return n.value
+
+    def _keywords(self, where, named, stats, rows, selector=_UNSET):
+        """-> (selector, stats, rows) of a call: the selector in place or under the stage's keyword; any other keyword - of a stage
+        without a statistics run stats= and rows= too - is refused as Python refuses an unknown one"""
+        named = dict(named)
+        if selector is not _UNSET:
+            selector = named.pop(self.SELECTOR, selector)
+        if not self.STATS:
+            named.update((k, v) for k, v in (("stats", stats), ("rows", rows)) if v is not _UNSET)
+        for k in named:
+            raise TypeError("%s.%s() got an unexpected keyword argument '%s'" % (type(self).__name__, where, k))
+        return selector, None if stats is _UNSET else stats, True if rows is _UNSET else rows
+
+    @classmethod
+    def check_run(cls, e, window_plan, windows, frames, selector, dtype, out, gain, accumulate, spans, stats, rows):
+        """every rule of run's arguments on engine `e`, before any library call and without a stage -> (the window table,
+        (channels, sample type, out, gain, accumulate, spans, stats or None))"""
+        _fir_sample_type(e.torch, cls.WHAT, dtype)  # the order of the checks is the one the call had before it took gain, spans and stats
+        windows = e.window_table(windows, True)
+        n = int(windows.shape[0])
+        if selector is not None:
+            e.tensor(cls.SELECTOR, selector, e.torch.int64, n, shape=(n,), contiguous=True)
+        return windows, _check_fir_run(e, cls.WHAT, n, windows.device, window_plan.header.num_channels, frames, dtype, out, gain,
+                                       accumulate, spans, stats, rows)
+
+    def run(self, window_plan, data, windows, frames, selector=None, dtype=None, out=None, gain=None, accumulate=False, spans=None,
+            stats=_UNSET, rows=_UNSET, **named):
+        """window_plan: a WindowDecodePlan of any kind over `data`; windows: int64 cuda tensor [N, 2] of (stream, first_frame in
+        source frames); selector (variant= of a Resampler, response= of a Convolver): contiguous int64 cuda tensor [N], None for
+        all 0 -> `out` ([N, channels, frames] of dtype torch.float32, torch.int16, torch.float16 or torch.bfloat16; allocated when
+        None): window w through the filter its selector names - the ratio select[stream][variant[w]], the response response[w] -
+        zeros where there is none.  Three steps on the engine's stream, ordered against torch's current one: the stage's Resolve,
+        the plan's own run into an int16 source batch of source_frames(frames) frames per row, and the stage's Run.  Neither table
+        is read on the host.  The source batch and the tables between the steps are temporaries of this call; torch's current
+        stream waits for the engine's before it can reuse them (Engine.window_table).
+        gain, accumulate, spans, and of a Resampler stats, rows: the meanings and refusals of WindowDecodePlan.run, on the
+        filtered rows - `spans` in OUTPUT frames; the FIR step is then the stage's RunGain or AADHip_ResamplerRunStats, and with
+        stats the source batch is decoded with its own statistics, whose `count` the FIR turns into the row's -> out, (out, stats)
+        or stats.  The call is decode_source and run_source composed."""
+        selector, stats, rows = self._keywords("run", named, stats, rows, selector)
+        windows, checked = self.check_run(self.engine, window_plan, windows, frames, selector, dtype, out, gain, accumulate, spans, stats,
+                                          rows)
+        source = self.decode_source(window_plan, data, windows, frames, selector, checked[-1] is not None if self.STATS else _UNSET)
+        return self._run_source(source, frames, *checked)
+
+    def decode_source(self, window_plan, data, windows, frames, selector=None, stats=_UNSET, **named):
+        """The first two steps of run: the stage's Resolve and the plan's own run into the int16 source batch, with stats=True (a
+        Resampler's) by AADHip_WindowDecodePlanRunStats -> FirSource(rows int16 [N, channels, source_frames], lanes int32 [N, 2],
+        source_frames, stats int64 [N, channels, 4] or None), what run_source reads - several times for one decode, as
+        Engine.mix_windows_resampled does."""
+        selector, stats, _ = self._keywords("decode_source", named, stats, _UNSET, selector)
+        e = self.engine
+        torch = e.torch
+        windows = e.window_table(windows, True)
+        n, frames = int(windows.shape[0]), int(frames)
+        if selector is not None:
+            e.tensor(self.SELECTOR, selector, torch.int64, n, shape=(n,), contiguous=True)
+        source_frames = self.source_frames(frames)
+        source_windows = torch.empty((n, 2), dtype=torch.int64, device=windows.device)
+        lanes = torch.empty((n, 2), dtype=torch.int32, device=windows.device)
+        cur = e._enter()
+        _check(self.PREFIX + "Resolve",
+               getattr(e.lib, self.PREFIX + "Resolve")(self.handle, n, windows.data_ptr(), selector.data_ptr() if selector is not None else None,
+                                                      frames, source_windows.data_ptr(), lanes.data_ptr()))
+        if stats:
+            rows, table = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False, stats=True)
+        else:
+            rows, table = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False), None
+        e._exit(cur)
+        return FirSource(rows, lanes, source_frames, table)
+
+    def run_source(self, source, frames, channels, dtype=None, out=None, gain=None, accumulate=False, spans=None, stats=_UNSET,
+                   rows=_UNSET, **named):
+        """The FIR step alone: the stage's Run, with gain / accumulate / spans its RunGain, with stats AADHip_ResamplerRunStats (the
+        source must have been decoded with stats=True) - over decode_source's record or, for a Convolver, any int16 rows [N,
+        channels, source_frames] with a lane table int32 [N, 2] of (response, shift): the rows of Resampler.run(dtype=torch.int16)
+        with a table of the caller's, for one.  channels: the rows per window of the plan that decoded the source - the record is
+        held to it: rows [N, channels, source_frames], statistics [N, channels, 4], lanes [N, 2], contiguous, refused otherwise
+        before any library call.  Arguments and return values as run."""
+        _, stats, rows = self._keywords("run_source", named, stats, rows)
+        e = self.engine
+        torch = e.torch
+        _fir_sample_type(torch, self.WHAT, dtype)
+        # the C calls take the record's pointers and `channels` rows per window: the record must be of that many
+        e.tensor("source.lanes", source.lanes, torch.int32, shape=(None, 2), contiguous=True)
+        n, ch, t_src = int(source.lanes.shape[0]), int(channels), int(source.source_frames)
+        e.tensor("source.rows", source.rows, torch.int16, run_extent("window_rows", rows=n, channels=ch, frames=t_src),
+                 shape=(n, ch, t_src), contiguous=True)
+        if self.STATS and source.stats is not None:
+            e.tensor("source.stats", source.stats, torch.int64, run_extent("stats", rows=n, channels=ch), shape=(n, ch, 4), contiguous=True)
+        checked = _check_fir_run(e, self.WHAT, n, source.lanes.device, ch, frames, dtype, out, gain, accumulate, spans, stats, rows)
+        if checked[-1] is not None and source.stats is None:
+            raise ValueError("stats: the source batch carries no statistics - decode it with decode_source(..., stats=True)")
+        if self.CHECKS_SOURCE and int(frames) > 0 and t_src < self.source_frames(frames):
+            raise ValueError("source.rows: %d frames per row where %d output frames read %d" % (t_src, int(frames), self.source_frames(frames)))
+        return self._run_source(source, frames, *checked)
+
+    def _run_source(self, source, frames, ch, kind, out, gain, accumulate, spans, stats):
+        e = self.engine
+        n, frames = int(source.lanes.shape[0]), int(frames)
+        head = (self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr())
+        spans_ptr = spans.data_ptr() if spans is not None else None
+        if stats is not None:
+            name, tail = "RunStats", (source.stats.data_ptr(), spans_ptr, frames, kind, out.data_ptr() if out is not None else None,
+                                      stats.data_ptr())
+        elif gain is not None or accumulate or spans is not None:
+            name, tail = "RunGain", (spans_ptr, frames, kind, out.data_ptr(), gain.data_ptr() if gain is not None else None,
+                                     WINDOW_GAIN_ADD if accumulate else WINDOW_GAIN_STORE)
+        else:
+            name, tail = "Run", (frames, kind, out.data_ptr())
+        cur = e._enter()
+        _check(self.PREFIX + name, getattr(e.lib, self.PREFIX + name)(*head, *tail))
+        e._exit(cur)
+        if stats is None:
+            return out
+        return (out, stats) if out is not None else stats
+
+    def close(self):
+        if self.handle:
+            getattr(self.engine.lib, self.PREFIX + "Destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Resampler(FirStage):
     """AADHip_Resampler*: banks of integer polyphase filters and the table that picks one per (stream, variant)."""
+    PREFIX, SELECTOR, WHAT, STATS = "AADHip_Resampler", "variant", "resample", True
 
     def __init__(self, engine, handle, ratios, select):
         self.engine, self.handle, self.ratios, self.select = engine, handle, ratios, select
@@ -1457,132 +1600,11 @@ class Resampler:
         _check("AADHip_ResamplerBank", lib.AADHip_ResamplerBank(self.handle, int(r), C.byref(L), C.byref(M), C.byref(K), h.ctypes.data, h.size))
         return L.value, M.value, h
 
-    def source_frames(self, frames):
-        """T_src: the frames of a source row that `frames` output frames read, over all the banks (AADHip_ResamplerSourceFrames)"""
-        n = C.c_uint32()
-        _check("AADHip_ResamplerSourceFrames", self.engine.lib.AADHip_ResamplerSourceFrames(self.handle, int(frames), C.byref(n)))
-        return n.value
 
-    def run(self, window_plan, data, windows, frames, variant=None, dtype=None, out=None, gain=None, accumulate=False, spans=None,
-            stats=None, rows=True):
-        """window_plan: a WindowDecodePlan of any kind over `data`; windows: int64 cuda tensor [N, 2] of (stream, first_frame in
-        source frames); variant: contiguous int64 cuda tensor [N], None for all 0 -> `out` ([N, channels, frames] of dtype
-        torch.float32, torch.int16, torch.float16 or torch.bfloat16; allocated when None): window w resampled by the ratio
-        select[stream][variant[w]], zeros where there is none.  Three steps on the engine's stream, ordered against torch's current
-        one: AADHip_ResamplerResolve, the plan's own run into an int16 source batch of source_frames(frames) frames per row, and
-        AADHip_ResamplerRun.  Neither table is read on the host.  The source batch and the tables between the steps are
-        temporaries of this call; torch's current stream waits for the engine's before it can reuse them (Engine.window_table).
-        gain, accumulate, spans, stats, rows: the meanings and refusals of WindowDecodePlan.run, on the resampled rows - `spans`
-        in OUTPUT frames; the FIR step is then AADHip_ResamplerRunGain or AADHip_ResamplerRunStats, and with stats the source
-        batch is decoded with its own statistics, whose `count` the FIR turns into the row's -> out, (out, stats) or stats.
-        The call is decode_source and run_source composed."""
-        e = self.engine
-        self._sample_type(dtype)  # the order of the checks is the one the call had before it took gain, spans and stats
-        windows = e.window_table(windows, True)
-        if variant is not None:
-            e.tensor("variant", variant, e.torch.int64, int(windows.shape[0]), shape=(int(windows.shape[0]),), contiguous=True)
-        checked = self._check_run(int(windows.shape[0]), windows.device, window_plan.header.num_channels, frames, dtype, out, gain,
-                                  accumulate, spans, stats, rows)
-        source = self.decode_source(window_plan, data, windows, frames, variant=variant, stats=checked[-1] is not None)
-        return self._run_source(source, frames, *checked)
-
-    def decode_source(self, window_plan, data, windows, frames, variant=None, stats=False):
-        """The first two steps of run: AADHip_ResamplerResolve and the plan's own run into the int16 source batch, with
-        stats=True by AADHip_WindowDecodePlanRunStats -> ResampleSource(rows int16 [N, channels, source_frames], lanes int32
-        [N, 2], source_frames, stats int64 [N, channels, 4] or None), what run_source reads - several times for one decode, as
-        Engine.mix_windows_resampled does."""
-        e = self.engine
-        torch = e.torch
-        windows = e.window_table(windows, True)
-        n, frames = int(windows.shape[0]), int(frames)
-        if variant is not None:
-            e.tensor("variant", variant, torch.int64, n, shape=(n,), contiguous=True)
-        source_frames = self.source_frames(frames)
-        source_windows = torch.empty((n, 2), dtype=torch.int64, device=windows.device)
-        lanes = torch.empty((n, 2), dtype=torch.int32, device=windows.device)
-        cur = e._enter()
-        _check("AADHip_ResamplerResolve",
-               e.lib.AADHip_ResamplerResolve(self.handle, n, windows.data_ptr(), variant.data_ptr() if variant is not None else None,
-                                             frames, source_windows.data_ptr(), lanes.data_ptr()))
-        if stats:
-            rows, table = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False, stats=True)
-        else:
-            rows, table = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False), None
-        e._exit(cur)
-        return ResampleSource(rows, lanes, source_frames, table)
-
-    def run_source(self, source, frames, channels, dtype=None, out=None, gain=None, accumulate=False, spans=None, stats=None,
-                   rows=True):
-        """The FIR step alone over decode_source's record: AADHip_ResamplerRun, with gain / accumulate / spans
-        AADHip_ResamplerRunGain, with stats AADHip_ResamplerRunStats (the source must have been decoded with stats=True).
-        channels: the rows per window of the plan that decoded the source - the record is held to it: rows [N, channels,
-        source_frames], statistics [N, channels, 4], lanes [N, 2], contiguous, refused otherwise before any library call.
-        Arguments and return values as run."""
-        e = self.engine
-        torch = e.torch
-        self._sample_type(dtype)
-        # the C calls take the record's pointers and `channels` rows per window: the record must be of that many
-        e.tensor("source.lanes", source.lanes, torch.int32, shape=(None, 2), contiguous=True)
-        n, ch, t_src = int(source.lanes.shape[0]), int(channels), int(source.source_frames)
-        e.tensor("source.rows", source.rows, torch.int16, run_extent("window_rows", rows=n, channels=ch, frames=t_src),
-                 shape=(n, ch, t_src), contiguous=True)
-        if source.stats is not None:
-            e.tensor("source.stats", source.stats, torch.int64, run_extent("stats", rows=n, channels=ch), shape=(n, ch, 4), contiguous=True)
-        checked = self._check_run(n, source.lanes.device, ch, frames, dtype, out, gain, accumulate, spans, stats, rows)
-        if checked[-1] is not None and source.stats is None:
-            raise ValueError("stats: the source batch carries no statistics - decode it with decode_source(..., stats=True)")
-        return self._run_source(source, frames, *checked)
-
-    def _sample_type(self, dtype):
-        """-> (dtype, None: torch.float32; its AAD_HIP_SAMPLE_* value)"""
-        return _fir_sample_type(self.engine.torch, "resample", dtype)
-
-    def _check_run(self, n, device, channels, frames, dtype, out, gain, accumulate, spans, stats, rows):
-        """every rule of run's arguments for n windows on `device`, before any library call -> (channels, sample type, out, gain,
-        accumulate, spans, stats or None)"""
-        return _check_fir_run(self.engine, "resample", n, device, channels, frames, dtype, out, gain, accumulate, spans, stats, rows)
-
-    def _run_source(self, source, frames, ch, kind, out, gain, accumulate, spans, stats):
-        e = self.engine
-        n, frames = int(source.lanes.shape[0]), int(frames)
-        cur = e._enter()
-        if stats is not None:
-            _check("AADHip_ResamplerRunStats",
-                   e.lib.AADHip_ResamplerRunStats(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
-                                                  source.stats.data_ptr(), spans.data_ptr() if spans is not None else None, frames,
-                                                  kind, out.data_ptr() if out is not None else None, stats.data_ptr()))
-        elif gain is not None or accumulate or spans is not None:
-            _check("AADHip_ResamplerRunGain",
-                   e.lib.AADHip_ResamplerRunGain(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
-                                                 spans.data_ptr() if spans is not None else None, frames, kind, out.data_ptr(),
-                                                 gain.data_ptr() if gain is not None else None,
-                                                 WINDOW_GAIN_ADD if accumulate else WINDOW_GAIN_STORE))
-        else:
-            _check("AADHip_ResamplerRun",
-                   e.lib.AADHip_ResamplerRun(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
-                                             frames, kind, out.data_ptr()))
-        e._exit(cur)
-        if stats is None:
-            return out
-        return (out, stats) if out is not None else stats
-
-    def close(self):
-        if self.handle:
-            self.engine.lib.AADHip_ResamplerDestroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-ConvolveSource = namedtuple("ConvolveSource", "rows lanes source_frames")  # Convolver.decode_source -> run_source
-
-
-class Convolver:
-    """AADHip_Convolver*: impulse responses as int16 taps with a scale exponent and a delay, one picked per window."""
+class Convolver(FirStage):
+    """AADHip_Convolver*: impulse responses as int16 taps with a scale exponent and a delay, one picked per window; T_src = frames +
+    the longest response's taps - 1."""
+    PREFIX, SELECTOR, WHAT, CHECKS_SOURCE = "AADHip_Convolver", "response", "convolve", True
 
     def __init__(self, engine, handle, num_responses):
         self.engine, self.handle, self.num_responses = engine, handle, num_responses
@@ -1596,104 +1618,6 @@ class Convolver:
         _check("AADHip_ConvolverResponse",
                lib.AADHip_ConvolverResponse(self.handle, int(r), C.byref(K), C.byref(q), C.byref(d), h.ctypes.data, h.size))
         return q.value, d.value, h
-
-    def source_frames(self, frames):
-        """T_src = frames + the longest response's taps - 1 (AADHip_ConvolverSourceFrames)"""
-        n = C.c_uint32()
-        _check("AADHip_ConvolverSourceFrames", self.engine.lib.AADHip_ConvolverSourceFrames(self.handle, int(frames), C.byref(n)))
-        return n.value
-
-    def run(self, window_plan, data, windows, frames, response=None, dtype=None, out=None, gain=None, accumulate=False, spans=None):
-        """window_plan: a WindowDecodePlan of any kind over `data`; windows: int64 cuda tensor [N, 2] of (stream, first_frame);
-        response: contiguous int64 cuda tensor [N], None for all 0 -> `out` ([N, channels, frames] of dtype torch.float32,
-        torch.int16, torch.float16 or torch.bfloat16; allocated when None): window w convolved with response[w], zeros where the
-        index names none.  Three steps on the engine's stream, ordered against torch's current one: AADHip_ConvolverResolve, the
-        plan's own run into an int16 source batch of source_frames(frames) frames per row, and AADHip_ConvolverRun - with gain,
-        accumulate or spans AADHip_ConvolverRunGain, their meanings and refusals those of Resampler.run.  Neither table is read on
-        the host; the source batch and the tables between the steps are temporaries of this call (Engine.window_table).
-        The call is decode_source and run_source composed."""
-        e = self.engine
-        self._sample_type(dtype)
-        windows = e.window_table(windows, True)
-        n = int(windows.shape[0])
-        if response is not None:
-            e.tensor("response", response, e.torch.int64, n, shape=(n,), contiguous=True)
-        checked = self._check_run(n, windows.device, window_plan.header.num_channels, frames, dtype, out, gain, accumulate, spans)
-        source = self.decode_source(window_plan, data, windows, frames, response=response)
-        return self._run_source(source, frames, *checked)
-
-    def decode_source(self, window_plan, data, windows, frames, response=None):
-        """The first two steps of run: AADHip_ConvolverResolve and the plan's own run into the int16 source batch ->
-        ConvolveSource(rows int16 [N, channels, source_frames], lanes int32 [N, 2], source_frames), what run_source reads."""
-        e = self.engine
-        torch = e.torch
-        windows = e.window_table(windows, True)
-        n, frames = int(windows.shape[0]), int(frames)
-        if response is not None:
-            e.tensor("response", response, torch.int64, n, shape=(n,), contiguous=True)
-        source_frames = self.source_frames(frames)
-        source_windows = torch.empty((n, 2), dtype=torch.int64, device=windows.device)
-        lanes = torch.empty((n, 2), dtype=torch.int32, device=windows.device)
-        cur = e._enter()
-        _check("AADHip_ConvolverResolve",
-               e.lib.AADHip_ConvolverResolve(self.handle, n, windows.data_ptr(), response.data_ptr() if response is not None else None,
-                                             frames, source_windows.data_ptr(), lanes.data_ptr()))
-        rows = window_plan.run(data, source_windows, source_frames, torch.int16, ordered=False)
-        e._exit(cur)
-        return ConvolveSource(rows, lanes, source_frames)
-
-    def run_source(self, source, frames, channels, dtype=None, out=None, gain=None, accumulate=False, spans=None):
-        """The FIR step alone: AADHip_ConvolverRun, with gain / accumulate / spans AADHip_ConvolverRunGain, over decode_source's
-        record or any int16 rows [N, channels, source_frames] with a lane table int32 [N, 2] of (response, shift) - the rows of
-        Resampler.run(dtype=torch.int16) with a table of the caller's, for one.  The record is held to `channels`, contiguous,
-        refused otherwise before any library call.  Arguments and return value as run."""
-        e = self.engine
-        torch = e.torch
-        self._sample_type(dtype)
-        e.tensor("source.lanes", source.lanes, torch.int32, shape=(None, 2), contiguous=True)
-        n, ch, t_src = int(source.lanes.shape[0]), int(channels), int(source.source_frames)
-        e.tensor("source.rows", source.rows, torch.int16, run_extent("window_rows", rows=n, channels=ch, frames=t_src),
-                 shape=(n, ch, t_src), contiguous=True)
-        checked = self._check_run(n, source.lanes.device, ch, frames, dtype, out, gain, accumulate, spans)
-        if int(frames) > 0 and t_src < self.source_frames(frames):
-            raise ValueError("source.rows: %d frames per row where %d output frames read %d" % (t_src, int(frames), self.source_frames(frames)))
-        return self._run_source(source, frames, *checked)
-
-    def _sample_type(self, dtype):
-        """-> (dtype, None: torch.float32; its AAD_HIP_SAMPLE_* value)"""
-        return _fir_sample_type(self.engine.torch, "convolve", dtype)
-
-    def _check_run(self, n, device, channels, frames, dtype, out, gain, accumulate, spans):
-        """the rules of Resampler.run's arguments, without statistics -> (channels, sample type, out, gain, accumulate, spans)"""
-        return _check_fir_run(self.engine, "convolve", n, device, channels, frames, dtype, out, gain, accumulate, spans, None, True)[:-1]
-
-    def _run_source(self, source, frames, ch, kind, out, gain, accumulate, spans):
-        e = self.engine
-        n, frames = int(source.lanes.shape[0]), int(frames)
-        cur = e._enter()
-        if gain is not None or accumulate or spans is not None:
-            _check("AADHip_ConvolverRunGain",
-                   e.lib.AADHip_ConvolverRunGain(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
-                                                 spans.data_ptr() if spans is not None else None, frames, kind, out.data_ptr(),
-                                                 gain.data_ptr() if gain is not None else None,
-                                                 WINDOW_GAIN_ADD if accumulate else WINDOW_GAIN_STORE))
-        else:
-            _check("AADHip_ConvolverRun",
-                   e.lib.AADHip_ConvolverRun(self.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr(),
-                                             frames, kind, out.data_ptr()))
-        e._exit(cur)
-        return out
-
-    def close(self):
-        if self.handle:
-            self.engine.lib.AADHip_ConvolverDestroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class HipEvent:
@@ -1897,4 +1821,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "Resampler", "Convolver", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "FirStage", "Resampler", "Convolver", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]
