@@ -127,7 +127,7 @@ HIP_SYMBOLS = [
     "AADHip_ResamplerResolve", "AADHip_ResamplerRun", "AADHip_ResamplerRunGain", "AADHip_ResamplerRunStats",
     "AADHip_ResamplerCreateWide",
     "AADHip_ConvolverCreate", "AADHip_ConvolverDestroy", "AADHip_ConvolverResponse", "AADHip_ConvolverSourceFrames",
-    "AADHip_ConvolverResolve", "AADHip_ConvolverRun", "AADHip_ConvolverRunGain",
+    "AADHip_ConvolverResolve", "AADHip_ConvolverRun", "AADHip_ConvolverRunGain", "AADHip_ConvolverRunStats",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -279,6 +279,8 @@ def _declare_hip(lib):
     lib.AADHip_ConvolverRun.restype = C.c_int
     lib.AADHip_ConvolverRunGain.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_int32, vp, vp, C.c_int32]
     lib.AADHip_ConvolverRunGain.restype = C.c_int
+    lib.AADHip_ConvolverRunStats.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_int32, vp, vp]
+    lib.AADHip_ConvolverRunStats.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

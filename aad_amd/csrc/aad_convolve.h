@@ -157,6 +157,16 @@ AAD_CONVOLVE_FN ConvolveResolved convolve_resolve(uint64_t stream, uint64_t firs
   return r;
 }
 
+/* `count` of a reverberated row (AADHip_ConvolverRunStats): the number of n < Le whose direct-path source element, element
+ * shift + n of the source row, the stream had - c_src being the source row's own count (AADHip_WindowDecodePlanRunStats over the
+ * source windows), never more than the row's length.  shift + n < c  <=>  n < c - shift.  In 64 bits: shift runs up to 2^32 - 1. */
+AAD_CONVOLVE_FN uint64_t convolve_output_count(uint64_t c_src, uint32_t source_frames, uint32_t shift, uint64_t Le)
+{
+  const uint64_t c = c_src < source_frames ? c_src : source_frames;
+  if (c <= shift) return 0;
+  return c - shift < Le ? c - shift : Le;
+}
+
 /* ---- elements ----------------------------------------------------------------------------------------------------------------- */
 
 /* INT16: clamp(floor((acc + (Q ? 2^(Q-1) : 0)) / 2^Q)); |acc| < 2^45 */

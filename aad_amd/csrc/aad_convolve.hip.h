@@ -1,6 +1,6 @@
-/* aad_convolve.hip.h - the device side of the convolve stage (AADHip_ConvolverResolve, AADHip_ConvolverRun, ...RunGain;
- * include/aad_hip.h "reverberation"): the resolve kernel in front of a window decode and the FIR kernels behind it.  The
- * arithmetic is aad_convolve.h's. */
+/* aad_convolve.hip.h - the device side of the convolve stage (AADHip_ConvolverResolve, AADHip_ConvolverRun, ...RunGain,
+ * ...RunStats; include/aad_hip.h "reverberation"): the resolve kernel in front of a window decode and the FIR kernels behind it.
+ * The arithmetic is aad_convolve.h's. */
 #ifndef AAD_CONVOLVE_HIP_H
 #define AAD_CONVOLVE_HIP_H
 
@@ -50,12 +50,27 @@ struct GainArgs {
   const float *gain;     /* [num_windows], or null: every gain is 1 */
 };
 
+/* AADHip_ConvolverRunStats: the plain run's arguments (r.out null: no rows) and the tables of the statistics run */
+struct StatsArgs {
+  RowsArgs r;
+  const uint64_t *spans;                   /* struct AADHipWindowSpan[num_windows] in output frames, or null: every span is (T, 0) */
+  const unsigned long long *source_stats;  /* struct AADHipRowStats[rows] of the source batch: `count` is read */
+  unsigned long long *stats;               /* struct AADHipRowStats[rows], cleared in front of the launch */
+};
+
 void launch_resolve(const ResolveArgs &a, hipStream_t stream);
 void launch_rows(const RowsArgs &a, int32_t sample_type, hipStream_t stream);
 /* sample_type: one of the three float types; add: AAD_HIP_WINDOW_GAIN_ADD */
 void launch_rows_gain(const GainArgs &a, int32_t sample_type, bool add, hipStream_t stream);
 
 } /* namespace convolve */
+
+/* the kernels of the statistics run (aad_convolve_stats.hip), in a namespace of their own: aad::convolve holds the kernels of
+ * aad_convolve.hip and no other */
+namespace convolve_levels {
+/* sample_type: any of the four; a.r.out null: statistics only */
+void launch_rows_stats(const convolve::StatsArgs &a, int32_t sample_type, hipStream_t stream);
+} /* namespace convolve_levels */
 } /* namespace aad */
 
 #endif /* AAD_CONVOLVE_HIP_H */

@@ -1,7 +1,8 @@
 /* aad_fir_stage.hip - host side of the FIR stages behind a window decode (include/aad_hip.h "resample", "reverberation"): every
  * AADHip_Resampler* and AADHip_Convolver* entry point.  No kernel is instantiated here: the launches are aad_resample.hip's,
- * aad_resample_wide.hip's and aad_convolve.hip's.  A stage is made by its own Create; what a Resolve or a Run refuses is one rule
- * for both (aad_fir_stage.h), asked through the few members a stage states about itself, and every launch ends in `launched`. */
+ * aad_resample_wide.hip's, aad_convolve.hip's and aad_convolve_stats.hip's.  A stage is made by its own Create; what a Resolve or
+ * a Run refuses is one rule for both (aad_fir_stage.h), asked through the few members a stage states about itself, and every
+ * launch ends in `launched`. */
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -82,7 +83,8 @@ struct AADHipConvolver {
     return true;
   }
   uint32_t lds_bytes() const { return 0; } /* static LDS alone: no launch of the stage is refused */
-  void fill(aad::convolve::GainArgs *m) const
+  template <class Args> /* GainArgs, StatsArgs */
+  void fill(Args *m) const
   {
     m->r.responses = d_responses;
     m->r.planes = d_planes;
@@ -176,6 +178,33 @@ AADApiResult run_gain(Stage *s, uint64_t num_windows, uint32_t channels, const i
   const bool add = mode == AAD_HIP_WINDOW_GAIN_ADD;
   return run_rows(s, "run with gain", num_windows, channels, device_source_rows, source_frames, device_lanes, frames, sample_type,
                   device_out, false, m, [&] { return launch(add); });
+}
+
+/* A run with statistics of either stage: what it refuses in front of run_rows, the tables into `m`, the clear of the records on
+ * the context's stream, and launch() */
+template <class Stage, class Lane, class Args, class Launch>
+AADApiResult run_stats(Stage *s, uint64_t num_windows, uint32_t channels, const int16_t *device_source_rows, uint32_t source_frames,
+                       const Lane *device_lanes, const struct AADHipRowStats *device_source_stats,
+                       const struct AADHipWindowSpan *device_spans, uint32_t frames, int32_t sample_type, void *device_out,
+                       struct AADHipRowStats *device_stats, Args *m, Launch launch)
+{
+  const aad::WindowStatsTable t = aad::window_stats_table(num_windows, channels, address(device_stats));
+  const aad::WindowStatsTable ts = aad::window_stats_table(num_windows, channels, address(device_source_stats));
+  if (!t.ok || !ts.ok || (address(device_spans) & 7u) != 0 || (device_out != nullptr && device_spans != nullptr)) {
+    snprintf(s->ctx->last_error, sizeof(s->ctx->last_error),
+             "%s run with statistics: a null or unaligned statistics table, a span table off 8-byte alignment, rows together "
+             "with spans, or %llu windows x %u channels x 32 bytes overflow 64 bits",
+             Stage::kName, (unsigned long long)num_windows, channels);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  m->spans = reinterpret_cast<const uint64_t *>(device_spans);
+  m->source_stats = reinterpret_cast<const unsigned long long *>(device_source_stats);
+  m->stats = reinterpret_cast<unsigned long long *>(device_stats);
+  return run_rows(s, "run with statistics", num_windows, channels, device_source_rows, source_frames, device_lanes, frames, sample_type,
+                  device_out, true, m, [&] {
+                    if (!hip_ok(s->ctx, hipMemsetAsync(device_stats, 0, t.bytes, s->ctx->stream), "hipMemsetAsync")) return AAD_APIRESULT_NG;
+                    return launch();
+                  });
 }
 
 /* a Destroy: the stage's device memory, once the context's stream has drained, and the stage */
@@ -361,26 +390,11 @@ AADApiResult AADHip_ResamplerRunStats(struct AADHipResampler *r, uint64_t num_wi
                                       void *device_out, struct AADHipRowStats *device_stats)
 {
   if (r == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
-  const aad::WindowStatsTable t = aad::window_stats_table(num_windows, channels, address(device_stats));
-  const aad::WindowStatsTable ts = aad::window_stats_table(num_windows, channels, address(device_source_stats));
-  if (!t.ok || !ts.ok || (address(device_spans) & 7u) != 0 || (device_out != nullptr && device_spans != nullptr)) {
-    snprintf(r->ctx->last_error, sizeof(r->ctx->last_error),
-             "resampler run with statistics: a null or unaligned statistics table, a span table off 8-byte alignment, rows together "
-             "with spans, or %llu windows x %u channels x 32 bytes overflow 64 bits",
-             (unsigned long long)num_windows, channels);
-    return AAD_APIRESULT_INVALID_ARGUMENT;
-  }
   aad::ResampleMixArgs m = {};
-  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
-  m.source_stats = reinterpret_cast<const unsigned long long *>(device_source_stats);
-  m.stats = reinterpret_cast<unsigned long long *>(device_stats);
   const auto rows = r->wide ? aad::launch_resample_rows_stats_wide : aad::launch_resample_rows_stats;
-  const auto launch = [&] {
-    if (!hip_ok(r->ctx, hipMemsetAsync(device_stats, 0, t.bytes, r->ctx->stream), "hipMemsetAsync")) return AAD_APIRESULT_NG;
-    return launched(r, "run with statistics", rows(m, sample_type, r->lds_bytes(), r->ctx->stream));
-  };
-  return run_rows(r, "run with statistics", num_windows, channels, device_source_rows, source_frames, device_lanes, frames, sample_type,
-                  device_out, true, &m, launch);
+  const auto launch = [&] { return launched(r, "run with statistics", rows(m, sample_type, r->lds_bytes(), r->ctx->stream)); };
+  return run_stats(r, num_windows, channels, device_source_rows, source_frames, device_lanes, device_source_stats, device_spans, frames,
+                   sample_type, device_out, device_stats, &m, launch);
 }
 
 AADApiResult AADHip_ConvolverCreate(struct AADHipContext *ctx, uint32_t num_responses, const float *const *taps, const uint32_t *lengths,
@@ -496,4 +510,20 @@ AADApiResult AADHip_ConvolverRunGain(struct AADHipConvolver *c, uint64_t num_win
   };
   return run_gain(c, num_windows, channels, device_source_rows, source_frames, device_lanes, device_spans, frames, sample_type,
                   device_out, device_gain, mode, &m, launch);
+}
+
+AADApiResult AADHip_ConvolverRunStats(struct AADHipConvolver *c, uint64_t num_windows, uint32_t channels,
+                                      const int16_t *device_source_rows, uint32_t source_frames,
+                                      const struct AADHipConvolveLane *device_lanes, const struct AADHipRowStats *device_source_stats,
+                                      const struct AADHipWindowSpan *device_spans, uint32_t frames, int32_t sample_type,
+                                      void *device_out, struct AADHipRowStats *device_stats)
+{
+  if (c == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  aad::convolve::StatsArgs m = {};
+  const auto launch = [&] {
+    aad::convolve_levels::launch_rows_stats(m, sample_type, c->ctx->stream);
+    return launched(c, "run with statistics", true);
+  };
+  return run_stats(c, num_windows, channels, device_source_rows, source_frames, device_lanes, device_source_stats, device_spans, frames,
+                   sample_type, device_out, device_stats, &m, launch);
 }

@@ -826,25 +826,108 @@ class Engine:
         return Convolver(self, handle, n)
 
     def decode_windows_reverberated(self, data, image_sizes, windows, frames, responses, response=None, delays=None, dtype=None,
-                                    channels=None, out=None, gain=None, accumulate=False, spans=None):
+                                    channels=None, out=None, gain=None, accumulate=False, spans=None, return_stats=False):
         """decode_windows_mixed with every window convolved with an impulse response: responses as for `convolver`, `response` an
         int64 cuda tensor [N] of indices into them, None for all 0.  The same response goes over every channel row; the direct path
         (delays) stays at the window's first frame, so the row is time-aligned with the dry one.  dtype, channels, out, gain /
-        accumulate, spans: as decode_windows_mixed, on the reverberated rows (Convolver.run).  Every argument is checked before
-        the convolver is built: a refused call has allocated nothing on the device but the plan's tables."""
+        accumulate, spans: as decode_windows_mixed, on the reverberated rows (Convolver.run).  return_stats: -> (rows, int64
+        [N, channels, 4] level statistics of the reverberated rows).  Every argument is checked before the convolver is built: a
+        refused call has allocated nothing on the device but the plan's tables."""
+        return self._reverberated(data, image_sizes, windows, frames, responses, response, delays, dtype, channels, out, gain,
+                                  accumulate, spans, True if return_stats else None, True)
+
+    def window_levels_reverberated(self, data, image_sizes, windows, frames, responses, response=None, delays=None, channels=None,
+                                   spans=None):
+        """The level statistics of decode_windows_reverberated's rows without the rows: int64 [N, channels, 4] of (sum_sq, sum_abs,
+        max_abs, count) per row in int16 units - the reverberant tail counts into the sums, count = the frames of the DRY row the
+        stream had.  Nothing is stored but the source batch and the table: what a rejection sampler asks of its candidates.
+        spans: int64 cuda tensor [N, 2] of (num_frames, out_frame) in output frames - the levels of each window's clipped crop."""
+        return self._reverberated(data, image_sizes, windows, frames, responses, response, delays, None, channels, None, None, False,
+                                  spans, True, False)
+
+    def _reverberated(self, data, image_sizes, windows, frames, responses, response, delays, dtype, channels, out, gain, accumulate,
+                      spans, stats, rows):
+        """decode_windows_reverberated and window_levels_reverberated: every check, then plan and convolver, then Convolver.run"""
         taps, delays = self._responses(responses, delays)
         plan = self._corpus_window_plan(data, image_sizes, channels)
         try:
-            windows, checked = Convolver.check_run(self, plan, windows, frames, response, dtype, out, gain, accumulate, spans, None, True)
-            out = checked[2]
+            windows, checked = Convolver.check_run(self, plan, windows, frames, response, dtype, out, gain, accumulate, spans, stats, rows)
+            out, stats = checked[2], checked[-1]
             conv = self._convolver(taps, delays)
             try:
                 return conv.run(plan, data, windows, frames, response=response, dtype=dtype, out=out, gain=gain,
-                                accumulate=accumulate, spans=spans)
+                                accumulate=accumulate, spans=spans, stats=stats, rows=rows)
             finally:
                 conv.close()  # synchronises the context's stream first
         finally:
             plan.close()
+
+    def mix_windows_reverberated(self, signal, noise, frames, snr_db, responses, response=None, delays=None, noise_responses=None,
+                                 noise_response=None, noise_delays=None, dtype=None, channels=None, noise_spans=None):
+        """mix_windows with the signal convolved with a room response, the SNR measured against the REVERBERANT signal: signal,
+        noise: each (data, image_sizes, windows) as for decode_windows_reverberated, the same number of windows; responses,
+        response, delays: the signal's, as there.  The signal corpus is decoded ONCE into its int16 source batch, with statistics
+        (Convolver.decode_source); the FIR then runs twice over it: statistics only for the levels and a STORE run with a gain of
+        ones.  noise_responses=None: the noise is dry - its plan's own statistics-only run (over noise_spans) and ADD run, exactly
+        as in mix_windows.  Else the noise gets a convolver of its own (noise_responses, noise_response, noise_delays), one decode
+        and two FIR runs, as in mix_windows_resampled -> (rows [N, channels, frames] of `dtype`, float32 [N] noise gains).  No
+        float32 batch, no elementwise pass; the roundings and the meaning of noise_spans (in output frames) and of the SNR are
+        mix_windows'.  Every argument is checked before anything but the plans' tables is built on the device."""
+        torch = self.torch
+        dtype = torch.float32 if dtype is None else dtype
+        taps, delays = self._responses(responses, delays)
+        wet_noise = noise_responses is not None
+        if wet_noise:
+            n_taps, n_delays = self._responses(noise_responses, noise_delays)
+        elif noise_response is not None or noise_delays is not None:
+            raise ValueError("noise_response / noise_delays: the noise has no responses - pass noise_responses")
+        s_plan = self._corpus_window_plan(signal[0], signal[1], channels)
+        try:
+            n_plan = self._corpus_window_plan(noise[0], noise[1], channels)
+            try:
+                ch, n_ch = int(s_plan.header.num_channels), int(n_plan.header.num_channels)
+                if ch != n_ch:
+                    raise ValueError("signal and noise: rows of %d and %d channels do not mix - pass channels=1 or channels=2 to bring "
+                                     "both corpora to one channel count" % (ch, n_ch))
+                # the four runs' arguments, before a convolver exists: levels and STORE of the signal, levels and ADD of the noise
+                _fir_sample_type(torch, Convolver.WHAT, dtype)
+                s_win = self.window_table(signal[2], True)
+                n = int(s_win.shape[0])
+                if response is not None:
+                    self.tensor("response", response, torch.int64, n, shape=(n,), contiguous=True)
+                if dtype == torch.int16:
+                    raise ValueError("gain / accumulate: float rows only (torch.float32, torch.float16, torch.bfloat16), not torch.int16")
+                n_win = self.window_table(noise[2], True, name="noise windows", rows=n)
+                if noise_spans is not None:
+                    noise_spans = self.window_table(noise_spans, True, name="noise_spans", rows=n)
+                if wet_noise and noise_response is not None:
+                    self.tensor("noise_response", noise_response, torch.int64, n, shape=(n,), contiguous=True)
+                s_conv = self._convolver(taps, delays)
+                try:
+                    s_src = s_conv.decode_source(s_plan, signal[0], s_win, frames, response=response, stats=True)
+                    s_stats = s_conv.run_source(s_src, frames, ch, stats=True, rows=False)
+                    if not wet_noise:
+                        n_stats = n_plan.run(noise[0], n_win, frames, stats=True, rows=False, spans=noise_spans)
+                        gains = snr_gains(s_stats, n_stats, snr_db)
+                        rows = s_conv.run_source(s_src, frames, ch, dtype, gain=torch.ones_like(gains))
+                        n_plan.run(noise[0], n_win, frames, dtype, out=rows, gain=gains, accumulate=True, spans=noise_spans)
+                        return rows, gains
+                    n_conv = self._convolver(n_taps, n_delays)
+                    try:
+                        n_src = n_conv.decode_source(n_plan, noise[0], n_win, frames, response=noise_response, stats=True)
+                        n_stats = n_conv.run_source(n_src, frames, n_ch, stats=True, rows=False, spans=noise_spans)
+                        gains = snr_gains(s_stats, n_stats, snr_db)
+                        rows = s_conv.run_source(s_src, frames, ch, dtype, gain=torch.ones_like(gains))
+                        n_conv.run_source(n_src, frames, n_ch, dtype, out=rows, gain=gains, accumulate=True, spans=noise_spans)
+                        return rows, gains
+                    finally:
+                        n_conv.close()  # synchronises the context's stream first
+                finally:
+                    s_conv.close()
+            finally:
+                n_plan.close()
+        finally:
+            s_plan.close()
 
     @staticmethod
     def _speeds(rate, speeds):
@@ -1436,7 +1519,7 @@ def _check_fir_run(e, what, n, device, channels, frames, dtype, out, gain, accum
 
 
 FirSource = namedtuple("FirSource", "rows lanes source_frames stats", defaults=(None,))  # FirStage.decode_source -> run_source
-ResampleSource = ConvolveSource = FirSource  # the convolver's record carries no statistics
+ResampleSource = ConvolveSource = FirSource  # a record built by hand without statistics serves every run that asks for none
 
 _UNSET = object()  # a keyword that the caller did not pass
 
@@ -1444,8 +1527,8 @@ _UNSET = object()  # a keyword that the caller did not pass
 class FirStage:
     """What Resampler and Convolver share: a FIR stage behind window decode plans, run in three steps - AADHip_<PREFIX>Resolve, the
     plan's own run into an int16 source batch, AADHip_<PREFIX>Run[Gain|Stats].  A stage states PREFIX; SELECTOR, the keyword of its
-    per-window table (run's fifth argument); WHAT, its name in refusals; STATS, whether it has a statistics run - where not,
-    stats= and rows= are unknown keywords; CHECKS_SOURCE, whether run_source itself refuses a short source row."""
+    per-window table (run's fifth argument); WHAT, its name in refusals; STATS, whether it has a statistics run (both have) - where
+    not, stats= and rows= are unknown keywords; CHECKS_SOURCE, whether run_source itself refuses a short source row."""
     PREFIX = SELECTOR = WHAT = None
     STATS = CHECKS_SOURCE = False
 
@@ -1490,10 +1573,11 @@ class FirStage:
         the plan's own run into an int16 source batch of source_frames(frames) frames per row, and the stage's Run.  Neither table
         is read on the host.  The source batch and the tables between the steps are temporaries of this call; torch's current
         stream waits for the engine's before it can reuse them (Engine.window_table).
-        gain, accumulate, spans, and of a Resampler stats, rows: the meanings and refusals of WindowDecodePlan.run, on the
-        filtered rows - `spans` in OUTPUT frames; the FIR step is then the stage's RunGain or AADHip_ResamplerRunStats, and with
-        stats the source batch is decoded with its own statistics, whose `count` the FIR turns into the row's -> out, (out, stats)
-        or stats.  The call is decode_source and run_source composed."""
+        gain, accumulate, spans, stats, rows: the meanings and refusals of WindowDecodePlan.run, on the filtered rows - `spans`
+        in OUTPUT frames; the FIR step is then the stage's RunGain or RunStats, and with stats the source batch is decoded with
+        its own statistics, whose `count` the FIR turns into the row's -> out, (out, stats) or stats.  The statistics are those
+        of the int16 row: a float row past full scale keeps its value, its record is clamped (max_abs 32767 or 32768 is the
+        witness).  The call is decode_source and run_source composed."""
         selector, stats, rows = self._keywords("run", named, stats, rows, selector)
         windows, checked = self.check_run(self.engine, window_plan, windows, frames, selector, dtype, out, gain, accumulate, spans, stats,
                                           rows)
@@ -1501,10 +1585,10 @@ class FirStage:
         return self._run_source(source, frames, *checked)
 
     def decode_source(self, window_plan, data, windows, frames, selector=None, stats=_UNSET, **named):
-        """The first two steps of run: the stage's Resolve and the plan's own run into the int16 source batch, with stats=True (a
-        Resampler's) by AADHip_WindowDecodePlanRunStats -> FirSource(rows int16 [N, channels, source_frames], lanes int32 [N, 2],
+        """The first two steps of run: the stage's Resolve and the plan's own run into the int16 source batch, with stats=True by
+        AADHip_WindowDecodePlanRunStats -> FirSource(rows int16 [N, channels, source_frames], lanes int32 [N, 2],
         source_frames, stats int64 [N, channels, 4] or None), what run_source reads - several times for one decode, as
-        Engine.mix_windows_resampled does."""
+        Engine.mix_windows_resampled and Engine.mix_windows_reverberated do."""
         selector, stats, _ = self._keywords("decode_source", named, stats, _UNSET, selector)
         e = self.engine
         torch = e.torch
@@ -1528,8 +1612,8 @@ class FirStage:
 
     def run_source(self, source, frames, channels, dtype=None, out=None, gain=None, accumulate=False, spans=None, stats=_UNSET,
                    rows=_UNSET, **named):
-        """The FIR step alone: the stage's Run, with gain / accumulate / spans its RunGain, with stats AADHip_ResamplerRunStats (the
-        source must have been decoded with stats=True) - over decode_source's record or, for a Convolver, any int16 rows [N,
+        """The FIR step alone: the stage's Run, with gain / accumulate / spans its RunGain, with stats its RunStats (the source must
+        have been decoded with stats=True) - over decode_source's record or, for a Convolver, any int16 rows [N,
         channels, source_frames] with a lane table int32 [N, 2] of (response, shift): the rows of Resampler.run(dtype=torch.int16)
         with a table of the caller's, for one.  channels: the rows per window of the plan that decoded the source - the record is
         held to it: rows [N, channels, source_frames], statistics [N, channels, 4], lanes [N, 2], contiguous, refused otherwise
@@ -1604,7 +1688,7 @@ class Resampler(FirStage):
 class Convolver(FirStage):
     """AADHip_Convolver*: impulse responses as int16 taps with a scale exponent and a delay, one picked per window; T_src = frames +
     the longest response's taps - 1."""
-    PREFIX, SELECTOR, WHAT, CHECKS_SOURCE = "AADHip_Convolver", "response", "convolve", True
+    PREFIX, SELECTOR, WHAT, STATS, CHECKS_SOURCE = "AADHip_Convolver", "response", "convolve", True, True
 
     def __init__(self, engine, handle, num_responses):
         self.engine, self.handle, self.num_responses = engine, handle, num_responses

@@ -693,7 +693,32 @@ AADApiResult AADHip_ResamplerRunStats(
  * alignment, frames == 0, channels == 0, source_frames below T_src, an unknown sample type, int16 rows or a mode outside {0, 1}
  * in the gain run, and extents past 64 bits.  No refused call writes anything.
  *
- * Out of scope, deliberately: level statistics of reverberated rows, a response per channel, responses past 32768 taps. */
+ * Records of AADHip_ConvolverRunStats: the last tool of the loader toolbox, for speech convolved with a room response and noise
+ * added at an SNR measured against the REVERBERANT speech.  The call takes AADHip_ResamplerRunStats' twelve arguments with the
+ * convolver's types; the record is struct AADHipRowStats, unchanged.  Let v[c][n] be the INT16 element above - whatever
+ * sample_type the run has.  Record w * C + c holds
+ *   sum_sq = sum of v^2, sum_abs = sum of |v|, max_abs = max of |v|, each over n < Le, Le by the rule of window decode with spans
+ *            in output frames, a NULL table: every span is (T, 0) - the reverberant tail behind the stream's end is part of the
+ *            row and counts into the sums;
+ *   count  = 0 when c' <= shift, else min(Le, c' - shift), in 64 bits, with c' = min(device_source_stats[w * C + c].count,
+ *            source_frames) and shift the window's lane field: the number of n < Le whose direct-path source element, shift + n,
+ *            the stream had (convolve_output_count, aad_convolve.h).
+ * Consequence: when the source batch was decoded with statistics over AADHip_ConvolverResolve's source windows, count equals the
+ * number of n < Le with first_frame + n < num_samples[stream] - the padding mask of the DRY row; the delay keeps the reverberant
+ * row aligned with it.  A window without a response gets an all-zero record, and rows of +0 where rows are asked for.  Rows,
+ * when device_out is not NULL, are byte for byte AADHip_ConvolverRun's.  The run clears the N * C records on the context's stream,
+ * then launches one kernel; every record is written, whatever the table held before.  The sums are integers: two runs give the
+ * same bits.
+ * The statistics are those of the INT16 row.  A float row that passes full scale is not clamped, but its record is - a response
+ * normalised in energy can do that - and a max_abs of 32767 or 32768 is the witness of a clipped record.  It is the resample
+ * stage's rule, kept so that level_dbfs, rmse and snr_gains stay in int16 units everywhere; an unclamped v^2 would not fit the
+ * record either: |acc| / 2^Q reaches 2^45.
+ * Refusals: exactly those of AADHip_ResamplerRunStats - a null or 8-byte-unaligned device_stats or device_source_stats while
+ * num_windows > 0, a device_spans off 8-byte alignment, device_out != NULL together with device_spans != NULL, N * C * 32 bytes
+ * past 64 bits, and everything AADHip_ConvolverRun refuses, with device_out optional (sample_type and the extents of the rows
+ * are validated all the same).  num_windows == 0 is OK and launches nothing.  A refused run writes nothing.
+ *
+ * Out of scope, deliberately: a response per channel, responses past 32768 taps. */
 struct AADHipConvolveLane { /* a contiguous torch int32 [N, 2] tensor on the device IS the table */
   uint32_t response;        /* the window's response, 0xFFFFFFFF: a row of zeros */
   uint32_t shift;           /* element of the source row that holds frame first_frame */
@@ -724,6 +749,14 @@ AADApiResult AADHip_ConvolverRunGain(
     uint32_t frames, int32_t sample_type, void *device_out,
     const float *device_gain,                      /* NULL: every gain is 1 */
     int32_t mode);                                 /* enum AADHipWindowGainMode */
+AADApiResult AADHip_ConvolverRunStats(
+    struct AADHipConvolver *convolver, uint64_t num_windows, uint32_t channels,
+    const int16_t *device_source_rows, uint32_t source_frames, const struct AADHipConvolveLane *device_lanes,
+    const struct AADHipRowStats *device_source_stats, /* N * C records: what AADHip_WindowDecodePlanRunStats wrote for the source batch */
+    const struct AADHipWindowSpan *device_spans,   /* NULL: every span is (T, 0); in output frames */
+    uint32_t frames, int32_t sample_type,
+    void *device_out,                              /* may be NULL: statistics only */
+    struct AADHipRowStats *device_stats);          /* N * C records, every one written */
 
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 

@@ -11,7 +11,14 @@ min and max for the FIR:
   fft       the composition the stage replaces: decode_windows into float32 rows of T + K - 1 frames' worth (here: the same source
             windows decoded as float32), torch.fft.rfft / irfft convolution with the float taps, crop and scale - timed by the
             host clock around the call and a synchronise, like the three steps together beside it
-The first window's row is checked against tests/convolve_oracle.py.  Prints one line per K; --out appends them to a file."""
+The first window's row is checked against tests/convolve_oracle.py.  Prints one line per K; --out appends them to a file.
+--mix adds two lines per K, as resample_probe.py --mix does for the resample stage:
+  fir variants   over one source batch decoded with statistics, timed in turn within each step (each behind an untimed plain run,
+            so that all of them find the caches as the same kernel left them), median (min - max): the plain FIR into float32,
+            AADHip_ConvolverRunStats without rows and with float32 rows, AADHip_ConvolverRunGain STORE and ADD
+  mix       Engine.mix_windows_reverberated end to end (dry noise) against the composition it replaces - a float32
+            decode_windows_reverberated batch, a float32 decode_windows batch, two vector_norm reductions and one addcmul -
+            by the host clock, with the peak of torch's allocator above the result"""
 import argparse
 import os
 import statistics
@@ -28,7 +35,7 @@ import torch  # noqa: E402
 from aad_amd.capi import SAMPLE_FLOAT32, make_parameter  # noqa: E402
 from aad_amd.engine import Engine, _check  # noqa: E402
 from aad_amd.synth import synth_pcm  # noqa: E402
-from resample_probe import pcm_decoded, timed, timed_all  # noqa: E402
+from resample_probe import host_timed, pcm_decoded, timed, timed_all, timed_in_turn  # noqa: E402
 
 
 def host_ms(steps, warmup, fn):
@@ -43,6 +50,47 @@ def host_ms(steps, warmup, fn):
     return statistics.median(ms)
 
 
+def mix_rows(engine, args, conv, plan, data, size, windows, h, K, lines):
+    """the two lines of --mix for one response"""
+    lib = engine.lib
+    n, frames, ch = args.windows, args.frames, 1
+    source = conv.decode_source(plan, data, windows, frames, stats=True)
+    out = torch.empty((n, ch, frames), dtype=torch.float32, device="cuda")
+    stats = torch.empty((n, ch, 4), dtype=torch.int64, device="cuda")
+    gain = torch.rand(n, device="cuda") + 0.5
+    head = (conv.handle, n, ch, source.rows.data_ptr(), source.source_frames, source.lanes.data_ptr())
+    run_stats = lambda rows: _check("AADHip_ConvolverRunStats", lib.AADHip_ConvolverRunStats(
+        *head, source.stats.data_ptr(), None, frames, SAMPLE_FLOAT32, rows, stats.data_ptr()))
+    run_gain = lambda mode: _check("AADHip_ConvolverRunGain", lib.AADHip_ConvolverRunGain(
+        *head, None, frames, SAMPLE_FLOAT32, out.data_ptr(), gain.data_ptr(), mode))
+    fns = (("plain", lambda: _check("AADHip_ConvolverRun", lib.AADHip_ConvolverRun(*head, frames, SAMPLE_FLOAT32, out.data_ptr()))),
+           ("stats", lambda: run_stats(None)), ("stats + rows", lambda: run_stats(out.data_ptr())),
+           ("gain", lambda: run_gain(0)), ("gain ADD", lambda: run_gain(1)))
+    ms = timed_in_turn(engine.stream, args.steps, args.warmup, fns)
+    lines.append("fir variants K=%d  N=%d C=%d T=%d  " % (K, n, ch, frames) + "  ".join(
+        "%s %.3f ms (%.3f - %.3f)" % (name, statistics.median(v), min(v), max(v)) for name, v in ms.items()))
+    print(lines[-1], flush=True)
+    del source, out, stats
+    noise_windows = windows.flip(0).contiguous()
+
+    def mix():
+        return engine.mix_windows_reverberated((data, size, windows), (data, size, noise_windows), frames, 6.0, [h])
+
+    def composed():
+        s = engine.decode_windows_reverberated(data, size, windows, frames, [h])
+        z = engine.decode_windows(data, size, noise_windows, frames)
+        p_s = torch.linalg.vector_norm(s, dim=(1, 2)).double().square()  # reductions without a temporary batch
+        p_n = torch.linalg.vector_norm(z, dim=(1, 2)).double().square()
+        g = torch.where(p_n > 0, (p_s / p_n.clamp(min=1e-300)).sqrt() * 10.0 ** (-6.0 / 20.0), torch.zeros_like(p_n)).float()
+        return torch.addcmul(s, z, g[:, None, None]), g
+
+    t_mix, peak_mix = host_timed(args.steps, args.warmup, mix)
+    t_comp, peak_comp = host_timed(args.steps, args.warmup, composed)
+    lines.append("mix K=%d  N=%d C=%d T=%d  mix_windows_reverberated %.3f ms, %.1f MB of temporaries  composed %.3f ms, %.1f MB of "
+                 "temporaries" % (K, n, ch, frames, t_mix, peak_mix / 1e6, t_comp, peak_comp / 1e6))
+    print(lines[-1], flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=1024)
@@ -52,6 +100,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--taps", type=int, action="append", help="a response length to time instead of 512, 4096 and 16384; repeatable")
     ap.add_argument("--out")
+    ap.add_argument("--mix", action="store_true", help="add the lines of the FIR variants and of mix_windows_reverberated")
     args = ap.parse_args()
     import convolve_oracle as co
     engine = Engine(0, stream=None)
@@ -115,8 +164,10 @@ def main():
                          "rows %.2e)  exact=%s" % (K, q, n, ch, frames, t_src, t["resolve"], t["decode"], t["fir"], min(fir_ms), max(fir_ms),
                                                    macs / t["fir"] / 1e9, t["three"], t["fft"], err, exact))
             print(lines[-1], flush=True)
-            conv.close()
             del rows, out
+            if args.mix:
+                mix_rows(engine, args, conv, plan, data, size, windows, h, K, lines)
+            conv.close()
         plan.close()
     if args.out:
         with open(args.out, "a") as f:
