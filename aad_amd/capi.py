@@ -128,6 +128,8 @@ HIP_SYMBOLS = [
     "AADHip_ResamplerCreateWide",
     "AADHip_ConvolverCreate", "AADHip_ConvolverDestroy", "AADHip_ConvolverResponse", "AADHip_ConvolverSourceFrames",
     "AADHip_ConvolverResolve", "AADHip_ConvolverRun", "AADHip_ConvolverRunGain", "AADHip_ConvolverRunStats",
+    "AADHip_SpectrogramCreate", "AADHip_SpectrogramDestroy", "AADHip_SpectrogramFrames", "AADHip_SpectrogramCoefficients",
+    "AADHip_SpectrogramRun",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -281,6 +283,16 @@ def _declare_hip(lib):
     lib.AADHip_ConvolverRunGain.restype = C.c_int
     lib.AADHip_ConvolverRunStats.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_int32, vp, vp]
     lib.AADHip_ConvolverRunStats.restype = C.c_int
+    lib.AADHip_SpectrogramCreate.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(vp)]
+    lib.AADHip_SpectrogramCreate.restype = C.c_int
+    lib.AADHip_SpectrogramDestroy.argtypes = [vp]
+    lib.AADHip_SpectrogramDestroy.restype = None
+    lib.AADHip_SpectrogramFrames.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.AADHip_SpectrogramFrames.restype = C.c_int
+    lib.AADHip_SpectrogramCoefficients.argtypes = [vp, C.POINTER(C.c_uint32), vp, C.c_uint64]
+    lib.AADHip_SpectrogramCoefficients.restype = C.c_int
+    lib.AADHip_SpectrogramRun.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp]
+    lib.AADHip_SpectrogramRun.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

@@ -30,6 +30,17 @@ constexpr uint32_t kConvolveNoResponse = 0xFFFFFFFFu; /* a lane's response: the 
 /* h_q[k] = rint(h[k] * 2^q), ties to even (the product in double is exact), q the largest of 0..15 with max |h_q| <= 32639; an
  * all-zero response gets 15.  delay < 0: the index of the largest |h_q|, the lowest on ties - the direct path.  False for K outside
  * 1..32768, a tap that is not finite, a tap past the bound at q = 0 and a delay >= K; nothing is written then. */
+/* the rule's two halves, for every quantiser of the project (aad_spectrogram.h has the other): the scale exponent of a set of
+ * values whose largest magnitude is `most` - rint is odd and monotone: the largest |h_q| is rint of the largest |h| - or -1 when
+ * q = 0 does not fit, and a value at that exponent */
+inline int32_t convolve_scale(double most)
+{
+  int32_t q = (int32_t)kConvolveMaxScale;
+  while (q >= 0 && !(rint(ldexp(most, q)) <= (double)kConvolveMaxTap)) q--;
+  return q;
+}
+inline int16_t convolve_round(double v, int32_t q) { return (int16_t)(int32_t)rint(ldexp(v, q)); }
+
 inline bool convolve_quantise(const float *h, uint32_t K, int32_t delay, int16_t *taps, uint32_t *q_out, uint32_t *delay_out)
 {
   if (h == nullptr || K == 0 || K > kConvolveMaxTaps || (delay >= 0 && (uint32_t)delay >= K)) return false;
@@ -39,14 +50,12 @@ inline bool convolve_quantise(const float *h, uint32_t K, int32_t delay, int16_t
     const double a = fabs((double)h[k]);
     most = a > most ? a : most;
   }
-  /* rint is odd and monotone: the largest |h_q| is rint of the largest |h| */
-  int32_t q = (int32_t)kConvolveMaxScale;
-  while (q >= 0 && !(rint(ldexp(most, q)) <= (double)kConvolveMaxTap)) q--;
+  const int32_t q = convolve_scale(most);
   if (q < 0) return false;
   int32_t peak = 0;
   uint32_t at = 0;
   for (uint32_t k = 0; k < K; k++) {
-    const int32_t v = (int32_t)rint(ldexp((double)h[k], q));
+    const int32_t v = convolve_round((double)h[k], q);
     taps[k] = (int16_t)v;
     const int32_t a = v < 0 ? -v : v;
     if (a > peak) {

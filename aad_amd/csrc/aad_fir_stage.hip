@@ -1,6 +1,7 @@
-/* aad_fir_stage.hip - host side of the FIR stages behind a window decode (include/aad_hip.h "resample", "reverberation"): every
- * AADHip_Resampler* and AADHip_Convolver* entry point.  No kernel is instantiated here: the launches are aad_resample.hip's,
- * aad_resample_wide.hip's, aad_convolve.hip's and aad_convolve_stats.hip's.  A stage is made by its own Create; what a Resolve or
+/* aad_fir_stage.hip - host side of the FIR stages behind a window decode (include/aad_hip.h "resample", "reverberation") and of
+ * the spectrogram stage behind any of them ("spectrogram"): every AADHip_Resampler*, AADHip_Convolver* and AADHip_Spectrogram*
+ * entry point.  No kernel is instantiated here: the launches are aad_resample.hip's, aad_resample_wide.hip's, aad_convolve.hip's,
+ * aad_convolve_stats.hip's and aad_spectrogram.hip's.  A stage is made by its own Create; what a Resolve or
  * a Run refuses is one rule for both (aad_fir_stage.h), asked through the few members a stage states about itself, and every
  * launch ends in `launched`. */
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 #include "aad_fir_stage.h"
 #include "aad_hip_context.hip.h"
 #include "aad_resample.hip.h"
+#include "aad_spectrogram.hip.h"
 
 static_assert(sizeof(AADHipResampleLane) == sizeof(aad::ResampleLane), "lane record layout");
 static_assert(sizeof(AADHipConvolveLane) == sizeof(aad::ConvolveLane), "lane record layout");
@@ -526,4 +528,135 @@ AADApiResult AADHip_ConvolverRunStats(struct AADHipConvolver *c, uint64_t num_wi
   };
   return run_stats(c, num_windows, channels, device_source_rows, source_frames, device_lanes, device_source_stats, device_spans, frames,
                    sample_type, device_out, device_stats, &m, launch);
+}
+
+/* ---- spectrogram (include/aad_hip.h "spectrogram") ------------------------------------------------------------------------------ */
+
+/* AADHip_SpectrogramCreate: the quantised matrices on the host (AADHip_SpectrogramCoefficients reads them) and, as byte planes
+ * with their column constants and the filters' bands, packed weights and per-pair lists, on the device */
+struct AADHipSpectrogram {
+  static constexpr const char *kName = "spectrogram";
+  AADHipContext *ctx = nullptr;
+  uint32_t n_fft = 0, win = 0, hop = 0, q = 0, num_filters = 0;
+  aad::SpectrumGeometry g = {};
+  std::vector<int16_t> cos_sin; /* [W][B][2] */
+  int8_t *d_planes = nullptr;
+  long long *d_consts = nullptr;
+  aad::SpectrumBand *d_bands = nullptr;
+  float *d_weights = nullptr;
+  uint32_t *d_tile_first = nullptr, *d_tile_list = nullptr;
+  uint32_t lds_bytes() const { return aad::spectrum_lds_bytes(g, num_filters != 0); }
+};
+
+AADApiResult AADHip_SpectrogramCreate(struct AADHipContext *ctx, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float *window,
+                                      uint32_t num_filters, const float *filters, struct AADHipSpectrogram **spectrogram)
+{
+  if (ctx == nullptr || spectrogram == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  *spectrogram = nullptr;
+  if (window == nullptr || !aad::spectrum_shape_ok(n_fft, win_length, hop) || (filters == nullptr) != (num_filters == 0)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "spectrogram: n_fft %u, window %u, hop %u (1 <= window <= n_fft <= 4096, hop >= 1), a null window, or filters without a "
+             "count", n_fft, win_length, hop);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  AADHipSpectrogram *s = new (std::nothrow) AADHipSpectrogram();
+  if (s == nullptr) return AAD_APIRESULT_NG;
+  s->ctx = ctx;
+  s->n_fft = n_fft;
+  s->win = win_length;
+  s->hop = hop;
+  s->num_filters = num_filters;
+  s->g = aad::spectrum_geometry(win_length, hop);
+  const uint32_t B = aad::spectrum_bins(n_fft), pairs = aad::spectrum_pairs(n_fft);
+  s->cos_sin.resize((size_t)win_length * B * 2);
+  std::vector<aad::SpectrumBand> bands(num_filters);
+  uint64_t total = 0;
+  if (!aad::spectrum_quantise(window, n_fft, win_length, s->cos_sin.data(), &s->q) ||
+      !aad::spectrum_bands(filters, num_filters, B, bands.data(), &total)) {
+    snprintf(ctx->last_error, sizeof(ctx->last_error),
+             "spectrogram: a window value that is not finite or a coefficient past 32639 at scale 0, or a filter weight that is not "
+             "finite or nonzero below 2^-60");
+    delete s;
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  std::vector<int8_t> planes((size_t)aad::spectrum_plane_bytes(n_fft, win_length));
+  aad::spectrum_build_planes(s->cos_sin.data(), n_fft, win_length, planes.data());
+  std::vector<long long> consts((size_t)32 * pairs);
+  static_assert(sizeof(long long) == sizeof(int64_t), "the column constants");
+  aad::spectrum_column_constants(s->cos_sin.data(), n_fft, win_length, reinterpret_cast<int64_t *>(consts.data()));
+  std::vector<float> weights((size_t)total);
+  aad::spectrum_pack_weights(filters, num_filters, B, bands.data(), weights.data());
+  std::vector<uint32_t> first(pairs + 1);
+  aad::spectrum_tile_lists(bands.data(), num_filters, B, pairs, first.data(), nullptr);
+  std::vector<uint32_t> list(first[pairs]);
+  aad::spectrum_tile_lists(bands.data(), num_filters, B, pairs, first.data(), list.data());
+  DeviceGuard guard(ctx);
+  if (!guard.ok || !upload(ctx, &s->d_planes, planes.data(), planes.size()) || !upload(ctx, &s->d_consts, consts.data(), consts.size()) ||
+      !upload(ctx, &s->d_bands, bands.data(), bands.size()) || !upload(ctx, &s->d_weights, weights.data(), weights.size()) ||
+      !upload(ctx, &s->d_tile_first, first.data(), first.size()) || !upload(ctx, &s->d_tile_list, list.data(), list.size())) {
+    AADHip_SpectrogramDestroy(s);
+    return AAD_APIRESULT_NG;
+  }
+  *spectrogram = s;
+  return AAD_APIRESULT_OK;
+}
+
+void AADHip_SpectrogramDestroy(struct AADHipSpectrogram *s)
+{
+  if (s != nullptr) destroy(s, {s->d_planes, s->d_consts, s->d_bands, s->d_weights, s->d_tile_first, s->d_tile_list});
+}
+
+AADApiResult AADHip_SpectrogramFrames(const struct AADHipSpectrogram *s, uint32_t frames, uint32_t *num_frames)
+{
+  if (s == nullptr || num_frames == nullptr || !aad::spectrum_frames(frames, s->win, s->hop, num_frames)) return AAD_APIRESULT_INVALID_ARGUMENT;
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_SpectrogramCoefficients(const struct AADHipSpectrogram *s, uint32_t *scale, int16_t *cos_sin, uint64_t capacity)
+{
+  if (s == nullptr || scale == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  if (cos_sin != nullptr && capacity < s->cos_sin.size()) return AAD_APIRESULT_INSUFFICIENT_BUFFER;
+  *scale = s->q;
+  if (cos_sin != nullptr) memcpy(cos_sin, s->cos_sin.data(), sizeof(int16_t) * s->cos_sin.size());
+  return AAD_APIRESULT_OK;
+}
+
+AADApiResult AADHip_SpectrogramRun(struct AADHipSpectrogram *s, uint64_t num_rows, const int16_t *device_rows, uint64_t row_pitch,
+                                   uint32_t frames, float *device_out)
+{
+  if (s == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  const uint32_t B = aad::spectrum_bins(s->n_fft);
+  const aad::SpectrumRows r = aad::spectrum_rows(num_rows, address(device_rows), row_pitch, frames, address(device_out), s->win, s->hop,
+                                                 s->num_filters != 0 ? s->num_filters : B, s->g.tile_frames);
+  if (!r.ok) {
+    snprintf(s->ctx->last_error, sizeof(s->ctx->last_error),
+             "spectrogram run: a null or unaligned pointer, %u frames below the window's %u, a row pitch of %llu below the frames, or "
+             "%llu rows past 64 bits", frames, s->win, (unsigned long long)row_pitch, (unsigned long long)num_rows);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(s->ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_rows == 0) return AAD_APIRESULT_OK;
+  aad::spectrum::Args a = {};
+  a.rows = device_rows;
+  a.row_pitch = row_pitch;
+  a.num_rows = num_rows;
+  a.frames = frames;
+  a.num_frames = r.num_frames;
+  a.hop = s->hop;
+  a.steps = aad::spectrum_steps(s->win);
+  a.pairs = aad::spectrum_pairs(s->n_fft);
+  a.bins = B;
+  a.q = s->q;
+  a.g = s->g;
+  a.tiles = r.tiles;
+  a.planes = s->d_planes;
+  a.consts = s->d_consts;
+  a.num_filters = s->num_filters;
+  a.bands = s->d_bands;
+  a.weights = s->d_weights;
+  a.tile_first = s->d_tile_first;
+  a.tile_list = s->d_tile_list;
+  a.out = device_out;
+  return launched(s, "run", aad::spectrum::launch(a, s->ctx->stream));
 }

@@ -929,6 +929,42 @@ class Engine:
         finally:
             s_plan.close()
 
+    # ---- spectrogram ------------------------------------------------------------------------------------------------------------
+    def spectrogram(self, n_fft, hop, win_length=None, window=None, filters=None):
+        """A spectrogram stage over int16 rows (AADHip_SpectrogramCreate, include/aad_hip.h "spectrogram"): n_fft up to 4096, hop
+        >= 1, win_length (None: n_fft) up to n_fft; window: 1-d float array [win_length], None for the periodic Hann window
+        computed in float64 and rounded to float32; filters: float array [M, n_fft // 2 + 1] such as mel_filters gives, None for
+        the power spectrum itself.  Spectrogram.run turns rows into [.., F, M] energies, or [.., F, B] powers."""
+        return self._spectrogram(*_spectrogram_arguments(n_fft, hop, win_length, window, filters))
+
+    def _spectrogram(self, n_fft, hop, win_length, window, filters):
+        handle = C.c_void_p()
+        m = 0 if filters is None else int(filters.shape[0])
+        _check("AADHip_SpectrogramCreate",
+               self.lib.AADHip_SpectrogramCreate(self._ctx, n_fft, win_length, hop, window.ctypes.data, m,
+                                                 filters.ctypes.data if m else None, C.byref(handle)))
+        return Spectrogram(self, handle, n_fft, hop, win_length, m)
+
+    def mel_windows(self, data, image_sizes, windows, frames, n_fft, hop, filters, channels=None, win_length=None, window=None):
+        """decode_windows_mixed's int16 rows through a spectrogram stage -> float32 [N, C, F, M] (M = n_fft // 2 + 1 powers for
+        filters=None): data, image_sizes, windows, frames, channels as decode_windows_mixed; n_fft, hop, filters, win_length,
+        window as `spectrogram`.  F = 1 + (frames - win_length) // hop.  The int16 batch is the one temporary.  Every argument is
+        checked before anything is built."""
+        args = _spectrogram_arguments(n_fft, hop, win_length, window, filters)
+        frames = int(frames)
+        if frames < args[2]:
+            raise ValueError("frames: %d is below the window's %d - such a row has no frame" % (frames, args[2]))
+        windows = self.window_table(windows, True)
+        plan = self._corpus_window_plan(data, image_sizes, channels)
+        try:
+            spec = self._spectrogram(*args)
+            try:
+                return spec.run(plan.run(data, windows, frames, self.torch.int16))
+            finally:
+                spec.close()  # synchronises the context's stream first
+        finally:
+            plan.close()
+
     @staticmethod
     def _speeds(rate, speeds):
         """what the resampled calls refuse of rate and speeds, before anything is built -> the speeds as pairs of ints"""
@@ -1704,6 +1740,135 @@ class Convolver(FirStage):
         return q.value, d.value, h
 
 
+def _spectrogram_arguments(n_fft, hop, win_length, window, filters):
+    """what `spectrogram` refuses, before anything is built -> (n_fft, hop, win_length, float32 window, float32 filters or None)"""
+    n_fft, hop = int(n_fft), int(hop)
+    win_length = n_fft if win_length is None else int(win_length)
+    if not (1 <= win_length <= n_fft <= 4096) or not (1 <= hop < 1 << 32):
+        raise ValueError("n_fft, win_length, hop: 1 <= win_length <= n_fft <= 4096 and hop >= 1 are needed, got %d, %d, %d"
+                         % (n_fft, win_length, hop))
+    if window is None:
+        window = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win_length, dtype=np.float64) / win_length)
+    window = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1).astype(np.float32))
+    if window.size != win_length or not np.isfinite(window).all():
+        raise ValueError("window: %d finite values are needed, got %d values" % (win_length, window.size))
+    if filters is not None:
+        filters = np.ascontiguousarray(np.asarray(filters, dtype=np.float32))
+        bins = n_fft // 2 + 1
+        if filters.ndim != 2 or filters.shape[0] == 0 or filters.shape[1] != bins:
+            raise ValueError("filters: shape [M >= 1, %d] is needed, got %s" % (bins, filters.shape))
+        a = np.abs(filters)
+        if not np.isfinite(filters).all() or bool(((a != 0) & (a < 2.0 ** -60)).any()):
+            raise ValueError("filters: every weight finite, every nonzero weight at least 2^-60 in magnitude")
+    return n_fft, hop, win_length, window, filters
+
+
+def mel_filters(rate, n_fft, n_mels, f_min=0.0, f_max=None):
+    """HTK triangular mel filters, unnormalised -> float32 numpy array [n_mels, n_fft // 2 + 1], computed in float64:
+    mel(f) = 2595 log10(1 + f / 700); n_mels + 2 points evenly spaced in mel from f_min to f_max (None: rate / 2); filter j rises
+    from point j to point j + 1 and falls to point j + 2 over the bin frequencies k rate / n_fft:
+    max(0, min((f - p[j]) / (p[j + 1] - p[j]), (p[j + 2] - f) / (p[j + 2] - p[j + 1]))).  A weight that rounds below 2^-60 is 0."""
+    rate, n_fft, n_mels = float(rate), int(n_fft), int(n_mels)
+    f_max = rate / 2.0 if f_max is None else float(f_max)
+    if n_mels < 1 or n_fft < 1 or not (0.0 <= float(f_min) < f_max):
+        raise ValueError("mel_filters: n_mels >= 1, n_fft >= 1 and 0 <= f_min < f_max are needed")
+    lo, hi = (2595.0 * np.log10(1.0 + f / 700.0) for f in (float(f_min), f_max))
+    points = 700.0 * (10.0 ** (np.linspace(lo, hi, n_mels + 2) / 2595.0) - 1.0)
+    f = np.arange(n_fft // 2 + 1, dtype=np.float64) * rate / n_fft
+    rise = (f[None, :] - points[:-2, None]) / (points[1:-1] - points[:-2])[:, None]
+    fall = (points[2:, None] - f[None, :]) / (points[2:] - points[1:-1])[:, None]
+    w = np.maximum(0.0, np.minimum(rise, fall)).astype(np.float32)
+    w[np.abs(w) < 2.0 ** -60] = 0
+    return w
+
+
+def frame_counts(count, win_length, hop):
+    """The padding mask of the features: for the `count` column of any statistics table (the leading frames of a row that the
+    stream had), the frames of the row's spectrogram that lie wholly inside the stream: 0 for count < win_length, else
+    1 + (count - win_length) // hop.  count: a torch tensor, a numpy array or an int -> the same kind."""
+    w, h = int(win_length), int(hop)
+    if w < 1 or h < 1:
+        raise ValueError("frame_counts: win_length >= 1 and hop >= 1 are needed")
+    if hasattr(count, "clamp"):  # torch
+        return ((count - w).div(h, rounding_mode="floor") + 1).clamp(min=0)
+    return np.maximum((np.asarray(count, dtype=np.int64) - w) // h + 1, 0)
+
+
+class Spectrogram:
+    """AADHip_Spectrogram*: a framed, windowed real DFT with int16 coefficients and, with filters, the filterbank behind it."""
+
+    def __init__(self, engine, handle, n_fft, hop, win_length, num_filters):
+        self.engine, self.handle, self.n_fft, self.hop, self.win_length, self.num_filters = engine, handle, n_fft, hop, win_length, num_filters
+        self.bins = n_fft // 2 + 1
+        self.columns = num_filters if num_filters else self.bins  # the last dimension of run's result
+
+    def frames(self, T):
+        """F = 1 + (T - win_length) // hop of rows of T elements (AADHip_SpectrogramFrames)"""
+        n = C.c_uint32()
+        _check("AADHip_SpectrogramFrames", self.engine.lib.AADHip_SpectrogramFrames(self.handle, int(T), C.byref(n)))
+        return n.value
+
+    def coefficients(self):
+        """-> (q, int16 array [win_length, bins, 2]): the cos and -sin matrices as the library quantised them"""
+        lib = self.engine.lib
+        q = C.c_uint32()
+        m = np.zeros((self.win_length, self.bins, 2), dtype=np.int16)
+        _check("AADHip_SpectrogramCoefficients", lib.AADHip_SpectrogramCoefficients(self.handle, C.byref(q), m.ctypes.data, m.size))
+        return q.value, m
+
+    def run(self, rows, out=None):
+        """rows: int16 cuda tensor [N, C, T] or [R, T], read where it lies: stride(-1) == 1 and one pitch between consecutive
+        rows, at least T - a window decode's, Resampler.run's or Convolver.run's rows with dtype=torch.int16, or a slice of them
+        -> out float32 [N, C, F, columns] or [R, F, columns], contiguous, allocated when None.  Asynchronous on the engine's
+        stream, ordered against torch's current one."""
+        e = self.engine
+        torch = e.torch
+        e.tensor("rows", rows, torch.int16)
+        if rows.dim() not in (2, 3):
+            raise ValueError("rows: [N, C, T] or [R, T] is needed, got shape %s" % (tuple(rows.shape),))
+        lead, T = [int(v) for v in rows.shape[:-1]], int(rows.shape[-1])
+        if T < self.win_length:
+            raise ValueError("rows: %d elements a row, below the window's %d - such a row has no frame" % (T, self.win_length))
+        n = int(np.prod(lead))
+        # one pitch: the stride of the innermost leading dimension with more than one row, the outer ones its multiples
+        strides = [int(v) for v in rows.stride()[:-1]]
+        pitch, step = T, None
+        for size, stride in zip(reversed(lead), reversed(strides)):
+            if size > 1:
+                if step is None:
+                    pitch = step = stride
+                elif stride != step:
+                    raise ValueError("rows: one pitch between consecutive rows is needed, got shape %s with strides %s - pass "
+                                     "rows.contiguous() if a copy is intended" % (tuple(rows.shape), tuple(rows.stride())))
+            step = None if step is None else step * size
+        if pitch < T:
+            raise ValueError("rows: a row pitch of at least %d elements is needed, got strides %s" % (T, tuple(rows.stride())))
+        e.tensor("rows", rows, torch.int16, (n - 1) * pitch + T if n else 0, rows_in_place=True)
+        F = 1 + (T - self.win_length) // self.hop
+        shape = tuple(lead) + (F, self.columns)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=rows.device)
+        else:
+            e.tensor("out", out, torch.float32, n * F * self.columns, shape=shape, contiguous=True)
+        if n == 0:
+            return out
+        cur = e._enter()
+        _check("AADHip_SpectrogramRun", e.lib.AADHip_SpectrogramRun(self.handle, n, rows.data_ptr(), pitch, T, out.data_ptr()))
+        e._exit(cur)
+        return out
+
+    def close(self):
+        if self.handle:
+            self.engine.lib.AADHip_SpectrogramDestroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HipEvent:
     """A hipEvent_t of our own (timing disabled): what AADHip_ContextSignalNextRun takes and hipStreamWaitEvent waits for.
     torch.cuda.Event cannot wrap a foreign handle and creates its own lazily, hence the few runtime calls made directly."""
@@ -1905,4 +2070,4 @@ def parse_header(data):
                          block_size=be(24, 2), num_samples_per_block=be(26, 4), ch_process_method=data[30])
 
 
-__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "FirStage", "Resampler", "Convolver", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]
+__all__ = ["Engine", "EncodePlan", "PlanarEncodePlan", "PlanarReconstructPlan", "DecodePlan", "WindowDecodePlan", "FirStage", "Resampler", "Convolver", "Spectrogram", "mel_filters", "frame_counts", "EncodeDecodePipeline", "SimdRoleAllocator", "parse_header", "make_parameter", "LANE_STATE_DTYPE", "rmse", "snr_db", "level_dbfs", "snr_gains", "select_least_bits", "run_extent", "tensor_span"]

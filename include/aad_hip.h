@@ -758,6 +758,63 @@ AADApiResult AADHip_ConvolverRunStats(
     void *device_out,                              /* may be NULL: statistics only */
     struct AADHipRowStats *device_stats);          /* N * C records, every one written */
 
+/* ---- spectrogram: int16 rows to power-spectrum or filterbank energies, exact integer DFT on the matrix cores ------------------ */
+
+/* The last step of a loader for models that read log-mel features: any int16 row batch on the device - a window decode's, a
+ * resampler's or a convolver's (sample type INT16) - framed, windowed, transformed and, with filters, reduced to filterbank
+ * energies by ONE kernel, with no float32 batch, no complex spectrum and no elementwise pass.  Every element is defined bit for
+ * bit, like every other stage's.
+ *
+ * Parameters.  n_fft with 1 <= win_length W <= n_fft <= 4096; hop H >= 1; window float32 [W], every value finite;
+ *   B = n_fft / 2 + 1 bins; num_filters M >= 0 with filters float32 [M][B], dense and row-major, every weight finite, every
+ *   nonzero weight of magnitude >= 2^-60 (no product below is subnormal), negative weights allowed; filters is NULL exactly when
+ *   M = 0.
+ * Coefficients.  In double, c[t][k] = (double)w[t] cos(2 pi ((k t) mod n_fft) / n_fft) and s[t][k] = -(double)w[t] sin(the same
+ *   angle), t < W, k < B, the reduction (k t) mod n_fft in integers.  Both matrices are quantised together by the convolver's
+ *   rule: cq = rint(c 2^q), sq = rint(s 2^q), ties to even, q the largest of 0..15 with max |.| <= 32639; Create refuses a
+ *   window for which q = 0 does not fit.  AADHip_SpectrogramCoefficients returns q and both matrices.
+ * Frames.  A row of T elements gives F = 1 + (T - W) / H frames (floor); T < W is refused.  No centring, no padding: a caller
+ *   who wants a centred frame starts the window earlier.
+ * Sums.  Re[f][k] = sum over t < W of x[f H + t] cq[t][k], Im[f][k] likewise with sq: exact integers below 2^42 in magnitude.
+ * Elements.  re = fl32(Re) 2^-(15 + q) - the 64-bit integer rounded once to nearest even, then an exact scale, the convolver's
+ *   FLOAT32 rule - im likewise, and P[f][k] = fl32(fl32(re re) + fl32(im im)): two multiplies and one add, never a fused one.
+ *   The units are those of a waveform in [-1, 1) under an unnormalised DFT: what torch.stft(center=False) followed by
+ *   abs() ** 2 approximates.
+ * Filters.  lo_j and hi_j are the indices of filter j's first and last nonzero weight.  E[f][j] starts at +0 and, for
+ *   k = lo_j, lo_j + 1, ..., hi_j in that order, E = fl32(E + fl32(filters[j][k] P[f][k])); a zero inside the band is multiplied
+ *   like any other weight; an all-zero filter gives +0.
+ * Output.  float32, contiguous: [num_rows, F, M] for M > 0, and [num_rows, F, B], P itself, for M = 0.  Two runs give the same
+ *   bits.
+ *
+ * The coefficients are int16 because the rows are decodes of a 2- to 4-bit codec, whose error lies orders of magnitude above a
+ * 2^-15 coefficient rounding; the price shows on a pure full-scale tone, where bands some 90 dB below the peak are coefficient
+ * noise (DESIGN.md "Spectrogram" has the measured floor).
+ *
+ * Not built: the logarithm (no correctly rounded log exists on the device, and one torch.log over an output 5 to 10 times smaller
+ * than the waveform is cheap); float16 / bfloat16 outputs (pointless in front of the log); magnitude (power = 1); the [.., M, F]
+ * layout (transpose(-1, -2) is a view); pre-emphasis, dither and DC removal; n_fft past 4096; coefficients wider than int16.
+ *
+ * Create returns AAD_APIRESULT_INVALID_ARGUMENT for anything the definition excludes.  Run is asynchronous on the context's
+ * stream; num_rows == 0 launches nothing and returns OK.  Otherwise the calls refuse a null pointer, device_rows off 2-byte or
+ * device_out off 4-byte alignment, frames < win_length, row_pitch < frames and extents past 64 bits; a refused call writes
+ * nothing. */
+struct AADHipSpectrogram;
+AADApiResult AADHip_SpectrogramCreate(
+    struct AADHipContext *context, uint32_t n_fft, uint32_t win_length, uint32_t hop, const float *window,
+    uint32_t num_filters, const float *filters, /* NULL exactly when num_filters == 0 */
+    struct AADHipSpectrogram **spectrogram);
+void AADHip_SpectrogramDestroy(struct AADHipSpectrogram *spectrogram);
+/* F of rows of `frames` elements */
+AADApiResult AADHip_SpectrogramFrames(const struct AADHipSpectrogram *spectrogram, uint32_t frames, uint32_t *num_frames);
+/* the scale exponent q and the quantised cos / -sin matrices, int16 [W][B][2]; cos_sin NULL: the scale alone.
+ * AAD_APIRESULT_INSUFFICIENT_BUFFER for a capacity (in elements) below W * B * 2 */
+AADApiResult AADHip_SpectrogramCoefficients(
+    const struct AADHipSpectrogram *spectrogram, uint32_t *scale, int16_t *cos_sin, uint64_t capacity);
+AADApiResult AADHip_SpectrogramRun(
+    struct AADHipSpectrogram *spectrogram, uint64_t num_rows, const int16_t *device_rows,
+    uint64_t row_pitch, /* in elements, >= frames */
+    uint32_t frames, float *device_out);
+
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */
 
 /* The write side of the planar layout window decode reads out: one row per channel, int16 or float32 - torch's [N, C, T] - encoded
