@@ -129,7 +129,7 @@ HIP_SYMBOLS = [
     "AADHip_ConvolverCreate", "AADHip_ConvolverDestroy", "AADHip_ConvolverResponse", "AADHip_ConvolverSourceFrames",
     "AADHip_ConvolverResolve", "AADHip_ConvolverRun", "AADHip_ConvolverRunGain", "AADHip_ConvolverRunStats",
     "AADHip_SpectrogramCreate", "AADHip_SpectrogramDestroy", "AADHip_SpectrogramFrames", "AADHip_SpectrogramCoefficients",
-    "AADHip_SpectrogramRun",
+    "AADHip_SpectrogramRun", "AADHip_SpectrogramRunMix",
 ]
 WAV_SYMBOLS = ["AADWav_ParseHeader", "AADWav_WriteHeader", "AADWav_ConvertToPcm16"]
 SYNTH_SYMBOLS = ["AADSynth_Generate"]
@@ -293,6 +293,8 @@ def _declare_hip(lib):
     lib.AADHip_SpectrogramCoefficients.restype = C.c_int
     lib.AADHip_SpectrogramRun.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp]
     lib.AADHip_SpectrogramRun.restype = C.c_int
+    lib.AADHip_SpectrogramRunMix.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
+    lib.AADHip_SpectrogramRunMix.restype = C.c_int
     lib.AADHip_EncodeBatch.argtypes = [vp, C.POINTER(AADEncodeParameter), C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.AADHip_EncodeBatch.restype = C.c_int
     lib.AADHip_DecodeBatch.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]

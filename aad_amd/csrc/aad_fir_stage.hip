@@ -1,7 +1,7 @@
 /* aad_fir_stage.hip - host side of the FIR stages behind a window decode (include/aad_hip.h "resample", "reverberation") and of
  * the spectrogram stage behind any of them ("spectrogram"): every AADHip_Resampler*, AADHip_Convolver* and AADHip_Spectrogram*
  * entry point.  No kernel is instantiated here: the launches are aad_resample.hip's, aad_resample_wide.hip's, aad_convolve.hip's,
- * aad_convolve_stats.hip's and aad_spectrogram.hip's.  A stage is made by its own Create; what a Resolve or
+ * aad_convolve_stats.hip's, aad_spectrogram.hip's and aad_spectrogram_mix.hip's.  A stage is made by its own Create; what a Resolve or
  * a Run refuses is one rule for both (aad_fir_stage.h), asked through the few members a stage states about itself, and every
  * launch ends in `launched`. */
 #include <hip/hip_runtime.h>
@@ -621,6 +621,38 @@ AADApiResult AADHip_SpectrogramCoefficients(const struct AADHipSpectrogram *s, u
   return AAD_APIRESULT_OK;
 }
 
+namespace {
+
+/* the kernels' arguments of a run the stage's rule has passed: the handle's and the run's */
+aad::spectrum::Args spectrogram_args(const AADHipSpectrogram *s, const aad::SpectrumRows &r, uint64_t num_rows, const int16_t *device_rows,
+                                     uint64_t row_pitch, uint32_t frames, float *device_out)
+{
+  aad::spectrum::Args a = {};
+  a.rows = device_rows;
+  a.row_pitch = row_pitch;
+  a.num_rows = num_rows;
+  a.frames = frames;
+  a.num_frames = r.num_frames;
+  a.hop = s->hop;
+  a.steps = aad::spectrum_steps(s->win);
+  a.pairs = aad::spectrum_pairs(s->n_fft);
+  a.bins = aad::spectrum_bins(s->n_fft);
+  a.q = s->q;
+  a.g = s->g;
+  a.tiles = r.tiles;
+  a.planes = s->d_planes;
+  a.consts = s->d_consts;
+  a.num_filters = s->num_filters;
+  a.bands = s->d_bands;
+  a.weights = s->d_weights;
+  a.tile_first = s->d_tile_first;
+  a.tile_list = s->d_tile_list;
+  a.out = device_out;
+  return a;
+}
+
+} /* namespace */
+
 AADApiResult AADHip_SpectrogramRun(struct AADHipSpectrogram *s, uint64_t num_rows, const int16_t *device_rows, uint64_t row_pitch,
                                    uint32_t frames, float *device_out)
 {
@@ -637,26 +669,37 @@ AADApiResult AADHip_SpectrogramRun(struct AADHipSpectrogram *s, uint64_t num_row
   DeviceGuard guard(s->ctx);
   if (!guard.ok) return AAD_APIRESULT_NG;
   if (num_rows == 0) return AAD_APIRESULT_OK;
-  aad::spectrum::Args a = {};
-  a.rows = device_rows;
-  a.row_pitch = row_pitch;
-  a.num_rows = num_rows;
-  a.frames = frames;
-  a.num_frames = r.num_frames;
-  a.hop = s->hop;
-  a.steps = aad::spectrum_steps(s->win);
-  a.pairs = aad::spectrum_pairs(s->n_fft);
-  a.bins = B;
-  a.q = s->q;
-  a.g = s->g;
-  a.tiles = r.tiles;
-  a.planes = s->d_planes;
-  a.consts = s->d_consts;
-  a.num_filters = s->num_filters;
-  a.bands = s->d_bands;
-  a.weights = s->d_weights;
-  a.tile_first = s->d_tile_first;
-  a.tile_list = s->d_tile_list;
-  a.out = device_out;
-  return launched(s, "run", aad::spectrum::launch(a, s->ctx->stream));
+  return launched(s, "run", aad::spectrum::launch(spectrogram_args(s, r, num_rows, device_rows, row_pitch, frames, device_out), s->ctx->stream));
+}
+
+AADApiResult AADHip_SpectrogramRunMix(struct AADHipSpectrogram *s, uint64_t num_rows, const int16_t *device_rows_a, uint64_t row_pitch_a,
+                                      const int16_t *device_rows_b, uint64_t row_pitch_b, uint32_t rows_per_gain, const float *device_gain_a,
+                                      const float *device_gain_b, const struct AADHipWindowSpan *device_spans, uint32_t frames,
+                                      float *device_out)
+{
+  if (s == nullptr) return AAD_APIRESULT_INVALID_ARGUMENT;
+  const aad::SpectrumRows r = aad::spectrum_mix_rows(num_rows, address(device_rows_a), row_pitch_a, address(device_rows_b), row_pitch_b,
+                                                     rows_per_gain, address(device_gain_a), address(device_gain_b), address(device_spans),
+                                                     frames, address(device_out), s->win, s->hop,
+                                                     s->num_filters != 0 ? s->num_filters : aad::spectrum_bins(s->n_fft), s->g.tile_frames);
+  if (!r.ok) {
+    snprintf(s->ctx->last_error, sizeof(s->ctx->last_error),
+             "spectrogram mix run: a null or unaligned pointer, %u frames below the window's %u, row pitches of %llu and %llu below the "
+             "frames, %llu rows past 64 bits or no multiple of %u rows a gain", frames, s->win, (unsigned long long)row_pitch_a,
+             (unsigned long long)row_pitch_b, (unsigned long long)num_rows, rows_per_gain);
+    return AAD_APIRESULT_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(s->ctx);
+  if (!guard.ok) return AAD_APIRESULT_NG;
+  if (num_rows == 0) return AAD_APIRESULT_OK;
+  static_assert(sizeof(AADHipWindowSpan) == 2 * sizeof(uint64_t), "span record layout");
+  aad::spectrum_mix::Args m = {};
+  m.s = spectrogram_args(s, r, num_rows, device_rows_a, row_pitch_a, frames, device_out);
+  m.rows_b = device_rows_b;
+  m.row_pitch_b = row_pitch_b;
+  m.rows_per_gain = rows_per_gain;
+  m.gain_a = device_gain_a;
+  m.gain_b = device_gain_b;
+  m.spans = reinterpret_cast<const uint64_t *>(device_spans);
+  return launched(s, "mix run", aad::spectrum_mix::launch(m, s->ctx->stream));
 }

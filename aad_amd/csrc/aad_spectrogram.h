@@ -265,6 +265,48 @@ inline SpectrumRows spectrum_rows(uint64_t num_rows, uint64_t rows, uint64_t row
   return r;
 }
 
+/* ---- a mix (include/aad_hip.h "spectrogram", paragraph "mix") -------------------------------------------------------------------- */
+
+/* The staged sample of AADHip_SpectrogramRunMix: m = fl32(ga a), inside b's span m = fl32(m + fl32(gb b)) - two multiplies and one
+ * add, never a fused one - then 0 for a NaN, else the nearest integer, ties to even, clamped to int16: an infinite m gives the
+ * rail.  The conversions of a and b are exact.  The kernel's stager (aad_spectrogram_mix.hip) and tests/spectrogram_mix_driver.cpp
+ * compile this one function. */
+AAD_CONVOLVE_FN int16_t spectrum_mix_sample(float ga, int16_t a, float gb, int16_t b, bool inside)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  float m = __fmul_rn(ga, (float)a);
+  if (inside) m = __fadd_rn(m, __fmul_rn(gb, (float)b));
+#else
+  volatile float pa = ga * (float)a, pb = gb * (float)b; /* the host's compiler may not fuse across a volatile */
+  float m = pa;
+  if (inside) m = pa + pb;
+#endif
+  if (!(m == m)) return 0;
+  const float r = rintf(m); /* to nearest even: no unit changes the rounding mode */
+  return (int16_t)(r < -32768.0f ? -32768 : r > 32767.0f ? 32767 : (int32_t)r);
+}
+
+/* Le of "Window decode with a span": 0 for o >= T, else min(L, T - o) - the comparison first, no sum of two 64-bit values */
+AAD_CONVOLVE_FN uint32_t spectrum_mix_span(uint64_t L, uint64_t o, uint32_t T)
+{
+  if (o >= T) return 0;
+  return L < T - o ? (uint32_t)L : (uint32_t)(T - o);
+}
+
+/* A mix run: spectrum_rows for both row batches, and rows_per_gain C >= 1 that divides num_rows; gain tables (0: none) on 4-byte
+ * and the span table (0: none) on 8-byte alignment, num_rows / C records each, whose bytes lie within 64 bits. */
+inline SpectrumRows spectrum_mix_rows(uint64_t num_rows, uint64_t rows_a, uint64_t row_pitch_a, uint64_t rows_b, uint64_t row_pitch_b,
+                                      uint32_t rows_per_gain, uint64_t gain_a, uint64_t gain_b, uint64_t spans, uint32_t frames, uint64_t out,
+                                      uint32_t W, uint32_t H, uint32_t columns, uint32_t tile_frames)
+{
+  SpectrumRows r = spectrum_rows(num_rows, rows_a, row_pitch_a, frames, out, W, H, columns, tile_frames);
+  uint64_t n = 0;
+  r.ok = r.ok && spectrum_rows(num_rows, rows_b, row_pitch_b, frames, out, W, H, columns, tile_frames).ok && rows_per_gain != 0 &&
+         num_rows % rows_per_gain == 0 && (gain_a & 3u) == 0 && (gain_b & 3u) == 0 && (spans & 7u) == 0 &&
+         !__builtin_mul_overflow(num_rows / rows_per_gain, (uint64_t)16, &n);
+  return r;
+}
+
 } /* namespace aad */
 
 #endif /* AAD_SPECTROGRAM_H */

@@ -1,5 +1,6 @@
-/* aad_spectrogram.hip.h - what the host side of the spectrogram stage (aad_fir_stage.hip) hands to its kernel
- * (aad_spectrogram.hip): the arguments and the launch.  No device code.  The arithmetic is aad_spectrogram.h's. */
+/* aad_spectrogram.hip.h - what the host side of the spectrogram stage (aad_fir_stage.hip) hands to its kernels
+ * (aad_spectrogram.hip, aad_spectrogram_mix.hip): the arguments and the launches.  No device code - that is
+ * aad_spectrogram_rows.hip.h's.  The arithmetic is aad_spectrogram.h's. */
 #ifndef AAD_SPECTROGRAM_HIP_H
 #define AAD_SPECTROGRAM_HIP_H
 
@@ -32,6 +33,23 @@ struct Args {
 bool launch(const Args &a, hipStream_t stream);
 
 } /* namespace spectrum */
+
+namespace spectrum_mix {
+
+/* AADHip_SpectrogramRunMix (aad_spectrogram_mix.hip): s.rows / s.row_pitch are a's; group G = row / rows_per_gain */
+struct Args {
+  spectrum::Args s;
+  const int16_t *rows_b; /* row r at rows_b + r * row_pitch_b, read below the group's Le alone */
+  uint64_t row_pitch_b;
+  uint32_t rows_per_gain;
+  const float *gain_a, *gain_b; /* [num_rows / rows_per_gain]; null: every gain 1 */
+  const uint64_t *spans;        /* AADHipWindowSpan records, (L, o) of group G at spans[2 G]; null: every span (T, 0) */
+};
+
+/* false: the device refuses the launch's LDS (spectrum_lds_bytes) */
+bool launch(const Args &a, hipStream_t stream);
+
+} /* namespace spectrum_mix */
 } /* namespace aad */
 
 #endif /* AAD_SPECTROGRAM_HIP_H */

@@ -965,6 +965,42 @@ class Engine:
         finally:
             plan.close()
 
+    def mel_mix_windows(self, signal, noise, frames, snr_db, n_fft, hop, filters, channels=None, win_length=None, window=None,
+                        noise_spans=None):
+        """The features of a noisy batch at a chosen SNR - mix_windows and mel_windows in one, without the float32 rows between
+        them: signal, noise, snr_db, channels, noise_spans as mix_windows; n_fft, hop, filters, win_length, window as
+        `spectrogram`.  Two statistics-only runs give the levels - the noise's over its spans - snr_gains the noise gains, two
+        decodes the int16 rows of signal and noise, and ONE Spectrogram.run_mix sums them per element as
+        clamp(rint(signal + fl32(gain * noise))) while it stages them -> (float32 [N, C, F, M], float32 [N] noise gains).  The two
+        int16 batches are the only temporaries.  Every argument is checked before anything is built."""
+        torch = self.torch
+        args = _spectrogram_arguments(n_fft, hop, win_length, window, filters)
+        frames = int(frames)
+        if frames < args[2]:
+            raise ValueError("frames: %d is below the window's %d - such a row has no frame" % (frames, args[2]))
+        s_windows = self.window_table(signal[2], True)
+        n_windows = self.window_table(noise[2], True, rows=int(s_windows.shape[0]))
+        if noise_spans is not None:
+            noise_spans = self.window_table(noise_spans, True, name="spans", rows=int(s_windows.shape[0]))
+        s_plan = self._corpus_window_plan(signal[0], signal[1], channels)
+        try:
+            n_plan = self._corpus_window_plan(noise[0], noise[1], channels)
+            try:
+                spec = self._spectrogram(*args)
+                try:
+                    s_stats = s_plan.run(signal[0], s_windows, frames, stats=True, rows=False)
+                    n_stats = n_plan.run(noise[0], n_windows, frames, stats=True, rows=False, spans=noise_spans)
+                    gains = snr_gains(s_stats, n_stats, snr_db)
+                    s_rows = s_plan.run(signal[0], s_windows, frames, torch.int16)
+                    n_rows = n_plan.run(noise[0], n_windows, frames, torch.int16)
+                    return spec.run_mix(s_rows, n_rows, other_gain=gains, spans=noise_spans), gains
+                finally:
+                    spec.close()  # synchronises the context's stream first
+            finally:
+                n_plan.close()
+        finally:
+            s_plan.close()
+
     @staticmethod
     def _speeds(rate, speeds):
         """what the resampled calls refuse of rate and speeds, before anything is built -> the speeds as pairs of ints"""
@@ -1816,19 +1852,16 @@ class Spectrogram:
         _check("AADHip_SpectrogramCoefficients", lib.AADHip_SpectrogramCoefficients(self.handle, C.byref(q), m.ctypes.data, m.size))
         return q.value, m
 
-    def run(self, rows, out=None):
-        """rows: int16 cuda tensor [N, C, T] or [R, T], read where it lies: stride(-1) == 1 and one pitch between consecutive
-        rows, at least T - a window decode's, Resampler.run's or Convolver.run's rows with dtype=torch.int16, or a slice of them
-        -> out float32 [N, C, F, columns] or [R, F, columns], contiguous, allocated when None.  Asynchronous on the engine's
-        stream, ordered against torch's current one."""
+    def _rows(self, name, rows):
+        """an int16 row batch [N, C, T] or [R, T] that a run reads where it lies -> (leading shape, T, rows, pitch)"""
         e = self.engine
         torch = e.torch
-        e.tensor("rows", rows, torch.int16)
+        e.tensor(name, rows, torch.int16)
         if rows.dim() not in (2, 3):
-            raise ValueError("rows: [N, C, T] or [R, T] is needed, got shape %s" % (tuple(rows.shape),))
+            raise ValueError("%s: [N, C, T] or [R, T] is needed, got shape %s" % (name, tuple(rows.shape)))
         lead, T = [int(v) for v in rows.shape[:-1]], int(rows.shape[-1])
         if T < self.win_length:
-            raise ValueError("rows: %d elements a row, below the window's %d - such a row has no frame" % (T, self.win_length))
+            raise ValueError("%s: %d elements a row, below the window's %d - such a row has no frame" % (name, T, self.win_length))
         n = int(np.prod(lead))
         # one pitch: the stride of the innermost leading dimension with more than one row, the outer ones its multiples
         strides = [int(v) for v in rows.stride()[:-1]]
@@ -1838,22 +1871,67 @@ class Spectrogram:
                 if step is None:
                     pitch = step = stride
                 elif stride != step:
-                    raise ValueError("rows: one pitch between consecutive rows is needed, got shape %s with strides %s - pass "
-                                     "rows.contiguous() if a copy is intended" % (tuple(rows.shape), tuple(rows.stride())))
+                    raise ValueError("%s: one pitch between consecutive rows is needed, got shape %s with strides %s - pass "
+                                     "%s.contiguous() if a copy is intended" % (name, tuple(rows.shape), tuple(rows.stride()), name))
             step = None if step is None else step * size
         if pitch < T:
-            raise ValueError("rows: a row pitch of at least %d elements is needed, got strides %s" % (T, tuple(rows.stride())))
-        e.tensor("rows", rows, torch.int16, (n - 1) * pitch + T if n else 0, rows_in_place=True)
+            raise ValueError("%s: a row pitch of at least %d elements is needed, got strides %s" % (name, T, tuple(rows.stride())))
+        e.tensor(name, rows, torch.int16, (n - 1) * pitch + T if n else 0, rows_in_place=True)
+        return lead, T, n, pitch
+
+    def _out(self, rows, lead, T, n, out):
+        """the result of a run over `rows`: float32 [lead.., F, columns], the caller's when it fits"""
+        torch = self.engine.torch
         F = 1 + (T - self.win_length) // self.hop
         shape = tuple(lead) + (F, self.columns)
         if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=rows.device)
-        else:
-            e.tensor("out", out, torch.float32, n * F * self.columns, shape=shape, contiguous=True)
+            return torch.empty(shape, dtype=torch.float32, device=rows.device)
+        return self.engine.tensor("out", out, torch.float32, n * F * self.columns, shape=shape, contiguous=True)
+
+    def run(self, rows, out=None):
+        """rows: int16 cuda tensor [N, C, T] or [R, T], read where it lies: stride(-1) == 1 and one pitch between consecutive
+        rows, at least T - a window decode's, Resampler.run's or Convolver.run's rows with dtype=torch.int16, or a slice of them
+        -> out float32 [N, C, F, columns] or [R, F, columns], contiguous, allocated when None.  Asynchronous on the engine's
+        stream, ordered against torch's current one."""
+        e = self.engine
+        lead, T, n, pitch = self._rows("rows", rows)
+        out = self._out(rows, lead, T, n, out)
         if n == 0:
             return out
         cur = e._enter()
         _check("AADHip_SpectrogramRun", e.lib.AADHip_SpectrogramRun(self.handle, n, rows.data_ptr(), pitch, T, out.data_ptr()))
+        e._exit(cur)
+        return out
+
+    def run_mix(self, rows, other, gain=None, other_gain=None, spans=None, out=None):
+        """The spectrogram of gain * rows + other_gain * other, summed and quantised to int16 while the kernel stages its samples
+        (AADHip_SpectrogramRunMix, include/aad_hip.h "spectrogram", paragraph "mix"): per element
+        clamp(rint(fl32(fl32(gain * rows) + fl32(other_gain * other)))), ties to even, a NaN 0 - no float32 batch, no quantise
+        pass.  rows, other: int16 cuda tensors of one shape [N, C, T] or [R, T], each read where it lies under `run`'s one-pitch
+        rule, each with a pitch of its own.  gain, other_gain: float32 cuda [N] - one pair for the C rows of a window - or [R],
+        None for 1.  spans: int64 cuda [N, 2] or [R, 2] of (num_frames, out_frame): `other` is an event of num_frames elements
+        added from element out_frame of the row on, clipped to the row as WindowDecodePlan.run clips a span; None for the whole
+        row.  -> out as `run`."""
+        e = self.engine
+        torch = e.torch
+        lead, T, n, pitch = self._rows("rows", rows)
+        if torch.is_tensor(other) and tuple(other.shape) != tuple(rows.shape):
+            raise ValueError("other: shape %s, that of rows, is needed, got %s" % (tuple(rows.shape), tuple(other.shape)))
+        other_pitch = self._rows("other", other)[3]
+        groups, per = lead[0], n // lead[0] if lead[0] else 1
+        for name, g in (("gain", gain), ("other_gain", other_gain)):
+            if g is not None:
+                e.tensor(name, g, torch.float32, groups, shape=(groups,), contiguous=True)
+        if spans is not None:
+            e.tensor("spans", spans, torch.int64, 2 * groups, shape=(groups, 2), contiguous=True)
+        out = self._out(rows, lead, T, n, out)
+        if n == 0:
+            return out
+        ptr = lambda t: None if t is None else t.data_ptr()
+        cur = e._enter()
+        _check("AADHip_SpectrogramRunMix",
+               e.lib.AADHip_SpectrogramRunMix(self.handle, n, rows.data_ptr(), pitch, other.data_ptr(), other_pitch, per, ptr(gain),
+                                              ptr(other_gain), ptr(spans), T, out.data_ptr()))
         e._exit(cur)
         return out
 

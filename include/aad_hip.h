@@ -409,8 +409,8 @@ AADApiResult AADHip_WindowDecodePlanRunStats(
  *   - a NULL table under STORE writes byte for byte what AADHip_WindowDecodePlanRun writes.
  *
  * Errors.  AADHip_WindowDecodePlanRun's, plus AAD_APIRESULT_INVALID_ARGUMENT for AAD_HIP_SAMPLE_INT16 (a gain on integer rows
- * needs a rounding and clipping rule that nobody has asked for), a mode outside {0, 1} and a device_gain that is not 4-byte
- * aligned.  num_windows == 0 is OK and launches nothing.  A refused run writes nothing.
+ * needs a rounding and clipping rule, which only AADHip_SpectrogramRunMix states), a mode outside {0, 1} and a device_gain that
+ * is not 4-byte aligned.  num_windows == 0 is OK and launches nothing.  A refused run writes nothing.
  *
  * There is no statistics variant: the levels are needed before the gains exist, so they come from a statistics-only
  * AADHip_WindowDecodePlanRunStats (device_out == NULL) first.
@@ -813,6 +813,42 @@ AADApiResult AADHip_SpectrogramCoefficients(
 AADApiResult AADHip_SpectrogramRun(
     struct AADHipSpectrogram *spectrogram, uint64_t num_rows, const int16_t *device_rows,
     uint64_t row_pitch, /* in elements, >= frames */
+    uint32_t frames, float *device_out);
+
+/* Mix.  The spectrogram of a sum of two int16 row batches at gains - speech plus noise at an SNR - with the sum formed while the
+ * kernel stages its samples: no float32 batch, no quantise pass.  Every other stage refuses a gain on int16 rows, because such a
+ * gain needs a rounding and clipping rule; this is the one stage that asks for it, and here it is.
+ *
+ * Definition.  T = frames.  For row r let G = r / rows_per_gain, ga = device_gain_a[G], gb = device_gain_b[G] (1 with NULL) and
+ * (L, o) = device_spans[G] ((T, 0) with NULL); Le follows "Window decode with a span": Le = 0 if o >= T, else min(L, T - o) - the
+ * comparison first, so huge and wrapped values are no error.  For element j < T, with a and b the int16 values converted to
+ * float32 exactly:
+ *   Outside the span:                  m = fl32(ga a[j])
+ *   Inside the span, o <= j < o + Le:  m = fl32(fl32(ga a[j]) + fl32(gb b[j - o]))  - two multiplies and one add, three
+ *                                      roundings, never a fused multiply-add
+ *   Quantise:                          x[j] = 0 if m is a NaN; else m rounded to the nearest integer, ties to even, and clamped
+ *                                      to [-32768, 32767] - an infinite m gives the rail.
+ * The output is, bit for bit, what AADHip_SpectrogramRun writes for a batch that holds x.  b is read only at indices below Le,
+ * a only below T; a and b may be the same memory.
+ *
+ * Two identities.  With ga = 1 and products that do not underflow, x = clamp(rint(32768 f)), f the float32 element that a STORE
+ * of a and an ADD of gb b with the same span write (AADHip_WindowDecodePlanRunPlaced): f = fl32(a 2^-15 + fl32(gb b 2^-15)), and
+ * scaling by a power of two commutes with every rounding above the subnormals.  It does NOT hold where the channel-mix plan
+ * down-mixes stereo to mono: the int16 row holds the floor of the mean, the float row the exact mean.
+ *
+ * No clip count is returned: a caller who must not clip bounds the peak with |ga| max_abs_a + |gb| max_abs_b from the statistics
+ * tables' peak column.  Out of scope: more than two operands, a span for a, and gains on the int16 rows of any other stage.
+ *
+ * Refused, each writing nothing: everything AADHip_SpectrogramRun refuses, for both row pointers and both pitches;
+ * rows_per_gain == 0 or num_rows not a multiple of it; a gain table off 4-byte or a span table off 8-byte alignment.
+ * num_rows == 0 is OK and launches nothing. */
+AADApiResult AADHip_SpectrogramRunMix(
+    struct AADHipSpectrogram *spectrogram, uint64_t num_rows,
+    const int16_t *device_rows_a, uint64_t row_pitch_a,
+    const int16_t *device_rows_b, uint64_t row_pitch_b,
+    uint32_t rows_per_gain,                                   /* C: rows that share one gain pair and one span */
+    const float *device_gain_a, const float *device_gain_b,   /* num_rows / rows_per_gain floats each; NULL: every gain 1 */
+    const struct AADHipWindowSpan *device_spans,              /* of b, num_rows / rows_per_gain records; NULL: (T, 0) */
     uint32_t frames, float *device_out);
 
 /* ---- planar encode: int16 / float32 rows per channel into .aad images ------------------------ */

@@ -12,6 +12,15 @@ the device, through n_fft 512, a 400-sample Hann window, --hop (repeatable; defa
             abs() ** 2 and a matmul with the filters (the rows padded by n_fft - W so that torch's frames are the stage's), with the peak of torch's allocator above its result
 The first window's features are checked against tests/spectrogram_oracle.py.  --out appends the lines to a file.
 
+--mix (needs the device): what the mix costs (DESIGN.md "Spectrogram of a mix"), at the same shape and by the same events: signal
+and noise windows drawn from the corpus, a gain per window.  Per hop:
+  mix       AADHip_SpectrogramRunMix over the two decoded int16 batches, and the two decodes + the mix together
+  stage     AADHip_SpectrogramRun over one of the batches: the floor
+  composed  the composition the mix replaces: the signal's rows STORED and gain * noise ADDED into float32 rows by the window
+            decode plans, torch.round(32768 x).clamp().to(int16), then AADHip_SpectrogramRun - with the peak of torch's allocator
+            above the result
+The mix's features are held against the composition's, bit for bit, and window 0's against the oracles.
+
 --accuracy (CPU only): the definition, from the oracle, against a float64 STFT and mel at the same shape on four signals - a
 440 Hz tone with noise, quiet noise, a full-scale pure tone and a decoded window of the golden corpus (the synthetic corpus
 through the codec's oracle when none is found): the largest and the median |d ln E| over the bands, and for the pure tone the
@@ -67,6 +76,90 @@ def accuracy(out):
             f.write("\n".join(lines) + "\n")
 
 
+def mix(args):
+    import torch
+    import spectrogram_mix_oracle as mo
+    import spectrogram_oracle as so
+    from aad_amd.capi import make_parameter
+    from aad_amd.engine import Engine, mel_filters
+    from aad_amd.synth import synth_pcm
+    from resample_probe import pcm_decoded, timed_all
+    engine = Engine(0, stream=None)
+    n, frames = args.windows, args.frames
+    samples = frames * 2 + 4096
+    pcm = synth_pcm(args.streams, samples, 1, seed=5)
+    filters = mel_filters(RATE, N_FFT, MELS)
+    lines = []
+    fmt = lambda ms: "%.3f ms (%.3f - %.3f)" % (statistics.median(ms), min(ms), max(ms))
+    with torch.cuda.stream(engine.stream):
+        data, size = engine.encode_uniform(torch.from_numpy(pcm).cuda(), make_parameter(1, 4, 1024, RATE, False, 0))
+        plan = engine._corpus_window_plan(data, size, None)
+        gen = torch.Generator(device="cuda").manual_seed(11)
+        draw = lambda: torch.stack([torch.randint(0, args.streams, (n,), generator=gen, device="cuda"),
+                                    torch.randint(0, samples // 2, (n,), generator=gen, device="cuda")], dim=1).contiguous()
+        s_windows, n_windows = draw(), draw()
+        gains = (torch.rand(n, generator=gen, device="cuda") * 0.9 + 0.05).contiguous()
+        ones = torch.ones_like(gains)
+        s_rows = torch.empty((n, 1, frames), dtype=torch.int16, device="cuda")
+        n_rows = torch.empty((n, 1, frames), dtype=torch.int16, device="cuda")
+
+        def decodes():
+            plan.run(data, s_windows, frames, torch.int16, out=s_rows, ordered=False)
+            plan.run(data, n_windows, frames, torch.int16, out=n_rows, ordered=False)
+
+        decodes()
+        for hop in args.hop or [160, 441]:
+            spec = engine.spectrogram(N_FFT, hop, WIN, None, filters)
+            F = spec.frames(frames)
+            out = torch.empty((n, 1, F, spec.columns), dtype=torch.float32, device="cuda")
+            other = torch.empty_like(out)
+            run_mix = lambda: spec.run_mix(s_rows, n_rows, other_gain=gains, out=out)
+            stage = lambda: spec.run(s_rows, out=other)
+
+            def both():
+                decodes()
+                run_mix()
+
+            def composed():
+                x = plan.run(data, s_windows, frames, torch.float32, gain=ones, ordered=False)
+                plan.run(data, n_windows, frames, torch.float32, out=x, gain=gains, accumulate=True, ordered=False)
+                return spec.run(torch.round(x * 32768.0).clamp(-32768, 32767).to(torch.int16), out=other)
+
+            t_mix = timed_all(engine.stream, args.steps, args.warmup, run_mix)
+            t_stage = timed_all(engine.stream, args.steps, args.warmup, stage)
+            t_both = timed_all(engine.stream, args.steps, args.warmup, both)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            t_comp = timed_all(engine.stream, args.steps, args.warmup, composed)
+            peak = torch.cuda.max_memory_allocated() - before
+            run_mix()
+            same = bool(torch.equal(composed().view(torch.int32), out.view(torch.int32)))
+            crops = []
+            for w in (s_windows, n_windows):
+                s0, f0 = (int(v) for v in w[0].cpu())
+                x = pcm_decoded(engine, data, size, s0)[:, 0]
+                crop = np.zeros(frames, dtype=np.int16)
+                k = max(0, min(frames, len(x) - f0))
+                crop[:k] = x[f0:f0 + k]
+                crops.append(crop[None])
+            x0 = mo.mix_rows(crops[0], crops[1], 1, None, gains[:1].cpu().numpy())
+            want = so.spectrogram(x0[0], so.hann(WIN), N_FFT, hop, filters)
+            exact = bool((out[0, 0].cpu().numpy().view(np.uint32) == want.view(np.uint32)).all())
+            lines.append("n_fft=%d W=%d H=%d M=%d  N=%d T=%d F=%d  (a) mix %s  two int16 decodes + mix %s  (b) stage over one batch %s  "
+                         "(c) float32 STORE + ADD decodes + quantise + stage %s, %.1f MB of temporaries (the mix: the two int16 batches, "
+                         "%.1f MB)  mix == composed: %s  exact=%s" % (N_FFT, WIN, hop, MELS, n, frames, F, fmt(t_mix), fmt(t_both), fmt(t_stage),
+                                                                    fmt(t_comp), peak / 1e6, 2 * n * frames * 2 / 1e6, same, exact))
+            print(lines[-1], flush=True)
+            spec.close()
+            del out, other
+        plan.close()
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=1024)
@@ -76,10 +169,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--hop", type=int, action="append")
     ap.add_argument("--accuracy", action="store_true")
+    ap.add_argument("--mix", action="store_true")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.accuracy:
         return accuracy(args.out)
+    if args.mix:
+        return mix(args)
     import torch
     import spectrogram_oracle as so
     from aad_amd.capi import make_parameter
